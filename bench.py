@@ -28,6 +28,10 @@ relays rank 0's JSON line and exits non-zero if any rank failed.  Launched under
 it simply is one of the ranks.  Every rank processes its own B images (weak scaling, the path shards by image, no
 data-path collective); the only collective is the start-up RCCL broadcast of MarginalNet weights, untimed.
 
+``--dump-outputs DIR`` writes, after the timed steps, what the main line's last timed step computed (the warped batch, or a
+fixed seeded sample of it) as DIR/<name>.npy in float32 / float64, at most 64 MiB; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+
 Output: ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     dominant kernel (remap_rows_kernel): algorithmic bytes (2*S*S*3*4 per image)
                / its mean launch duration measured live with HIP events inside the timed region,
@@ -515,6 +519,7 @@ def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn
     ow = pipeline.OverlappedWarp([x[0] for x in st.sets], [x[1] for x in st.sets], st.starts,
                                  channels_last=(layout == "hwc"), mode=mode)
     wall, wall_local = time_overlapped(ow, K, W, D, prewarm_s)
+    last = ow.outs[(K - 1) % ow.n]                 # what the last of the K timed steps wrote (batch K-1 of the stream)
     # serial reference of every ring slot, AFTER the timed region: the overlapped outputs must equal it bit for bit
     same = True
     for r in range(min(ow.n, K)):                  # the slots the K timed steps wrote
@@ -556,6 +561,7 @@ def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn
                 del ref
             paired = {"ms_per_step": round(wall_p / K * 1e3, 4), "images_per_s": round(B * K / wall_p, 1),
                       "bit_identical_to_serial": same_p, "wall": wall_p, "wall_local": wall_p_local}
+            last_p = pw.outs[(K - 1) % pw.n]
         del pw
     w_e, _ = time_steps(st, K, W, D)
     sb = step_bytes(B, S, esize)
@@ -565,6 +571,7 @@ def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn
                    else "as branches of one HIP graph"))
     if paired and "wall" in paired and paired["wall"] < wall and paired["bit_identical_to_serial"]:
         wall, wall_local, same = paired["wall"], paired["wall_local"], paired["bit_identical_to_serial"]
+        last = last_p
         path_txt = ("pipeline.PairedStepWarp: resample(2p), (2p+1) + maps(2p+2), (2p+3) + reduce(2p+4), (2p+5) as block ranges of ONE "
                     "launch per TWO batches (attwarp_warp_step_fused_slots)")
     if paired:
@@ -583,7 +590,7 @@ def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn
                      "roofline": roofline_of(st),
                      "path": "three eager launches per step with HIP events between them (the events are where the "
                              "per-kernel durations come from)"}}
-    return res, wall, wall_local, st, ow
+    return res, wall, wall_local, st, ow, last
 
 
 def traffic_note(roof):
@@ -722,6 +729,7 @@ def leg_main_batched(dev, torch, pipeline, K):
         torch.cuda.empty_cache()
     ref = [c for c in out["cases"] if (c["B"], c["S"]) == (32, 336)][0]
     out["value"] = ref["stream"]["images_per_s"]
+    out["ms_per_step"] = ref["stream"]["ms_per_step"]
     out["value_is"] = ("the stream step at the reference's own scale: B=32, 336 -> 500, one batch per launch "
                        "(`two_batches_per_launch` beside it)")
     out["step_over_copy"] = (ref.get("calibration") or {}).get("step_over_copy")
@@ -867,7 +875,9 @@ def leg_main_batched_ragged(dev, torch, pipeline, K, D=None, rank=0, world=1, gr
             out[k] = ref[k]
         out["value_is"] = "whole-job rate of the ragged stream step at the reference's batch size (B=32 per rank), one launch per batch"
     else:
-        out["value"] = max(ref["stream"]["eager"]["images_per_s"], ref["stream"]["graphs"]["images_per_s"])
+        best = max(("eager", "graphs"), key=lambda m: ref["stream"][m]["images_per_s"])
+        out["value"] = ref["stream"][best]["images_per_s"]
+        out["ms_per_step"] = ref["stream"][best]["ms_per_batch"]        # one step = one batch through the one-launch chain
         out["value_is"] = "the ragged stream step at the reference's batch size (B=32), one launch per batch"
     out["step_over_copy"] = (ref.get("calibration") or {}).get("step_over_copy")
     if rank == 0 and full:
@@ -1110,7 +1120,7 @@ def leg_small(wl, dev, args, K, D, torch, pipeline, attn_dtype=None, rank=0, wor
     """BASELINE configs[1] / configs[3]'s per-rank batch as a secondary line of the 1024 run (graph-replayed stream step).
     In a process group EVERY rank runs it on its own batches (weak scaling: `value` is the whole job's rate)."""
     B2, S2, cfg2 = WORKLOADS[wl]
-    res, wall, wall_local, st, ow = small_workload(B2, S2, dev, 99 + rank, args.mode, args.layout, K, args.warmup, D, torch,
+    res, wall, wall_local, st, ow, _ = small_workload(B2, S2, dev, 99 + rank, args.mode, args.layout, K, args.warmup, D, torch,
                                                    pipeline, attn_dtype=attn_dtype)
     what = (f"batch-{B2} {S2}x{S2} per GPU (BASELINE configs[{cfg2}]), mode={args.mode}" if attn_dtype is None else
             f"batch-{B2} {S2}x{S2} per GPU, attention rows float16 (images float32), mode={args.mode}")
@@ -1159,6 +1169,63 @@ LEGS = {
 }
 
 
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files together
+DUMP_WHOLE_BYTES = 48 << 20    # an output up to this size is written whole, a larger one as a fixed seeded sample
+
+
+def dump_sample(out, seed: int = 20240) -> dict:
+    """Host copies (float32) of what a caller of the timed path receives, the warped batch `out` ([B, ...], any dtype):
+    the whole batch when it is small, else `warped_images` (up to 3 whole images at seeded positions, their batch indices in
+    `warped_image_index`) and `warped_sample` (up to 2^21 single values at seeded flat positions of the whole batch,
+    those positions in `warped_sample_index`, float64 = exact).  The positions depend on the shape and the seed only."""
+    import numpy as np
+    import torch
+    if out.numel() * 4 <= DUMP_WHOLE_BYTES:
+        return {"warped": out.float().cpu().numpy()}
+    rng = np.random.default_rng(seed)
+    B = out.shape[0]
+    n_img = max(1, min(3, B, (DUMP_WHOLE_BYTES - (24 << 20)) // (out[0].numel() * 4)))
+    img_idx = np.sort(rng.choice(B, n_img, replace=False))
+    flat_idx = np.unique(rng.integers(0, out.numel(), 1 << 21, dtype=np.int64))
+    flat = out.reshape(-1)[torch.from_numpy(flat_idx).to(out.device)]
+    d = {"warped_images": out[torch.from_numpy(img_idx).to(out.device)].float().cpu().numpy(),
+         "warped_image_index": img_idx.astype(np.float64),
+         "warped_sample": flat.float().cpu().numpy(), "warped_sample_index": flat_idx.astype(np.float64)}
+    assert sum(a.nbytes for a in d.values()) <= DUMP_LIMIT_BYTES
+    return d
+
+
+def write_dump(dirname: str, arrays: dict) -> list:
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(arrays)
+
+
+LINE_TEXT_MAX = 32             # nested descriptive text in the result line: this many characters, then "..."
+LINE_TEXT_WHOLE = ("error", "unavailable")     # a failure's reason is never shortened
+
+
+def result_line(result: dict) -> str:
+    """The ONE JSON line, compact.  Top-level fields, the main line's `config` and every `error` / `unavailable` reason are
+    printed whole; any other string nested in a roofline block or secondary leg (the `path`, `workload`, `kernel`, `note`,
+    `traffic_source` descriptions) longer than LINE_TEXT_MAX is cut there and marked with "...".  Every key, number and flag
+    stays.  With every leg attached and that text in full the line was 25.6 KB (profiles/round6_bench.json), and the
+    benchmark record of that run holds no parsed result (BENCH_r06.json, "parsed": null), while the 18 KB line before it
+    was read (BENCH_r05.json); shortened, the line is about 17 KB."""
+    def cut(o):
+        if isinstance(o, dict):
+            return {k: (v if k in LINE_TEXT_WHOLE else cut(v)) for k, v in o.items()}
+        if isinstance(o, list):
+            return [cut(v) for v in o]
+        if isinstance(o, str) and len(o) > LINE_TEXT_MAX:
+            return o[:LINE_TEXT_MAX - 3] + "..."
+        return o
+    return json.dumps({k: (v if k == "config" or not isinstance(v, (dict, list)) else cut(v)) for k, v in result.items()},
+                      separators=(",", ":"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1188,7 +1255,12 @@ def main():
                          "exactly the code of a rank of N -- RCCL init, weight broadcast, all_gather / all_reduce / barrier")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: rendezvous, weight broadcast, counters and the JSON line only (CPU tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the main line's last timed step computed (the warped batch: whole if "
+                         "it fits, else a fixed seeded sample) as DIR/<name>.npy, float32, at most 64 MiB in all (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.list_legs:
         for name, doc in LEGS.items():
             print(f"{name:28s} {doc}")
@@ -1202,6 +1274,11 @@ def main():
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))          # parent: no torch import, no GPU call
 
+    if args.dump_outputs and (args.dry_run or args.workload in ("config5", "main_batched", "main_batched_ragged")):
+        raise SystemExit("bench.py: --dump-outputs covers the GPU runs of the 1024 / 336 / 336x256 workloads")
+    # exactly --steps timed steps: the chain streams need an even number of at least their pipeline depth (10)
+    if args.workload in ("main_batched", "main_batched_ragged") and (args.steps < 10 or args.steps % 2):
+        raise SystemExit(f"bench.py: --workload {args.workload} times a stream of batches: --steps must be even and >= 10")
     if args.workload in ("config5", "main_batched", "main_batched_ragged"):
         import torch
         from attwarp_amd import _lib, pipeline
@@ -1210,15 +1287,17 @@ def main():
         _lib.load()
         dev = torch.device("cuda", args.device or 0)
         torch.cuda.set_device(dev)
-        res = leg_config5(dev, torch, pipeline, 64, max(args.steps // 4, 3)) if args.workload == "config5" else \
-            leg_main_batched(dev, torch, pipeline, max(args.steps, 48)) if args.workload == "main_batched" else \
-            leg_main_batched_ragged(dev, torch, pipeline, max(args.steps, 48))
+        res = leg_config5(dev, torch, pipeline, 64, args.steps) if args.workload == "config5" else \
+            leg_main_batched(dev, torch, pipeline, args.steps) if args.workload == "main_batched" else \
+            leg_main_batched_ragged(dev, torch, pipeline, args.steps)
         print(json.dumps(dict({"metric": "warped images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
                                "dtype": "u8" if args.workload.startswith("main_batched") else "f16 tower / f32 MarginalNet / u8 warp",
                                "config": {"workload": res["workload"]}}, **res)), flush=True)
         return
     B, S, cfg_idx = WORKLOADS[args.workload]
+    if args.workload != "1024" and args.steps < 2:
+        raise SystemExit("bench.py: the 336 workloads time a stream of batches: --steps must be >= 2")
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     rank_env = int(os.environ.get("RANK", "0"))
     if world_env != args.gpus:
@@ -1315,7 +1394,7 @@ def main():
     if small:
         # configs[1] / configs[3]: the step is ~0.09-0.25 ms, so the timed loop is a HIP-graph replay with no host call
         # per kernel (the eager three-launch line with HIP events is attached as "also_eager")
-        res, wall, wall_local, step, ow = small_workload(B, S, dev, 1234 + rank, args.mode, args.layout, args.steps,
+        res, wall, wall_local, step, ow, last = small_workload(B, S, dev, 1234 + rank, args.mode, args.layout, args.steps,
                                                          args.warmup, D, torch, pipeline,
                                                          prewarm_s=PREWARM_SMALL_S if args.prewarm < 0 else args.prewarm / 10.0)
         roof = res["eager"]["roofline"]
@@ -1324,7 +1403,8 @@ def main():
                  "step_frac_of_hbm_peak": res["step_frac_of_hbm_peak"], "bit_identical_to_serial": res["bit_identical_to_serial"],
                  "path": res["path"], "also_eager": res["eager"]}
         nrot = res["rotating_batches"]
-        del ow
+        dumped = dump_sample(last) if args.dump_outputs and rank == 0 else None
+        del ow, last
     else:
         step = Step(B, S, dev, seed=1234 + rank, mode=args.mode, layout=args.layout)
         # optional extra pre-conditioning (--prewarm; none by default: the contract's W warm-up steps are the warm-up)
@@ -1349,6 +1429,7 @@ def main():
         for _ in range(5):
             main_step()
         wall, wall_local = time_steps(main_step, args.steps, args.warmup, D)
+        dumped = dump_sample(main_step.ow.out) if args.dump_outputs and rank == 0 else None
         roof = roofline_of(main_step, load_pmc_traffic(args.workload, args.mode))
         if roof["traffic"] is not None:                 # a committed constant, not a counter read in this run
             roof["traffic_source"] = pmc_traffic_source(args.workload, args.mode)
@@ -1387,6 +1468,9 @@ def main():
         "roofline": roof,
     }
     result.update(extra)
+    if dumped is not None:
+        result["dump_outputs"] = write_dump(args.dump_outputs, dumped)
+        del dumped
     if small:
         st_ms = step.stage_ms()
         result["stages_ms"] = {"attn_reduce_step_kernel": round(st_ms[0], 4), "axis_maps_from_steps_kernel": round(st_ms[1], 4),
@@ -1477,7 +1561,7 @@ def main():
                 torch.cuda.empty_cache()
 
     if rank == 0:
-        print(json.dumps(result), flush=True)
+        print(result_line(result), flush=True)
     D.shutdown()
 
 

@@ -25,7 +25,7 @@ def _worker(rank, world, port, q):
                       LOCAL_RANK=str(rank))
     from attwarp_amd import dist as d
     from attwarp_amd.model import MarginalNet
-    r, w, _ = d.init(backend="gloo")
+    r, w, _ = d.init(backend="gloo", use_gpu=False)   # CPU ranks: on a GPU box rank 1 must not select device 1
     assert (r, w) == (rank, world)
     torch.manual_seed(100 + rank)               # different random init per rank
     net = MarginalNet(8, 12, hidden=4)
@@ -48,10 +48,16 @@ def test_two_rank_gloo():
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
-    res = sorted(q.get(timeout=90) for _ in range(world))
-    for p in procs:
-        p.join(30)
-        assert p.exitcode == 0
+    try:
+        res = sorted(q.get(timeout=90) for _ in range(world))
+        for p in procs:
+            p.join(30)
+            assert p.exitcode == 0
+    finally:                                       # a rank that failed must not leave its peer waiting in the rendezvous
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join(10)
     (r0, nb0, c0, s0, g0, m0), (r1, nb1, c1, s1, g1, m1) = res
     assert nb0 == nb1 > 0
     assert c0 == c1                                # rank 1 received rank 0's weights exactly

@@ -444,6 +444,55 @@ def test_bench_lists_and_validates_legs():
     assert r.returncode != 0 and "unknown leg" in (r.stderr + r.stdout)
 
 
+def test_bench_refuses_step_counts_it_cannot_time_exactly():
+    """--steps is the number of timed steps: a count a workload cannot run exactly is refused before any GPU work."""
+    import subprocess
+    import sys
+    for args, msg in ((["--steps", "0"], ">= 1"), (["--workload", "336", "--steps", "1"], ">= 2"),
+                      (["--workload", "main_batched", "--steps", "9"], "even and >= 10"),
+                      (["--workload", "main_batched_ragged", "--steps", "8"], "even and >= 10")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and msg in r.stderr, (args, r.stderr[-500:])
+
+
+def test_bench_dump_sample_is_seeded_exact_and_bounded(tmp_path):
+    """bench.py --dump-outputs: a small output is written whole; a large one as whole images at seeded batch positions plus
+    single values at seeded flat positions -- the same positions every run, each value the output's own, 64 MiB at most."""
+    import bench
+    small = torch.rand(2, 40, 40, 3)
+    d = bench.dump_sample(small)
+    assert list(d) == ["warped"] and np.array_equal(d["warped"], small.numpy())
+    out = torch.rand(8, 1024, 1024, 3)                             # 100 MB: sampled
+    a, b = bench.dump_sample(out), bench.dump_sample(out.clone())
+    assert sorted(a) == ["warped_image_index", "warped_images", "warped_sample", "warped_sample_index"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)             # seeded: identical positions and values
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    idx = a["warped_sample_index"].astype(np.int64)
+    assert np.array_equal(idx.astype(np.float64), a["warped_sample_index"]) and len(np.unique(idx)) == len(idx) > 1 << 20
+    assert np.array_equal(a["warped_sample"], out.numpy().reshape(-1)[idx])
+    assert np.array_equal(a["warped_images"], out.numpy()[a["warped_image_index"].astype(np.int64)])
+    names = bench.write_dump(str(tmp_path / "dump"), a)
+    assert names == sorted(a)
+    assert all(np.array_equal(np.load(tmp_path / "dump" / f"{n}.npy"), a[n]) for n in names)
+
+
+def test_bench_result_line_keeps_failures_and_config_whole():
+    """The result line shortens nested descriptions only: every key stays, a leg's error / unavailable reason and the main
+    line's config are printed whole, a shortened text is marked."""
+    import json
+    import bench
+    res = {"value": 1.5, "path": "p" * 300, "config": {"workload": "w" * 200, "mode": "cv2"},
+           "also_u8": {"error": "RuntimeError: " + "y" * 250},
+           "also": {"one_launch_per_two_batches": {"unavailable": "u" * 150}, "cases": [{"kernel": "k" * 90, "ms": 0.25}]}}
+    d = json.loads(bench.result_line(res))
+    assert d["value"] == 1.5 and d["path"] == res["path"] and d["config"] == res["config"]
+    assert d["also_u8"] == res["also_u8"] and d["also"]["one_launch_per_two_batches"] == res["also"]["one_launch_per_two_batches"]
+    k = d["also"]["cases"][0]["kernel"]
+    assert k.endswith("...") and len(k) == bench.LINE_TEXT_MAX and res["also"]["cases"][0]["kernel"].startswith(k[:-3])
+    assert d["also"]["cases"][0]["ms"] == 0.25
+
+
 def test_pair_slots_views():
     """pipeline.pair_slots (two batches of a stream as one): views, not copies; adjacency and parity are checked."""
     from attwarp_amd import pipeline

@@ -50,9 +50,9 @@ keep trace_full
 # 3. the other workloads as main lines; the line a rank of N prints (one-rank RCCL group, dist legs on "every" rank)
 python3 $ROOT/bench.py --workload 336 --no-cpu-baseline > $OUT/bench_336.json 2> $OUT/bench_336.err
 python3 $ROOT/bench.py --workload 336x256 --no-cpu-baseline > $OUT/bench_336x256.json 2> $OUT/bench_336x256.err
-python3 $ROOT/bench.py --workload main_batched > $OUT/bench_main_batched.json 2> $OUT/bench_main_batched.err
-python3 $ROOT/bench.py --workload main_batched_ragged > $OUT/bench_main_batched_ragged.json 2> $OUT/bench_main_batched_ragged.err
-python3 $ROOT/bench.py --workload config5 > $OUT/bench_config5.json 2> $OUT/bench_config5.err
+python3 $ROOT/bench.py --workload main_batched --steps 48 > $OUT/bench_main_batched.json 2> $OUT/bench_main_batched.err
+python3 $ROOT/bench.py --workload main_batched_ragged --steps 48 > $OUT/bench_main_batched_ragged.json 2> $OUT/bench_main_batched_ragged.err
+python3 $ROOT/bench.py --workload config5 --steps 5 > $OUT/bench_config5.json 2> $OUT/bench_config5.err
 python3 $ROOT/bench.py --gpus 1 --force-dist --no-cpu-baseline --legs 336,main_batched_ragged > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err
 
 # 4. per-stage tools
