@@ -95,9 +95,13 @@ SIGNATURES = {
     "attwarp_resize_linear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "attwarp_remap_bilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_int, c_void_p]),
+    "attwarp_overlay_workspace_bytes": (c_size_t, [c_int]),
+    "attwarp_heatmap_overlay": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p]),
 }
 
 PIL_LANCZOS, PIL_BICUBIC = 0, 1
+OVERLAY_BLEND_MASK, OVERLAY_SAVE_WARPED = 0, 1       # attwarp_heatmap_overlay styles
+RGB, BGR = 0, 1
 
 
 class RaggedImage(ctypes.Structure):

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib, _tables
@@ -454,12 +455,20 @@ def upsample_mask_lanczos(mask: torch.Tensor, size_wh) -> torch.Tensor:
     return out
 
 
+def blend_alpha(grayscale) -> float:
+    """blend_mask's overlay weight, reference :264: ``grayscale`` if it is an int / float in (0, 1], else 0.5 (both drivers
+    pass 0: main_batched.py:185, main.py:334)."""
+    return grayscale if (isinstance(grayscale, (int, float)) and 0 < grayscale <= 1) else 0.5
+
+
 def blend_mask(image_path_or_pil_image, mask: torch.Tensor, enhance_coe, kernel_size, interpolate_method, grayscale):
-    """Reference :240-270.  Returns ``(image, mask_pil)``: the mask branch (revise -> uint8 ->
-    LANCZOS to the image size, mode "L") is computed on the GPU; the first element is the input
-    image itself -- the Jet heat-map overlay of the reference is visualisation only and is out of
-    scope (component 3)."""
+    """Reference :240-270.  Returns ``(merged, mask_pil)``, both computed on the GPU: the mask branch (revise -> uint8 ->
+    LANCZOS to the image size, mode "L") and the merged RGB image -- the Jet heat-map overlay of the reference
+    (cv2.normalize(NORM_MINMAX) of the mask, COLORMAP_JET, addWeighted(image, 1 - alpha, heat, alpha, 0) with alpha =
+    :func:`blend_alpha` (grayscale); ``pipeline.heatmap_overlay`` style "blend_mask", arithmetic in DESIGN.md "Heat-map
+    overlay")."""
     from PIL import Image
+    from . import pipeline
     if isinstance(image_path_or_pil_image, str):
         image = Image.open(image_path_or_pil_image)
     elif isinstance(image_path_or_pil_image, Image.Image):
@@ -473,4 +482,6 @@ def blend_mask(image_path_or_pil_image, mask: torch.Tensor, enhance_coe, kernel_
         mask = mask.to(_lib.default_device())
     rev = revise_mask(mask.float().reshape(24, 24), kernel_size=kernel_size, enhance_coe=enhance_coe)
     up = upsample_mask_lanczos(rev.unsqueeze(0), image.size)[0]
-    return image, Image.fromarray(up.cpu().numpy(), mode="L")
+    rgb = torch.from_numpy(np.array(image.convert("RGB"))).to(up.device)
+    merged = pipeline.heatmap_overlay([rgb], [up], blend_alpha(grayscale), "blend_mask")[0]
+    return Image.fromarray(merged.cpu().numpy()), Image.fromarray(up.cpu().numpy(), mode="L")

@@ -168,8 +168,9 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
     """Reference :405-506.  Warps ``image_path`` (path or PIL image) by ``att_map`` and writes the
     result to ``output_path``; returns True, or prints the error and returns False (the reference
     swallows every exception, :504-506).  Images are handled in BGR order like the reference;
-    files are written with Pillow.  The overlay / visualisation strip outputs are out of scope
-    (visualisation only): ``masked_overlay_save_path`` and ``vis_path`` are accepted and ignored.
+    files are written with Pillow.  ``masked_overlay_save_path``: the Jet heat-map overlay of :455-475, computed on the GPU
+    before the warp (:func:`masked_overlay`; an error there returns False before the warp, as in the reference).  The
+    visualisation strip is out of scope: ``vis_path`` is accepted and ignored.
     ``mode`` (not in the reference) selects the resample arithmetic: "cv2" (default, what the reference's
     ``cv2.remap`` call computes) or "exact"."""
     try:
@@ -185,6 +186,9 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
         if original_image_save_path:
             _imwrite(original_image_save_path, image)
         att_map = _coerce_att_map(att_map, width, height)
+        if masked_overlay_save_path:
+            overlay = masked_overlay(image, att_map, attention_alpha)
+            Image.fromarray(overlay).save(masked_overlay_save_path)
         image_for_warping = resize_image_to_match_attmap(image, att_map, mode)
         if image_for_warping is None:
             raise ValueError("Failed to resize image to match attention map dimensions for warping")
@@ -198,6 +202,38 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
     except Exception as e:  # noqa: BLE001 - reference behaviour
         print(f"Error during processing: {e}", file=sys.stderr)
         return False
+
+
+def masked_overlay(image_bgr: np.ndarray, att_map: np.ndarray, attention_alpha: float = 0.5) -> np.ndarray:
+    """save_warped_image's masked overlay (reference :455-475) on the GPU -> RGB uint8 [H,W,3] (the reference writes the same
+    pixels from BGR with cv2.imwrite).  ``cv2.resize(att_map, (W, H), INTER_LINEAR)`` to the image's size (a copy when the
+    sizes match, as in both drivers; otherwise attwarp_resize_linear for uint8 / float32 maps), min-max in the map's dtype
+    with EPSILON, COLORMAP_JET, ``addWeighted(heat, alpha, image, 1 - alpha, 0)``.  Maps: uint8, float32, float64; other
+    integer maps of at most 32 bits are taken as float64 (exact) at the image's size.  Raises for a non-uint8 image (OpenCV's
+    addWeighted refuses mixed depths) and for maps it does not handle."""
+    from . import pipeline
+    img = np.asarray(image_bgr)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise TypeError(f"masked overlay: addWeighted needs a uint8 [H,W,3] image like the heat map (got {img.dtype} {img.shape})")
+    a = np.asarray(att_map)
+    H, W = img.shape[:2]
+    if a.dtype not in (np.uint8, np.float32, np.float64):
+        if a.dtype.kind in "iu" and a.dtype.itemsize <= 4 and a.shape == (H, W):
+            a = a.astype(np.float64)
+        else:
+            raise TypeError(f"masked overlay: attention maps of dtype {a.dtype} are not supported")
+    dev = _lib.default_device()
+    m = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    if a.shape != (H, W):
+        if a.dtype == np.float64:
+            raise TypeError("masked overlay: resizing a float64 attention map is not supported (uint8 / float32 are)")
+        r = torch.empty((H, W), device=dev, dtype=m.dtype)
+        with torch.cuda.device(dev):
+            call("attwarp_resize_linear", ptr(m), ptr(r), _lib.dtype_id(m), 1, 1, a.shape[0], a.shape[1], H, W, stream_ptr(dev))
+        m = r
+    t = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+    out = pipeline.heatmap_overlay([t], [m], attention_alpha, "save_warped", order="bgr", out_order="rgb")[0]
+    return out.cpu().numpy()
 
 
 def _cvt_rgb2bgr(image: np.ndarray) -> np.ndarray:

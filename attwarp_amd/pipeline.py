@@ -908,6 +908,13 @@ class MaskChainStream:
         intermediates of parity j & 1 (all built by the constructor)."""
         return self._rb[(j % self.n, j & 1)]
 
+    def ragged_batch(self, j: int) -> RaggedBatch:
+        """The RaggedBatch that carries batch j of a ``pattern="ragged"`` stream (e.g. for :func:`heatmap_overlay_ragged`:
+        its masks are valid from step j - 3 on and overwritten by step j - 1, see there)."""
+        if self.pattern != "ragged":
+            raise ValueError("MaskChainStream.ragged_batch: the stream does not run the ragged pattern")
+        return self._ragged(j)
+
     def _ragged_launch(self, **stages):
         ragged_chain_launch(**{s: self._ragged(j) for s, j in stages.items()}, enhance_coe=self.enhance_coe, kernel_size=self.kernel_size,
                             transform=self.transform, exp_scale=self.exp_scale, exp_divisor=self.exp_divisor,
@@ -1387,6 +1394,120 @@ class RaggedMaskChainStream:
             for s in stages:
                 self._stages(**{s: r[j % n]})
         self.k += self.DEPTH
+
+
+# ---- Jet heat-map overlays (blend_mask's merged image, save_warped_image's masked overlay) ----
+_OVERLAY_IMAGE_DTYPE = np.dtype([("image", "<u8"), ("map", "<u8"), ("out", "<u8"), ("H", "<i4"), ("W", "<i4")])  # attwarp_overlay_image
+OVERLAY_STYLES = {"blend_mask": _lib.OVERLAY_BLEND_MASK, "save_warped": _lib.OVERLAY_SAVE_WARPED}
+_CHANNEL_ORDERS = {"rgb": _lib.RGB, "bgr": _lib.BGR}
+
+
+def _overlay_launch(images, maps, outs, alpha, style, order, out_order):
+    """ONE attwarp_heatmap_overlay call: lists of uint8 [H,W,3] images, [H,W] maps (one dtype: uint8 / float32 / float64)
+    and uint8 [H,W,3] outputs, any sizes.  The records go to the device through the pooled pinned staging buffer."""
+    if style not in OVERLAY_STYLES:
+        raise ValueError(f"heatmap_overlay: style must be one of {sorted(OVERLAY_STYLES)}")
+    out_order = order if out_order is None else out_order
+    if order not in _CHANNEL_ORDERS or out_order not in _CHANNEL_ORDERS:
+        raise ValueError("heatmap_overlay: channel orders are 'rgb' or 'bgr'")
+    B = len(images)
+    if B == 0 or len(maps) != B or len(outs) != B:
+        raise ValueError("heatmap_overlay: one map and one output per image, at least one image")
+    dev = require_gpu(*images, *maps, *outs)
+    mdt = maps[0].dtype
+    if mdt not in (torch.uint8, torch.float32, torch.float64) or any(m.dtype != mdt for m in maps):
+        raise TypeError("heatmap_overlay: the maps of one call share one dtype: uint8, float32 or float64")
+    for im, m, o in zip(images, maps, outs):
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
+            raise TypeError("heatmap_overlay: images must be contiguous uint8 [H,W,3] tensors")
+        if m.dim() != 2 or tuple(m.shape) != tuple(im.shape[:2]) or not m.is_contiguous():
+            raise ValueError(f"heatmap_overlay: map {tuple(m.shape)} must be a contiguous [H,W] tensor of the image's size "
+                             f"{tuple(im.shape[:2])}")
+        if o.dtype != torch.uint8 or o.shape != im.shape or not o.is_contiguous():
+            raise ValueError("heatmap_overlay: outputs must be contiguous uint8 tensors of the images' shapes")
+    rec = np.zeros(B, dtype=_OVERLAY_IMAGE_DTYPE)
+    rec["image"] = [t.data_ptr() for t in images]
+    rec["map"] = [t.data_ptr() for t in maps]
+    rec["out"] = [t.data_ptr() for t in outs]
+    rec["H"] = [int(t.shape[0]) for t in images]
+    rec["W"] = [int(t.shape[1]) for t in images]
+    _overlay_call(rec, dev, _lib.dtype_id(maps[0]), style, alpha, order, out_order)
+
+
+def _overlay_call(rec: np.ndarray, dev: torch.device, map_dtype: int, style, alpha, order, out_order):
+    """attwarp_heatmap_overlay on host records (attwarp_overlay_image); the device copy goes through the pooled pinned
+    staging buffer, the workspace comes from the caching allocator (both stream ordered)."""
+    B = int(rec.shape[0])
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rec_dev = torch.empty(rec.nbytes, device=dev, dtype=torch.uint8)
+        _upload(rec.view(np.uint8), rec_dev)
+        ws = torch.empty(lib.attwarp_overlay_workspace_bytes(B), device=dev, dtype=torch.uint8)
+        call("attwarp_heatmap_overlay", rec.ctypes.data, ptr(rec_dev), B, map_dtype, OVERLAY_STYLES[style],
+             float(alpha), _CHANNEL_ORDERS[order], _CHANNEL_ORDERS[out_order], ptr(ws), stream_ptr(dev))
+
+
+def heatmap_overlay(images, maps, alpha: float = 0.5, style: str = "blend_mask", order: str = "rgb",
+                    out_order: Optional[str] = None):
+    """Jet heat-map overlays of a batch in one call (two launches), on the GPU:
+
+        style="blend_mask"   blend_mask's merged image (llava.py:254-269): cv2.normalize(NORM_MINMAX) of the uint8 mask,
+                             COLORMAP_JET, addWeighted(image, 1 - alpha, heat, alpha, 0)      -- uint8 maps only
+        style="save_warped"  save_warped_image's masked overlay (new_method.py:455-475): min-max in the map's dtype with
+                             EPSILON = 1e-9, COLORMAP_JET, addWeighted(heat, alpha, image, 1 - alpha, 0)
+
+    ``images``: uint8 [B,H,W,3] with ``maps`` [B,H,W] (dense batch -> dense [B,H,W,3]), or lists of uint8 [H_i,W_i,3] and
+    [H_i,W_i] GPU tensors of any sizes (-> list of [H_i,W_i,3]).  Maps: uint8, float32 or float64, one dtype per call, at the
+    images' sizes.  ``order`` / ``out_order``: channel order of the images / of the result ("rgb" or "bgr"; the result
+    defaults to the images' order).  Arithmetic: DESIGN.md "Heat-map overlay" (bit-exact with the numpy restatement of
+    tests/overlay_ref.py; OpenCV itself is pinned where it is installed, exact at alpha = 0.5)."""
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4 or not isinstance(maps, torch.Tensor) or maps.dim() != 3 or maps.shape[0] != images.shape[0]:
+            raise ValueError("heatmap_overlay: a dense batch is images [B,H,W,3] with maps [B,H,W]")
+        images, maps = images.contiguous(), maps.contiguous()
+        out = torch.empty_like(images)
+        _overlay_launch([images[b] for b in range(images.shape[0])], [maps[b] for b in range(maps.shape[0])],
+                        [out[b] for b in range(out.shape[0])], alpha, style, order, out_order)
+        return out
+    images, maps = list(images), list(maps)
+    outs = [torch.empty_like(im) for im in images]
+    _overlay_launch(images, maps, outs, alpha, style, order, out_order)
+    return outs
+
+
+def heatmap_overlay_ragged(rb: RaggedBatch, alpha: float = 0.5, order: str = "rgb", out_order: Optional[str] = None):
+    """blend_mask's merged images for every image of a ragged batch, from the up-sampled masks the chain already holds
+    (``rb.mota``, read in place through :meth:`RaggedBatch.mota_of`: no copy) -> ``(packed, views)``: one uint8 buffer
+    and the [H_i,W_i,3] view of each image in it (images at 16-byte aligned offsets).  ``alpha``: blend_mask's alpha (0.5
+    for both reference drivers).  ``order``: channel order of ``rb.images`` (upload_images gives RGB).
+
+    When to enqueue it: after the launch that ran the batch's L stage (mask up-sampling) and before anything overwrites
+    ``rb.mota``.  A batch of :func:`warp_from_masks_ragged` (``return_batch=True``) or one returned by
+    :meth:`RaggedMaskChainStream.push` / ``flush`` owns its masks: any time later on the same stream.  The batches of one
+    parity of ``MaskChainStream(pattern="ragged")`` SHARE one mask buffer (``RaggedBatch(share=...)``): batch j's mask is
+    written by step j - 3 (L(j)) and overwritten by step j - 1 (L(j + 2)), so its overlay goes right after step j - 3 or
+    step j - 2, with batch j's images already in their ring slot."""
+    B = rb.B
+    if rb.C != 3:
+        raise ValueError("heatmap_overlay_ragged: three-channel images only")
+    out_order = order if out_order is None else out_order
+    if order not in _CHANNEL_ORDERS or out_order not in _CHANNEL_ORDERS:
+        raise ValueError("heatmap_overlay_ragged: channel orders are 'rgb' or 'bgr'")
+    # the records straight from the batch's table (mota_off of every image): no per-image tensor on the launch path
+    tab = (_RaggedImageDev * B).from_address(rb.table_host.ctypes.data + int(rb.header.off_images))
+    rec = np.zeros(B, dtype=_OVERLAY_IMAGE_DTYPE)
+    rec["image"] = [im.data_ptr() for im in rb.images]
+    rec["H"] = [int(t.H) for t in tab]
+    rec["W"] = [int(t.W) for t in tab]
+    npx = rec["H"].astype(np.int64) * rec["W"]
+    rec["map"] = rb.mota.data_ptr() + np.array([int(t.mota_off) for t in tab], dtype=np.int64)
+    sizes = (3 * npx + 15) // 16 * 16                    # outputs at 16-byte aligned offsets
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    packed = torch.empty(int(sizes.sum()), device=rb._dev, dtype=torch.uint8)
+    rec["out"] = packed.data_ptr() + offs
+    _overlay_call(rec, rb._dev, _lib.U8, "blend_mask", alpha, order, out_order)
+    views = [packed[o:o + 3 * n].view(h, w, 3) for o, n, h, w in zip(offs.tolist(), npx.tolist(), rec["H"].tolist(), rec["W"].tolist())]
+    return packed, views
 
 
 def capture_steps(step_fn, k0: int, n: int, dev: torch.device):

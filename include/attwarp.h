@@ -387,6 +387,37 @@ ATTWARP_API int attwarp_axis_maps_from_attention(const void* att, int dtype, int
 ATTWARP_API int attwarp_resize_linear(const void* src, void* dst, int dtype, int B, int C, int H, int W, int H_out,
                           int W_out, void* stream);
 
+/* ---- Jet heat-map overlays of the reference's drivers, a whole batch of differently sized images per call:
+ *   ATTWARP_OVERLAY_BLEND_MASK  blend_mask's merged image, AGW/attention_extraction/llava.py:254-269:
+ *       idx = (uint8) fmaf(m, a, b) with cv2.normalize(NORM_MINMAX)'s a = (float)(255 / (max - min)) (0 when max == min),
+ *       b = -(float)(min * a) -- uint8 masks only; out = addWeighted(image, 1 - alpha, jet[idx], alpha, 0)
+ *   ATTWARP_OVERLAY_SAVE_WARPED save_warped_image's masked overlay, AGW/new_method.py:455-475:
+ *       idx = (uint8)((m - min) / (max - min) * 255) in the map's dtype (uint8 differences divided in float64; float32
+ *       stays float32), 0 everywhere unless max > min + 1e-9 (a NaN anywhere fails that test); out = addWeighted(jet[idx],
+ *       alpha, image, 1 - alpha, 0)
+ * jet = cv2.COLORMAP_JET, restated from OpenCV's colormap.cpp (csrc/overlay_jet.hpp, tools/gen_jet_table.py).  addWeighted
+ * on 8-bit data: cvRound(fmaf(s1, w1, fmaf(s2, w2, 0))) with the weights alpha and 1 - alpha (double) rounded to float32 --
+ * OpenCV's AVX2 vector path; exact in any evaluation order at alpha = 0.5, OpenCV's scalar tail may differ by 1 elsewhere.
+ * Parity with OpenCV itself is unpinned here (OpenCV is absent; tests/test_overlay_vs_opencv.py pins it where present).
+ *   images     : HOST array of B records (validated here; the grid is sized from it)
+ *   images_dev : a DEVICE copy of the same B records, 8-byte aligned (the kernels read it)
+ *   map_dtype  : U8, F32 or F64 (one dtype for the batch); in_order / out_order: ATTWARP_RGB or ATTWARP_BGR
+ *   ws         : attwarp_overlay_workspace_bytes(B) bytes, 16-byte aligned (per-block min / max partials)
+ * Images: [H,W,3] uint8 interleaved at any byte address (683 x 3-byte rows, images packed back to back); maps: [H,W] dense,
+ * uint8 at any byte address, float32 / float64 element aligned; out: [H,W,3] uint8 at any byte address (may equal image).
+ * Two launches (per-block min / max, then colour + blend), each over the whole batch.  H * W <= 2^30, B <= 65535. */
+enum { ATTWARP_OVERLAY_BLEND_MASK = 0, ATTWARP_OVERLAY_SAVE_WARPED = 1 };
+enum { ATTWARP_RGB = 0, ATTWARP_BGR = 1 };
+typedef struct attwarp_overlay_image {
+  const uint8_t* image;                            /* device: [H,W,3] uint8 */
+  const void* map;                                 /* device: [H,W] of map_dtype (e.g. a view into a ragged batch's packed masks) */
+  uint8_t* out;                                    /* device: [H,W,3] uint8 */
+  int32_t H, W;
+} attwarp_overlay_image;
+ATTWARP_API size_t attwarp_overlay_workspace_bytes(int B);
+ATTWARP_API int attwarp_heatmap_overlay(const attwarp_overlay_image* images, const attwarp_overlay_image* images_dev, int B,
+                            int map_dtype, int style, double alpha, int in_order, int out_order, void* ws, void* stream);
+
 /* ---- A12 / A13 tail: cv2.remap(INTER_LINEAR, BORDER_REPLICATE) with separable maps,
  * AGW/new_method.py:268-271, MN/checkpoint_utils.py:195-198.
  * src [B,H,W,C] (HWC) or [B,C,H,W] (CHW), dtype F32, U8 or F64 -> dst same layout with (H_out,W_out).
