@@ -537,8 +537,7 @@ extern "C" int attwarp_mask_upsample_lanczos(const float* mask_f32, const uint8_
     const int max_chunks = (out_h + 63) / 64;
     if (nchunks > max_chunks) nchunks = max_chunks;
     if (nchunks < 1) nchunks = 1;
-    int rows_per_chunk = (int)((out_h + nchunks - 1) / nchunks);
-    if (const int v = tune(TUNE_LANCZOS_ROWS); v >= 1) rows_per_chunk = v < out_h ? v : out_h;
+    const int rows_per_chunk = (int)((out_h + nchunks - 1) / nchunks);
     nchunks = (out_h + rows_per_chunk - 1) / rows_per_chunk;
     const size_t lds = (size_t)((h * w + 3) & ~3) + (size_t)h * NT;
     LanczosStripArgs la{mask_f32, mask_u8, h, w, out_h, out_w, bounds_x, kk_x, ksize_x, bounds_y, kk_y, (int)nchunks, rows_per_chunk, out};
@@ -553,8 +552,7 @@ extern "C" int attwarp_mask_upsample_lanczos(const float* mask_f32, const uint8_
     if (need_h && need_v && !two_kernel && (long long)h * w <= 4096 && out_w % 4 == 0 && ksize_x <= 8 &&
         ksize_y <= 32 &&
         lds <= 48 * 1024 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0) {
-      int R = out_h >= 448 ? 64 : 32;   // measured: 24->336 R=32 27 us (two-kernel form 34), 24->1024 B=256 R=64 258 us (287)
-      if (const int v = tune(TUNE_LANCZOS_ROWS); v >= 1 && v <= (ksize_y == 8 ? 1024 : 64)) R = v;
+      const int R = out_h >= 448 ? 64 : 32;   // measured: 24->336 R=32 27 us (two-kernel form 34), 24->1024 B=256 R=64 258 us (287)
       hipLaunchKernelGGL((lanczos_fused_kernel<8>), dim3((out_h + R - 1) / R, B), dim3(NT), lds, st, mask_f32, mask_u8,
                          h, w, out_h, out_w, bounds_x, kk_x, ksize_x, bounds_y, kk_y, ksize_y, R, out);
       return check_launch("lanczos_fused_kernel");

@@ -56,7 +56,6 @@ static_assert(sizeof(attwarp_ragged_header) % 8 == 0, "table layout");
 
 struct RaggedStepArgs {
   ChainOrder ord;
-  int prio;
   int g, ks, C, Ho, Wo;
   float coe;
   // V(k+4)
@@ -85,7 +84,6 @@ __device__ __forceinline__ int ragged_step_block(const RaggedStepArgs& a, uint8_
   int j;
   const int kind = chain_order_decode(a.ord, blockIdx.x, j);
   if (kind == CHAIN_F) {
-    if (a.prio) __builtin_amdgcn_s_setprio(3);
     const int b = (int)a.f_order[j >> 1];           // largest images first: their chains are the longest blocks of the launch
     const RaggedImage& im = a.f_img[b];
     const RaggedPlan& Pw = a.f_plans[im.plan_w];
@@ -99,7 +97,6 @@ __device__ __forceinline__ int ragged_step_block(const RaggedStepArgs& a, uint8_
 #endif
     attention_maps_finalize_block(Pw, Ph, fa, j & 1, reinterpret_cast<double*>(pool));
   } else if (kind == CHAIN_V) {
-    if (a.prio) __builtin_amdgcn_s_setprio(3);
     float* x = reinterpret_cast<float*>(pool);
     double* red = reinterpret_cast<double*>(pool + 32 * 32 * sizeof(float));
     float* fred = reinterpret_cast<float*>(red + RAGGED_NT / WAVE);
@@ -524,10 +521,7 @@ extern "C" int attwarp_mask_chain_ragged(const void* r_host, const void* r_dev, 
   }
   a.g = any ? any->g : g;
   if (any) { a.C = any->C; a.Ho = any->H_out; a.Wo = any->W_out; }
-  a.prio = tune(TUNE_STEP_PRIO) >= 0 ? tune(TUNE_STEP_PRIO) : 0;
-  a.ord.nF8 = (a.ord.nF + 7) / 8;
-  a.ord.nV8 = (a.ord.nV + 7) / 8;
-  build_interleave(a.ord, tune(TUNE_CHAIN_SEQ) >= 0 ? tune(TUNE_CHAIN_SEQ) : CHAIN_ORDER_DEFAULT);
+  build_interleave(a.ord);
 #ifdef ATTWARP_TUNING
   a.trace = trace_buffer();
 #endif

@@ -11,10 +11,10 @@
 // Launched one behind the other (what pipeline.warp_from_masks does for one batch) every boundary costs a drain and a
 // dispatch ramp and nothing overlaps although the stages are bound by different units; as branches of a HIP graph the
 // hardware overlaps them but pays five launches and a fork / join per step.  Here they are block ranges of one grid:
-// the F and V blocks first (the longest dependent chains start at once), then P, L and R blocks INTERLEAVED in
-// proportion to their counts -- the VALU-bound and the HBM-bound blocks are resident on every CU side by side for the
+// the F and V blocks first (the longest dependent chains start at once), then all of P, then L and R blocks INTERLEAVED
+// in proportion to their counts -- the VALU-bound and the HBM-bound blocks are resident on every CU side by side for the
 // whole launch instead of one kind after the other -- in units of 8 consecutive blocks, so that block % 8 keeps naming
-// the XCD for the resample's XCD-aware order.  Every body is the stand-alone kernel's body (same arithmetic, bit for
+// the XCD for the resample's XCD-aware order (chain_order.hpp).  Every body is the stand-alone kernel's body (same arithmetic, bit for
 // bit); LDS is one pool sized for the largest of them.
 #include "common.hpp"
 #include "chain_order.hpp"
@@ -28,12 +28,10 @@
 namespace attwarp {
 
 constexpr int CHAIN_NT = 256;
-constexpr int CHAIN_PRIO_DEFAULT = 0;
-constexpr int CHAIN_WAVES_DEFAULT = 8;      // waves per SIMD the register allocation leaves room for
+constexpr int CHAIN_WAVES = 8;              // waves per SIMD the register allocation leaves room for
 
 struct ChainStepArgs {
   int B;
-  int prio;                                 // 1: the F and V blocks (one lane's dependent chain each) raise their wave priority
   ChainOrder ord;                           // which block does what (chain_order.hpp)
   // V: masks [B,g,g] -> rev_out
   const float* masks; int g, ks; float coe; float* rev_out;
@@ -48,7 +46,6 @@ struct ChainStepArgs {
   u8k::Params rp;
 #ifdef ATTWARP_TUNING
   unsigned long long* trace;                // block timeline (common.hpp: trace_buffer), null = off
-  int bound;                                // TUNE_BOUND (upper-bound experiments, garbage output)
 #endif
 };
 
@@ -60,22 +57,15 @@ __device__ __forceinline__ int chain_step_block(const ChainStepArgs& a, const Pa
   int j;
   const int kind = chain_order_decode(a.ord, blockIdx.x, j);
   if (kind == CHAIN_F) {
-    if (a.prio) __builtin_amdgcn_s_setprio(3);
     attention_maps_finalize_block(Pw, Ph, maps_finalize_image(a.fa, j >> 1, Pw.nleaves), j & 1, reinterpret_cast<double*>(pool));
   } else if (kind == CHAIN_V) {
-    if (a.prio) __builtin_amdgcn_s_setprio(3);
     float* x = reinterpret_cast<float*>(pool);
     double* red = reinterpret_cast<double*>(pool + 32 * 32 * sizeof(float));
     float* fred = reinterpret_cast<float*>(red + CHAIN_NT / WAVE);
     mask_postproc_block(a.masks, a.g, a.ks, a.coe, a.rev_out, j, x, red, fred);
   } else if (kind == CHAIN_P) {
     const int b = j / Pw.nleaves, leaf = j - b * Pw.nleaves;
-#ifdef ATTWARP_TUNING
-    const int bsrc = (a.bound & 2) ? (b & 1) : b;     // bound: every image reads the mask of image 0 / 1 (L2 hits)
-#else
-    const int bsrc = b;
-#endif
-    const uint8_t* att = a.mota_in + (size_t)bsrc * a.fa.h * a.fa.w;
+    const uint8_t* att = a.mota_in + (size_t)b * a.fa.h * a.fa.w;
     double* col = a.col_out + (size_t)b * a.fa.w;
     double* ls = a.ls_out + (size_t)b * a.fa.h * Pw.nleaves;
     // (block uniform: the transform of new_method.py:134-179 the caller selected; identity is what both drivers pass)
@@ -90,12 +80,7 @@ __device__ __forceinline__ int chain_step_block(const ChainStepArgs& a, const Pa
                                             Pw.nleaves, leaf, col, ls, pool);
   } else if (kind == CHAIN_L) {
     const int b = j / a.l_bx, bx = j - b * a.l_bx;
-#ifdef ATTWARP_TUNING
-    const int bdst = (a.bound & 2) ? (b & 1) : b;     // bound: every image's mask is written over image 0 / 1
-#else
-    const int bdst = b;
-#endif
-    lanczos_strip_block<8>(a.la, bx, (size_t)b * a.la.h * a.la.w, a.la.out + (size_t)bdst * a.la.out_h * a.la.out_w, pool);
+    lanczos_strip_block<8>(a.la, bx, (size_t)b * a.la.h * a.la.w, a.la.out + (size_t)b * a.la.out_h * a.la.out_w, pool);
   } else if (kind == CHAIN_R) {
     u8k::remap_rows_u8i_block<KI, KD, true, PD>(a.rp, j, reinterpret_cast<float*>(pool));
   }
@@ -119,16 +104,10 @@ template <int KI, int KD>
 static int launch_chain_kikd(const ChainStepArgs& a, const PairwisePlan& Pw, const PairwisePlan& Ph, size_t lds, unsigned grid,
                              hipStream_t st) {
   constexpr int PD = KI <= 2 ? 4 : 2;       // as launch_u8i_depth (remap_u8.hip)
-#ifdef ATTWARP_TUNING
-  if (tune(TUNE_CHAIN_WAVES) == 14 - CHAIN_WAVES_DEFAULT) {     // the other of {6, 8}
-    hipLaunchKernelGGL((mask_chain_step_kernel<KI, KD, PD, 14 - CHAIN_WAVES_DEFAULT, false>), dim3(grid), dim3(CHAIN_NT), lds, st, a, Pw, Ph);
-    return check_launch("mask_chain_step_kernel");
-  }
-#endif
   if (a.p_lut || a.p_square || a.fa.apply_inverse)
-    hipLaunchKernelGGL((mask_chain_step_kernel<KI, KD, PD, CHAIN_WAVES_DEFAULT, true>), dim3(grid), dim3(CHAIN_NT), lds, st, a, Pw, Ph);
+    hipLaunchKernelGGL((mask_chain_step_kernel<KI, KD, PD, CHAIN_WAVES, true>), dim3(grid), dim3(CHAIN_NT), lds, st, a, Pw, Ph);
   else
-    hipLaunchKernelGGL((mask_chain_step_kernel<KI, KD, PD, CHAIN_WAVES_DEFAULT, false>), dim3(grid), dim3(CHAIN_NT), lds, st, a, Pw, Ph);
+    hipLaunchKernelGGL((mask_chain_step_kernel<KI, KD, PD, CHAIN_WAVES, false>), dim3(grid), dim3(CHAIN_NT), lds, st, a, Pw, Ph);
   return check_launch("mask_chain_step_kernel");
 }
 template <int KI>
@@ -182,7 +161,6 @@ extern "C" int attwarp_mask_chain_step(const uint8_t* images, uint8_t* out, int 
   if (!u8i_params(a.rp, images, out, ATTWARP_HWC, B, C, H, W, H_out, W_out, map_x, map_y) || a.rp.unaligned)
     return fail(ATTWARP_E_UNSUPPORTED, "mask_chain_step: this image shape / alignment does not run on the integer cv2 resample");
   a.B = B;
-  a.prio = tune(TUNE_STEP_PRIO) >= 0 ? tune(TUNE_STEP_PRIO) : CHAIN_PRIO_DEFAULT;
   a.masks = masks; a.g = g; a.ks = kernel_size; a.coe = enhance_coe; a.rev_out = rev_out;
   {   // L geometry: as attwarp_mask_upsample_lanczos
     const int nstrips = (W + MASK_NT - 1) / MASK_NT;
@@ -204,17 +182,13 @@ extern "C" int attwarp_mask_chain_step(const uint8_t* images, uint8_t* out, int 
   a.fa = MapsFinalizeArgs{col_in, col_in + (size_t)B * W, H, W, W_out, H_out, transform, exp_scale, exp_divisor, apply_inverse ? 1 : 0,
                           map_x_next, map_y_next, pw_depth(Pw)};
   a.ord.nF = 2 * B; a.ord.nV = B;
-  a.ord.nF8 = (2 * B + 7) / 8;
-  a.ord.nV8 = (B + 7) / 8;
   a.ord.nP = Pw.nleaves * B;
   a.ord.nL = a.l_bx * B;
   a.ord.nR = a.rp.nblocks;
-  build_interleave(a.ord, tune(TUNE_CHAIN_SEQ) >= 0 ? tune(TUNE_CHAIN_SEQ) : CHAIN_ORDER_DEFAULT);
+  build_interleave(a.ord);
 #ifdef ATTWARP_TUNING
   a.trace = trace_buffer();
   a.fa.trace = a.trace;
-  a.bound = tune(TUNE_BOUND) > 0 ? tune(TUNE_BOUND) : 0;
-  a.fa.bound = a.bound;
 #endif
   const long long octs = chain_order_octets(a.ord);
   if (octs * 8 > 2147483647LL) return fail(ATTWARP_E_UNSUPPORTED, "mask_chain_step: grid too large");

@@ -168,26 +168,14 @@ enum TuneKey {
   TUNE_REMAP_CHW_SPLIT,     // 0 / 1: planar images plane by plane
   TUNE_REMAP_TILED,         // 0: rows wider than the LDS row take the generic kernel
   TUNE_REMAP_TILE_KO,       // 8 / 12
-  TUNE_REMAP_ALT,           // 0: every row block sweeps top-down
   TUNE_REMAP_NOSWZ,         // 0: contiguous range of row blocks per XCD, 1: plain order, g >= 2: XCDs interleaved in groups of g
-  TUNE_REMAP_LDSPAD,        // extra dynamic LDS bytes (occupancy experiments)
   TUNE_REMAP_NT,            // 0 / 1: nontemporal loads for block-private source rows
   TUNE_LANCZOS_VARIANT,     // 1: two-kernel form, 2: row-block fused kernel (default: column-strip kernel when it applies)
-  TUNE_LANCZOS_ROWS,
   TUNE_CLIP_VARIANT,        // 1: generic kernels
   TUNE_PROFILES_VARIANT,    // 1: generic (non byte-packed) profile kernel for uint8 attention
   TUNE_REMAP_CPW,           // row blocks per workgroup of the float32 staged resample (strided inside the image)
-  TUNE_REMAP_SKEW,          // XCD x starts x * skew blocks into its contiguous range of row blocks
   TUNE_ATTN_HU,             // heads in flight per wave of the four-tokens-per-lane attention reduce (1, 2, 4, 8)
   TUNE_U8_AHEAD,            // integer uint8 resample: output rows whose source rows are requested ahead (1, 2, 4)
-  TUNE_CHAIN_SEQ,           // block order of the one-launch mask-chain step: 0 interleaved, 1 P / L / R ranges, 2 P first then L / R interleaved, 3 P + R then L, 4 P + L then R, 10..99 P spread over that per cent of L / R
-  TUNE_CHAIN_WAVES,         // 6 / 8: waves per SIMD its register allocation leaves room for
-  TUNE_REMAP_CV2_DOUBLE,    // cv2 rows of 8-12 KB: 0 = one [top | bottom] LDS buffer and two barriers per row instead of two buffers and one (48 KB)
-  TUNE_STEP_PRIO,           // one-launch steps: 1 = the latency-chain blocks (maps / finalize / revise) run at raised wave priority
-  TUNE_BOUND,               // UPPER-BOUND experiments (outputs are garbage; docs/experiments.md round 5): bit 0 float32 cv2 resample stages
-                            //   only the top row in a 3-row LDS pool (what a three-slot ring could save at most); bit 1 chain step: the
-                            //   up-sampled masks of all images alias two images (L's stores and P's loads stay in L2: what fusing L
-                            //   into P could save at most); bit 2 finalize body without its np.cumsum chain; bit 3 finalize body returns at once
   TUNE_TRACE_LO,            // block timeline of the one-launch steps (tools/gantt.py): bits 0..23 and 24..47 of the address of a
   TUNE_TRACE_HI,            //   device buffer of TRACE_WORDS x uint64 per block (layout below)
   TUNE_COUNT

@@ -373,15 +373,12 @@ struct MapsFinalizeArgs {
   int depth_w;               // pw_depth of the row plan (the per-thread stack of the leaf-combine program)
 #ifdef ATTWARP_TUNING
   unsigned long long* trace; // block timeline (common.hpp), null = off
-  int bound;                 // TUNE_BOUND bits 2 / 3 (upper-bound experiments, garbage output)
 #endif
 };
 #ifdef ATTWARP_TUNING
 #define ATTWARP_F_MARK(i_) trace_mark(a.trace, i_);
-#define ATTWARP_F_BOUND(bit_) (a.bound & (bit_))
 #else
 #define ATTWARP_F_MARK(i_)
-#define ATTWARP_F_BOUND(bit_) false
 #endif
 // LDS of one workgroup: knots (max(h,w) + 2 doubles) | red | per-thread stacks | leaf sums | the two plans
 inline size_t maps_finalize_lds_bytes(int h, int w, const PairwisePlan& Pw, const PairwisePlan& Ph) {
@@ -394,7 +391,6 @@ template <typename SrcPlan>
 __device__ __forceinline__ void attention_maps_finalize_block(const SrcPlan& Pw_arg, const SrcPlan& Ph_arg,
                                                               const MapsFinalizeArgs& a, int axis, double* lds) {
   constexpr int NT = PROF_NT;
-  if (ATTWARP_F_BOUND(8)) return;
   const double* __restrict__ col = a.col; const double* __restrict__ ls = a.ls;
   const int h = a.h, w = a.w, new_w = a.new_w, new_h = a.new_h, transform = a.transform, apply_inverse = a.apply_inverse;
   const double exp_scale = a.exp_scale, exp_divisor = a.exp_divisor;
@@ -469,7 +465,7 @@ __device__ __forceinline__ void attention_maps_finalize_block(const SrcPlan& Pw_
     total = (total != total) ? total : (total > 1e-9 ? total : 1e-9);   // python max(total, EPS): NaN stays
     __syncthreads();
   }
-  if (threadIdx.x == 0 && !ATTWARP_F_BOUND(4)) {
+  if (threadIdx.x == 0) {
     // np.cumsum: sequential running sum (adds only; the division below is elementwise and parallel).  32 values are
     // requested from LDS before the first add of a batch: one LDS round trip per 32 dependent adds instead of per 4
     // (the lane spent most of its time waiting: 1024 knots 16 us -> 5 us).
@@ -503,7 +499,6 @@ __device__ __forceinline__ void attention_maps_finalize_block(const SrcPlan& Pw_
   ATTWARP_F_MARK(7)
 }
 #undef ATTWARP_F_MARK
-#undef ATTWARP_F_BOUND
 // the arguments of image b of a dense batch
 __device__ __forceinline__ MapsFinalizeArgs maps_finalize_image(MapsFinalizeArgs a, int b, int nleaves_w) {
   a.col += (size_t)b * a.w;

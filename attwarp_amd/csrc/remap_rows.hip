@@ -110,7 +110,7 @@ int launch_remap_rows(const float* src, float* dst, int layout, int B, int C, in
     group = 0;
   } else if (!tiled && row_bytes < 5 * 1024 && (long long)B * ((Ho + R - 1) / R) >= 8192) {
     group = 2;        // large batches of small images (336x336x3, B=256): 0.1434 -> 0.1414 ms alone, 0.215 -> 0.209 ms
-  }                   // inside the fused step (tools/attic/ab_fused336.py); B=64 is fastest with the contiguous order
+  }                   // inside the fused step; B=64 is fastest with the contiguous order
   if (const int v = tune(TUNE_REMAP_ROWS); v >= 1 && v <= RMAX) R = v;
   if (R > Ho) R = Ho;
   p.R = R;
@@ -124,12 +124,7 @@ int launch_remap_rows(const float* src, float* dst, int layout, int B, int C, in
   p.nblocks = (int)nb;
   p.no_swz = tune(TUNE_REMAP_NOSWZ) >= 0 ? tune(TUNE_REMAP_NOSWZ) : group;
 #ifdef ATTWARP_TUNING
-  p.alt_dir = tune(TUNE_REMAP_ALT) != 0;
-  p.skew = tune(TUNE_REMAP_SKEW) >= 0 ? tune(TUNE_REMAP_SKEW) : 0;
-  p.lds_pad = 0;
-  if (const int v = tune(TUNE_REMAP_LDSPAD); v >= 0 && v <= 90000) p.lds_pad = v;
   p.trace = trace_buffer();
-  p.bound = tune(TUNE_BOUND) > 0 ? (tune(TUNE_BOUND) & 1) : 0;
   p.nt_loads = tune(TUNE_REMAP_NT) > 0 ? tune(TUNE_REMAP_NT) : 0;      // bit 0: nontemporal loads of block-private rows, bit 1: nontemporal stores
 #endif
   *handled = true;
@@ -188,7 +183,6 @@ int step_fused_impl(const SlotPtrs* sl, int nslots, int layout, int B, int C, in
   StepExtra ex;
   memset(&ex, 0, sizeof(ex));
   ex.nslots = nslots;
-  ex.prio = tune(TUNE_STEP_PRIO) >= 0 ? tune(TUNE_STEP_PRIO) : 0;
 #ifdef ATTWARP_TUNING
   ex.trace = trace_buffer();
 #endif

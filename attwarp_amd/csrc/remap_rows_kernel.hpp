@@ -137,14 +137,10 @@ struct RowsParams {
   int nblocks;       // total
   int no_swz;        // block order: 0 = contiguous range per XCD, 1 = plain, g >= 2 = XCDs interleaved in groups of g blocks
 #ifdef ATTWARP_TUNING  // measurement knobs of the tuning flavour (attwarp_debug_set); constants in the product library
-  int alt_dir;       // 1: odd row blocks sweep bottom-up so both neighbours meet at the shared halo rows
-  int lds_pad;       // extra dynamic LDS bytes (occupancy experiments)
-  int skew;          // block order 0: XCD x starts x * skew blocks into its contiguous range
   int nt_loads;      // bit 0: nontemporal loads of the source rows, bit 1: nontemporal stores
-  int bound;         // TUNE_BOUND bit 0: stage only the top row, 3-row LDS pool (upper bound of a three-slot ring; garbage output)
   unsigned long long* trace;   // block timeline (common.hpp: trace_buffer): phase cycles of this block go to words 7..10
 #else
-  static constexpr int alt_dir = 1, lds_pad = 0, skew = 0, nt_loads = 0, bound = 0;
+  static constexpr int nt_loads = 0;
 #endif
   int map_div;       // maps belong to image b / map_div (planes of a planar image dispatched as images)
   int ntiles;        // TILED: column tiles per row (each KO*NT output elements), else 1
@@ -190,7 +186,7 @@ __device__ __forceinline__ void remap_rows_block(const RowsParams& p, const int 
   constexpr int ROWF = KI * NT * 4;                     // floats per staged source row (padded to whole waves)
   constexpr int BUF = CV ? 2 * ROWF : ROWF;             // floats per LDS buffer (CV2: top row, then bottom row)
   float* rows0 = smem + RMAX;                           // two buffers, addressed with immediates
-  float* rows1 = SINGLE ? rows0 : rows0 + ((CV && p.bound) ? ROWF : BUF);
+  float* rows1 = SINGLE ? rows0 : rows0 + BUF;
   const int tid = threadIdx.x;
 
   // XCD-aware block order: blocks bid, bid+8, ... share an XCD (and its L2); hand each XCD a
@@ -199,10 +195,8 @@ __device__ __forceinline__ void remap_rows_block(const RowsParams& p, const int 
   {
     const int n = p.nblocks, q = n >> 3, r = n & 7, xcd = bid & 7, idx = bid >> 3;
     if (p.no_swz == 0) {
-      const int len = (xcd < r) ? q + 1 : q, start = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-      int j = idx + xcd * p.skew;                          // XCD x starts x * skew blocks into its range (wraps)
-      if (p.skew) j %= len;
-      bid = start + j;
+      const int start = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+      bid = start + idx;
     }
     else if (p.no_swz >= 2) {
       // XCD x owns every 8th GROUP of g consecutive row blocks (g = no_swz): neighbouring blocks of a group still share
@@ -340,7 +334,7 @@ __device__ __forceinline__ void remap_rows_block(const RowsParams& p, const int 
         if (CV) *reinterpret_cast<rows_v4f_a4*>(at_ + ROWF) = XC[k];                                \
       } else {                                                                                      \
         rowv_[tid + NT * k] = v_;                                                                   \
-        if (CV && !p.bound) rowv_[ROWF / 4 + tid + NT * k] = XC[k];                                 \
+        if (CV) rowv_[ROWF / 4 + tid + NT * k] = XC[k];                                             \
       }                                                                                             \
     }                                                                                               \
   } while (0)
@@ -410,7 +404,7 @@ __device__ __forceinline__ void remap_rows_block(const RowsParams& p, const int 
     for (int i = tid; i < ntot; i += NT) {
       const int rbi = i / p.R, j = i - rbi * p.R, rb = rbl + rbi * p.wpi;
       const int y0 = rb * p.R, nr = min(p.R, p.Ho - y0);
-      const int y = y0 + ((p.alt_dir && (rb & 1)) ? nr - 1 - j : j);
+      const int y = y0 + ((rb & 1) ? nr - 1 - j : j);   // odd row blocks sweep bottom-up: neighbours meet at the shared halo rows
       s_yy[i] = y;
       s_my[i] = p.my[(long long)bm * p.Ho + y];
     }
@@ -569,7 +563,6 @@ struct StepExtra {
   AttnStepArgsAny attn;    // nA reduce blocks per slot (0: none); its dtype is also the dtype of maps.steps
   int nM8, nA, nA8, nR8;   // blocks / 8 of the ranges: ceil(nslots * 2B / 8), ceil(nslots * nA / 8), ceil(nR / 8) PER SLOT
   int nslots;              // 1 or 2
-  int prio;                // 1: the map blocks (one lane's dependent chain each) raise their wave priority
   StepSlot2 s1;            // slot 1 (slot 0 = the pointers of RowsParams / maps / attn)
 #ifdef ATTWARP_TUNING
   unsigned long long* trace;   // block timeline (common.hpp: trace_buffer), null = off
@@ -594,7 +587,6 @@ __device__ __forceinline__ int warp_step_block(const RowsParams& p, const StepEx
     const int jj = blk - (s1 ? 2 * ex.maps.B : 0);
     StepsMapsArgs m = ex.maps;
     if (s1) { m.steps = ex.s1.steps; m.map_x = ex.s1.map_x; m.map_y = ex.s1.map_y; }
-    if (ex.prio) __builtin_amdgcn_s_setprio(3);
     double* sd = reinterpret_cast<double*>(smem);
     if (m.step_dtype == ATTWARP_F32) axis_maps_from_steps_block<8, float>(m, jj >> 1, jj & 1, sd, s_tmp, s_pm);
     else if (m.step_dtype == ATTWARP_F16) axis_maps_from_steps_block<8, __half>(m, jj >> 1, jj & 1, sd, s_tmp, s_pm);
@@ -648,8 +640,7 @@ constexpr size_t rows_lds_bytes(int KI, int NT) {
 // compile side by side instead of two twice as long.
 template <int NT, int KI, int KO, int MODE, bool SINGLE, bool FUSED>
 static int launch_rows_t(const RowsParams& p, hipStream_t st, const StepExtra* ex) {
-  size_t lds = rows_lds_bytes<MODE, SINGLE>(KI, NT) + (size_t)p.lds_pad;
-  if (MODE == ATTWARP_CV2 && !SINGLE && p.bound) lds = (size_t)(RMAX + 3 * KI * NT * 4) * sizeof(float);
+  size_t lds = rows_lds_bytes<MODE, SINGLE>(KI, NT);
   const dim3 t(NT);
   if constexpr (FUSED) {   // warp_step_kernel: map blocks, then the reduce blocks, then the resample blocks
     if (ex->nA > 0) lds = std::max(lds, attn_v4_lds_bytes<3>());
@@ -703,7 +694,7 @@ static int launch_rows_mode(const RowsParams& p, int tile_ko, hipStream_t st, co
 #ifdef ATTWARP_TUNING
     if (tile_ko == 4) {     // round-5 experiment: 1024-float column tiles (4 KB, like the rows of a planar batch)
       if constexpr (KIMIN <= 2 && 2 <= KIMAX) {
-        const size_t lds = rows_lds_bytes<MODE, SINGLE>(2, NT) + (size_t)p.lds_pad;
+        const size_t lds = rows_lds_bytes<MODE, SINGLE>(2, NT);
         hipLaunchKernelGGL((remap_rows_kernel<NT, 2, 4, true, false, true, MODE, SINGLE>), dim3(p.nblocks), dim3(NT), lds, st, p);
         return check_launch("remap_rows_kernel");
       }
@@ -712,7 +703,7 @@ static int launch_rows_mode(const RowsParams& p, int tile_ko, hipStream_t st, co
 #endif
     if (tile_ko == 8) {
       if constexpr (KIMIN <= 3 && 3 <= KIMAX) {
-        const size_t lds = rows_lds_bytes<MODE, SINGLE>(3, NT) + (size_t)p.lds_pad;
+        const size_t lds = rows_lds_bytes<MODE, SINGLE>(3, NT);
         hipLaunchKernelGGL((remap_rows_kernel<NT, 3, 8, true, false, true, MODE, SINGLE>), dim3(p.nblocks), dim3(NT), lds, st, p);
         return check_launch("remap_rows_kernel");
       }
@@ -720,7 +711,7 @@ static int launch_rows_mode(const RowsParams& p, int tile_ko, hipStream_t st, co
     }
     if (tile_ko == 12) {
       if constexpr (KIMIN <= 4 && 4 <= KIMAX) {
-        const size_t lds = rows_lds_bytes<MODE, SINGLE>(4, NT) + (size_t)p.lds_pad;
+        const size_t lds = rows_lds_bytes<MODE, SINGLE>(4, NT);
         hipLaunchKernelGGL((remap_rows_kernel<NT, 4, 12, true, false, true, MODE, SINGLE>), dim3(p.nblocks), dim3(NT), lds, st, p);
         return check_launch("remap_rows_kernel");
       }

@@ -9,7 +9,7 @@ namespace attwarp {
 
 template <int KI, int KO, int MODE, bool SINGLE>
 static int launch_ua_t(const RowsParams& p, hipStream_t st) {
-  const size_t lds = rows_lds_bytes<MODE, SINGLE>(KI, NT_BIG) + (size_t)p.lds_pad;
+  const size_t lds = rows_lds_bytes<MODE, SINGLE>(KI, NT_BIG);
   hipLaunchKernelGGL((remap_rows_kernel<NT_BIG, KI, KO, true, false, false, MODE, SINGLE, true>), dim3(p.nblocks), dim3(NT_BIG), lds, st, p);
   return check_launch("remap_rows_kernel (unaligned rows)");
 }
