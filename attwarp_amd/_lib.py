@@ -97,9 +97,31 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_int, c_void_p]),
     "attwarp_overlay_workspace_bytes": (c_size_t, [c_int]),
     "attwarp_heatmap_overlay": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p]),
+    # the MarginalNet training losses (losses.hip, profiles.hip)
+    "attwarp_cdf_downsample": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "attwarp_build_axis_cdf_targets": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_l1_cdf_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_l1_cdf_loss_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_sym_kl": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_sym_kl_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_recon_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "attwarp_recon_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
+    "attwarp_scale_shift": (c_int, [c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p]),
+    "attwarp_entropy": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_entropy_backward": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "attwarp_pdf_l1_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_pdf_l1_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_trainer_attention_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p]),
 }
 
 PIL_LANCZOS, PIL_BICUBIC = 0, 1
+RECON_MSE, RECON_L1 = 0, 1                          # attwarp_recon_loss kinds
+TT_IDENTITY, TT_SQRT, TT_NONE = 0, 1, 2              # attwarp_trainer_attention_targets modes
 OVERLAY_BLEND_MASK, OVERLAY_SAVE_WARPED = 0, 1       # attwarp_heatmap_overlay styles
 RGB, BGR = 0, 1
 

@@ -10,6 +10,7 @@
 #include "common.hpp"
 #include "interp.hpp"
 #include "profiles_blocks.hpp"
+#include "loss_blocks.hpp"
 
 namespace attwarp {
 
@@ -259,10 +260,34 @@ __global__ __launch_bounds__(NT) void marginals_finalize_kernel(const double* __
   for (int k = threadIdx.x; k < n; k += blockDim.x) dst[k] = (float)smem_d[k] / tot;
 }
 
-// ---- A5: adaptive average pool.  grid = (oh, B), one band of rows per block ---------------
-__global__ __launch_bounds__(NT) void adaptive_pool_kernel(const float* __restrict__ A, int H, int W, int oh, int ow,
-                                                           int sanitize, int vec_ok, float* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) double colsum[];   // W doubles
+// The element transforms of the pool.  PoolPlain: none.  The trainer's per-sample transform of the full-resolution map
+// (MN/trainer.py:188-193), A+.sqrt() * m + A+ * (1 - m) with A+ = A.clamp_min(0) (NaN propagates), in float32 with the
+// multiplications by 1 dropped (exact): PoolSqrt (m = 1) is sqrt(A+) + A+ * 0, PoolIdentity (m = 0) is A+ + sqrt(A+) * 0,
+// where sqrt(A+) * 0 and A+ * 0 are the same value (0 of A+'s sign; NaN for NaN and +inf).  So finite cells give exactly
+// sqrt(A+) or A+, NaN and +inf give NaN in either branch (inf * 0), -inf gives 0 -- the trainer's bits, no sqrt on the
+// identity branch.
+struct PoolPlain {
+  __device__ __forceinline__ double operator()(float v) const { return (double)v; }
+};
+struct PoolSqrt {
+  __device__ __forceinline__ double operator()(float v) const {
+    const float a = clamp_pos_f32(v);
+    return (double)fadd(sqrtf(a), fmul(a, 0.0f));
+  }
+};
+struct PoolIdentity {
+  __device__ __forceinline__ double operator()(float v) const {
+    const float a = clamp_pos_f32(v);
+    return (double)fadd(a, fmul(a, 0.0f));
+  }
+};
+
+// ---- A5: adaptive average pool of one band of output rows -------------------------------------------------------
+// `in` transforms every element as it is loaded; the summation order does not depend on it, so the pooled map of a
+// transform equals the plain kernel's on the transformed map bit for bit.
+template <typename XF>
+__device__ __forceinline__ void adaptive_pool_band(const float* __restrict__ A, int H, int W, int oh, int ow, int sanitize,
+                                                   int vec_ok, float* __restrict__ out, double* colsum, XF in) {
   const int b = blockIdx.y, i = blockIdx.x;
   const int ys = (int)(((long long)i * H) / oh);
   const int ye = (int)((((long long)(i + 1)) * H + oh - 1) / oh);
@@ -281,11 +306,11 @@ __global__ __launch_bounds__(NT) void adaptive_pool_kernel(const float* __restri
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = __builtin_nontemporal_load(src + (size_t)(r + k) * rs);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { a0 += (double)v[k].x; a1 += (double)v[k].y; a2 += (double)v[k].z; a3 += (double)v[k].w; }
+        for (int k = 0; k < 8; ++k) { a0 += in(v[k].x); a1 += in(v[k].y); a2 += in(v[k].z); a3 += in(v[k].w); }
       }
       for (; r < ye; ++r) {
         const v4f v = __builtin_nontemporal_load(src + (size_t)r * rs);
-        a0 += (double)v.x; a1 += (double)v.y; a2 += (double)v.z; a3 += (double)v.w;
+        a0 += in(v.x); a1 += in(v.y); a2 += in(v.z); a3 += in(v.w);
       }
       colsum[4 * q] = a0; colsum[4 * q + 1] = a1; colsum[4 * q + 2] = a2; colsum[4 * q + 3] = a3;
     }
@@ -298,9 +323,9 @@ __global__ __launch_bounds__(NT) void adaptive_pool_kernel(const float* __restri
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = base[(size_t)(r + q) * W + x];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc += (double)v[q];
+      for (int q = 0; q < 4; ++q) acc += in(v[q]);
     }
-    for (; r < ye; ++r) acc += (double)base[(size_t)r * W + x];
+    for (; r < ye; ++r) acc += in(base[(size_t)r * W + x]);
     colsum[x] = acc;
   }
   __syncthreads();
@@ -315,6 +340,22 @@ __global__ __launch_bounds__(NT) void adaptive_pool_kernel(const float* __restri
     if (sanitize) v = (v > 0.0f && v <= 3.402823466e38f) ? v : 0.0f;
     out[((size_t)b * oh + i) * ow + j] = v;
   }
+}
+
+// grid = (oh, B), one band of rows per block
+__global__ __launch_bounds__(NT) void adaptive_pool_kernel(const float* __restrict__ A, int H, int W, int oh, int ow,
+                                                           int sanitize, int vec_ok, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double colsum[];   // W doubles
+  adaptive_pool_band(A, H, W, oh, ow, sanitize, vec_ok, out, colsum, PoolPlain{});
+}
+// the trainer's transform first, branch by the sample's mode (uniform per block)
+__global__ __launch_bounds__(NT) void trainer_pool_kernel(const float* __restrict__ A, const int32_t* __restrict__ modes,
+                                                          int H, int W, int oh, int ow, int vec_ok, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double colsum[];   // W doubles
+  if (modes[blockIdx.y] == ATTWARP_TT_SQRT)
+    adaptive_pool_band(A, H, W, oh, ow, 1, vec_ok, out, colsum, PoolSqrt{});
+  else
+    adaptive_pool_band(A, H, W, oh, ow, 1, vec_ok, out, colsum, PoolIdentity{});
 }
 
 // ---- A13 finalize: body attention_maps_finalize_block (profiles_blocks.hpp).  grid = (B, 2) ----
@@ -333,6 +374,54 @@ static int launch_profiles(const void* A, int B, int H, int W, XF xf, const Pair
   hipLaunchKernelGGL((profiles_kernel<T, XF>), dim3(P.nleaves, B), dim3(NT), 0, st, (const T*)A, H, W, xf, P, col, ls,
                      vec_ok);
   return check_launch("profiles_kernel");
+}
+
+// ---- L: build_axis_cdf_targets finalise (MN/losses.py:50-67): the axis sums of the nan_to_num'd map -> normalise ->
+// adaptive_avg_pool1d to L -> cumsum -> renormalise -> last entry 1 (pooled_cdf_block).  grid = (B, 2) ---------------
+__global__ __launch_bounds__(NT) void axis_cdf_targets_kernel(const double* __restrict__ col, const double* __restrict__ ls,
+                                                              int nleaves, int H, int W, int L, float* __restrict__ Fx,
+                                                              float* __restrict__ Fy) {
+  extern __shared__ __attribute__((aligned(16))) double smem_d[];   // n + L doubles
+  __shared__ double red[NT / WAVE];
+  const int b = blockIdx.x, axis = blockIdx.y;
+  const int n = axis ? H : W;
+  for (int k = threadIdx.x; k < n; k += blockDim.x) {
+    double v;
+    if (axis) {
+      v = 0.0;
+      const double* l = ls + ((size_t)b * H + k) * nleaves;
+      for (int j = 0; j < nleaves; ++j) v += l[j];
+    } else {
+      v = col[(size_t)b * W + k];
+    }
+    smem_d[k] = v;
+  }
+  __syncthreads();
+  pooled_cdf_block(smem_d, n, L, smem_d + n, red, (axis ? Fy : Fx) + (size_t)b * L);
+}
+
+// ---- L: the trainer's GT marginals of the pooled map (gt_marginals, MN/trainer.py:220) with the uniform override of
+// "none" samples (:222-236).  grid = B; the pooled map is small (oh x ow) and already sanitised (>= 0, finite) --------
+__global__ __launch_bounds__(NT) void trainer_marginals_kernel(const float* __restrict__ pooled,
+                                                               const int32_t* __restrict__ modes, int oh, int ow,
+                                                               float* __restrict__ px, float* __restrict__ py) {
+  __shared__ double red[NT / WAVE];
+  const int b = blockIdx.x;
+  const float* P = pooled + (size_t)b * oh * ow;
+  const bool none = modes[b] == ATTWARP_TT_NONE;
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < oh * ow; k += blockDim.x) acc += (double)P[k];
+  const double den = fmax(block_sum(acc, red), 1e-6);
+  for (int w = threadIdx.x; w < ow; w += blockDim.x) {
+    double c = 0.0;
+    for (int h = 0; h < oh; ++h) c += (double)P[(size_t)h * ow + w];
+    px[(size_t)b * ow + w] = none ? 1.0f / (float)ow : (float)(c / den);
+  }
+  for (int h = threadIdx.x; h < oh; h += blockDim.x) {
+    double r = 0.0;
+    for (int w = 0; w < ow; ++w) r += (double)P[(size_t)h * ow + w];
+    py[(size_t)b * oh + h] = none ? 1.0f / (float)oh : (float)(r / den);
+  }
 }
 
 }  // namespace attwarp
@@ -449,4 +538,41 @@ extern "C" int attwarp_axis_maps_from_attention(const void* att, int dtype, int 
   if (const int rc2 = grant_dynamic_lds(attention_maps_finalize_kernel, lds, "axis_maps_from_attention")) return rc2;
   hipLaunchKernelGGL(attention_maps_finalize_kernel, dim3(B, 2), dim3(NT), lds, st, Pw, Ph, fa);
   return check_launch("attention_maps_finalize_kernel");
+}
+
+extern "C" int attwarp_build_axis_cdf_targets(const float* A, int B, int H, int W, int L, float* Fx, float* Fy, void* ws,
+                                              void* stream) {
+  ATTWARP_REQUIRE(A && Fx && Fy && ws, "build_axis_cdf_targets: null pointer");
+  ATTWARP_REQUIRE(B > 0 && H > 0 && W > 0 && L > 0, "build_axis_cdf_targets: non-positive size");
+  if (B > 65535) return fail(ATTWARP_E_UNSUPPORTED, "build_axis_cdf_targets: B > 65535");
+  if (L > LOSS_MAX_N) return fail(ATTWARP_E_UNSUPPORTED, "build_axis_cdf_targets: L=%d > %d", L, LOSS_MAX_N);
+  PairwisePlan P;
+  if (!pw_build(W, P) || H > 16384) return fail(ATTWARP_E_UNSUPPORTED, "build_axis_cdf_targets: H, W must be <= 16384");
+  const int n = H > W ? H : W;
+  const size_t lds = (size_t)(n + L) * sizeof(double);
+  if (const int rc = grant_dynamic_lds(axis_cdf_targets_kernel, lds, "build_axis_cdf_targets")) return rc;
+  double* col = (double*)ws;
+  double* ls = col + (size_t)B * W;
+  hipStream_t st = as_stream(stream);
+  bool handled = false;
+  int rc = launch_profiles_f32<XfClampFinite>(A, B, H, W, XfClampFinite{}, P, col, ls, st, &handled);
+  if (!handled) rc = launch_profiles<float, XfClampFinite>(A, B, H, W, XfClampFinite{}, P, col, ls, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(axis_cdf_targets_kernel, dim3(B, 2), dim3(NT), lds, st, col, ls, P.nleaves, H, W, L, Fx, Fy);
+  return check_launch("axis_cdf_targets_kernel");
+}
+
+extern "C" int attwarp_trainer_attention_targets(const float* A, const int32_t* modes, int B, int H, int W, int oh,
+                                                 int ow, float* pooled, float* px, float* py, void* stream) {
+  ATTWARP_REQUIRE(A && modes && pooled && px && py, "trainer_attention_targets: null pointer");
+  ATTWARP_REQUIRE(B > 0 && H > 0 && W > 0 && oh > 0 && ow > 0, "trainer_attention_targets: non-positive size");
+  if (oh > 65535 || B > 65535) return fail(ATTWARP_E_UNSUPPORTED, "trainer_attention_targets: oh/B > 65535");
+  if (W > 16384) return fail(ATTWARP_E_UNSUPPORTED, "trainer_attention_targets: W=%d > 16384", W);
+  const int vec_ok = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(trainer_pool_kernel, dim3(oh, B), dim3(NT), (size_t)W * sizeof(double), st, A, modes, H, W, oh, ow,
+                     vec_ok, pooled);
+  if (const int rc = check_launch("trainer_pool_kernel")) return rc;
+  hipLaunchKernelGGL(trainer_marginals_kernel, dim3(B), dim3(NT), 0, st, pooled, modes, oh, ow, px, py);
+  return check_launch("trainer_marginals_kernel");
 }

@@ -20,6 +20,10 @@ struct XfClampPos {  // gt_marginals: A.clamp_min(0)
   __device__ __forceinline__ double operator()(double v) const { return (v != v) ? v : (v > 0.0 ? v : 0.0); }  // NaN propagates
   __device__ __forceinline__ double from_f32(float v) const { return (double)clamp_pos_f32(v); }
 };
+struct XfClampFinite {  // build_axis_cdf_targets: nan_to_num(A.clamp_min(0), nan=0, posinf=0, neginf=0)
+  __device__ __forceinline__ double operator()(double v) const { return (v > 0.0 && v <= 3.4028234663852886e38) ? v : 0.0; }
+  __device__ __forceinline__ double from_f32(float v) const { return (v > 0.0f && v <= 3.402823466e38f) ? (double)v : 0.0; }
+};
 // (internal) the uint8 block with its 256-entry table of XfAttention<TR>(byte) handed in by the caller instead of built per
 // workgroup: the one-launch chain steps serve sqrt / exp / log from a table computed ONCE per (transform, exp_scale,
 // exp_divisor) by attwarp_attention_transform_lut with the same device functions -- no exp / log code in those kernels

@@ -8,12 +8,15 @@ mean, FiLM + the two axis means) on HIP kernels that read each tensor once.  Par
 reference's, so checkpoints saved by the reference trainer (``{"model": state_dict}``,
 MN/trainer.py:660-683) load unchanged.
 Its weights are the payload of the one RCCL broadcast of the multi-GPU path (``attwarp_amd.dist``).
+``mix_with_uniform`` and ``entropy`` (reference :98-106), the two helpers of the trainer's step, run forward and
+backward on the row kernels of ``attwarp_amd.losses``.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import call, ptr, require_gpu, stream_ptr
@@ -134,6 +137,68 @@ class MarginalNet(nn.Module):
             return safe_softmax(lx, dim=1, eps=self.eps), safe_softmax(ly, dim=1, eps=self.eps)
         lx, ly = self.forward_logits_fused(fmap_v, H, W, txt_tok, txt_mask)
         return safe_softmax(lx, dim=1, eps=self.eps), safe_softmax(ly, dim=1, eps=self.eps)
+
+
+class _MixUniform(torch.autograd.Function):
+    """out = (1 - alpha) p + alpha / N, backward dp = (1 - alpha) g: both the scale-shift kernel, float32."""
+
+    @staticmethod
+    def forward(ctx, p, alpha):
+        dev = require_gpu(p)
+        x = p.detach().to(torch.float32).contiguous()
+        c1 = 1.0 - alpha                     # both constants reach the kernel rounded to float32, as torch's scalars
+        out = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            call("attwarp_scale_shift", ptr(x), x.numel(), c1, alpha / p.size(1), ptr(out), stream_ptr(dev))
+        ctx.c1, ctx.dtype = c1, p.dtype
+        return out.to(p.dtype) if p.dtype.is_floating_point else out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        dev = g.device
+        x = g.detach().to(torch.float32).contiguous()
+        out = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            call("attwarp_scale_shift", ptr(x), x.numel(), ctx.c1, 0.0, ptr(out), stream_ptr(dev))
+        return out.to(ctx.dtype), None
+
+
+def mix_with_uniform(p: torch.Tensor, alpha: float) -> torch.Tensor:
+    """``(1 - alpha) * p + alpha / p.size(1)`` (reference model.py:98-101); returns ``p`` itself when alpha <= 0."""
+    if alpha <= 0:
+        return p
+    return _MixUniform.apply(p, float(alpha))
+
+
+class _Entropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, eps):
+        from .losses import _loss, _rows
+        dev = require_gpu(p)
+        x = _rows(p, "p")
+        B, N = x.shape
+        ctx.save_for_backward(x)
+        ctx.eps, ctx.dtype = float(eps), p.dtype
+        return _loss("attwarp_entropy", dev, B, ptr(x), B, N, float(eps))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        dev = x.device
+        B, N = x.shape
+        gs = g.detach().to(torch.float32).reshape(()).contiguous()
+        gp = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            call("attwarp_entropy_backward", ptr(x), B, N, ctx.eps, ptr(gs), ptr(gp), stream_ptr(dev))
+        return gp.to(ctx.dtype), None
+
+
+def entropy(p: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
+    """``-(q * q.log()).sum(dim=1).mean()`` with q = p.clamp_min(eps) (reference model.py:104-106); p (B, N) -> float32
+    scalar.  Forward and backward on HIP (gradient 0 where p < eps)."""
+    return _Entropy.apply(p, eps)
 
 
 def load_reference_checkpoint(net: MarginalNet, path_or_dict) -> MarginalNet:

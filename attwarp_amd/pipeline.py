@@ -50,6 +50,38 @@ def adaptive_avg_pool2d(A: torch.Tensor, output_size=(GRID, GRID), sanitize: boo
     return out
 
 
+def trainer_attention_targets(A_full: torch.Tensor, transforms, grid=(GRID, GRID)
+                              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The trainer's attention targets (MN/trainer.py:173-202 and :220-236) in one pass over the full-resolution map.
+
+    A_full (B,1,H,W) float; ``transforms``: one name per sample as ``transform_for_sample`` returns them ("sqrt": the
+    sqrt branch; "none": identity plus the uniform override of the GT marginals; anything else: identity).
+    Returns ``(A, px_gt_vis, py_gt_vis)``: the pooled map (B,1,gh,gw) after the trainer's sanitise -- bit for bit the
+    stock-op transform followed by ``adaptive_avg_pool2d(..., sanitize=True)`` -- and its ``gt_marginals`` (B,gw), (B,gh)
+    with the "none" rows set to 1/L.  A NaN or +inf cell makes its window 0 (the trainer's blend turns it into NaN, the
+    sanitise into 0); -inf counts as 0.  Forward only (the trainer computes it under its data path, not the graph)."""
+    dev = require_gpu(A_full)
+    if A_full.dim() != 4 or A_full.shape[1] != 1:
+        raise ValueError(f"trainer_attention_targets expects A_full (B,1,H,W); got {tuple(A_full.shape)}")
+    B, _, H, W = A_full.shape
+    names = list(transforms)
+    if len(names) != B:
+        raise ValueError(f"trainer_attention_targets: {len(names)} transform names for a batch of {B}")
+    gh, gw = (int(grid), int(grid)) if isinstance(grid, int) else (int(grid[0]), int(grid[1]))
+    # pinned host memory + an asynchronous copy: the launch does not wait for the host (the caching host allocator keeps
+    # the buffer until the copy has run)
+    modes = torch.tensor([_lib.TT_SQRT if t == "sqrt" else _lib.TT_NONE if t == "none" else _lib.TT_IDENTITY
+                          for t in names], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    x = A_full.detach().float().contiguous()
+    A = torch.empty(B, 1, gh, gw, device=dev, dtype=torch.float32)
+    px = torch.empty(B, gw, device=dev, dtype=torch.float32)
+    py = torch.empty(B, gh, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        call("attwarp_trainer_attention_targets", ptr(x), ptr(modes), B, H, W, gh, gw, ptr(A), ptr(px), ptr(py),
+             stream_ptr(dev))
+    return A, px, py
+
+
 def axis_maps_from_pdf(px: torch.Tensor, py: torch.Tensor, size_hw: Tuple[int, int],
                        out_size: Optional[Tuple[int, int]] = None, eps: float = 1e-8
                        ) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -432,6 +432,62 @@ ATTWARP_API int attwarp_remap_bilinear(const void* src, void* dst, int dtype, in
                            int H_out, int W_out, const float* map_x, const float* map_y, int mode,
                            void* stream);
 
+/* ---- L: the MarginalNet training losses, MN/losses.py:11-77, MN/model.py:98-106, MN/trainer.py:173-257
+ * Row kernels (one 256-thread workgroup per sample, or per (sample, axis)), float32 in and out, float64 sums.
+ * A loss forward writes one float32 scalar `loss` through a deterministic in-launch reduction: every workgroup stores
+ * its partial into `parts` (float64 [nparts] as documented per call), the last one to draw from `ticket` sums them in
+ * index order and resets *ticket to 0.  `ticket` is one uint32 that is 0 before the launch; launches sharing a ticket
+ * must be stream ordered.  A backward reads the incoming gradient from the device scalar `gout` (float32) and
+ * follows torch autograd's conventions at ties (DESIGN.md "training losses").
+ * Row lengths: N, H, W, L <= 4096 except pdf_l1 (W, H <= 8192) and the target builders (see attwarp_gt_marginals). */
+enum { ATTWARP_RECON_MSE = 0, ATTWARP_RECON_L1 = 1 };
+/* trainer_attention_targets transform per sample: identity, sqrt, and "none" (identity + uniform marginals) */
+enum { ATTWARP_TT_IDENTITY = 0, ATTWARP_TT_SQRT = 1, ATTWARP_TT_NONE = 2 };
+
+/* cdf_from_density_downsample (:70-77): p [B,N] -> F [B,L].  build_axis_cdf_targets (:50-67): A [B,H,W] -> Fx, Fy
+ * [B,L]; ws: attwarp_axis_sums_workspace_bytes(B,H,W) bytes.  Both forward only. */
+ATTWARP_API int attwarp_cdf_downsample(const float* p, int B, int N, int L, float* F, void* stream);
+ATTWARP_API int attwarp_build_axis_cdf_targets(const float* A, int B, int H, int W, int L, float* Fx, float* Fy, void* ws,
+                                   void* stream);
+/* l1_cdf_loss (:11-12), p, q [B,N]; parts [B].  Backward -> gp, gq [B,N]. */
+ATTWARP_API int attwarp_l1_cdf_loss(const float* p, const float* q, int B, int N, double* parts, uint32_t* ticket,
+                        float* loss, void* stream);
+ATTWARP_API int attwarp_l1_cdf_loss_backward(const float* p, const float* q, int B, int N, const float* gout, float* gp,
+                                 float* gq, void* stream);
+/* sym_kl (:15-22), p, q [B,N]; parts [B].  Backward -> gp, gq [B,N]. */
+ATTWARP_API int attwarp_sym_kl(const float* p, const float* q, int B, int N, float eps, double* parts, uint32_t* ticket,
+                   float* loss, void* stream);
+ATTWARP_API int attwarp_sym_kl_backward(const float* p, const float* q, int B, int N, float eps, const float* gout,
+                            float* gp, float* gq, void* stream);
+/* separable_recon_loss (kind MSE, :25-34) and recon_l1 (kind L1, :37-47): px [B,W], py [B,H], A [B,H,W]; parts [B].
+ * The (B,H,W) outer product is never stored.  Backward -> gpx [B,W], gpy [B,H] (A is a target). */
+ATTWARP_API int attwarp_recon_loss(const float* px, const float* py, const float* A, int B, int H, int W, int kind,
+                       double* parts, uint32_t* ticket, float* loss, void* stream);
+ATTWARP_API int attwarp_recon_loss_backward(const float* px, const float* py, const float* A, int B, int H, int W, int kind,
+                                const float* gout, float* gpx, float* gpy, void* stream);
+/* mix_with_uniform (model.py:98-101): out = c1 * p + c2 elementwise over n floats, c1 = 1 - alpha, c2 = alpha / N
+ * (the backward is the same call with c2 = 0).  entropy (model.py:104-106), p [B,N]; parts [B]. */
+ATTWARP_API int attwarp_scale_shift(const float* p, int64_t n, float c1, float c2, float* out, void* stream);
+ATTWARP_API int attwarp_entropy(const float* p, int B, int N, float eps, double* parts, uint32_t* ticket, float* loss,
+                    void* stream);
+ATTWARP_API int attwarp_entropy_backward(const float* p, int B, int N, float eps, const float* gout, float* gp,
+                             void* stream);
+/* The trainer's image-resolution PDF loss (MN/trainer.py:216-250): px, gx [B,Lx], py, gy [B,Ly] low-resolution PDFs
+ * (prediction, target) -> right-inverse up-sample to W / H (inv_x: [Lx,Lx], inv_y: [Ly,Ly] as for
+ * attwarp_upsample_pdf_right_inverse), clamp_min(0), renormalise, l1_loss(x) + l1_loss(y); parts [2B].
+ * Lx, Ly <= 64.  Backward -> gpx [B,Lx], gpy [B,Ly] (the targets get none). */
+ATTWARP_API int attwarp_pdf_l1_loss(const float* px, const float* py, const float* gx, const float* gy, int B, int Lx,
+                        int Ly, int W, int H, const double* inv_x, const double* inv_y, double* parts,
+                        uint32_t* ticket, float* loss, void* stream);
+ATTWARP_API int attwarp_pdf_l1_loss_backward(const float* px, const float* py, const float* gx, const float* gy, int B,
+                                 int Lx, int Ly, int W, int H, const double* inv_x, const double* inv_y,
+                                 const float* gout, float* gpx, float* gpy, void* stream);
+/* The trainer's attention targets (MN/trainer.py:173-202, 220-236): A [B,H,W] float32, modes [B] int32 ATTWARP_TT_*
+ * -> pooled [B,oh,ow] = sanitise(adaptive_avg_pool2d(transform(A))) (bit for bit attwarp_adaptive_avg_pool with
+ * sanitize = 1 of the transformed map), px [B,ow], py [B,oh] = gt_marginals(pooled), 1/L on ATTWARP_TT_NONE rows. */
+ATTWARP_API int attwarp_trainer_attention_targets(const float* A, const int32_t* modes, int B, int H, int W, int oh,
+                                      int ow, float* pooled, float* px, float* py, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
