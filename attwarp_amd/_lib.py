@@ -45,6 +45,10 @@ SIGNATURES = {
                                                c_void_p, c_void_p, c_void_p]),
     "attwarp_masked_token_mean": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "attwarp_film_axis_means": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "attwarp_film_axis_means_t": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p]),
+    "attwarp_film_axis_means_backward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                                  c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "attwarp_mask_postproc": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "attwarp_mask_upsample_lanczos": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                                c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -56,6 +60,7 @@ SIGNATURES = {
     "attwarp_axis_sums_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "attwarp_gt_marginals": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "attwarp_safe_softmax": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "attwarp_safe_softmax_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "attwarp_upsample_pdf_right_inverse": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "attwarp_cdf_from_density": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "attwarp_make_strictly_increasing": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
@@ -254,10 +259,11 @@ def require_gpu(*tensors: torch.Tensor) -> torch.device:
 
 
 def needs_grad(*tensors) -> bool:
-    """True when autograd has to see through the call (grad mode on and some input requires grad).  The HIP kernels
-    are forward-only; the training-time call sites of the reference (``net(...)`` and
-    ``upsample_pdf_right_inverse(px_s, ...)`` on the loss path, MN/trainer.py:210-260) then take a differentiable
-    route: stock PyTorch-ROCm ops on the same GPU, or an autograd.Function around the kernel."""
+    """True when autograd has to see through the call (grad mode on and some input requires grad).  The training-time
+    call sites of the reference (``net(...)`` and ``upsample_pdf_right_inverse(px_s, ...)`` on the loss path,
+    MN/trainer.py:210-260) then take a differentiable route: an autograd.Function whose forward and backward are HIP
+    kernels (MarginalNet's FiLM tail and safe_softmax, the losses, the right inverse), or, for inputs those kernels do
+    not cover (documented per function), the same formula on stock PyTorch-ROCm ops on the same GPU."""
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 

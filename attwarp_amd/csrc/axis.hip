@@ -118,6 +118,86 @@ __global__ __launch_bounds__(NT) void safe_softmax_kernel(const float* __restric
   for (int k = threadIdx.x; k < N; k += blockDim.x) out[(size_t)b * N + k] = x[k] / d;
 }
 
+// ---- A7 backward: torch autograd's rules for the formula of safe_softmax_kernel, in reverse ------------------------
+//   z = nan_to_num(logits); zc = z - amax(z); pv = nan_to_num(softmax(zc)); S2 = sum(pv); d = clamp_min(S2, eps); out = pv/d
+// The forward is recomputed from the logits exactly as safe_softmax_kernel does (only the logits are saved), then
+//   dpv = g/d + [S2 >= eps] * dd,  dd = -sum(g * ((pv/d)/d))          (div backward; clamp_min passes where S2 >= eps)
+//   dpv = 0 where softmax(zc) is non-finite                             (nan_to_num backward)
+//   dzc = sm * (dpv - sum(dpv * sm)),  sm = softmax(zc)                 (softmax backward)
+//   dz  = dzc - [z == amax] * sum(dzc) / #[z == amax]                  (amax backward: split evenly over tied maxima)
+//   dlogits = 0 where the logit is non-finite                           (nan_to_num backward)
+// Elementwise steps are float32 roundings; sums are float64, rounded once (the losses' convention).
+// One workgroup per row, N <= 4096: z, sm and dpv (3N floats) live in LDS.
+__global__ __launch_bounds__(NT) void safe_softmax_backward_kernel(const float* __restrict__ logits,
+                                                                   const float* __restrict__ g, int N, float eps,
+                                                                   float* __restrict__ dlogits) {
+  extern __shared__ __attribute__((aligned(16))) double smem_d[];
+  double* red = smem_d;
+  __shared__ float wred[NT / WAVE];
+  float* z = reinterpret_cast<float*>(smem_d + 8);
+  float* sm = z + N;
+  float* q = sm + N;
+  const size_t row = (size_t)blockIdx.x * N;
+  float mx = -INFINITY;
+  for (int k = threadIdx.x; k < N; k += blockDim.x) {
+    float v = logits[row + k];
+    v = (isnan(v) || isinf(v)) ? 0.0f : v;
+    z[k] = v;
+    mx = fmaxf(mx, v);
+  }
+  mx = wave_max(mx);
+  if ((threadIdx.x & (WAVE - 1)) == 0) wred[threadIdx.x / WAVE] = mx;
+  __syncthreads();
+  mx = wred[0];
+  for (int i = 1; i < NT / WAVE; ++i) mx = fmaxf(mx, wred[i]);
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < N; k += blockDim.x) {
+    const float e = (float)exp((double)fsub(fsub(z[k], mx), 0.0f));
+    sm[k] = e;
+    acc += (double)e;
+  }
+  const float s = (float)block_sum(acc, red);
+  acc = 0.0;
+  for (int k = threadIdx.x; k < N; k += blockDim.x) {
+    const float pv = sm[k] / s;
+    sm[k] = pv;
+    acc += (isnan(pv) || isinf(pv)) ? 0.0 : (double)pv;
+  }
+  const float S2 = (float)block_sum(acc, red);
+  const float d = fmaxf(S2, eps);
+  // out = pv / d
+  acc = 0.0;
+  for (int k = threadIdx.x; k < N; k += blockDim.x) {
+    const float pv = (isnan(sm[k]) || isinf(sm[k])) ? 0.0f : sm[k];
+    acc += (double)fmul(g[row + k], (pv / d) / d);
+  }
+  const float dd = -(float)block_sum(acc, red);
+  const float dS2 = S2 >= eps ? dd : 0.0f;
+  acc = 0.0;
+  for (int k = threadIdx.x; k < N; k += blockDim.x) {
+    const float dpv = (isnan(sm[k]) || isinf(sm[k])) ? 0.0f : fadd(g[row + k] / d, dS2);
+    q[k] = dpv;
+    acc += (double)dpv * (double)sm[k];
+  }
+  const float c = (float)block_sum(acc, red);
+  acc = 0.0;
+  double ties = 0.0;
+  for (int k = threadIdx.x; k < N; k += blockDim.x) {
+    const float dz = fmul(sm[k], fsub(q[k], c));
+    q[k] = dz;
+    acc += (double)dz;
+    ties += z[k] == mx ? 1.0 : 0.0;
+  }
+  const float m = (float)block_sum(acc, red);
+  const float cnt = (float)block_sum(ties, red);
+  const float gmx = -m / cnt;
+  for (int k = threadIdx.x; k < N; k += blockDim.x) {
+    const float l = logits[row + k];
+    const float dz = z[k] == mx ? fadd(q[k], gmx) : q[k];
+    dlogits[row + k] = (isnan(l) || isinf(l)) ? 0.0f : dz;
+  }
+}
+
 // ---- A10: _make_strictly_increasing (MN/checkpoint_utils.py:17-28), in LDS -----------------
 // f: LDS float[N] in/out.
 __device__ void strictly_increasing_block(float* f, int N, double eps) {
@@ -269,6 +349,17 @@ extern "C" int attwarp_safe_softmax(const float* logits, int B, int N, float eps
   const size_t lds = 8 * sizeof(double) + (size_t)N * sizeof(float);
   hipLaunchKernelGGL(safe_softmax_kernel, dim3(B), dim3(NT), lds, as_stream(stream), logits, N, eps, out);
   return check_launch("safe_softmax_kernel");
+}
+
+extern "C" int attwarp_safe_softmax_backward(const float* logits, const float* g, int B, int N, float eps,
+                                             float* dlogits, void* stream) {
+  ATTWARP_REQUIRE(logits && g && dlogits, "safe_softmax_backward: null pointer");
+  ATTWARP_REQUIRE(B > 0 && N > 0, "safe_softmax_backward: non-positive size");
+  if (N > 4096) return fail(ATTWARP_E_UNSUPPORTED, "safe_softmax_backward: N=%d > 4096", N);
+  const size_t lds = 8 * sizeof(double) + 3 * (size_t)N * sizeof(float);
+  hipLaunchKernelGGL(safe_softmax_backward_kernel, dim3(B), dim3(NT), lds, as_stream(stream), logits, g, N, eps,
+                     dlogits);
+  return check_launch("safe_softmax_backward_kernel");
 }
 
 extern "C" int attwarp_make_strictly_increasing(const float* F, int B, int N, double eps, float* out, void* stream) {

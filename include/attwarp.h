@@ -164,6 +164,18 @@ ATTWARP_API int attwarp_masked_token_mean(const void* tok, int dtype, const floa
                               float* out, void* stream);
 ATTWARP_API int attwarp_film_axis_means(const float* v, const float* gamma_beta, int B, int Ch, int H, int W,
                             float* vx, float* vy, void* stream);
+/* Training (autograd) forms of film_axis_means.  _t: v and gamma_beta in their own dtypes (v_dtype, gb_dtype: F32, F16
+ * or BF16, as the trainer's autocast gives them), upcast exactly and computed as above; float32 inputs give the bits of
+ * attwarp_film_axis_means.  _backward: upstream gradients gx [B,Ch,W], gy [B,Ch,H] float32 ->
+ *   dv [B,Ch,H,W] (v_dtype) = gamma * (gx*(1/H) + gy*(1/W)), bit for bit torch's float32 autograd on the GPU (which
+ *   divides by a scalar as a multiply by its float32 reciprocal);
+ *   dgamma_beta [B,2*Ch] (gb_dtype) = (sum_yx v*gw | sum_yx gw), gw = gx*(1/H) + gy*(1/W), float64 sums rounded once.
+ * One wave per (b, c) plane: deterministic, no atomics.  H*(W+1) <= 4096. */
+ATTWARP_API int attwarp_film_axis_means_t(const void* v, int v_dtype, const void* gamma_beta, int gb_dtype, int B,
+                              int Ch, int H, int W, float* vx, float* vy, void* stream);
+ATTWARP_API int attwarp_film_axis_means_backward(const void* v, int v_dtype, const void* gamma_beta, int gb_dtype,
+                                     const float* gx, const float* gy, int B, int Ch, int H, int W, void* dv,
+                                     void* dgamma_beta, void* stream);
 
 /* ---- A5: F.adaptive_avg_pool2d(A,(oh,ow)), call sites MN/trainer.py:197,433,465
  * A [B,H,W] float32 -> out [B,oh,ow] float32.  sanitize != 0 also applies the trainer's
@@ -179,6 +191,11 @@ ATTWARP_API int attwarp_gt_marginals(const float* A, int B, int H, int W, float*
 
 /* ---- A7: safe_softmax(dim=1), MN/model.py:8-14.  logits [B,N] -> out [B,N], N <= 4096. */
 ATTWARP_API int attwarp_safe_softmax(const float* logits, int B, int N, float eps, float* out, void* stream);
+/* Its backward: logits [B,N], upstream gradient g [B,N] -> dlogits [B,N], all float32, N <= 4096.  The forward is
+ * recomputed from the logits; torch autograd's rules are applied in reverse (amax: split evenly over tied maxima;
+ * nan_to_num: 0 at non-finite logits).  Elementwise float32, float64 row sums. */
+ATTWARP_API int attwarp_safe_softmax_backward(const float* logits, const float* g, int B, int N, float eps,
+                                  float* dlogits, void* stream);
 
 /* ---- A8: upsample_pdf_right_inverse, MN/checkpoint_utils.py:64-131
  * y [N,Lo] float32 -> out [N,L] float32.  inv: device float64 [Lo,Lo] = (A A^T + eps I)^-1 of the
