@@ -14,13 +14,20 @@ Workloads (``--workload``):
   336x256  BASELINE configs[3]: B=256 per GPU, S=336 (2048 images over 8 ranks)
 Arithmetic (``--mode``): ``cv2`` (default) = what the reference's cv2.remap(INTER_LINEAR) call computes (1/32-px
 quantised coordinates, 4 table weights); ``exact`` = unquantised bilinear (= F.grid_sample).  Both run on the same
-staged kernel; the default line measures cv2 and attaches the exact-mode, CHW-layout and 336 measurements under
-"also_exact", "also_chw", "also".
+staged kernel; the default line measures cv2, and ``--full`` attaches the exact-mode, CHW-layout and 336 measurements
+under "also_exact", "also_chw", "also".
+
+A plain run measures the main line only: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line.  ``--full`` adds everything else: the CPU baselines, the secondary legs (``--legs``), the dist legs every rank of a
+group runs, the `calibration` of the roofline, the 1024 line's bit-identity check against the serial launches (the 336
+lines keep theirs in every run: they pick between two paths by it) and the eager three-launch timing ("also_eager").
+``--workload config5 / main_batched / main_batched_ragged`` are measurements of their own and run the same with or
+without it.
 
 The timed step is the steady state of a batch STREAM: at 1024x1024 two launches (attention reduce of batch k+2 + map
 construction of batch k+1 as one, then the resample of batch k; HIP events around the resample), at 336x336 one launch
 for all three, replayed as HIP graphs.  Every step runs exactly one reduce, one map construction and one resample,
-bit-identical to the serial launches; the plain three-launch step on one batch is attached as "also_eager".
+bit-identical to the serial launches; ``--full`` attaches the plain three-launch step on one batch as "also_eager".
 
 ``--gpus N`` (N > 1) is self-launching: when RANK is not in the environment the parent -- before it touches the GPU --
 starts N child processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set), one per GPU,
@@ -32,12 +39,13 @@ data-path collective); the only collective is the start-up RCCL broadcast of Mar
 fixed seeded sample of it) as DIR/<name>.npy in float32 / float64, at most 64 MiB; the inputs are seeded, so two builds run
 with the same arguments can be compared output for output.
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Output: ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline     dominant kernel (remap_rows_kernel): algorithmic bytes (2*S*S*3*4 per image)
                / its mean launch duration measured live with HIP events inside the timed region,
-               against the 8 TB/s HBM peak.
-  cpu_baseline the plain-C restatement of the same path (oracle/warp_ref.c, "port") timed on this
-               box's host on a bounded sample: one thread, and one process per host core.
+               against the 8 TB/s HBM peak (1024 workload; the 336 workloads time graph replays without
+               per-kernel events and take theirs from the eager pass of --full).
+  cpu_baseline (--full) the plain-C restatement of the same path (oracle/warp_ref.c, "port") timed on the
+               host on a bounded sample: one thread, and one process per host core.
 """
 from __future__ import annotations
 
@@ -504,9 +512,11 @@ def step_bytes(B: int, S: int, attn_esize: int = 4) -> float:
 PREWARM_SMALL_S = 0.0          # seconds of extra untimed graph replays before the warm-up steps of the 336 workloads (--prewarm, tenths of a second)
 
 
-def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn_dtype=None, prewarm_s=0.0):
+def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn_dtype=None, prewarm_s=0.0, full=True):
     """configs[1] / configs[3]'s per-rank batch: the overlapped graph path over a ring of independent batches (>= 2 GiB,
-    every step streams from HBM) as the headline, the eager three-launch step with HIP events beside it.
+    every step streams from HBM) as the headline, the eager three-launch step with HIP events beside it (`full` only: it runs
+    after the timed region and the headline does not depend on it).  The bit-identity checks of the ring slots stay in every
+    run: the two-batches-per-launch path is the line only when it is faster AND equal to the serial launches.
     attn_dtype (torch.float16 / bfloat16): the attention rows in the model dtype LLaVA emits instead of float32."""
     st = Step(B, S, dev, seed=seed, mode=mode, layout=layout)
     esize = 4
@@ -563,7 +573,7 @@ def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn
                       "bit_identical_to_serial": same_p, "wall": wall_p, "wall_local": wall_p_local}
             last_p = pw.outs[(K - 1) % pw.n]
         del pw
-    w_e, _ = time_steps(st, K, W, D)
+    w_e = time_steps(st, K, W, D)[0] if full else None
     sb = step_bytes(B, S, esize)
     one = {"ms_per_step": round(wall / K * 1e3, 4), "images_per_s": round(B * K / wall, 1), "bit_identical_to_serial": same}
     path_txt = ("pipeline.OverlappedWarp, pattern '" + ow.pattern + "': resample(k) + maps(k+1) + reduce(k+2) "
@@ -583,13 +593,14 @@ def small_workload(B, S, dev, seed, mode, layout, K, W, D, torch, pipeline, attn
            "rotating_batches": ow.n, "bit_identical_to_serial": same,
            "path": path_txt + f", HIP-graph replay (one host call per 8 batches), ring of {ow.n} independent batches (>= 2 GiB: every "
                    f"step streams from HBM), exactly {K} of each piece of work in the timed region",
-           "one_launch_per_batch": one, "one_launch_per_two_batches": paired,
-           "eager": {"ms_per_step": round(w_e / K * 1e3, 4), "images_per_s": round(B * K / w_e, 1),
-                     "step_TBps": round(sb / (w_e / K) / 1e12, 3),
-                     "stages_ms": [round(v, 4) for v in st.stage_ms()],
-                     "roofline": roofline_of(st),
-                     "path": "three eager launches per step with HIP events between them (the events are where the "
-                             "per-kernel durations come from)"}}
+           "one_launch_per_batch": one, "one_launch_per_two_batches": paired}
+    if full:
+        res["eager"] = {"ms_per_step": round(w_e / K * 1e3, 4), "images_per_s": round(B * K / w_e, 1),
+                        "step_TBps": round(sb / (w_e / K) / 1e12, 3),
+                        "stages_ms": [round(v, 4) for v in st.stage_ms()],
+                        "roofline": roofline_of(st),
+                        "path": "three eager launches per step with HIP events between them (the events are where the "
+                                "per-kernel durations come from)"}
     return res, wall, wall_local, st, ow, last
 
 
@@ -1134,15 +1145,15 @@ def leg_small(wl, dev, args, K, D, torch, pipeline, attn_dtype=None, rank=0, wor
     return out
 
 
-SCALING_CURVE_NOTE = ("one point per run: `value` is the whole-job rate at n_gpus = N (and `also_336x256` -- BASELINE configs[3], 256 images "
-                      "per rank -- and `also_main_batched_ragged` carry theirs); the 1/2/4/8 curve and its efficiency are computed by the "
-                      "driver from the per-N lines, never reported here")
+SCALING_CURVE_NOTE = ("one point per run: `value` is the whole-job rate at n_gpus = N (with --full, `also_336x256` -- BASELINE configs[3], "
+                      "256 images per rank -- and `also_main_batched_ragged` carry theirs); the 1/2/4/8 curve and its efficiency are "
+                      "computed by the driver from the per-N lines, never reported here")
 
 
 def dist_leg_plan(workload: str, want, grouped: bool):
     """(key, images per rank per step) of the secondary legs that run on EVERY rank of a process group behind the main 1024
-    line: BASELINE configs[3] (batch-2048 at 336 x 336 over 8 ranks = 256 per rank, the only config BASELINE names for the
-    scaling curve) and the reference driver's own uint8 chain on differently sized images."""
+    line of a --full run: BASELINE configs[3] (batch-2048 at 336 x 336 over 8 ranks = 256 per rank, the only config BASELINE
+    names for the scaling curve) and the reference driver's own uint8 chain on differently sized images."""
     if workload != "1024" or not grouped:
         return []
     plan = []
@@ -1153,7 +1164,7 @@ def dist_leg_plan(workload: str, want, grouped: bool):
     return plan
 
 
-# secondary measurements attached to the default (1024) line on one GPU; `--legs a,b` selects, `--list-legs` prints
+# secondary measurements a --full run attaches to the default (1024) line on one GPU; `--legs a,b` selects, `--list-legs` prints
 LEGS = {
     "exact": "the main batch in the other arithmetic mode (also_exact / also_cv2)",
     "chw": "the main batch in the other layout (also_chw / also_hwc)",
@@ -1236,16 +1247,21 @@ def main():
     ap.add_argument("--prewarm", type=int, default=-1,
                     help="EXTRA untimed device pre-conditioning in front of the W warm-up steps: steps of the 1024 workload / tenths "
                          "of a second of graph replays for the 336 workloads.  Default: none (the untimed work in front of the K timed "
-                         "steps of the main line is the pipeline priming + W; the three-launch `also_eager` measurement, itself W + K "
-                         "steps, runs before it).  The first ~20 launches of a process run 1-2 %% slower (clock ramp): a run that times "
-                         "a 336 workload as its FIRST work can add `--prewarm 5`; reported as `prewarm_steps`")
+                         "steps of the main line is the pipeline priming + W; the three-launch pass of the 1024 workload, itself W + K "
+                         "steps, runs before it in every run and is reported as `also_eager` by --full).  The first ~20 launches of a "
+                         "process run 1-2 %% slower (clock ramp): a run that times a 336 workload as its FIRST work can add "
+                         "`--prewarm 5`; reported as `prewarm_steps`")
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["config5", "main_batched", "main_batched_ragged"], default="1024")
     ap.add_argument("--mode", choices=["cv2", "exact"], default="cv2", help="resample arithmetic of the main line")
     ap.add_argument("--layout", choices=["hwc", "chw"], default="hwc")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip every secondary measurement (the also_* legs)")
-    ap.add_argument("--legs", default="all",
-                    help="comma-separated secondary legs to run beside the main line (see --list-legs); 'all' (default) or 'none'")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the main line: CPU baselines, the secondary legs, the dist legs "
+                         "of a process group, the roofline's calibration, the bit-identity checks and the eager three-launch "
+                         "timing (a plain run measures the main line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="a --full run without the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="a --full run without the secondary legs (every also_* entry but also_eager)")
+    ap.add_argument("--legs", default=None,
+                    help="comma-separated secondary legs of a --full run (see --list-legs); 'all' (default) or 'none'")
     ap.add_argument("--list-legs", action="store_true", help="print the names of the secondary legs and exit")
     ap.add_argument("--dist-backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--device", type=int, default=None,
@@ -1265,10 +1281,13 @@ def main():
         for name, doc in LEGS.items():
             print(f"{name:28s} {doc}")
         return
-    want = set(LEGS) if args.legs == "all" else set() if args.legs == "none" else set(args.legs.split(","))
+    legs = args.legs or "all"
+    want = set(LEGS) if legs == "all" else set() if legs == "none" else set(legs.split(","))
     if want - set(LEGS):
         raise SystemExit(f"bench.py: unknown leg(s) {sorted(want - set(LEGS))}; --list-legs names them")
-    if args.no_also:
+    if args.legs not in (None, "none") and not args.full:
+        raise SystemExit("bench.py: --legs selects among the secondary legs of a --full run; add --full")
+    if args.no_also or not args.full:
         want = set()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -1308,7 +1327,7 @@ def main():
 
     # all-core CPU baseline: forked workers, so it runs BEFORE anything initialises the GPU in this process
     cpu_all = None
-    want_cpu = rank_env == 0 and world_env == 1 and not args.no_cpu_baseline and not args.dry_run
+    want_cpu = args.full and rank_env == 0 and world_env == 1 and not args.no_cpu_baseline and not args.dry_run
     if want_cpu:
         cpu_all = cpu_baseline_all_cores(S, args.mode)
     # one rank per GPU: stay on the cores next to that GPU (before torch starts its threads)
@@ -1393,15 +1412,19 @@ def main():
     extra = {}
     if small:
         # configs[1] / configs[3]: the step is ~0.09-0.25 ms, so the timed loop is a HIP-graph replay with no host call
-        # per kernel (the eager three-launch line with HIP events is attached as "also_eager")
+        # per kernel (--full attaches the eager three-launch line with HIP events as "also_eager", and its roofline)
         res, wall, wall_local, step, ow, last = small_workload(B, S, dev, 1234 + rank, args.mode, args.layout, args.steps,
                                                          args.warmup, D, torch, pipeline,
-                                                         prewarm_s=PREWARM_SMALL_S if args.prewarm < 0 else args.prewarm / 10.0)
-        roof = res["eager"]["roofline"]
-        roof["measured_in"] = "the eager pass right after the timed graph region (a graph replay has no per-kernel events)"
+                                                         prewarm_s=PREWARM_SMALL_S if args.prewarm < 0 else args.prewarm / 10.0,
+                                                         full=args.full)
         extra = {"step_algorithmic_bytes": res["step_algorithmic_bytes"], "step_TBps": res["step_TBps"],
                  "step_frac_of_hbm_peak": res["step_frac_of_hbm_peak"], "bit_identical_to_serial": res["bit_identical_to_serial"],
-                 "path": res["path"], "also_eager": res["eager"]}
+                 "path": res["path"]}
+        roof = None
+        if args.full:
+            roof = res["eager"]["roofline"]
+            roof["measured_in"] = "the eager pass right after the timed graph region (a graph replay has no per-kernel events)"
+            extra["also_eager"] = res["eager"]
         nrot = res["rotating_batches"]
         dumped = dump_sample(last) if args.dump_outputs and rank == 0 else None
         del ow, last
@@ -1412,15 +1435,19 @@ def main():
         for _ in range(n_prewarm):
             step()
         torch.cuda.synchronize()
-        # (a) the plain step: reduce -> maps -> resample of ONE batch, three eager launches (reported as "also_eager")
+        # (a) the plain step: reduce -> maps -> resample of ONE batch, three eager launches (reported as "also_eager" by
+        # --full).  It runs in every run: its W + K steps have always preceded the main line's warm-up, and the main line
+        # is measured in the state they leave the device in
         wall_e, _ = time_steps(step, args.steps, args.warmup, D)
-        st_e = step.stage_ms()
-        eager = {"workload": "the same step as three eager launches on one batch (reduce -> maps -> resample), HIP events between them",
-                 "value": round(world * B * args.steps / wall_e, 1), "unit": "images/s",
-                 "ms_per_step": round(wall_e / args.steps * 1e3, 4),
-                 "stages_ms": {"attn_reduce_step_kernel": round(st_e[0], 4), "axis_maps_from_steps_kernel": round(st_e[1], 4),
-                               "remap_rows_kernel": round(st_e[2], 4)},
-                 "roofline": roofline_of(step)}
+        eager = None
+        if args.full:
+            st_e = step.stage_ms()
+            eager = {"workload": "the same step as three eager launches on one batch (reduce -> maps -> resample), HIP events between them",
+                     "value": round(world * B * args.steps / wall_e, 1), "unit": "images/s",
+                     "ms_per_step": round(wall_e / args.steps * 1e3, 4),
+                     "stages_ms": {"attn_reduce_step_kernel": round(st_e[0], 4), "axis_maps_from_steps_kernel": round(st_e[1], 4),
+                                   "remap_rows_kernel": round(st_e[2], 4)},
+                     "roofline": roofline_of(step)}
         # (b) the main line: the same work per step as a batch STREAM -- reduce of batch k+2 + maps of batch k+1 in one
         # launch, then the resample of batch k (pipeline.OverlappedWarp pattern "am", driven eagerly here so that HIP
         # events bracket the resample): one launch boundary less, and the resample no longer starts behind the
@@ -1433,18 +1460,22 @@ def main():
         roof = roofline_of(main_step, load_pmc_traffic(args.workload, args.mode))
         if roof["traffic"] is not None:                 # a committed constant, not a counter read in this run
             roof["traffic_source"] = pmc_traffic_source(args.workload, args.mode)
-        ref_main = pipeline.warp_from_attention_stack(step.sets[0][0], step.sets[0][1], step.starts,
-                                                      channels_last=(args.layout == "hwc"), mode=args.mode)
-        extra = {"bit_identical_to_serial": bool(torch.equal(main_step.ow.out, ref_main)),
-                 "path": "a stream of batches, two launches per step: attention reduce of batch k+2 + map construction of batch "
+        extra = {"path": "a stream of batches, two launches per step: attention reduce of batch k+2 + map construction of batch "
                          "k+1 as ONE launch (attwarp_attn_reduce_and_maps), then the resample of batch k "
                          "(pipeline.OverlappedWarp pattern 'am', eager, HIP events around the resample); every step runs exactly "
-                         "one reduce, one map construction and one resample",
-                 "also_eager": eager}
-        del ref_main
+                         "one reduce, one map construction and one resample"}
+        if args.full:
+            ref_main = pipeline.warp_from_attention_stack(step.sets[0][0], step.sets[0][1], step.starts,
+                                                          channels_last=(args.layout == "hwc"), mode=args.mode)
+            extra = dict({"bit_identical_to_serial": bool(torch.equal(main_step.ow.out, ref_main))}, **extra, also_eager=eager)
+            del ref_main
         nrot = step.nrot
-    roof["calibration"] = calibration_of(step)
-    per_rank = D.all_gather_counters({"images_per_s": B * args.steps / wall_local, "roofline_frac": roof["frac"]})
+    counters = {"images_per_s": B * args.steps / wall_local}
+    if roof is not None:
+        if args.full:
+            roof["calibration"] = calibration_of(step)
+        counters["roofline_frac"] = roof["frac"]
+    per_rank = D.all_gather_counters(counters)
     ms_per_step = wall / args.steps * 1e3
     value = world * B * args.steps / wall
 
@@ -1465,16 +1496,18 @@ def main():
         "config": {"workload": workload_txt, "mode": args.mode, "batch_per_gpu": B, "image_size": S,
                    "layout": args.layout.upper(), "global_batch": world * B, "rotating_batches": nrot,
                    "sharding": "contiguous image blocks per rank, no data-path collective"},
-        "roofline": roof,
     }
+    if roof is not None:
+        result["roofline"] = roof
     result.update(extra)
     if dumped is not None:
         result["dump_outputs"] = write_dump(args.dump_outputs, dumped)
         del dumped
     if small:
-        st_ms = step.stage_ms()
-        result["stages_ms"] = {"attn_reduce_step_kernel": round(st_ms[0], 4), "axis_maps_from_steps_kernel": round(st_ms[1], 4),
-                               "remap_rows_kernel": round(st_ms[2], 4)}
+        if args.full:
+            st_ms = step.stage_ms()
+            result["stages_ms"] = {"attn_reduce_step_kernel": round(st_ms[0], 4), "axis_maps_from_steps_kernel": round(st_ms[1], 4),
+                                   "remap_rows_kernel": round(st_ms[2], 4)}
     else:
         st_ms = main_step.stage_ms()
         result["stages_ms"] = {"attn_maps_kernel": round(st_ms[0], 4), "remap_rows_kernel": round(st_ms[1], 4)}
@@ -1483,7 +1516,8 @@ def main():
     if grouped:
         rates = per_rank["images_per_s"]
         result["per_rank_images_per_s"] = [round(v, 1) for v in rates]
-        result["per_rank_roofline_frac"] = [round(v, 4) for v in per_rank["roofline_frac"]]
+        if "roofline_frac" in per_rank:
+            result["per_rank_roofline_frac"] = [round(v, 4) for v in per_rank["roofline_frac"]]
         # `value` is N * B * K / the SLOWEST rank's time, and GPUs of one node differ by several per cent: this
         # is the job's rate against N x the mean rank -- 1.0 means the ranks lose nothing to each other beyond their own
         # spread -- so the curve can be read apart from which GPU the N=1 run happened to land on

@@ -110,16 +110,33 @@ def test_bench_default_workload_carries_the_dist_legs(n):
     import json
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dist-backend", "gloo", "--dry-run",
-                        "--steps", "2"], env=_clean_env(), capture_output=True, text=True, timeout=280)
+                        "--steps", "2", "--full"], env=_clean_env(), capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == n and d["config"]["workload"] == "1024"
     _check_dist_legs(d, n)
     # --legs narrows them like every other leg
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--dry-run",
-                        "--steps", "2", "--legs", "336"], env=_clean_env(), capture_output=True, text=True, timeout=280)
+                        "--steps", "2", "--full", "--legs", "336"], env=_clean_env(), capture_output=True, text=True, timeout=280)
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert "also_336x256" in d and "also_main_batched_ragged" not in d
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_carries_the_main_line_only():
+    """Without --full the line is the main measurement alone: no dist legs on any rank, and a leg asked for by name is refused
+    (it would only run under --full) before anything starts."""
+    import json
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--dry-run",
+                        "--steps", "2"], env=_clean_env(), capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["n_gpus"] == 2 and d["ranks_seen"] == [0, 1] and d["per_rank_images"] == [512.0, 512.0]
+    assert not [k for k in d if k.startswith("also") or k == "cpu_baseline"], sorted(d)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "336"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr, r.stderr[-500:]
 
 
 def test_bench_exits_nonzero_when_a_rank_is_missing_from_the_gather(monkeypatch):
@@ -197,7 +214,7 @@ def test_bench_under_torch_distributed_run():
     import subprocess
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--dist-backend", "gloo", "--dry-run"], env=_clean_env(), capture_output=True, text=True, timeout=380)
+                        "--dist-backend", "gloo", "--dry-run", "--full"], env=_clean_env(), capture_output=True, text=True, timeout=380)
     assert r.returncode == 0, (r.stderr[-2000:], r.stdout[-500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines

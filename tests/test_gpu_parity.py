@@ -2033,7 +2033,7 @@ def test_bench_gpus2_self_launch_on_one_gpu(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--device", "0",
-                        "--workload", "336", "--steps", "5", "--warmup", "2"], env=env, capture_output=True, text=True,
+                        "--workload", "336", "--steps", "5", "--warmup", "2", "--full"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -2063,7 +2063,7 @@ def test_bench_gpus2_default_workload_runs_the_dist_legs_on_every_rank(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--device", "0",
-                        "--steps", "6", "--warmup", "2", "--legs", "336,main_batched_ragged"], env=env, capture_output=True, text=True,
+                        "--steps", "6", "--warmup", "2", "--full", "--legs", "336,main_batched_ragged"], env=env, capture_output=True, text=True,
                        timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -2127,7 +2127,7 @@ def test_bench_force_dist_goes_through_rccl_on_one_gpu(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--workload", "336x256",
-                        "--steps", "8", "--warmup", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["dist_backend"] == "nccl" and d["rccl_ranks_seen"] == [0]
@@ -2147,7 +2147,7 @@ def test_bench_force_dist_default_workload_carries_the_dist_legs(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "8", "--warmup", "2",
-                        "--no-cpu-baseline", "--legs", "336,main_batched_ragged"], env=env, capture_output=True,
+                        "--full", "--no-cpu-baseline", "--legs", "336,main_batched_ragged"], env=env, capture_output=True,
                        text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -2162,6 +2162,29 @@ def test_bench_force_dist_default_workload_carries_the_dist_legs(dev):
     rag = d["also_main_batched_ragged"]
     assert [c["B"] for c in rag["cases"]] == [32, 256] and all(c["bit_identical_to_serial"] for c in rag["cases"])
     assert rag["step_over_copy"] is not None and rag["cases"][0]["calibration"]["ms"] > 0
+
+
+def test_bench_plain_run_is_the_main_line_only(dev, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the contract's fields, the roofline of the timed launches and
+    the dumped outputs -- and nothing measured or checked beside them (no CPU baseline, no secondary leg, no calibration)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "warped images/sec" and d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["value"] > 0
+    assert abs(d["value"] - 256 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    assert d["roofline"]["launches_timed"] == 4 and d["roofline"]["frac"] > 0.3 and "calibration" not in d["roofline"]
+    assert not [k for k in d if k.startswith("also") or k in ("cpu_baseline", "bit_identical_to_serial")], sorted(d)
+    assert sorted(d["dump_outputs"]) == ["warped_image_index", "warped_images", "warped_sample", "warped_sample_index"]
+    assert all((tmp_path / "dump" / f"{n}.npy").exists() for n in d["dump_outputs"])
 
 
 def test_wide_rows_sorted_random_maps(dev):

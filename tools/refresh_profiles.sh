@@ -37,23 +37,23 @@ done
 python3 $ROOT/tools/make_profiles.py $TAG $NAME --pmc-only > $OUT/pmc_traffic.log 2>&1     # -> profiles/pmc_traffic.json ON THIS BOX
 
 # 2. the bench line (reads the pmc_traffic.json just written), then the same command under the kernel trace
-python3 $ROOT/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 $ROOT/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # the headline agreement: ONLY the main measurement (25 pre-conditioning + 3 warm-up + 20 timed steps), so that the
 # average duration of remap_rows_kernel in the stats is the average of the launches bench.py times
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --no-cpu-baseline --no-also > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 keep trace
 # the whole default command (exact / CHW / fused / peaked / zero attention / 336 workloads share kernel names: its
 # per-kernel averages mix those measurements)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_full -- python3 $ROOT/bench.py --no-cpu-baseline > $OUT/bench_profiled_full.json 2> $OUT/bench_profiled_full.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_full -- python3 $ROOT/bench.py --full --no-cpu-baseline > $OUT/bench_profiled_full.json 2> $OUT/bench_profiled_full.err
 keep trace_full
 
 # 3. the other workloads as main lines; the line a rank of N prints (one-rank RCCL group, dist legs on "every" rank)
-python3 $ROOT/bench.py --workload 336 --no-cpu-baseline > $OUT/bench_336.json 2> $OUT/bench_336.err
-python3 $ROOT/bench.py --workload 336x256 --no-cpu-baseline > $OUT/bench_336x256.json 2> $OUT/bench_336x256.err
+python3 $ROOT/bench.py --workload 336 --full --no-cpu-baseline > $OUT/bench_336.json 2> $OUT/bench_336.err
+python3 $ROOT/bench.py --workload 336x256 --full --no-cpu-baseline > $OUT/bench_336x256.json 2> $OUT/bench_336x256.err
 python3 $ROOT/bench.py --workload main_batched --steps 48 > $OUT/bench_main_batched.json 2> $OUT/bench_main_batched.err
 python3 $ROOT/bench.py --workload main_batched_ragged --steps 48 > $OUT/bench_main_batched_ragged.json 2> $OUT/bench_main_batched_ragged.err
 python3 $ROOT/bench.py --workload config5 --steps 5 > $OUT/bench_config5.json 2> $OUT/bench_config5.err
-python3 $ROOT/bench.py --gpus 1 --force-dist --no-cpu-baseline --legs 336,main_batched_ragged > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err
+python3 $ROOT/bench.py --gpus 1 --force-dist --full --no-cpu-baseline --legs 336,main_batched_ragged > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err
 
 # 4. per-stage tools
 for t in attn_bench u8_bench stage_bench chain_bench probe_bench remap_bench remap_lines; do
