@@ -43,6 +43,9 @@ SIGNATURES = {
     "attwarp_attn_probe_last_query": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int64,
                                                c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_float,
                                                c_void_p, c_void_p, c_void_p]),
+    "attwarp_attn_probe_head_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int64,
+                                              c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_float,
+                                              c_void_p, c_void_p, c_void_p]),
     "attwarp_masked_token_mean": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "attwarp_film_axis_means": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "attwarp_film_axis_means_t": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
@@ -102,6 +105,12 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_int, c_void_p]),
     "attwarp_overlay_workspace_bytes": (c_size_t, [c_int]),
     "attwarp_heatmap_overlay": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p]),
+    # the layer-selection study's LANCZOS4 maps and box metrics (grounding.hip)
+    "attwarp_lanczos4_coeffs": (c_int, [c_int, c_int, c_void_p, c_void_p]),
+    "attwarp_resize_lanczos4": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "attwarp_box_metrics_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "attwarp_box_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
     # the MarginalNet training losses (losses.hip, profiles.hip)
     "attwarp_cdf_downsample": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "attwarp_build_axis_cdf_targets": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

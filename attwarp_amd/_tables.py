@@ -5,6 +5,8 @@
   (MN/checkpoint_utils.py:104-120, incl. a Python loop with 48 ``.item()`` host syncs).
 * ``lanczos_tables``: Pillow's 8-bit LANCZOS coefficient tables (``precompute_coeffs`` +
   ``normalize_coeffs_8bpc`` in Pillow's Resample.c) behind ``invtrans`` (llava.py:195-196).
+* ``lanczos4_tables``: OpenCV's INTER_LANCZOS4 tables of ``resizeGeneric_`` (offsets + 8 float32 taps per output
+  index) behind the layer-selection study's ``cv2.resize`` (uncertainty_attn_maps_llava.py:63-64).
 """
 from __future__ import annotations
 
@@ -117,4 +119,25 @@ def lanczos_tables(n_in: int, n_out: int, device: torch.device, filt: str = "lan
             kk = np.concatenate([kk, np.zeros((kk.shape[0], 8 - ksize), dtype=np.int32)], axis=1)
             ksize = 8
         t = _cache_put(key, (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize))
+    return t
+
+
+@functools.lru_cache(maxsize=1024)
+def lanczos4_tables_host(n_in: int, n_out: int):
+    """OpenCV's INTER_LANCZOS4 tables for one axis n_in -> n_out from the library's HOST helper attwarp_lanczos4_coeffs
+    (interpolateLanczos4 with glibc's sin / cos): (ofs int32 [n_out], coeffs float32 [n_out,8])."""
+    from . import _lib
+    ofs = np.zeros(n_out, dtype=np.int32)
+    coeffs = np.zeros((n_out, 8), dtype=np.float32)
+    _lib.call("attwarp_lanczos4_coeffs", int(n_in), int(n_out), ofs.ctypes.data, coeffs.ctypes.data)
+    return ofs, coeffs
+
+
+def lanczos4_tables(n_in: int, n_out: int, device: torch.device):
+    """The same tables on the device, uploaded once per (n_in, n_out, device): (ofs int32 [n_out], coeffs float32 [n_out,8])."""
+    key = ("lanczos4", n_in, n_out, str(device))
+    t = _DEV_CACHE.get(key)
+    if t is None:
+        ofs, coeffs = lanczos4_tables_host(n_in, n_out)
+        t = _cache_put(key, (torch.from_numpy(ofs).to(device), torch.from_numpy(coeffs).to(device)))
     return t

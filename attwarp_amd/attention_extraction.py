@@ -81,6 +81,20 @@ def probe_last_query(query: torch.Tensor, key: torch.Tensor, starts: torch.Tenso
     query [B,heads,q,D] (or [B,heads,D]); key [B,kv_heads,kv,D]; starts int32 [B] on the device;
     kv_begin int32 [B] = number of left-padding keys per sample (None: none); scaling defaults to D**-0.5.
     Equals ``attn_reduce_step`` applied to HF's eager attention weights (same dtype transitions)."""
+    return _probe("attwarp_attn_probe_last_query", query, key, starts, ntok, kv_begin, scaling)
+
+
+def probe_head_mean(query: torch.Tensor, key: torch.Tensor, starts: torch.Tensor, ntok: int = NUM_IMAGE_TOKENS,
+                    kv_begin: Optional[torch.Tensor] = None, scaling: Optional[float] = None) -> torch.Tensor:
+    """The layer-selection study's raw row (Ablations/uncertainty_attn_maps_llava.py:56,
+    ``attentions[L-1][b, :, -1, span].mean(0)``) from the post-RoPE query of the last token and the key cache: the
+    same arguments and per-head probabilities as :func:`probe_last_query`, but the plain mean over heads of the eager
+    probabilities, WITHOUT the per-head renormalisation (summed in double, divided by heads, rounded once to the model
+    dtype).  -> [B,ntok] in the model dtype."""
+    return _probe("attwarp_attn_probe_head_mean", query, key, starts, ntok, kv_begin, scaling)
+
+
+def _probe(entry: str, query, key, starts, ntok, kv_begin, scaling) -> torch.Tensor:
     dev = require_gpu(query, key, starts)
     q = query[:, :, -1] if query.dim() == 4 else query
     B, heads, D = q.shape
@@ -107,10 +121,20 @@ def probe_last_query(query: torch.Tensor, key: torch.Tensor, starts: torch.Tenso
         kb = kv_begin.to(torch.int32).contiguous()
     st = starts.to(torch.int32).contiguous()
     with torch.cuda.device(dev):
-        call("attwarp_attn_probe_last_query", ptr(q), ptr(k), dt, B, heads, kv_heads, D, kv, q.stride(0), q.stride(1),
+        call(entry, ptr(q), ptr(k), dt, B, heads, kv_heads, D, kv, q.stride(0), q.stride(1),
              k.stride(0), k.stride(1), k.stride(2), ptr(kb) if kb is not None else None, ptr(st), int(ntok),
              float(D ** -0.5 if scaling is None else scaling), ptr(out), ptr(ws), stream_ptr(dev))
     return out
+
+
+def kv_begin_from_mask(attention_mask, kv: int) -> Optional[torch.Tensor]:
+    """First attended key of the last query per sample (= its left padding), int32 [B] on the mask's device, from the
+    4-D mask the attention implementation receives (bool, or additive with finfo.min); None for any other mask."""
+    if isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4:
+        row = attention_mask[:, 0, -1, :kv]                   # what the last query may attend to
+        valid = row if row.dtype == torch.bool else row > torch.finfo(row.dtype).min / 2
+        return valid.to(torch.int32).argmax(dim=-1).to(torch.int32)   # first attended key = left padding
+    return None
 
 
 class BatchMaskHookLogger(object):
@@ -202,11 +226,7 @@ class BatchMaskHookLogger(object):
         _check_slices(self.image_token_starts[:bsz], ntok, kv, "BatchMaskHookLogger._probe_attention")
         if self._starts_dev is None or self._starts_dev.device != key.device:
             self._starts_dev = torch.tensor(self.image_token_starts, dtype=torch.int32, device=key.device)
-        kv_begin = None
-        if isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4:
-            row = attention_mask[:, 0, -1, :kv]                   # what the last query may attend to
-            valid = row if row.dtype == torch.bool else row > torch.finfo(row.dtype).min / 2
-            kv_begin = valid.to(torch.int32).argmax(dim=-1).to(torch.int32)   # first attended key = left padding
+        kv_begin = kv_begin_from_mask(attention_mask, kv)
         self.step_attentions.append(probe_last_query(query, key, self._starts_dev[:bsz], ntok, kv_begin, scaling))
 
     def register_probe(self):

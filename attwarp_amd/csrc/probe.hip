@@ -180,6 +180,85 @@ static int launch_t(const void* q, const void* k, const Params& p, int lpr, int 
 
 static size_t esize(int dtype) { return dtype == ATTWARP_F32 ? 4 : 2; }
 
+// The layer-selection study's raw row (Ablations/uncertainty_attn_maps_llava.py:56: attentions[L-1][b, :, -1, span].mean(0)):
+// out[b, t] = mean over heads of p[b, h, st+t], WITHOUT the per-head renormalisation of A1.  Sum in double in head order,
+// divided by heads in double, rounded once to T.  One thread per (b, t): consecutive t are consecutive addresses.
+template <typename T>
+__global__ __launch_bounds__(NT) void head_mean_kernel(const T* __restrict__ probs, int B, int heads, int ntok,
+                                                       T* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+  if (i >= (int64_t)B * ntok) return;
+  const int64_t b = i / ntok, t = i - b * ntok;
+  const T* p = probs + b * heads * ntok + t;
+  double s = (double)to_f32<T>(p[0]);
+  for (int h = 1; h < heads; ++h) s += (double)to_f32<T>(p[(int64_t)h * ntok]);
+  out[i] = from_f64<T>(s / (double)heads);
+}
+
+static int launch_head_mean(int dtype, const void* probs, int B, int heads, int ntok, void* out, hipStream_t st) {
+  const unsigned grid = (unsigned)(((int64_t)B * ntok + NT - 1) / NT);
+  switch (dtype) {
+    case ATTWARP_F32:
+      hipLaunchKernelGGL(head_mean_kernel<float>, dim3(grid), dim3(NT), 0, st, (const float*)probs, B, heads, ntok, (float*)out);
+      break;
+    case ATTWARP_F16:
+      hipLaunchKernelGGL(head_mean_kernel<__half>, dim3(grid), dim3(NT), 0, st, (const __half*)probs, B, heads, ntok,
+                         (__half*)out);
+      break;
+    default:
+      hipLaunchKernelGGL(head_mean_kernel<__hip_bfloat16>, dim3(grid), dim3(NT), 0, st, (const __hip_bfloat16*)probs, B,
+                         heads, ntok, (__hip_bfloat16*)out);
+      break;
+  }
+  return check_launch("head_mean_kernel");
+}
+
+// Validation and the per-head probability launch shared by both probe entry points: p[B,heads,ntok] (the image-token slice
+// of every head's last-query row) lands at ws + 16, the word at ws is the chained A1 reduction's slice start.
+static int probe_rows(const char* who, const void* q, const void* k, int dtype, int B, int heads, int kv_heads,
+                      int head_dim, int kv_len, int64_t q_stride_b, int64_t q_stride_h, int64_t k_stride_b,
+                      int64_t k_stride_h, int64_t k_stride_t, const int32_t* kv_begin, const int32_t* starts, int ntok,
+                      float scaling, void* out, void* ws, hipStream_t st) {
+  ATTWARP_REQUIRE(q && k && starts && out && ws, "%s: null pointer", who);
+  ATTWARP_REQUIRE(B > 0 && heads > 0 && kv_heads > 0 && head_dim > 0 && kv_len > 0 && ntok > 0,
+                  "%s: non-positive size", who);
+  ATTWARP_REQUIRE(dtype == ATTWARP_F32 || dtype == ATTWARP_F16 || dtype == ATTWARP_BF16,
+                  "%s: dtype must be F32, F16 or BF16 (got %d)", who, dtype);
+  ATTWARP_REQUIRE(heads % kv_heads == 0, "%s: heads=%d is not a multiple of kv_heads=%d", who, heads, kv_heads);
+  ATTWARP_REQUIRE(ntok <= kv_len, "%s: ntok=%d > kv_len=%d", who, ntok, kv_len);
+  if ((long long)B * heads > 2147483647LL) return fail(ATTWARP_E_UNSUPPORTED, "%s: B*heads too large", who);
+  if (ntok > 1024) return fail(ATTWARP_E_UNSUPPORTED, "%s: ntok=%d > 1024", who, ntok);
+  if (kv_len > MAX_KV) return fail(ATTWARP_E_UNSUPPORTED, "%s: kv_len=%d > %d", who, kv_len, MAX_KV);
+  const size_t es = esize(dtype);
+  const int per = (int)(16 / es);                      // elements per 16-byte chunk
+  if (head_dim % per != 0)
+    return fail(ATTWARP_E_UNSUPPORTED, "%s: head_dim=%d is not a multiple of %d", who, head_dim, per);
+  const int64_t strides[5] = {q_stride_b, q_stride_h, k_stride_b, k_stride_h, k_stride_t};
+  for (int i = 0; i < 5; ++i)
+    if (strides[i] % per != 0)
+      return fail(ATTWARP_E_UNSUPPORTED, "%s: strides must be multiples of %d elements (16 bytes)", who, per);
+  if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(ws)) & 15u) != 0)
+    return fail(ATTWARP_E_UNSUPPORTED, "%s: q, k and ws must be 16-byte aligned", who);
+  const int nc = head_dim / per;                       // chunks per row
+  int lpr = 16;
+  while (nc % lpr != 0) lpr >>= 1;
+  const int cpl = nc / lpr;
+  if (cpl > MAXCPL)
+    return fail(ATTWARP_E_UNSUPPORTED, "%s: head_dim=%d needs %d chunks per lane (max %d)", who, head_dim, cpl, MAXCPL);
+
+  Params p;
+  p.heads = heads; p.group = heads / kv_heads; p.kv = kv_len; p.ntok = ntok;
+  p.q_sb = q_stride_b; p.q_sh = q_stride_h; p.k_sb = k_stride_b; p.k_sh = k_stride_h; p.k_st = k_stride_t;
+  p.kv_begin = kv_begin; p.starts = starts; p.scale = scaling;
+  p.zero = reinterpret_cast<int32_t*>(ws);
+  void* probs = reinterpret_cast<char*>(ws) + 16;
+  switch (dtype) {
+    case ATTWARP_F32: return launch_t<float>(q, k, p, lpr, cpl, B, probs, st);
+    case ATTWARP_F16: return launch_t<__half>(q, k, p, lpr, cpl, B, probs, st);
+    default: return launch_t<__hip_bfloat16>(q, k, p, lpr, cpl, B, probs, st);
+  }
+}
+
 }  // namespace probe
 }  // namespace attwarp
 
@@ -196,51 +275,26 @@ extern "C" int attwarp_attn_probe_last_query(const void* q, const void* k, int d
                                              int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
                                              const int32_t* kv_begin, const int32_t* starts, int ntok, float scaling,
                                              void* out, void* ws, void* stream) {
-  ATTWARP_REQUIRE(q && k && starts && out && ws, "attn_probe_last_query: null pointer");
-  ATTWARP_REQUIRE(B > 0 && heads > 0 && kv_heads > 0 && head_dim > 0 && kv_len > 0 && ntok > 0,
-                  "attn_probe_last_query: non-positive size");
-  ATTWARP_REQUIRE(dtype == ATTWARP_F32 || dtype == ATTWARP_F16 || dtype == ATTWARP_BF16,
-                  "attn_probe_last_query: dtype must be F32, F16 or BF16 (got %d)", dtype);
-  ATTWARP_REQUIRE(heads % kv_heads == 0, "attn_probe_last_query: heads=%d is not a multiple of kv_heads=%d", heads,
-                  kv_heads);
-  ATTWARP_REQUIRE(ntok <= kv_len, "attn_probe_last_query: ntok=%d > kv_len=%d", ntok, kv_len);
-  if ((long long)B * heads > 2147483647LL) return fail(ATTWARP_E_UNSUPPORTED, "attn_probe_last_query: B*heads too large");
-  if (ntok > 1024) return fail(ATTWARP_E_UNSUPPORTED, "attn_probe_last_query: ntok=%d > 1024", ntok);
-  if (kv_len > probe::MAX_KV)
-    return fail(ATTWARP_E_UNSUPPORTED, "attn_probe_last_query: kv_len=%d > %d", kv_len, probe::MAX_KV);
-  const size_t es = probe::esize(dtype);
-  const int per = (int)(16 / es);                      // elements per 16-byte chunk
-  if (head_dim % per != 0)
-    return fail(ATTWARP_E_UNSUPPORTED, "attn_probe_last_query: head_dim=%d is not a multiple of %d", head_dim, per);
-  const int64_t strides[5] = {q_stride_b, q_stride_h, k_stride_b, k_stride_h, k_stride_t};
-  for (int i = 0; i < 5; ++i)
-    if (strides[i] % per != 0)
-      return fail(ATTWARP_E_UNSUPPORTED, "attn_probe_last_query: strides must be multiples of %d elements (16 bytes)",
-                  per);
-  if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(ws)) & 15u) != 0)
-    return fail(ATTWARP_E_UNSUPPORTED, "attn_probe_last_query: q, k and ws must be 16-byte aligned");
-  const int nc = head_dim / per;                       // chunks per row
-  int lpr = 16;
-  while (nc % lpr != 0) lpr >>= 1;
-  const int cpl = nc / lpr;
-  if (cpl > probe::MAXCPL)
-    return fail(ATTWARP_E_UNSUPPORTED, "attn_probe_last_query: head_dim=%d needs %d chunks per lane (max %d)",
-                head_dim, cpl, probe::MAXCPL);
-
-  probe::Params p;
-  p.heads = heads; p.group = heads / kv_heads; p.kv = kv_len; p.ntok = ntok;
-  p.q_sb = q_stride_b; p.q_sh = q_stride_h; p.k_sb = k_stride_b; p.k_sh = k_stride_h; p.k_st = k_stride_t;
-  p.kv_begin = kv_begin; p.starts = starts; p.scale = scaling;
-  p.zero = reinterpret_cast<int32_t*>(ws);
-  void* probs = reinterpret_cast<char*>(ws) + 16;
   hipStream_t st = as_stream(stream);
-  int rc;
-  switch (dtype) {
-    case ATTWARP_F32: rc = probe::launch_t<float>(q, k, p, lpr, cpl, B, probs, st); break;
-    case ATTWARP_F16: rc = probe::launch_t<__half>(q, k, p, lpr, cpl, B, probs, st); break;
-    default: rc = probe::launch_t<__hip_bfloat16>(q, k, p, lpr, cpl, B, probs, st); break;
-  }
-  if (rc) return rc;
+  if (const int rc = probe::probe_rows("attn_probe_last_query", q, k, dtype, B, heads, kv_heads, head_dim, kv_len,
+                                       q_stride_b, q_stride_h, k_stride_b, k_stride_h, k_stride_t, kv_begin, starts, ntok,
+                                       scaling, out, ws, st))
+    return rc;
   // A1 on the probed rows: probs [B,heads,ntok], slice start 0 for every sample
-  return launch_attn_step_dtype(dtype, probs, B, heads, (int64_t)heads * ntok, ntok, 0, 1, p.zero, 1, 0, ntok, out, st);
+  void* probs = reinterpret_cast<char*>(ws) + 16;
+  return launch_attn_step_dtype(dtype, probs, B, heads, (int64_t)heads * ntok, ntok, 0, 1, reinterpret_cast<int32_t*>(ws), 1,
+                                0, ntok, out, st);
+}
+
+extern "C" int attwarp_attn_probe_head_mean(const void* q, const void* k, int dtype, int B, int heads, int kv_heads,
+                                            int head_dim, int kv_len, int64_t q_stride_b, int64_t q_stride_h,
+                                            int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                                            const int32_t* kv_begin, const int32_t* starts, int ntok, float scaling,
+                                            void* out, void* ws, void* stream) {
+  hipStream_t st = as_stream(stream);
+  if (const int rc = probe::probe_rows("attn_probe_head_mean", q, k, dtype, B, heads, kv_heads, head_dim, kv_len,
+                                       q_stride_b, q_stride_h, k_stride_b, k_stride_h, k_stride_t, kv_begin, starts, ntok,
+                                       scaling, out, ws, st))
+    return rc;
+  return probe::launch_head_mean(dtype, reinterpret_cast<char*>(ws) + 16, B, heads, ntok, out, st);
 }

@@ -123,6 +123,17 @@ ATTWARP_API int attwarp_attn_probe_last_query(const void* q, const void* k, int 
                                   const int32_t* kv_begin, const int32_t* starts, int ntok, float scaling,
                                   void* out, void* ws, void* stream);
 
+/* ---- the layer-selection study's raw row (Ablations/uncertainty_attn_maps_llava.py:56:
+ * out.attentions[L-1][b, :, -1, span].mean(0)): same arguments, workspace and per-head probabilities as
+ * attwarp_attn_probe_last_query, but out[b,t] = mean over heads of p[b,h,st+t] WITHOUT the per-head renormalisation:
+ * the head probabilities (model dtype) summed in double in head order, divided by heads in double, rounded once to
+ * `dtype`.  Two launches (probabilities, head mean). */
+ATTWARP_API int attwarp_attn_probe_head_mean(const void* q, const void* k, int dtype, int B, int heads, int kv_heads,
+                                 int head_dim, int kv_len, int64_t q_stride_b, int64_t q_stride_h,
+                                 int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                                 const int32_t* kv_begin, const int32_t* starts, int ntok, float scaling,
+                                 void* out, void* ws, void* stream);
+
 /* ---- A3: revise_mask = normalize("min") -> enhance -> k x k box filter, llava.py:207-238
  * mask [B,n,n] float32 -> out [B,n,n] float32 (n <= 32, odd kernel_size <= 7). */
 ATTWARP_API int attwarp_mask_postproc(const float* mask, int B, int n, int kernel_size, float enhance_coe,
@@ -434,6 +445,42 @@ typedef struct attwarp_overlay_image {
 ATTWARP_API size_t attwarp_overlay_workspace_bytes(int B);
 ATTWARP_API int attwarp_heatmap_overlay(const attwarp_overlay_image* images, const attwarp_overlay_image* images_dev, int B,
                             int map_dtype, int style, double alpha, int in_order, int out_order, void* ws, void* stream);
+
+/* ---- the layer-selection study's maps and box metrics (Ablations/uncertainty_attn_maps_llava.py:62-64, 164;
+ * Ablations/attention_redistribution/metrics.py:15-25), a whole batch of differently sized maps per call.
+ * cv2.resize(float32 grid [h,w], (W, H), INTER_LANCZOS4) = OpenCV 4.x resizeGeneric_ (HResizeLanczos4, VResizeLanczos4)
+ * for one channel: horizontal pass, then vertical pass, float32 with every product and sum rounded, taps in ascending
+ * order; dsize == ssize copies.  Parity with OpenCV itself is a few ulp (its vectorised vertical pass sums in another
+ * order); bit-exact with tests/grounding_ref.py.
+ *
+ * HOST: attwarp_lanczos4_coeffs(n_in, n_out, ofs int32 [n_out], coeffs float [n_out,8]): the per-axis tables of
+ * resizeGeneric_ (source index ofs[d] = floor((float)((d + 0.5) * n_in / n_out - 0.5)), taps ofs-3 .. ofs+4 clamped into
+ * the source, interpolateLanczos4 with glibc's sin / cos).  Callers upload them once per distinct size.
+ *
+ * A call takes M records (a HOST array, validated here and used to size the grid, plus a DEVICE copy of the same bytes,
+ * 8-byte aligned): */
+typedef struct attwarp_grid_map {
+  const float* src;                                /* device: grid [h,w] (resize, fused metrics) or map [H,W] (dense metrics) */
+  float* out;                                      /* device: [H,W] output of attwarp_resize_lanczos4 (unused by the metrics) */
+  const int32_t* ofs_x; const float* coef_x;       /* device: attwarp_lanczos4_coeffs(w, W) tables (unused when dense) */
+  const int32_t* ofs_y; const float* coef_y;       /* device: attwarp_lanczos4_coeffs(h, H) tables */
+  int32_t H, W;                                    /* output / map size */
+  int64_t box_x, box_y, box_w, box_h;              /* metrics: the box as interpret_bbox gives it (top1's inequalities) */
+  int32_t r0, r1, c0, c1;                          /* metrics: the box's numpy slice a[r0:r1, c0:c1], resolved by the caller */
+} attwarp_grid_map;
+/* resize: every record's src is a grid [h,w] (h, w <= 64), out its own [H,W].  H, W <= 32768, M <= 65535.
+ * box metrics: fused != 0 -- src is a grid [h,w] and the value of a pixel is its LANCZOS4 value, computed on the fly
+ * (the full-resolution map is never written); fused == 0 -- src is a float32 map [H,W] in memory (h, w ignored).
+ * Per record: argmax (int64, row-major, np.argmax: first index among equal maxima, -0.0 == 0.0, the first NaN wins),
+ * top1 (int32: box_x <= c < box_x + box_w and box_y <= r < box_y + box_h at the argmax), am (float64: sum over the slice
+ * / (sum over the map + 1e-12), both sums in float64).  ws: attwarp_box_metrics_workspace_bytes(maps, M) bytes, 16-byte
+ * aligned.  Deterministic (fixed-order reductions, two launches); both paths give identical bits on identical values. */
+ATTWARP_API int attwarp_lanczos4_coeffs(int n_in, int n_out, int32_t* ofs, float* coeffs);
+ATTWARP_API int attwarp_resize_lanczos4(const attwarp_grid_map* maps, const attwarp_grid_map* maps_dev, int M, int h, int w,
+                            void* stream);
+ATTWARP_API size_t attwarp_box_metrics_workspace_bytes(const attwarp_grid_map* maps, int M);
+ATTWARP_API int attwarp_box_metrics(const attwarp_grid_map* maps, const attwarp_grid_map* maps_dev, int M, int fused, int h,
+                        int w, int64_t* argmax, int32_t* top1, double* am, void* ws, void* stream);
 
 /* ---- A12 / A13 tail: cv2.remap(INTER_LINEAR, BORDER_REPLICATE) with separable maps,
  * AGW/new_method.py:268-271, MN/checkpoint_utils.py:195-198.
