@@ -123,9 +123,13 @@ __device__ void right_inverse_block(const float* y, int Lo, int L, const double*
   }
   __syncthreads();
   for (int l = threadIdx.x; l < L; l += blockDim.x) {
+    // Window k covers l iff floor(k L / Lo) <= l < ceil((k+1) L / Lo), i.e. iff k0 <= k <= k1 with k0 = floor(l Lo / L)
+    // and k1 = floor(((l+1) Lo - 1) / L) <= Lo - 1.  For L >= Lo, k1 <= k0 + 1 (at most three trips, as before); for
+    // L < Lo an output lies in up to ceil(Lo / L) + 1 windows.  Windows that do not cover l add nothing.
     const int k0 = (int)(((unsigned)l * (unsigned)Lo) / (unsigned)L);
+    const int k1 = (int)((((unsigned)l + 1u) * (unsigned)Lo - 1u) / (unsigned)L);
     float x = 0.0f;
-    for (int k = max(k0 - 1, 0); k <= min(k0 + 1, Lo - 1); ++k) {
+    for (int k = max(k0 - 1, 0); k <= min(k1, Lo - 1); ++k) {
       int s, e;
       adaptive_window(k, L, Lo, s, e);
       if (l >= s && l < e) {

@@ -146,9 +146,12 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 // A launch gets at most 64 KB of dynamic LDS unless the kernel has been granted more (a CU of gfx950 has 160 KB).  The
 // per-axis kernels keep a whole axis in LDS (12 bytes per pixel of max(W, H): 64 KB is reached near 4800 pixels), so
 // their launchers call this first; it is idempotent and touches only the runtime's attribute of that one kernel.
+// static_bytes: the kernel's own __shared__ variables (the "LDS Size" of -Rpass-analysis=kernel-resource-usage at zero
+// dynamic LDS), for launchers whose dynamic size can come within that of a limit; the grant then covers both.
 constexpr size_t LDS_DEFAULT_MAX = 64 * 1024, LDS_CU_BYTES = 160 * 1024;
 template <typename K>
-inline int grant_dynamic_lds(K kernel, size_t bytes, const char* what) {
+inline int grant_dynamic_lds(K kernel, size_t bytes, const char* what, size_t static_bytes = 0) {
+  bytes += static_bytes;
   if (bytes <= LDS_DEFAULT_MAX) return ATTWARP_OK;
   if (bytes > LDS_CU_BYTES) return fail(ATTWARP_E_UNSUPPORTED, "%s: needs %zu bytes of LDS (> %zu)", what, bytes, LDS_CU_BYTES);
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);

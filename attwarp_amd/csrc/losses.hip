@@ -12,6 +12,9 @@ namespace attwarp {
 namespace {
 
 constexpr int NT = LOSS_NT;
+// static LDS next to the dynamic rows (kernel-resource-usage: 32 bytes for a kernel's `red`, 80 with finish_loss's
+// `red` and `last`), counted where a launcher's dynamic LDS can reach a limit
+constexpr size_t RED_LDS = (NT / WAVE) * sizeof(double), FINISH_LDS = 48;
 
 // ---- cdf_from_density_downsample (MN/losses.py:70-77).  grid = B ----------------------------------------------------
 __global__ __launch_bounds__(NT) void cdf_downsample_kernel(const float* __restrict__ p, int N, int L, float* __restrict__ F) {
@@ -426,8 +429,9 @@ extern "C" int attwarp_cdf_downsample(const float* p, int B, int N, int L, float
   ATTWARP_REQUIRE(L > 0, "cdf_downsample: non-positive size");
   if (const int rc = launch_dims_ok(B, N, "cdf_downsample")) return rc;
   if (L > LOSS_MAX_N) return fail(ATTWARP_E_UNSUPPORTED, "cdf_downsample: L=%d > %d", L, LOSS_MAX_N);
-  hipLaunchKernelGGL(cdf_downsample_kernel, dim3(B), dim3(NT), (size_t)(N + L) * sizeof(double), as_stream(stream), p, N,
-                     L, F);
+  const size_t lds = (size_t)(N + L) * sizeof(double);
+  if (const int rc = grant_dynamic_lds(cdf_downsample_kernel, lds, "cdf_downsample", RED_LDS)) return rc;
+  hipLaunchKernelGGL(cdf_downsample_kernel, dim3(B), dim3(NT), lds, as_stream(stream), p, N, L, F);
   return check_launch("cdf_downsample_kernel");
 }
 
@@ -435,8 +439,9 @@ extern "C" int attwarp_l1_cdf_loss(const float* p, const float* q, int B, int N,
                                    float* loss, void* stream) {
   ATTWARP_REQUIRE(p && q && parts && ticket && loss, "l1_cdf_loss: null pointer");
   if (const int rc = launch_dims_ok(B, N, "l1_cdf_loss")) return rc;
-  hipLaunchKernelGGL(l1_cdf_kernel, dim3(B), dim3(NT), (size_t)2 * N * sizeof(double), as_stream(stream), p, q, B, N,
-                     parts, ticket, loss);
+  const size_t lds = (size_t)2 * N * sizeof(double);
+  if (const int rc = grant_dynamic_lds(l1_cdf_kernel, lds, "l1_cdf_loss", RED_LDS + FINISH_LDS)) return rc;
+  hipLaunchKernelGGL(l1_cdf_kernel, dim3(B), dim3(NT), lds, as_stream(stream), p, q, B, N, parts, ticket, loss);
   return check_launch("l1_cdf_kernel");
 }
 
@@ -444,8 +449,9 @@ extern "C" int attwarp_l1_cdf_loss_backward(const float* p, const float* q, int 
                                             float* gq, void* stream) {
   ATTWARP_REQUIRE(p && q && gout && gp && gq, "l1_cdf_loss_backward: null pointer");
   if (const int rc = launch_dims_ok(B, N, "l1_cdf_loss_backward")) return rc;
-  hipLaunchKernelGGL(l1_cdf_backward_kernel, dim3(B), dim3(NT), (size_t)3 * N * sizeof(double), as_stream(stream), p, q,
-                     B, N, gout, gp, gq);
+  const size_t lds = (size_t)3 * N * sizeof(double);
+  if (const int rc = grant_dynamic_lds(l1_cdf_backward_kernel, lds, "l1_cdf_loss_backward", RED_LDS)) return rc;
+  hipLaunchKernelGGL(l1_cdf_backward_kernel, dim3(B), dim3(NT), lds, as_stream(stream), p, q, B, N, gout, gp, gq);
   return check_launch("l1_cdf_backward_kernel");
 }
 

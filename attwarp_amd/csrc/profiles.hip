@@ -449,8 +449,9 @@ extern "C" int attwarp_gt_marginals(const float* A, int B, int H, int W, float* 
   if (!handled) rc = launch_profiles<float, XfClampPos>(A, B, H, W, XfClampPos{}, P, col, ls, st);
   if (rc) return rc;
   const int n = H > W ? H : W;
-  hipLaunchKernelGGL(marginals_finalize_kernel, dim3(B, 2), dim3(NT), (size_t)n * sizeof(double), st, col, ls,
-                     P.nleaves, H, W, px, py);
+  const size_t lds = (size_t)n * sizeof(double);
+  if (const int rc2 = grant_dynamic_lds(marginals_finalize_kernel, lds, "gt_marginals", 32)) return rc2;   // 32: its `red`
+  hipLaunchKernelGGL(marginals_finalize_kernel, dim3(B, 2), dim3(NT), lds, st, col, ls, P.nleaves, H, W, px, py);
   return check_launch("marginals_finalize_kernel");
 }
 
@@ -461,8 +462,10 @@ extern "C" int attwarp_adaptive_avg_pool(const float* A, int B, int H, int W, in
   if (oh > 65535 || B > 65535) return fail(ATTWARP_E_UNSUPPORTED, "adaptive_avg_pool: oh/B > 65535");
   if (W > 16384) return fail(ATTWARP_E_UNSUPPORTED, "adaptive_avg_pool: W=%d > 16384", W);
   const int vec_ok = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0);
-  hipLaunchKernelGGL(adaptive_pool_kernel, dim3(oh, B), dim3(NT), (size_t)W * sizeof(double), as_stream(stream), A, H,
-                     W, oh, ow, sanitize, vec_ok, out);
+  const size_t lds = (size_t)W * sizeof(double);            // (no static LDS in this kernel)
+  if (const int rc = grant_dynamic_lds(adaptive_pool_kernel, lds, "adaptive_avg_pool")) return rc;
+  hipLaunchKernelGGL(adaptive_pool_kernel, dim3(oh, B), dim3(NT), lds, as_stream(stream), A, H, W, oh, ow, sanitize,
+                     vec_ok, out);
   return check_launch("adaptive_pool_kernel");
 }
 
@@ -550,7 +553,8 @@ extern "C" int attwarp_build_axis_cdf_targets(const float* A, int B, int H, int 
   if (!pw_build(W, P) || H > 16384) return fail(ATTWARP_E_UNSUPPORTED, "build_axis_cdf_targets: H, W must be <= 16384");
   const int n = H > W ? H : W;
   const size_t lds = (size_t)(n + L) * sizeof(double);
-  if (const int rc = grant_dynamic_lds(axis_cdf_targets_kernel, lds, "build_axis_cdf_targets")) return rc;
+  // 32: the kernel's `red`.  n = 16384 with L = 4096 is 160 KB of rows, a CU's whole LDS: with `red` it does not fit.
+  if (const int rc = grant_dynamic_lds(axis_cdf_targets_kernel, lds, "build_axis_cdf_targets", 32)) return rc;
   double* col = (double*)ws;
   double* ls = col + (size_t)B * W;
   hipStream_t st = as_stream(stream);
@@ -570,8 +574,9 @@ extern "C" int attwarp_trainer_attention_targets(const float* A, const int32_t* 
   if (W > 16384) return fail(ATTWARP_E_UNSUPPORTED, "trainer_attention_targets: W=%d > 16384", W);
   const int vec_ok = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(trainer_pool_kernel, dim3(oh, B), dim3(NT), (size_t)W * sizeof(double), st, A, modes, H, W, oh, ow,
-                     vec_ok, pooled);
+  const size_t lds = (size_t)W * sizeof(double);            // (no static LDS in this kernel)
+  if (const int rc = grant_dynamic_lds(trainer_pool_kernel, lds, "trainer_attention_targets")) return rc;
+  hipLaunchKernelGGL(trainer_pool_kernel, dim3(oh, B), dim3(NT), lds, st, A, modes, H, W, oh, ow, vec_ok, pooled);
   if (const int rc = check_launch("trainer_pool_kernel")) return rc;
   hipLaunchKernelGGL(trainer_marginals_kernel, dim3(B), dim3(NT), 0, st, pooled, modes, oh, ow, px, py);
   return check_launch("trainer_marginals_kernel");

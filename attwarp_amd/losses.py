@@ -280,7 +280,10 @@ def pdf_l1_loss(px_s: torch.Tensor, py_s: torch.Tensor, px_gt_vis: torch.Tensor,
     """The trainer's ``L_pdf`` (MN/trainer.py:216-250): the low-resolution PDFs (px_s, px_gt_vis (B,Lx); py_s, py_gt_vis
     (B,Ly)) are up-sampled by the right inverse to W and H (``eps``: its ridge term, as ``upsample_pdf_right_inverse``),
     clamped at 0 and renormalised with clamp_min(1e-6); returns ``l1_loss(x) + l1_loss(y)``.  One launch forward, one
-    backward (gradients for px_s and py_s; the GT PDFs are targets)."""
+    backward (gradients for px_s and py_s; the GT PDFs are targets).  An image axis shorter than its low resolution has a
+    singular system once the float32 Gram matrix has lost a ridge as small as the default: building its table raises
+    ``numpy.linalg.LinAlgError`` (the reference's float32 solve fails there too); with an ``eps`` that float32 keeps the
+    kernels serve such lengths."""
     W, H = int(W), int(H)
     require_gpu(px_s, py_s, px_gt_vis, py_gt_vis)
     if _lib.needs_grad(px_gt_vis, py_gt_vis):

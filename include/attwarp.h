@@ -509,7 +509,9 @@ enum { ATTWARP_RECON_MSE = 0, ATTWARP_RECON_L1 = 1 };
 enum { ATTWARP_TT_IDENTITY = 0, ATTWARP_TT_SQRT = 1, ATTWARP_TT_NONE = 2 };
 
 /* cdf_from_density_downsample (:70-77): p [B,N] -> F [B,L].  build_axis_cdf_targets (:50-67): A [B,H,W] -> Fx, Fy
- * [B,L]; ws: attwarp_axis_sums_workspace_bytes(B,H,W) bytes.  Both forward only. */
+ * [B,L]; ws: attwarp_axis_sums_workspace_bytes(B,H,W) bytes.  Both forward only.  build_axis_cdf_targets keeps
+ * max(H,W) + L doubles in LDS: H, W <= 16384 and L <= 4096, but not the largest of both at once (ATTWARP_E_UNSUPPORTED
+ * when max(H,W) + L > 20476). */
 ATTWARP_API int attwarp_cdf_downsample(const float* p, int B, int N, int L, float* F, void* stream);
 ATTWARP_API int attwarp_build_axis_cdf_targets(const float* A, int B, int H, int W, int L, float* Fx, float* Fy, void* ws,
                                    void* stream);
@@ -539,7 +541,8 @@ ATTWARP_API int attwarp_entropy_backward(const float* p, int B, int N, float eps
 /* The trainer's image-resolution PDF loss (MN/trainer.py:216-250): px, gx [B,Lx], py, gy [B,Ly] low-resolution PDFs
  * (prediction, target) -> right-inverse up-sample to W / H (inv_x: [Lx,Lx], inv_y: [Ly,Ly] as for
  * attwarp_upsample_pdf_right_inverse), clamp_min(0), renormalise, l1_loss(x) + l1_loss(y); parts [2B].
- * Lx, Ly <= 64.  Backward -> gpx [B,Lx], gpy [B,Ly] (the targets get none). */
+ * Lx, Ly <= 64; W and H may be shorter than Lx and Ly (the kernels walk every window that covers an output; the table
+ * is the caller's).  Backward -> gpx [B,Lx], gpy [B,Ly] (the targets get none). */
 ATTWARP_API int attwarp_pdf_l1_loss(const float* px, const float* py, const float* gx, const float* gy, int B, int Lx,
                         int Ly, int W, int H, const double* inv_x, const double* inv_y, double* parts,
                         uint32_t* ticket, float* loss, void* stream);

@@ -2,13 +2,17 @@
 tolerance is written next to the stage): attention maps from uint8 / float32 / float64 attention with every transform
 (A13), PDF -> CDF -> maps chain with hostile densities (A8-A11), cdf repair / resample (A10), attention reduce with
 random geometry (A1/A2), LANCZOS mask up-sample vs the Pillow restatement (A4), revise_mask (A3), adaptive pool and
-gt_marginals (A5/A6), safe_softmax (A7).   usage: fuzz_stages.py [seconds per stage] [seed]"""
+gt_marginals (A5/A6), safe_softmax (A7), and the training kernels (row losses, recon losses, pdf_l1 with the trainer's targets:
+forward and backward against the float64 restatement tests/losses_ref.py at the bounds of tests/test_losses_gpu.py).
+usage: fuzz_stages.py [seconds per stage] [seed]"""
 import os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from attwarp_amd import checkpoint_utils as cu, attention_extraction as ae, new_method as nm, pipeline, model
+sys.path.insert(1, os.path.join(ROOT, "tests"))
+from attwarp_amd import checkpoint_utils as cu, attention_extraction as ae, new_method as nm, pipeline, model, losses, _tables
 from oracle import warp_oracle as O
+import losses_ref as R
 dev = torch.device("cuda:0")
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 20.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -278,7 +282,74 @@ def g_ragged_chain():
         ok = ok and len(got) == nb and all(bool(torch.equal(g, o)) for g, o in zip(got, outs))
     return ok, (B, nb, Ho, Wo, [tuple(i.shape[:2]) for i in imgs], xf)
 
-for name, gen in (("ragged chain vs per-image + oracle", g_ragged_chain), ("MaskChainStream vs warp_from_masks", g_mask_chain_stream), ("clip_preprocess (+pad) (f3)", g_clip), ("probe_last_query (f4)", g_probe), ("MarginalNet tail (f1)", g_mn_tail), ("MarginalNet forward fused vs stock (f1)", g_marginalnet),
+# ---- the training kernels against tests/losses_ref.py (float64, CPU autograd).  Bounds as tests/test_losses_gpu.py: loss 1e-5
+# relative, targets 2e-6 absolute, gradients |g - g_ref|_inf <= 1e-4 |g_ref|_inf + 1e-9.  An L1 case without the generator's
+# sign margin (losses_ref.l1_margin_ok) is drawn again (the generator returns None).
+def loss_ok(got, ref): return abs(float(got.detach()) - float(ref)) <= 1e-5 * abs(float(ref)) + 1e-12
+def grad_ok(got, ref): return np.abs(got.detach().double().cpu().numpy() - ref).max() <= 1e-4 * np.abs(ref).max() + 1e-9
+def target_ok(got, ref): return np.abs(got.detach().double().cpu().numpy() - ref.detach().numpy()).max() <= 2e-6
+def loss_case(fn, ref_fn, arrays, grad_of):
+    xs = [T(a).requires_grad_(i in grad_of) for i, a in enumerate(arrays)]
+    rs = [R.t64(a, i in grad_of) for i, a in enumerate(arrays)]
+    up = float(rng.choice([1.0, 0.1, -2.5]))
+    loss, ref = fn(*xs), ref_fn(*rs)
+    ok = loss_ok(loss, ref.detach())
+    (loss * up).backward()
+    for i, g in zip(grad_of, R.grads(ref, [rs[i] for i in grad_of], up)): ok = ok and bool(grad_ok(xs[i].grad, g))
+    return ok
+
+def g_row_losses():
+    B = int(rng.choice([1, 2, 3, 7, 255, 257, 300])); n = dim(1, 4097); L = dim(1, 4097); peak = float(rng.choice([0.5, 1.0, 3.0]))
+    if B > 7: n = min(n, 400)
+    p, q = R.softmax_rows(rng, B, n, peak), R.softmax_rows(rng, B, n, peak)
+    ok = loss_case(losses.sym_kl, R.sym_kl, (p, q), (0, 1)) and loss_case(model.entropy, R.entropy, (p,), (0,))
+    h = p.copy()
+    if rng.random() < 0.3: h[0, rng.integers(0, n)] = rng.choice([np.nan, np.inf, -np.inf, -0.25])
+    if rng.random() < 0.2: h[-1] = 0
+    ok = ok and bool(target_ok(losses.cdf_from_density_downsample(T(h), L), R.cdf_from_density_downsample(R.t64(h), L)))
+    a = float(rng.choice([0.05, 0.3, 1.0]))
+    ok = ok and bool(target_ok(model.mix_with_uniform(T(p), a), R.mix_with_uniform(R.t64(p), a)))
+    if R.l1_cdf_margin_ok(p, q): ok = ok and loss_case(losses.l1_cdf_loss, R.l1_cdf_loss, (p, q), (0, 1))
+    return ok, (B, n, L, peak, a)
+
+def g_recon():
+    B = int(rng.choice([1, 2, 3, 300])); H, W = dim(1, 4097), dim(1, 4097)
+    if H * W * B > 1 << 22: H = max(1, (1 << 22) // (W * B))
+    px, py = R.softmax_rows(rng, B, W), R.softmax_rows(rng, B, H)
+    A = R.unit_map(rng, (B, 1, H, W)) + np.float32(1 / 16)
+    r = rng.random()
+    if r < 0.2: A[0] = 0
+    elif r < 0.4: A[0, 0, : max(1, H // 2)] *= -1
+    ok = loss_case(losses.separable_recon_loss, R.separable_recon_loss, (px, py, A), (0, 1))
+    if R.recon_margin_ok(px, py, A): ok = ok and loss_case(losses.recon_l1, R.recon_l1, (px, py, A), (0, 1))
+    return ok, (B, H, W, r)
+
+def g_pdf_l1():
+    B = int(rng.choice([1, 2, 3, 129])); Lx, Ly = int(rng.integers(1, 65)), int(rng.integers(1, 65))
+    W, H = dim(1, 8193), dim(1, 8193)
+    eps = 1e-8 if W >= Lx and H >= Ly else 0.5             # L < Lo: a ridge float32 keeps (the default builds no table there)
+    tfms = [str(rng.choice(["sqrt", "none", "identity"])) for _ in range(B)]
+    h, w = int(rng.integers(1, 300)), int(rng.integers(1, 300))
+    A_full = R.hostile_map(rng, B, h, w) if rng.random() < 0.4 else R.unit_map(rng, (B, 1, h, w))
+    A, pxg, pyg = pipeline.trainer_attention_targets(T(A_full), tfms, (Ly, Lx))
+    rA, rpx, rpy = R.trainer_attention_targets(R.t64(A_full), tfms, (Ly, Lx))
+    ok = bool(target_ok(A, rA) and target_ok(pxg, rpx) and target_ok(pyg, rpy))
+    Fx, Fy = losses.build_axis_cdf_targets(T(A_full), L=Lx)
+    rFx, rFy = R.build_axis_cdf_targets(R.t64(A_full), Lx)
+    ok = ok and bool(target_ok(Fx, rFx) and target_ok(Fy, rFy))
+    gx, gy = pxg.cpu().numpy(), pyg.cpu().numpy()            # the kernel's own float32 targets: the same inputs on both sides
+    px, py = R.softmax_rows(rng, B, Lx, 1.0), R.softmax_rows(rng, B, Ly, 1.0)
+    inv_x, inv_y = _tables._right_inverse_inv_host(Lx, W, eps), _tables._right_inverse_inv_host(Ly, H, eps)
+    # (float32 up-sampled rows: the 1e-5 of the loss needs rows that are not nearly equal, see pdf_l1_well_conditioned)
+    if not (R.pdf_l1_margin_ok(px, py, gx, gy, W, H, inv_x, inv_y) and R.pdf_l1_well_conditioned(px, py, gx, gy, W, H, inv_x, inv_y)):
+        return (ok, (B, Lx, Ly, W, H, "targets only")) if not ok else None
+    ok = ok and loss_case(lambda a, b, c, d: losses.pdf_l1_loss(a, b, c, d, W, H, eps),
+                          lambda a, b, c, d: R.pdf_l1_loss(a, b, c, d, W, H, inv_x, inv_y), (px, py, gx, gy), (0, 1))
+    return ok, (B, Lx, Ly, W, H, eps, h, w, tfms[:3])
+
+for name, gen in (("row losses vs float64 restatement (L)", g_row_losses), ("recon losses vs float64 restatement (L)", g_recon),
+                  ("trainer targets + pdf_l1 vs float64 restatement (L)", g_pdf_l1),
+                  ("ragged chain vs per-image + oracle", g_ragged_chain), ("MaskChainStream vs warp_from_masks", g_mask_chain_stream), ("clip_preprocess (+pad) (f3)", g_clip), ("probe_last_query (f4)", g_probe), ("MarginalNet tail (f1)", g_mn_tail), ("MarginalNet forward fused vs stock (f1)", g_marginalnet),
                   ("warp_image_by_attention chain", g_chain_u8), ("attention stack -> warp (bench path)", g_stack_chain),
                   ("attention_axis_maps (A13)", g_att_maps), ("axis_maps_from_pdf (A8-A11)", g_pdf_chain),
                   ("cdf / repair / resample (A9-A10)", g_cdf_stages), ("attn reduce step (A1)", g_attn),

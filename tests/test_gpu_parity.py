@@ -736,6 +736,98 @@ def test_pdf_cdf_chain(dev, golden, L):
     assert (np.diff(F, axis=1) >= 0).all() and (F[:, -1] == 1).all()
 
 
+def _ri_row(rng, n, Lo):
+    y = rng.random((n, Lo), dtype=np.float32) ** 3 + np.float32(1e-3)
+    return (y / y.sum(1, keepdims=True)).astype(np.float32)
+
+
+def _ri_abi(dev, y, L, table=None):
+    """attwarp_upsample_pdf_right_inverse with the package's table (or ``table``, numpy float64 [Lo, Lo]) -> (rows float32,
+    the table as numpy float64)."""
+    from attwarp_amd import _tables
+    n, Lo = y.shape
+    inv = _tables.right_inverse_inv(Lo, L, 1e-8, dev) if table is None else T(np.ascontiguousarray(table, np.float64), dev)
+    yd, out = T(y, dev), torch.empty(n, L, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.call("attwarp_upsample_pdf_right_inverse", _lib.ptr(yd), n, Lo, L, _lib.ptr(inv), _lib.ptr(out), _lib.stream_ptr(dev))
+    return N(out), inv.cpu().numpy()
+
+
+@pytest.mark.parametrize("Lo", [1, 7, 8, 9, 24, 37, 63, 64])
+def test_right_inverse_geometry(dev, Lo):
+    """Every low-resolution length the ABI takes (the 8-wide dot product with its tail: Lo = 7, 8, 9, 63, 64) against every
+    window geometry of L >= Lo: one window per output (L = Lo), windows of 1 and 2 (Lo + 1), overlapping windows of 2 and 3
+    (2 Lo - 1), exact windows (2 Lo) and the inference size 336; bit for bit against the numpy oracle, and against the C
+    oracle on the package's own table."""
+    from attwarp_amd import checkpoint_utils as cu
+    from oracle import c_oracle as C
+    rng = np.random.default_rng(900 + Lo)
+    for L in sorted({Lo, Lo + 1, 2 * Lo - 1, 2 * Lo, 336}):
+        y = _ri_row(rng, 3, Lo)
+        got = N(cu.upsample_pdf_right_inverse(T(y, dev), L))
+        assert got.shape == (3, L)
+        assert np.array_equal(got, O.upsample_pdf_right_inverse(y, L)), (Lo, L)
+        abi, inv = _ri_abi(dev, y, L)
+        assert np.array_equal(abi, got), (Lo, L)
+        assert np.array_equal(abi, np.stack([C.right_inverse(r, L, inv) for r in y])), (Lo, L)
+        # the docstring invariant, pool(x_hat) = y - eps z with z = inv y: to the ridge term and the float32 rounding of
+        # x_hat (at most 3 terms tmp[k] / len per output, 2 roundings each and their sum; a column of A sums to <= 2)
+        pooled = got.astype(np.float64) @ O.pooling_matrix(Lo, L, np.float64).T
+        zmax = np.abs(y.astype(np.float64) @ inv.T).max()
+        assert np.abs(pooled - y).max() <= (1e-8 + 12 * 2.0 ** -24) * zmax, (Lo, L, np.abs(pooled - y).max(), zmax)
+
+
+@pytest.mark.parametrize("Lo,L", [(24, 8), (24, 6), (24, 1), (64, 21), (64, 5), (9, 8), (63, 62), (2, 1)])
+def test_right_inverse_shorter_than_low_resolution(dev, Lo, L):
+    """L < Lo: an output lies in up to ceil(Lo / L) + 1 windows, more than the three the block once visited (Lo = 24,
+    L = 8: output 0 lies in windows 0, 1, 2).  A A^T has rank L < Lo and its float32 form loses the 1e-8 ridge, so the
+    Python routes refuse these lengths when they build their table (LinAlgError, as the reference's float32 solve); the
+    ABI takes any table.  Both sides get one well-conditioned table here, (A A^T + 1e-3 I)^-1 in float64: the kernel
+    through the ABI, the C oracle (which walks whole windows) as an argument."""
+    from attwarp_amd import checkpoint_utils as cu
+    from oracle import c_oracle as C
+    rng = np.random.default_rng(950 + 64 * Lo + L)
+    y = _ri_row(rng, 3, Lo)
+    A = O.pooling_matrix(Lo, L, np.float64)
+    abi, inv = _ri_abi(dev, y, L, np.linalg.inv(A @ A.T + 1e-3 * np.eye(Lo)))
+    want = np.stack([C.right_inverse(r, L, inv) for r in y])
+    assert np.isfinite(want).all()
+    assert np.array_equal(abi, want), (Lo, L, np.abs(abi - want).max())
+    with pytest.raises(np.linalg.LinAlgError):                                       # never a silent row
+        cu.upsample_pdf_right_inverse(T(y, dev), L)
+    # with a ridge that float32 keeps, the Python route serves these lengths: bit for bit the numpy oracle's rows
+    assert np.array_equal(N(cu.upsample_pdf_right_inverse(T(y, dev), L, eps=2.0 ** -10)),
+                          O.upsample_pdf_right_inverse(y, L, eps=2.0 ** -10)), (Lo, L)
+    # every window's tmp reaches the row: the float64 product on the same table, to float32 rounding of its terms
+    dense = (y.astype(np.float64) @ inv.T) @ A
+    scale = (np.abs(y.astype(np.float64) @ inv.T) @ A).max()
+    # n = ceil(Lo / L) + 1 terms at most, each tmp[k] * (1 / len) with three float32 roundings (tmp, 1 / len, the product),
+    # added in sequence: |error| <= (n + 3) 2^-24 sum |terms|
+    n = -(-Lo // L) + 1
+    assert np.abs(abi - dense).max() <= (n + 3) * 2.0 ** -24 * scale, (Lo, L)
+
+
+@pytest.mark.parametrize("Lo,L", [(24, 500), (9, 17), (64, 64), (1, 5)])
+def test_right_inverse_backward_is_the_dense_adjoint(dev, Lo, L):
+    """With grad: forward == the kernel, backward == w @ M^T with M = inv @ A (as test_marginalnet_train_and_loss_helpers
+    has it at 24 -> 500), on the package's table."""
+    from attwarp_amd import checkpoint_utils as cu, _tables
+    g = torch.Generator().manual_seed(Lo * 1000 + L)
+    y = torch.rand(3, Lo, generator=g).to(dev).requires_grad_(True)
+    out = cu.upsample_pdf_right_inverse(y, L)
+    with torch.no_grad():
+        assert torch.equal(out, cu.upsample_pdf_right_inverse(y.detach(), L))
+    w = torch.randn(3, L, generator=g).to(dev)
+    (out * w).sum().backward()
+    inv = _tables.right_inverse_inv(Lo, L, 1e-8, dev).cpu()
+    M = inv @ torch.from_numpy(O.pooling_matrix(Lo, L, np.float64))                # [Lo, L]
+    want = (w.double().cpu() @ M.T).numpy()
+    # float32 pooling of w over windows of at most ceil(L / Lo) + 1 cells, a float64 product with inv, one rounding to
+    # float32: |error| <= (ceil(L / Lo) + 3) 2^-24 (|w| @ |M|^T)
+    bound = (-(-L // Lo) + 3) * 2.0 ** -24 * (np.abs(w.double().cpu().numpy()) @ np.abs(M.numpy()).T).max()
+    assert np.abs(N(y.grad) - want).max() <= bound, (Lo, L, np.abs(N(y.grad) - want).max(), bound)
+
+
 def test_right_inverse_shapes_and_bad_density(dev, golden):
     from attwarp_amd import checkpoint_utils as cu
     g = golden("pdf_cdf")

@@ -7,6 +7,7 @@ import json
 import pytest
 
 ATTWARP_E_ARG = -1
+ATTWARP_E_UNSUPPORTED = -2
 
 
 @pytest.fixture(scope="module")
@@ -79,3 +80,24 @@ def test_new_entry_points_reject_bad_arguments(lib):
     for name, cases in calls.items():
         for args in cases:
             assert getattr(lib, name)(*args) == ATTWARP_E_ARG, (name, args)
+    # size limits: a valid request the build cannot serve, refused before anything is enqueued
+    too_big = {
+        "attwarp_cdf_downsample": [(P, 2, 4097, 24, P, None), (P, 2, 24, 4097, P, None), (P, 65536, 24, 24, P, None)],
+        "attwarp_l1_cdf_loss": [(P, P, 2, 4097, P, P, P, None)],
+        "attwarp_l1_cdf_loss_backward": [(P, P, 2, 4097, P, P, P, None)],
+        "attwarp_sym_kl": [(P, P, 2, 4097, 1e-6, P, P, P, None)],
+        "attwarp_entropy": [(P, 2, 4097, 1e-8, P, P, P, None)],
+        "attwarp_entropy_backward": [(P, 2, 4097, 1e-8, P, P, None)],
+        "attwarp_recon_loss": [(P, P, P, 2, 4097, 24, 0, P, P, P, None), (P, P, P, 2, 24, 4097, 1, P, P, P, None)],
+        "attwarp_recon_loss_backward": [(P, P, P, 2, 4097, 24, 0, P, P, P, None)],
+        "attwarp_pdf_l1_loss": [(P, P, P, P, 2, 24, 24, 8193, 512, P, P, P, P, P, None),
+                                (P, P, P, P, 2, 65, 24, 512, 512, P, P, P, P, P, None)],
+        "attwarp_pdf_l1_loss_backward": [(P, P, P, P, 2, 24, 24, 512, 8193, P, P, P, P, P, None)],
+        # 16384 + 4096 doubles are a compute unit's whole LDS; with the kernel's own 32 bytes the launch cannot fit
+        "attwarp_build_axis_cdf_targets": [(P, 2, 24, 16384, 4096, P, P, P, None), (P, 2, 16384, 24, 4096, P, P, P, None),
+                                           (P, 2, 24, 16385, 24, P, P, P, None), (P, 2, 24, 24, 4097, P, P, P, None)],
+        "attwarp_trainer_attention_targets": [(P, P, 2, 96, 16385, 24, 24, P, P, P, None)],
+    }
+    for name, cases in too_big.items():
+        for args in cases:
+            assert getattr(lib, name)(*args) == ATTWARP_E_UNSUPPORTED, (name, args)

@@ -200,6 +200,50 @@ def test_three_step_division_bfloat16():
     assert checked > 20_000_000 and bad == 0
 
 
+def _window_loop_model(tmp, Lo, L, three_windows):
+    """right_inverse_block's second loop (axis_blocks.hpp) in numpy float32: output l adds tmp[k] / len(window k) over the
+    windows the loop visits, ascending k.  three_windows: the loop bound k0 - 1 .. k0 + 1 the block once had."""
+    out = np.zeros(L, np.float32)
+    for l in range(L):
+        k0, k1 = (l * Lo) // L, ((l + 1) * Lo - 1) // L
+        hi = min(k0 + 1, Lo - 1) if three_windows else min(k1, Lo - 1)
+        for k in range(max(k0 - 1, 0), hi + 1):
+            s, e = (k * L) // Lo, ((k + 1) * L + Lo - 1) // Lo
+            if s <= l < e:
+                out[l] = np.float32(out[l] + np.float32(tmp[k] * (np.float32(1.0) / np.float32(max(e - s, 1)))))
+    return out
+
+
+def test_right_inverse_window_loop_covers_every_window():
+    """The block's loop bound k0 - 1 .. k1 visits every window that covers an output, for every length pair the ABI takes:
+    the model equals the whole-window walk of both oracles bit for bit.  The three-window bound equals it for L >= Lo and
+    drops windows for L <= Lo / 3 (Lo = 24, L = 8, 6, 1)."""
+    from oracle import c_oracle as C
+    rng = np.random.default_rng(11)
+
+    def whole(tmp, Lo, L):                                     # O.upsample_pdf_right_inverse's walk over pooling_matrix
+        A = O.pooling_matrix(Lo, L, np.float32)
+        x = np.zeros(L, np.float32)
+        for k in range(Lo):
+            nz = np.nonzero(A[k])[0]
+            x[nz] = (x[nz] + (tmp[k] * A[k, nz]).astype(np.float32)).astype(np.float32)
+        return x
+    pairs = [(Lo, L) for Lo in (1, 2, 7, 8, 9, 24, 37, 63, 64) for L in (1, 2, 5, 6, 8, 21, 23, 24, 25, 47, 48, 63, 64, 65, 336)]
+    for Lo, L in pairs:
+        tmp = (rng.standard_normal(Lo) + 2.0).astype(np.float32)
+        want = whole(tmp, Lo, L)
+        assert np.array_equal(_window_loop_model(tmp, Lo, L, False), want), (Lo, L)
+        # the C oracle with the identity as its table: tmp = y
+        assert np.array_equal(C.right_inverse(tmp, L, np.eye(Lo)), want), (Lo, L)
+        if L >= Lo:
+            assert np.array_equal(_window_loop_model(tmp, Lo, L, True), want), (Lo, L)
+    for L in (8, 6, 1):
+        tmp = (rng.standard_normal(24) + 2.0).astype(np.float32)
+        got, want = _window_loop_model(tmp, 24, L, True), whole(tmp, 24, L)
+        # every dropped window carries a positive term: the rows differ by whole terms, not by rounding
+        assert np.abs(got - want).max() > 0.05 * np.abs(want).max(), (L, got, want)
+
+
 if __name__ == "__main__":
     for dt in ("float16", "bfloat16"):
         print(dt, "exhaustive (pairs x 3 reciprocals, mismatches):", _three_step_division_mismatches(dt, 1), flush=True)
