@@ -256,6 +256,9 @@ static int validate_maps(const char* who, const Map* maps, const Map* maps_dev, 
 }
 
 static size_t lds_bytes(int h) { return (size_t)h * TILE * sizeof(float); }
+// metrics_kernel's own __shared__ variables (red, s_v, s_i): its "LDS Size" at zero dynamic LDS.  With them the fused
+// kernel needs 65616 bytes at h = 64, past the 64 KB a launch gets by default, so its launcher asks for the grant.
+constexpr size_t METRICS_STATIC_LDS = 80;
 
 }  // namespace grounding
 }  // namespace attwarp
@@ -281,6 +284,7 @@ extern "C" int attwarp_resize_lanczos4(const attwarp_grid_map* maps, const attwa
                                        void* stream) {
   int mb = 0;
   if (const int rc = validate_maps("resize_lanczos4", maps, maps_dev, M, h, w, true, false, &mb)) return rc;
+  if (const int rc = grant_dynamic_lds(resize_kernel, lds_bytes(h), "resize_lanczos4")) return rc;   // (no static LDS: 64 KB at h = 64)
   hipLaunchKernelGGL(resize_kernel, dim3((unsigned)mb, (unsigned)M), dim3(NT), lds_bytes(h), as_stream(stream), maps_dev, h, w);
   return check_launch("resize_kernel");
 }
@@ -313,8 +317,12 @@ extern "C" int attwarp_box_metrics(const attwarp_grid_map* maps, const attwarp_g
   hipStream_t st = as_stream(stream);
   Part* parts = static_cast<Part*>(ws);
   const dim3 grid((unsigned)mb, (unsigned)M);
-  if (dense) hipLaunchKernelGGL(metrics_kernel<false>, grid, dim3(NT), 0, st, maps_dev, h, w, mb, parts);
-  else hipLaunchKernelGGL(metrics_kernel<true>, grid, dim3(NT), lds_bytes(h), st, maps_dev, h, w, mb, parts);
+  if (dense) {
+    hipLaunchKernelGGL(metrics_kernel<false>, grid, dim3(NT), 0, st, maps_dev, h, w, mb, parts);
+  } else {
+    if (const int rc = grant_dynamic_lds(metrics_kernel<true>, lds_bytes(h), "box_metrics", METRICS_STATIC_LDS)) return rc;
+    hipLaunchKernelGGL(metrics_kernel<true>, grid, dim3(NT), lds_bytes(h), st, maps_dev, h, w, mb, parts);
+  }
   if (const int rc = check_launch("metrics_kernel")) return rc;
   hipLaunchKernelGGL(metrics_final_kernel, dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, st, maps_dev, M, mb, parts, argmax,
                      top1, am);

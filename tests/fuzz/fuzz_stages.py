@@ -3,19 +3,23 @@ tolerance is written next to the stage): attention maps from uint8 / float32 / f
 (A13), PDF -> CDF -> maps chain with hostile densities (A8-A11), cdf repair / resample (A10), attention reduce with
 random geometry (A1/A2), LANCZOS mask up-sample vs the Pillow restatement (A4), revise_mask (A3), adaptive pool and
 gt_marginals (A5/A6), safe_softmax (A7), and the training kernels (row losses, recon losses, pdf_l1 with the trainer's targets:
-forward and backward against the float64 restatement tests/losses_ref.py at the bounds of tests/test_losses_gpu.py).
-usage: fuzz_stages.py [seconds per stage] [seed]"""
-import os, sys, time
+forward and backward against the float64 restatement tests/losses_ref.py at the bounds of tests/test_losses_gpu.py), and the
+layer-selection study's kernels (LANCZOS4 resize, dense and fused box metrics, the head-mean probe) against tests/grounding_ref.py.
+usage: fuzz_stages.py [seconds per stage] [seed] [only the stages whose name contains this]"""
+import os, sys, time, math
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(1, os.path.join(ROOT, "tests"))
 from attwarp_amd import checkpoint_utils as cu, attention_extraction as ae, new_method as nm, pipeline, model, losses, _tables
+from attwarp_amd import grounding as G
 from oracle import warp_oracle as O
 import losses_ref as R
+import grounding_ref as GR
 dev = torch.device("cuda:0")
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 20.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+only = sys.argv[3] if len(sys.argv) > 3 else ""
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 N = lambda t: t.detach().cpu().numpy()
 def run(name, gen):
@@ -347,7 +351,71 @@ def g_pdf_l1():
                           lambda a, b, c, d: R.pdf_l1_loss(a, b, c, d, W, H, inv_x, inv_y), (px, py, gx, gy), (0, 1))
     return ok, (B, Lx, Ly, W, H, eps, h, w, tfms[:3])
 
-for name, gen in (("row losses vs float64 restatement (L)", g_row_losses), ("recon losses vs float64 restatement (L)", g_recon),
+# ---- the layer-selection study's kernels against tests/grounding_ref.py: resize bit for bit (NaN positions where a grid holds
+# non-finite values), fused == dense bit for bit, argmax / top1 exact, am within the bound tests/test_grounding_sweep_gpu.py
+# derives: |am - ref| <= 2e-9 max(1, |ref|) sum|v| / |sum v + 1e-12| against math.fsum sums of the float64 reference map.
+def g_side(n):
+    r = rng.random()
+    if r < 0.25: return int(rng.integers(1, n + 1))                      # at or below the grid's side
+    if r < 0.65: return int(rng.integers(1, 257))
+    if r < 0.9: return int(rng.integers(257, 700))
+    return int(rng.choice([255, 256, 257, 512, 513, 1024, 1500]))
+def g_box(W, H):
+    big = (1 << 40) - 1; r = rng.random(); e = int(rng.choice([255, 256, 257]))
+    if r < 0.25: return (int(rng.integers(0, W)), int(rng.integers(0, H)), int(rng.integers(1, W + 1)), int(rng.integers(1, H + 1)))
+    if r < 0.35: return (0, 0, W, H)
+    if r < 0.45: return (int(rng.integers(0, W)), int(rng.integers(0, H)), int(rng.integers(-3, 1)), int(rng.integers(-3, 1)))
+    if r < 0.6: return (int(rng.integers(-W - 2, 0)), int(rng.integers(-H - 2, 0)), int(rng.integers(0, W + 6)), int(rng.integers(0, H + 6)))
+    if r < 0.7: return (W + int(rng.integers(0, 6)), H + int(rng.integers(0, 6)), 3, 3)
+    if r < 0.8: return (int(rng.choice([0, W - 1])), int(rng.choice([0, H - 1])), 1, 1)
+    if r < 0.9: return [(0, 0, e, e), (e, e, W, H), (e - 1, e - 1, 2, 2)][int(rng.integers(0, 3))]
+    return tuple(int(v) for v in rng.choice([big, -big, 0, 1], 4))
+def g_grounding():
+    M = int(rng.integers(1, 7)); h, w = int(rng.integers(1, 65)), int(rng.integers(1, 65))
+    g = rng.random((M, h, w), dtype=np.float32)
+    g = (1 + g if rng.random() < 0.5 else g ** 4).astype(np.float32); g = (g / g.sum(axis=(1, 2), keepdims=True)).astype(np.float32)
+    if rng.random() < 0.3:                                               # hostile grids
+        for _ in range(int(rng.integers(1, 4))):
+            g[rng.integers(0, M), rng.integers(0, h), rng.integers(0, w)] = rng.choice([np.nan, np.inf, -np.inf, -0.0, 1e-45, -3e-39, 3e38])
+    sizes = [(g_side(w), g_side(h)) for _ in range(M)]
+    if rng.random() < 0.2: sizes[0] = (w, h)                             # dsize == ssize
+    boxes = [g_box(W, H) for (W, H) in sizes]
+    tg = T(g); g = N(tg)
+    views = G.resize_lanczos4(tg, sizes); fused = G.grid_box_metrics(tg, sizes, boxes); dense = G.box_metrics(views, boxes)
+    ok = bool(torch.equal(fused.argmax, dense.argmax) and torch.equal(fused.top1, dense.top1)) and np.array_equal(N(fused.am).view(np.uint64), N(dense.am).view(np.uint64))
+    for i, (W, H) in enumerate(sizes):
+        want = GR.resize_lanczos4(g[i], W, H); got = N(views[i]); nan = np.isnan(want)
+        ok = ok and np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
+        arg, t1, am_np = GR.box_metrics(want, boxes[i]); am = float(fused.am[i])
+        ok = ok and int(fused.argmax[i]) == arg and int(fused.top1[i]) == t1
+        if np.isfinite(want).all():
+            a64 = want.astype(np.float64); x0, y0, bw, bh = boxes[i]
+            tot, sabs = math.fsum(a64.ravel().tolist()), math.fsum(np.abs(a64).ravel().tolist())
+            ref = math.fsum(a64[y0:y0 + bh, x0:x0 + bw].ravel().tolist()) / (tot + 1e-12)
+            ok = ok and abs(am - ref) <= 2e-9 * max(1.0, abs(ref)) * sabs / abs(tot + 1e-12)
+        else:
+            ok = ok and ((np.isnan(am) and np.isnan(am_np)) or am == am_np)
+    return ok, (M, h, w, sizes, boxes)
+
+HEAD_MEAN_NC = [16, 32, 48, 64, 8, 24, 4, 12, 2, 6, 1, 3]                # 16-byte chunks per key row: every (lanes, chunks per lane) the probe has
+def g_head_mean():
+    B = int(rng.integers(1, 4)); dt = [torch.float16, torch.float32, torch.bfloat16][int(rng.integers(0, 3))]
+    D = int(rng.choice(HEAD_MEAN_NC)) * (4 if dt == torch.float32 else 8)
+    Hkv = int(rng.choice([1, 2, 4])); H = Hkv * int(rng.choice([1, 4, 8]))
+    if H * D > 4096: Hkv, H = 1, int(rng.choice([1, 4, 8]))             # (the restatement holds the repeated keys in float64)
+    ntok = int(rng.choice([576, 64, 100, 1, 1024])); kv = ntok + int(rng.choice([0, 1, int(rng.integers(2, 120))]))
+    q = T(rng.standard_normal((B, H, D)).astype(np.float32)).to(dt); k = T(rng.standard_normal((B, Hkv, kv, D)).astype(np.float32)).to(dt)
+    bf = dt == torch.bfloat16
+    pads = np.array([int(rng.choice([0, int(rng.integers(0, kv)), kv - 1])) for _ in range(B)], np.int32)     # (kv_begin == kv has no defined answer)
+    starts = np.array([int(rng.choice([0, kv - ntok, int(rng.integers(0, kv - ntok + 1))])) for _ in range(B)], np.int32)
+    sc = float(D) ** -0.5
+    got = N(ae.probe_head_mean(q, k, T(starts), ntok, T(pads), sc).float())
+    want = GR.head_mean_rows(N(q.float() if bf else q), N(k.float() if bf else k), starts, ntok, sc, pads, bf16=bf)
+    ok = np.array_equal(got, want.astype(np.float32))
+    return ok, (B, H, Hkv, D, ntok, kv, str(dt), pads.tolist(), starts.tolist())
+
+for name, gen in (("layer sweep: resize + box metrics (3.8)", g_grounding), ("layer sweep: head-mean probe (3.8)", g_head_mean),
+                  ("row losses vs float64 restatement (L)", g_row_losses), ("recon losses vs float64 restatement (L)", g_recon),
                   ("trainer targets + pdf_l1 vs float64 restatement (L)", g_pdf_l1),
                   ("ragged chain vs per-image + oracle", g_ragged_chain), ("MaskChainStream vs warp_from_masks", g_mask_chain_stream), ("clip_preprocess (+pad) (f3)", g_clip), ("probe_last_query (f4)", g_probe), ("MarginalNet tail (f1)", g_mn_tail), ("MarginalNet forward fused vs stock (f1)", g_marginalnet),
                   ("warp_image_by_attention chain", g_chain_u8), ("attention stack -> warp (bench path)", g_stack_chain),
@@ -355,6 +423,7 @@ for name, gen in (("row losses vs float64 restatement (L)", g_row_losses), ("rec
                   ("cdf / repair / resample (A9-A10)", g_cdf_stages), ("attn reduce step (A1)", g_attn),
                   ("LANCZOS mask up-sample (A4)", g_lanczos), ("pool24 + gt_marginals (A5-A6)", g_pool_marg),
                   ("revise_mask + safe_softmax (A3,A7)", g_revise_softmax)):
+    if only not in name: continue
     try:
         run(name, gen)
     except Exception as e:   # noqa: BLE001

@@ -120,20 +120,21 @@ def _taps(ofs, n_src):
 
 def resize_lanczos4(grid: np.ndarray, W: int, H: int, tables=None) -> np.ndarray:
     """cv2.resize(grid, (W, H), interpolation=cv2.INTER_LANCZOS4) for a float32 [h,w] grid: horizontal pass, vertical
-    pass, float32 products and sums, taps in ascending order from the first product."""
+    pass, float32 products and sums, taps in ascending order from the first product.  Leading axes are a batch of grids
+    resized to one size ([...,h,w] -> [...,H,W]): the same operations element by element."""
     g = np.asarray(grid, dtype=F32)
-    h, w = g.shape
+    h, w = g.shape[-2:]
     if (H, W) == (h, w):
         return g.copy()
     (ox, cx), (oy, cy) = tables if tables is not None else (lanczos4_coeffs(w, W), lanczos4_coeffs(h, H))
     tx = _taps(ox, w)
-    hrow = g[:, tx[:, 0]] * cx[:, 0]
+    hrow = g[..., tx[:, 0]] * cx[:, 0]
     for j in range(1, 8):
-        hrow = (hrow + (g[:, tx[:, j]] * cx[:, j]).astype(F32)).astype(F32)
+        hrow = (hrow + (g[..., tx[:, j]] * cx[:, j]).astype(F32)).astype(F32)
     ty = _taps(oy, h)
-    out = hrow[ty[:, 0], :] * cy[:, 0:1]
+    out = hrow[..., ty[:, 0], :] * cy[:, 0:1]
     for k in range(1, 8):
-        out = (out + (hrow[ty[:, k], :] * cy[:, k:k + 1]).astype(F32)).astype(F32)
+        out = (out + (hrow[..., ty[:, k], :] * cy[:, k:k + 1]).astype(F32)).astype(F32)
     return out.astype(F32)
 
 

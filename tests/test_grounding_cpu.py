@@ -61,6 +61,23 @@ def test_lanczos4_coeffs_from_one_pixel(lib, n_out):
     assert np.array_equal(ofs, rofs) and np.array_equal(co.view(np.uint32), rco.view(np.uint32))
 
 
+LIMIT_N_OUT = [1, 2, 3, 5, 17, 18, 27, 63, 64, 65, 255, 256, 257, 500, 1000]
+
+
+@pytest.mark.parametrize("n_in", range(1, 65))
+def test_lanczos4_coeffs_bit_exact_for_every_grid_side(lib, n_in):
+    """Every grid side the kernels take (1 .. 64) against output sides around the grid's own, a 256-pixel tile and beyond,
+    down-sampling included; the longest tables (4096 and the limit, 32768) for the largest grid."""
+    from attwarp_amd import _tables
+    for n_out in LIMIT_N_OUT + ([4096, 32768] if n_in == 64 else []):
+        ofs, co = _tables.lanczos4_tables_host(n_in, n_out)
+        rofs, rco = R.lanczos4_coeffs(n_in, n_out)
+        assert ofs.dtype == np.int32 and co.dtype == np.float32 and co.shape == (n_out, 8)
+        assert np.array_equal(ofs, rofs), (n_in, n_out)
+        assert np.array_equal(co.view(np.uint32), rco.view(np.uint32)), (n_in, n_out)
+        assert np.isfinite(co).all() and -1 <= int(ofs.min()) and int(ofs.max()) <= n_in - 1, (n_in, n_out)
+
+
 def test_box_slice_follows_numpy_slicing():
     from attwarp_amd import grounding as G
     rng = np.random.default_rng(7)
