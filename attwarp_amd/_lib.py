@@ -111,6 +111,16 @@ SIGNATURES = {
     "attwarp_box_metrics_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_box_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+    # the Stable-Diffusion warp ablation (sdwarp.hip)
+    "attwarp_xattn_chunk": (c_int, [c_int]),
+    "attwarp_xattn_reduce_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "attwarp_xattn_reduce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "attwarp_cubic_coeffs": (c_int, [c_int, c_int, c_void_p, c_void_p]),
+    "attwarp_resize_cubic": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "attwarp_gaussian5_taps": (c_int, [c_double, c_void_p]),
+    "attwarp_blur5_minmax_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "attwarp_blur5_minmax": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "attwarp_minmax_normalize": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     # the MarginalNet training losses (losses.hip, profiles.hip)
     "attwarp_cdf_downsample": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "attwarp_build_axis_cdf_targets": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

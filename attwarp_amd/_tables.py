@@ -7,6 +7,8 @@
   ``normalize_coeffs_8bpc`` in Pillow's Resample.c) behind ``invtrans`` (llava.py:195-196).
 * ``lanczos4_tables``: OpenCV's INTER_LANCZOS4 tables of ``resizeGeneric_`` (offsets + 8 float32 taps per output
   index) behind the layer-selection study's ``cv2.resize`` (uncertainty_attn_maps_llava.py:63-64).
+* ``cubic_tables``: OpenCV's INTER_CUBIC tables (offsets + 4 float32 taps per output index) behind the Stable-Diffusion
+  warp ablation's ``cv2.resize`` calls (Stable_diffusion_based_warp.py:159, 396, 409).
 """
 from __future__ import annotations
 
@@ -139,5 +141,26 @@ def lanczos4_tables(n_in: int, n_out: int, device: torch.device):
     t = _DEV_CACHE.get(key)
     if t is None:
         ofs, coeffs = lanczos4_tables_host(n_in, n_out)
+        t = _cache_put(key, (torch.from_numpy(ofs).to(device), torch.from_numpy(coeffs).to(device)))
+    return t
+
+
+@functools.lru_cache(maxsize=1024)
+def cubic_tables_host(n_in: int, n_out: int):
+    """OpenCV's INTER_CUBIC tables for one axis n_in -> n_out from the library's HOST helper attwarp_cubic_coeffs
+    (interpolateCubic, A = -0.75f): (ofs int32 [n_out], coeffs float32 [n_out,4])."""
+    from . import _lib
+    ofs = np.zeros(n_out, dtype=np.int32)
+    coeffs = np.zeros((n_out, 4), dtype=np.float32)
+    _lib.call("attwarp_cubic_coeffs", int(n_in), int(n_out), ofs.ctypes.data, coeffs.ctypes.data)
+    return ofs, coeffs
+
+
+def cubic_tables(n_in: int, n_out: int, device: torch.device):
+    """The same tables on the device, uploaded once per (n_in, n_out, device)."""
+    key = ("cubic", n_in, n_out, str(device))
+    t = _DEV_CACHE.get(key)
+    if t is None:
+        ofs, coeffs = cubic_tables_host(n_in, n_out)
         t = _cache_put(key, (torch.from_numpy(ofs).to(device), torch.from_numpy(coeffs).to(device)))
     return t

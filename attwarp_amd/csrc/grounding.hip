@@ -22,6 +22,7 @@
 // the same bits, and the dense and fused paths -- the same kernel body with another value source -- give identical bits on
 // identical values.
 #include "common.hpp"
+#include "resize_axis.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -269,11 +270,9 @@ using namespace attwarp::grounding;
 extern "C" int attwarp_lanczos4_coeffs(int n_in, int n_out, int32_t* ofs, float* coeffs) {
   ATTWARP_REQUIRE(ofs && coeffs, "lanczos4_coeffs: null pointer");
   ATTWARP_REQUIRE(n_in > 0 && n_out > 0, "lanczos4_coeffs: non-positive size %d -> %d", n_in, n_out);
-  const double inv = (double)n_out / n_in, scale = 1. / inv;
   for (int d = 0; d < n_out; ++d) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    const int s = (int)std::floor(f);          // cvFloor
-    f -= s;
+    int s;
+    const float f = resize_source_coord(n_in, n_out, d, &s);
     ofs[d] = s;
     interpolate_lanczos4(f, coeffs + (size_t)d * 8);
   }

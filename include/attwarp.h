@@ -482,6 +482,72 @@ ATTWARP_API size_t attwarp_box_metrics_workspace_bytes(const attwarp_grid_map* m
 ATTWARP_API int attwarp_box_metrics(const attwarp_grid_map* maps, const attwarp_grid_map* maps_dev, int M, int fused, int h,
                         int w, int64_t* argmax, int32_t* top1, double* am, void* ws, void* stream);
 
+/* ---- the Stable-Diffusion warp ablation (Ablations/Stable_diffusion_based_warp.py:142-172, 310-413, 445-456): the
+ * cross-attention reductions behind compute_token_importance / aggregate_attention_map_for_tokens, cv2.resize(float32
+ * map, INTER_CUBIC), cv2.GaussianBlur(5 x 5, sigma 1) and the in-place min-max.  Every call takes a HOST array of
+ * records (validated here and used to size the grid) plus a DEVICE copy of the same bytes (8-byte aligned), M <= 65535.
+ * No floating-point atomics anywhere: the same inputs give the same bits (summation orders: DESIGN.md 3.9; restated in
+ * tests/sdwarp_ref.py, bit for bit).
+ *
+ * attwarp_xattn_reduce: one pass over every captured tensor attn [B,heads,HW,tokens] (dense, element aligned only; one
+ * dtype F32 / F16 / BF16 and one tokens in 1 .. 256 per call).  Per record, in the tensor's dtype:
+ *   token_sums [tokens] = attn.sum(dim=(0,1,2,3)), accumulated in float64, rounded once (float16 beyond 65504 -> inf);
+ *   hw_tok [HW,tokens]  = attn.sum(dim=0).sum(dim=0): float64 over B, rounded, float64 over heads, rounded (NULL: skip).
+ * A workgroup owns attwarp_xattn_chunk(tokens) consecutive positions of HW for all (b, head) and leaves float64
+ * partials [tokens] in ws (attwarp_xattn_reduce_workspace_bytes bytes, 16-byte aligned); a second small launch adds a
+ * record's partials in chunk order. */
+typedef struct attwarp_xattn_map {
+  const void* attn;                                /* device: [B,heads,HW,tokens] */
+  void* token_sums;                                /* device: [tokens] */
+  void* hw_tok;                                    /* device: [HW,tokens] or NULL */
+  int32_t B, heads, HW;
+} attwarp_xattn_map;
+ATTWARP_API int attwarp_xattn_chunk(int tokens);
+ATTWARP_API size_t attwarp_xattn_reduce_workspace_bytes(const attwarp_xattn_map* maps, int M, int tokens);
+ATTWARP_API int attwarp_xattn_reduce(const attwarp_xattn_map* maps, const attwarp_xattn_map* maps_dev, int M, int dtype,
+                         int tokens, void* ws, void* stream);
+
+/* cv2.resize(float32 map [h,w], (W, H), INTER_CUBIC) = OpenCV 4.x resizeGeneric_ with the scalar HResizeCubic /
+ * VResizeCubic for one channel: horizontal pass, then vertical pass, float32 with every product and sum rounded, taps
+ * ofs-1 .. ofs+2 (clamped into the source) in ascending order from the first product; dsize == ssize copies; plain cubic
+ * when down-sampling (no anti-aliasing).  Published algorithm, parity with OpenCV itself unpinned (OpenCV is absent
+ * where this is built; its vectorised passes may sum in another order); bit-exact with tests/sdwarp_ref.py.
+ * HOST: attwarp_cubic_coeffs(n_in, n_out, ofs int32 [n_out], coeffs float [n_out,4]): source coordinate and cvFloor split
+ * as attwarp_lanczos4_coeffs, interpolateCubic in float32 with A = -0.75f.
+ * The source may have any size up to 32768 x 32768: each thread keeps the horizontal results of the four source rows of
+ * its column's current window and moves it as ofs_y advances; nothing is held for the whole source. */
+typedef struct attwarp_cubic_map {
+  const float* src;                                /* device: [h,w] */
+  float* out;                                      /* device: [H,W] */
+  const int32_t* ofs_x; const float* coef_x;       /* device: attwarp_cubic_coeffs(w, W) (unused when H == h and W == w) */
+  const int32_t* ofs_y; const float* coef_y;       /* device: attwarp_cubic_coeffs(h, H) */
+  int32_t h, w, H, W;                              /* all 1 .. 32768 */
+} attwarp_cubic_map;
+ATTWARP_API int attwarp_cubic_coeffs(int n_in, int n_out, int32_t* ofs, float* coeffs);
+ATTWARP_API int attwarp_resize_cubic(const attwarp_cubic_map* maps, const attwarp_cubic_map* maps_dev, int M, void* stream);
+
+/* cv2.GaussianBlur(map, (5, 5), sigmaX=1.0) of float32 maps [H,W] (:410) and the min-max of :160 / :400-401 / :411-412.
+ * HOST: attwarp_gaussian5_taps(sigma, taps float [5]) = getGaussianKernel(5, sigma): exp(-i*i / (2 sigma^2)) normalised
+ * in double, each tap rounded to float32.  Blur: row pass then column pass, BORDER_REFLECT_101 (sides 1 and 2 included),
+ * symmetric form k0*s0 + k1*(s-1 + s1) + k2*(s-2 + s2), every operation rounded.  Published algorithm, parity with OpenCV
+ * unpinned.  blur != 0: out = blur(src) (not in place); blur == 0: out is not written.  With ws != NULL every workgroup
+ * leaves the min / max of what it produced (blur != 0) or read (blur == 0) in ws
+ * (attwarp_blur5_minmax_workspace_bytes bytes, 8-byte aligned; NaN marks "a NaN was seen", numpy's min / max).
+ * attwarp_minmax_normalize (same M and sizes as the call that filled ws): out = (src - min) / (float)(max' + 1e-9f) in
+ * float32, max' the maximum after the subtraction (numpy 2 scalar rules: a constant map gives 0, a NaN gives NaN
+ * everywhere); may run in place (out == src).  Two launches: the partials of a map in index order, then the map. */
+typedef struct attwarp_f32_map {
+  const float* src;                                /* device: [H,W] */
+  float* out;                                      /* device: [H,W] */
+  int32_t H, W;                                    /* 1 .. 32768 */
+} attwarp_f32_map;
+ATTWARP_API int attwarp_gaussian5_taps(double sigma, float* taps);
+ATTWARP_API size_t attwarp_blur5_minmax_workspace_bytes(const attwarp_f32_map* maps, int M);
+ATTWARP_API int attwarp_blur5_minmax(const attwarp_f32_map* maps, const attwarp_f32_map* maps_dev, int M, int blur, void* ws,
+                         void* stream);
+ATTWARP_API int attwarp_minmax_normalize(const attwarp_f32_map* maps, const attwarp_f32_map* maps_dev, int M, void* ws,
+                             void* stream);
+
 /* ---- A12 / A13 tail: cv2.remap(INTER_LINEAR, BORDER_REPLICATE) with separable maps,
  * AGW/new_method.py:268-271, MN/checkpoint_utils.py:195-198.
  * src [B,H,W,C] (HWC) or [B,C,H,W] (CHW), dtype F32, U8 or F64 -> dst same layout with (H_out,W_out).
