@@ -13,6 +13,8 @@ Attention Guided Warping/new_method.py      attwarp_amd.new_method       (warp_i
                                               save_warped_image, set_transform_function)
 Attention Guided Warping/                   attwarp_amd.attention_extraction (BatchMaskHookLogger,
   attention_extraction/llava.py               revise_mask, blend_mask)
+model/marginalnet_full_dataset/             attwarp_amd.dataloader       (prepare_images,
+  dataloader.py, data.py                      prepare_attention_maps, collate, transform_for_sample)
 =========================================  =====================================================
 
 plus ``attwarp_amd.pipeline`` (batched device-resident launcher) and ``attwarp_amd.dist``

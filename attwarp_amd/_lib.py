@@ -141,9 +141,16 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "attwarp_trainer_attention_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                                   c_void_p, c_void_p]),
+    # the trainer's batches from decoded samples (dataprep.hip)
+    "attwarp_prep_images_table_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "attwarp_prep_images_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    "attwarp_prep_images_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "attwarp_pil_nearest_index": (c_int, [c_int, c_int, c_void_p]),
+    "attwarp_prep_attention_workspace_bytes": (c_size_t, [c_int]),
+    "attwarp_prep_attention_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
-PIL_LANCZOS, PIL_BICUBIC = 0, 1
+PIL_LANCZOS, PIL_BICUBIC, PIL_BILINEAR = 0, 1, 2
 RECON_MSE, RECON_L1 = 0, 1                          # attwarp_recon_loss kinds
 TT_IDENTITY, TT_SQRT, TT_NONE = 0, 1, 2              # attwarp_trainer_attention_targets modes
 OVERLAY_BLEND_MASK, OVERLAY_SAVE_WARPED = 0, 1       # attwarp_heatmap_overlay styles
@@ -166,6 +173,16 @@ class RaggedHeader(ctypes.Structure):
                 ("table_bytes", ctypes.c_uint64), ("mota_bytes", ctypes.c_uint64), ("sums_bytes", ctypes.c_uint64),
                 ("lds_bytes", ctypes.c_uint64), ("off_images", ctypes.c_uint64), ("off_plans", ctypes.c_uint64),
                 ("off_lmap", ctypes.c_uint64), ("off_pmap", ctypes.c_uint64), ("off_order", ctypes.c_uint64)]
+
+
+class PrepHeader(ctypes.Structure):
+    """attwarp_prep_header: the first bytes of a table written by attwarp_prep_images_plan."""
+    _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("C", ctypes.c_int32), ("S_h", ctypes.c_int32),
+                ("S_w", ctypes.c_int32), ("n_fused_images", ctypes.c_int32), ("n_fused_items", ctypes.c_int32),
+                ("n_split_images", ctypes.c_int32), ("n_h_items", ctypes.c_int32), ("n_v_items", ctypes.c_int32),
+                ("ks", ctypes.c_int32), ("n_wide_items", ctypes.c_int32),
+                ("table_bytes", ctypes.c_uint64), ("tmp_bytes", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64),
+                ("off_images", ctypes.c_uint64), ("off_items", ctypes.c_uint64)]
 
 
 _lib = None            # the library every call goes to: the product, or the tuning flavour inside debug_override()

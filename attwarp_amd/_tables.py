@@ -87,7 +87,8 @@ def attention_transform_lut(transform: str, exp_scale: float, exp_divisor: float
     return t
 
 
-_FILTER_IDS = {"lanczos": 0, "bicubic": 1}          # ATTWARP_PIL_LANCZOS / ATTWARP_PIL_BICUBIC
+_FILTER_IDS = {"lanczos": 0, "bicubic": 1, "bilinear": 2}          # ATTWARP_PIL_LANCZOS / ATTWARP_PIL_BICUBIC / ATTWARP_PIL_BILINEAR
+_FILTER_SUPPORT = {"lanczos": 3.0, "bicubic": 2.0, "bilinear": 1.0}
 
 
 @functools.lru_cache(maxsize=1024)          # (host copies: ~12 bytes x taps per output pixel; the device cache below is the hot one)
@@ -100,7 +101,7 @@ def _lanczos_tables_host(n_in: int, n_out: int, filt: str = "lanczos"):
     if n_in == n_out:
         cols = 1
     else:
-        support = (3.0 if filt == "lanczos" else 2.0) * max(n_in / n_out, 1.0)
+        support = _FILTER_SUPPORT[filt] * max(n_in / n_out, 1.0)
         cols = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((n_out, 2), dtype=np.int32)
     kk = np.zeros((n_out, cols), dtype=np.int32)

@@ -207,6 +207,10 @@ static double pil_bicubic(double x) {
   if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
   return 0.0;
 }
+static double pil_bilinear(double x) {
+  if (x < 0.0) x = -x;
+  return x < 1.0 ? 1.0 - x : 0.0;
+}
 
 // ---- host: the table of one batch ----------------------------------------------------------------------------------
 struct RaggedLayout {
@@ -359,9 +363,10 @@ using namespace attwarp;
 extern "C" int attwarp_pil_coeffs_8bpc(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk, int kk_cols) try {
   ATTWARP_REQUIRE(bounds && kk, "pil_coeffs_8bpc: null pointer");
   ATTWARP_REQUIRE(in_size > 0 && out_size > 0 && kk_cols > 0, "pil_coeffs_8bpc: non-positive size");
-  ATTWARP_REQUIRE(filter == ATTWARP_PIL_LANCZOS || filter == ATTWARP_PIL_BICUBIC, "pil_coeffs_8bpc: unknown filter %d", filter);
-  double (*fn)(double) = filter == ATTWARP_PIL_LANCZOS ? pil_lanczos3 : pil_bicubic;
-  const double support0 = filter == ATTWARP_PIL_LANCZOS ? 3.0 : 2.0;
+  ATTWARP_REQUIRE(filter == ATTWARP_PIL_LANCZOS || filter == ATTWARP_PIL_BICUBIC || filter == ATTWARP_PIL_BILINEAR,
+                  "pil_coeffs_8bpc: unknown filter %d", filter);
+  double (*fn)(double) = filter == ATTWARP_PIL_LANCZOS ? pil_lanczos3 : filter == ATTWARP_PIL_BICUBIC ? pil_bicubic : pil_bilinear;
+  const double support0 = filter == ATTWARP_PIL_LANCZOS ? 3.0 : filter == ATTWARP_PIL_BICUBIC ? 2.0 : 1.0;
   constexpr int PRECISION_BITS = 32 - 8 - 2;
   if (in_size == out_size) {     // Pillow skips the pass; an identity table makes clip8((v << 22 + 2^21) >> 22) == v
     for (int o = 0; o < out_size; ++o) {

@@ -350,7 +350,7 @@ ATTWARP_API int attwarp_attention_transform_lut(int transform, double exp_scale,
  * 4096 bytes on both sides (W*C, W_out*C), H, W > g (the mask is up-sampled on both axes), max(H,W) <= 8192, g <= 32,
  * B <= 65535.  Any alignment: 683 x 3-byte rows are served by the same staged kernels as 684 x 3. */
 #define ATTWARP_RAGGED_MAX_LEAVES 64
-enum { ATTWARP_PIL_LANCZOS = 0, ATTWARP_PIL_BICUBIC = 1 };
+enum { ATTWARP_PIL_LANCZOS = 0, ATTWARP_PIL_BICUBIC = 1, ATTWARP_PIL_BILINEAR = 2 };
 typedef struct attwarp_ragged_image {
   const uint8_t* image;                            /* device: [H,W,C] uint8 interleaved, any byte address */
   const int32_t* bounds_x; const int32_t* kk_x;    /* device: Pillow tables g -> W: int32 [W,2], int32 [W,ksize_x] */
@@ -620,6 +620,64 @@ ATTWARP_API int attwarp_pdf_l1_loss_backward(const float* px, const float* py, c
  * sanitize = 1 of the transformed map), px [B,ow], py [B,oh] = gt_marginals(pooled), 1/L on ATTWARP_TT_NONE rows. */
 ATTWARP_API int attwarp_trainer_attention_targets(const float* A, const int32_t* modes, int B, int H, int W, int oh,
                                       int ow, float* pooled, float* px, float* py, void* stream);
+
+/* ---- the trainer's batches from decoded samples (MN/dataloader.py:123-137, 160-189, 204-273; MN/data.py collate_str):
+ * images of their own sizes -> T.Resize((S_h,S_w)) (Pillow's 8-bit BILINEAR resample, ATTWARP_PIL_BILINEAR tables) ->
+ * ToTensor (float32(float64(u8) * (1/255)) == u8 / 255 in IEEE float32, channels first), stacked: out [B,C,S_h,S_w].
+ *
+ * As for the ragged chain, a batch is described by a table the host builds once and copies to the device unchanged:
+ *   1. fill attwarp_prep_image[B] (HOST array of DEVICE pointers): image, size, Pillow tables W -> S_w and H -> S_h
+ *      (attwarp_pil_coeffs_8bpc; identity tables on an axis that keeps its size: Pillow skips that pass);
+ *   2. attwarp_prep_images_table_bytes(...) -> size; attwarp_prep_images_plan(...) writes header, records and the work
+ *      items (image, band of output rows) into HOST memory; header.tmp_bytes is the uint8 intermediate the caller provides;
+ *   3. copy table_bytes to the device (8-byte aligned); 4. attwarp_prep_images_u8(host copy, device copy, tmp, out, stream).
+ * An image runs on the one-launch kernel (both passes, the uint8 intermediate in LDS) when its horizontal taps fit the
+ * 16-tap register window, a band of 8 output rows fits the LDS and the horizontal pass comes first; the others (and every image in the tuning library under
+ * prep_variant = 1) take two more launches with the intermediate in `tmp`.  Both compute the same bytes.
+ * Images with 9 .. 16 horizontal taps run as a second launch of the same kernel with the wider window (n_wide_items).
+ * The LDS rows of a band are bounded on the host from H, S_h and ksize_y, which holds for the tables of
+ * attwarp_pil_coeffs_8bpc; a band whose tables reach further is written as NaN, never computed from clamped taps.
+ * Limits: C 1 or 3, S_w * C <= 65536, H, W <= 65535, B <= 2^20. */
+typedef struct attwarp_prep_image {
+  const uint8_t* image;                            /* device: [H,W,C] uint8 interleaved, any byte address */
+  const int32_t* bounds_x; const int32_t* kk_x;    /* device: W -> S_w: int32 [S_w,2], int32 [S_w,ksize_x] */
+  const int32_t* bounds_y; const int32_t* kk_y;    /* device: H -> S_h: int32 [S_h,2], int32 [S_h,ksize_y] */
+  int32_t H, W, ksize_x, ksize_y;
+  int32_t vertical_first, reserved;                /* 1: vertical pass first (what PIL.Image.resize does when H > 100 * W and
+                                                      S_h < H); such an image takes the two-launch route */
+} attwarp_prep_image;
+typedef struct attwarp_prep_header {               /* first bytes of a table written by attwarp_prep_images_plan */
+  uint32_t magic;
+  int32_t B, C, S_h, S_w;
+  int32_t n_fused_images, n_fused_items;           /* images / (image, band) items of the one-launch kernel */
+  int32_t n_split_images, n_h_items, n_v_items;    /* the two-launch route: its images, row-block items of either pass */
+  int32_t ks;                                      /* widest register window of the batch: 8 or 16 taps */
+  int32_t n_wide_items;                            /* the last n_wide_items of n_fused_items belong to images with 9 .. 16
+                                                      horizontal taps: they run as a launch of their own on the 16-tap window */
+  uint64_t table_bytes, tmp_bytes, lds_bytes;
+  uint64_t off_images, off_items;
+} attwarp_prep_header;
+ATTWARP_API size_t attwarp_prep_images_table_bytes(const attwarp_prep_image* images, int B, int C, int S_h, int S_w);
+ATTWARP_API int attwarp_prep_images_plan(const attwarp_prep_image* images, int B, int C, int S_h, int S_w, void* table,
+                             size_t table_bytes);
+ATTWARP_API int attwarp_prep_images_u8(const void* table_host, const void* table_dev, uint8_t* tmp, float* out, void* stream);
+
+/* HOST: the source index of every output position of Pillow's NEAREST resize n_in -> n_out (the affine scale path:
+ * a = n_in / n_out in double, xo = a * 0.5, idx = floor(xo), xo += a -- accumulated, which the closed form does not equal). */
+ATTWARP_API int attwarp_pil_nearest_index(int n_in, int n_out, int32_t* idx);
+
+/* The attention maps of the same samples (MN/dataloader.py:178-189, 230-231): float32 maps of their own sizes -> (if
+ * normalize and max > 1: / max in float32; a NaN anywhere makes the max NaN, so nothing is divided) -> NaN, +-inf -> 0 ->
+ * clip(0,1) -> trunc(v * 255) -> NEAREST resize by the index tables -> / 255: out [B,1,S_h,S_w] float32.  normalize = 0
+ * (the overlay branch, values gray / 255) skips only the division.  ws: attwarp_prep_attention_workspace_bytes(B) bytes. */
+typedef struct attwarp_prep_attention {
+  const float* map;                                /* device: [h,w] float32, dense */
+  const int32_t* idx_x; const int32_t* idx_y;      /* device: int32 [S_w], int32 [S_h] (attwarp_pil_nearest_index) */
+  int32_t h, w, normalize, reserved;
+} attwarp_prep_attention;
+ATTWARP_API size_t attwarp_prep_attention_workspace_bytes(int B);
+ATTWARP_API int attwarp_prep_attention_f32(const attwarp_prep_attention* maps_dev, int B, int S_h, int S_w, void* ws, float* out,
+                               void* stream);
 
 #ifdef __cplusplus
 }
