@@ -15,6 +15,8 @@ Attention Guided Warping/                   attwarp_amd.attention_extraction (Ba
   attention_extraction/llava.py               revise_mask, blend_mask)
 model/marginalnet_full_dataset/             attwarp_amd.dataloader       (prepare_images,
   dataloader.py, data.py                      prepare_attention_maps, collate, transform_for_sample)
+model/marginalnet_full_dataset/trainer.py   attwarp_amd.optim            (AdamW: GradScaler unscale,
+  (the optimiser lines)                       gradient-norm clip and the step in two launches)
 =========================================  =====================================================
 
 plus ``attwarp_amd.pipeline`` (batched device-resident launcher) and ``attwarp_amd.dist``

@@ -148,6 +148,10 @@ SIGNATURES = {
     "attwarp_pil_nearest_index": (c_int, [c_int, c_int, c_void_p]),
     "attwarp_prep_attention_workspace_bytes": (c_size_t, [c_int]),
     "attwarp_prep_attention_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # the trainer's optimiser step (optim.hip)
+    "attwarp_adamw_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "attwarp_adamw_step": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
 }
 
 PIL_LANCZOS, PIL_BICUBIC, PIL_BILINEAR = 0, 1, 2
@@ -183,6 +187,13 @@ class PrepHeader(ctypes.Structure):
                 ("ks", ctypes.c_int32), ("n_wide_items", ctypes.c_int32),
                 ("table_bytes", ctypes.c_uint64), ("tmp_bytes", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64),
                 ("off_images", ctypes.c_uint64), ("off_items", ctypes.c_uint64)]
+
+
+class AdamWTensor(ctypes.Structure):
+    """attwarp_adamw_tensor: one parameter of an optimiser step, device pointers in a host array."""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("numel", c_int64),
+                ("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
+                ("step_slot", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 _lib = None            # the library every call goes to: the product, or the tuning flavour inside debug_override()

@@ -679,6 +679,33 @@ ATTWARP_API size_t attwarp_prep_attention_workspace_bytes(int B);
 ATTWARP_API int attwarp_prep_attention_f32(const attwarp_prep_attention* maps_dev, int B, int S_h, int S_w, void* ws, float* out,
                                void* stream);
 
+/* ---- the trainer's optimiser step (MN/trainer.py:259-264): GradScaler unscale, global L2 gradient norm, clip and
+ * torch.optim.AdamW (decoupled weight decay, no amsgrad, no maximize) in two kernels per group of 64 tensors.
+ *   g = g_raw * inv_scale, inv_scale = float32(1 / float64(*grad_scale)) (1 when grad_scale is NULL);
+ *   total_norm = sqrt(sum g^2) over every tensor of the call, x^2 accumulated in float64 in a fixed order;
+ *   coef = min(max_norm / (total_norm + norm_eps), 1) (1 when max_norm < 0), g = g * coef;
+ *   p = p * (1 - lr * wd);  m = m + (1 - beta1) * (g - m);  v = beta2 * v + (1 - beta2) * g * g;
+ *   p = p - lr / (1 - beta1^t) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps)),  t = steps[step_slot] + 1 (stored back).
+ * Every float32 operation is rounded on its own; the scalars that depend on t, lr and the betas are computed in float64
+ * and rounded once.  When found_inf is not NULL and *found_inf != 0 nothing is written but grad_norm (p, m, v and steps
+ * keep their bits).  Gradients are only read.  grad_norm (float32, device) receives total_norm.
+ * `tensors` is a HOST array of n records of DEVICE pointers; p, g, m, v are dense float32 arrays of numel elements at
+ * any 4-byte aligned address (16-byte loads and stores when all four of a tensor are 16-byte aligned).  steps: device
+ * float32 array indexed by step_slot (0 <= step_slot < the n_tensors the workspace was sized for).  The workspace is
+ * attwarp_adamw_workspace_bytes(total_numel, n_tensors) bytes for calls whose numel sum to at most total_numel, ZERO
+ * before its first use, 16-byte aligned, and handed over with the SAME workspace_bytes every call; calls sharing it
+ * must be stream ordered.  Nothing is allocated, nothing synchronises; 2 * ceil(n / 64) launches. */
+typedef struct attwarp_adamw_tensor {
+  float* p; const float* g; float* m; float* v;    /* device */
+  int64_t numel;
+  double lr, beta1, beta2, eps, weight_decay;
+  int32_t step_slot, reserved;
+} attwarp_adamw_tensor;
+ATTWARP_API size_t attwarp_adamw_workspace_bytes(int64_t total_numel, int n_tensors);
+ATTWARP_API int attwarp_adamw_step(const attwarp_adamw_tensor* tensors, int n, double max_norm, double norm_eps,
+                       const float* grad_scale, const float* found_inf, float* steps, float* grad_norm,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
