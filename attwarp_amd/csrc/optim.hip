@@ -186,10 +186,14 @@ struct Coefs {
   float inv_scale, coef, decay, w1, b2, w2, eps, step_size, bc2_sqrt;
 };
 
+// The moment update is torch.lerp(m, g, w1) as torch.optim.AdamW takes it: m + w1 (g - m) below a weight of 0.5 and
+// g - (g - m)(1 - w1) from there on (beta1 <= 0.5), where the first form would leave a rounding of size ulp(m) in a result
+// of size |g| (beta1 = 0 must give exactly g).  1 - w1 is taken in float32.
 __device__ __forceinline__ void adamw_element(const Coefs& c, float graw, float& p, float& m, float& v) {
   const float g = fmul(fmul(graw, c.inv_scale), c.coef);
   p = fmul(p, c.decay);
-  m = fadd(m, fmul(c.w1, fsub(g, m)));
+  const float d = fsub(g, m);
+  m = (c.w1 < 0.5f) ? fadd(m, fmul(c.w1, d)) : fsub(g, fmul(d, fsub(1.0f, c.w1)));
   v = fadd(fmul(v, c.b2), fmul(fmul(c.w2, g), g));
   const float denom = fadd(sqrtf(v) / c.bc2_sqrt, c.eps);
   p = fsub(p, fmul(c.step_size, m / denom));

@@ -45,7 +45,8 @@ class AdamW(torch.optim.Optimizer):
     ``g = grad * inv_scale``; ``total_norm`` = L2 norm of g over all tensors of all groups (float64 accumulation, fixed
     order: bitwise repeatable); ``coef = min(max_grad_norm / (total_norm + norm_eps), 1)`` (1 when ``max_grad_norm`` is
     None); then AdamW on ``g * coef``.  ``grad_norm`` (0-dim float32 on the device) holds ``total_norm`` of the last
-    ``step()``, before clipping: the value ``clip_grad_norm_`` returns.
+    ``step()``, before clipping: the value ``clip_grad_norm_`` returns.  The first moment is ``torch.lerp(m, g, 1 - beta1)``
+    in both of its forms: ``m + w (g - m)`` for ``w < 0.5`` and ``g - (g - m)(1 - w)`` from 0.5 on (``beta1 <= 0.5``).
 
     **Gradients are read, never written**: after ``step()`` every ``.grad`` still holds the values backward left there
     (scaled by the GradScaler, unclipped), unlike after ``scaler.unscale_`` and ``clip_grad_norm_``.

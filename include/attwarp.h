@@ -684,7 +684,8 @@ ATTWARP_API int attwarp_prep_attention_f32(const attwarp_prep_attention* maps_de
  *   g = g_raw * inv_scale, inv_scale = float32(1 / float64(*grad_scale)) (1 when grad_scale is NULL);
  *   total_norm = sqrt(sum g^2) over every tensor of the call, x^2 accumulated in float64 in a fixed order;
  *   coef = min(max_norm / (total_norm + norm_eps), 1) (1 when max_norm < 0), g = g * coef;
- *   p = p * (1 - lr * wd);  m = m + (1 - beta1) * (g - m);  v = beta2 * v + (1 - beta2) * g * g;
+ *   p = p * (1 - lr * wd);  m = lerp(m, g, w1) with w1 = 1 - beta1 as torch.lerp takes it: m + w1 * (g - m) for w1 < 0.5,
+ *   g - (g - m) * (1 - w1) from 0.5 on (beta1 <= 0.5; 1 - w1 in float32);  v = beta2 * v + (1 - beta2) * g * g;
  *   p = p - lr / (1 - beta1^t) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps)),  t = steps[step_slot] + 1 (stored back).
  * Every float32 operation is rounded on its own; the scalars that depend on t, lr and the betas are computed in float64
  * and rounded once.  When found_inf is not NULL and *found_inf != 0 nothing is written but grad_norm (p, m, v and steps
