@@ -167,6 +167,25 @@ class RaggedImage(ctypes.Structure):
                 ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("ksize_x", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class RaggedImageDev(ctypes.Structure):
+    """The per-image record inside a table written by attwarp_ragged_plan (chain_ragged.hip: RaggedImage): the caller's
+    record up to ksize_x, then what the plan adds."""
+    _fields_ = RaggedImage._fields_[:-1] + [
+        ("plan_w", ctypes.c_int32), ("plan_h", ctypes.c_int32), ("l_nchunks", ctypes.c_int32),
+        ("l_rows_per_chunk", ctypes.c_int32), ("ki", ctypes.c_int32), ("mota_off", c_int64), ("sums_off", c_int64)]
+
+
+class StepSlot(ctypes.Structure):
+    """attwarp_step_slot: one batch of an attwarp_warp_step_fused_slots launch, device pointers."""
+    _fields_ = [(n, c_void_p) for n in ("src", "dst", "map_x", "map_y", "steps_in", "map_x_next", "map_y_next", "rows",
+                                        "starts", "steps_out")]
+
+
+class OverlayImage(ctypes.Structure):
+    """attwarp_overlay_image: one image of an attwarp_heatmap_overlay call, device pointers in a host array."""
+    _fields_ = [("image", c_void_p), ("map", c_void_p), ("out", c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
 class RaggedHeader(ctypes.Structure):
     """attwarp_ragged_header: the first bytes of a table written by attwarp_ragged_plan."""
     _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("C", ctypes.c_int32), ("g", ctypes.c_int32),

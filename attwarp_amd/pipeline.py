@@ -18,6 +18,9 @@ captured in a HIP graph (``capture_step``).
 """
 from __future__ import annotations
 
+import ctypes
+import math
+import threading
 from typing import Optional, Tuple
 
 import numpy as np
@@ -29,7 +32,7 @@ from . import attention_extraction as ae
 from . import checkpoint_utils as cu
 from . import new_method as nm
 
-GRID = 24
+GRID = 24                             # side of the image-token grid (ae.NUM_IMAGE_TOKENS = GRID * GRID)
 
 
 def adaptive_avg_pool2d(A: torch.Tensor, output_size=(GRID, GRID), sanitize: bool = False) -> torch.Tensor:
@@ -240,7 +243,6 @@ def clip_preprocess(images_u8: torch.Tensor, size: int = 336, dtype: torch.dtype
     (LLaVA casts to float16, functions.py:270-271).  Bit-identical to the processor for float32.
     ``pad_to_square=True`` runs :func:`expand2square` first (LLaVA-1.5's ``image_aspect_ratio="pad"``; a no-op for
     the square warps of the reference drivers)."""
-    import ctypes
     dev = require_gpu(images_u8)
     if images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
         raise TypeError("clip_preprocess expects a uint8 [B,H,W,C] tensor")
@@ -345,7 +347,97 @@ def capture_step(fn, *args, warmup: int = 2):
     return g, out
 
 
-class OverlappedWarp:
+def capture_steps(step_fn, k0: int, n: int, dev: torch.device):
+    """Capture step_fn(k0, main) .. step_fn(k0 + n - 1, main) as one HIP graph.  The steps launch on the current stream,
+    which is ``main``, a private capture stream, over static buffers; a step that forks side streams joins them back into
+    ``main`` before it returns."""
+    g = torch.cuda.CUDAGraph()
+    main = torch.cuda.Stream(device=dev)
+    main.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(main):
+        with torch.cuda.graph(g, stream=main):
+            for k in range(k0, k0 + n):
+                step_fn(k, main)
+    torch.cuda.current_stream().wait_stream(main)
+    return g
+
+
+class _StepGraphs:
+    """Base of the four stream drivers: their HIP graphs, captured on first use, kept by the state they start from and
+    replayed after.  A driver defines
+
+        _graph_step(k, main)   the launches of step k inside a capture (see :func:`capture_steps`)
+        _graph_start()         (state, k0): the hashable state a graph captured now would start from -- everything that
+                               decides which buffers its steps touch -- and the k of its first step
+        _advance(m)            move the driver m steps on
+
+    A driver that is reset and run again finds the states of its first pass and captures nothing new (``graph_captures``
+    counts).  A base class, not a member holding callbacks: a driver must not sit in a reference cycle.  It owns HIP graphs
+    and device buffers, and what reference counting does not free the collector frees whenever it runs -- in the middle of
+    another driver's capture, where that is an error."""
+
+    def _init_graphs(self, dev):
+        self._graph_dev, self._graphs, self.graph_captures = dev, {}, 0
+
+    def _replay(self, key, k0: int, n: int):
+        """The graph of steps k0 .. k0 + n - 1 kept under ``key``: captured on a miss, replayed either way."""
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = capture_steps(self._graph_step, k0, n, self._graph_dev)
+            self.graph_captures += 1
+        g.replay()
+
+    def _play(self, n: int):
+        """n steps from the current state as ONE graph (one host call), then advance."""
+        state, k0 = self._graph_start()
+        self._replay((state, n), k0, n)
+        self._advance(n)
+
+    def _run_graphs(self, n: int, unroll: int) -> int:
+        """Graphs of ``unroll`` steps while they fit into n (none for unroll < 1); returns the number of steps left."""
+        while unroll > 0 and n >= unroll:
+            self._play(unroll)
+            n -= unroll
+        return n
+
+    def _run(self, n: int, unroll: int):
+        """n steps: graphs of ``unroll`` steps while they fit, then single steps."""
+        for _ in range(self._run_graphs(n, unroll)):
+            self._play(1)
+
+
+def _ring(x, who: str, what: str, dtypes, ndim: Optional[int], mismatch=TypeError, strided=TypeError) -> list:
+    """A tensor or a list of tensors -> the ring (list) of static buffers a stream driver cycles through: not empty, one
+    shape (of ``ndim`` dimensions, None: any), one dtype (out of ``dtypes``, None: any), contiguous -- a graph holds raw
+    pointers.  ``mismatch`` / ``strided``: the exception types of the shape-and-dtype and of the contiguity check."""
+    ring = list(x) if isinstance(x, (list, tuple)) else [x]
+    if not ring:
+        raise ValueError(f"{who}: {what} must be a tensor or a non-empty list of tensors")
+    t0 = ring[0]
+    if any(t.shape != t0.shape or t.dtype != t0.dtype or (ndim is not None and t.dim() != ndim)
+           or (dtypes is not None and t.dtype not in dtypes) for t in ring):
+        names = "any dtype" if dtypes is None else " / ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise mismatch(f"{who}: {what} must have one shape{'' if ndim is None else f' of {ndim} dimensions'} and one dtype "
+                       f"({names})")
+    if not all(t.is_contiguous() for t in ring):
+        raise strided(f"{who}: {what} must be contiguous (static buffers: the graphs hold raw pointers)")
+    return ring
+
+
+_ATTENTION_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+_TRANSFORM_KW = ("transform", "exp_scale", "exp_divisor", "apply_inverse")
+
+
+def _transform_args(transform="identity", exp_scale=1.0, exp_divisor=1.0, apply_inverse=False) -> tuple:
+    """save_warped_image's keyword arguments (new_method.py:405-411; ``_TRANSFORM_KW`` names them in this order) as the
+    launches take them: unknown names mean identity (:400-403), float scale and divisor, bool inverse.  A tuple: every
+    ragged launch calls this."""
+    return transform if transform in nm._KNOWN else "identity", float(exp_scale), float(exp_divisor), bool(apply_inverse)
+
+
+class OverlappedWarp(_StepGraphs):
     """Steady-state form of ``warp_from_attention_stack`` for a stream of equally shaped batches.  The three kernels of
     a step belong to three different batches and are independent --
         R: the resample of batch k                      (HBM-bound, maps[c])
@@ -379,45 +471,38 @@ class OverlappedWarp:
         if pattern not in ("auto", "fused", "am", "dag", "join"):
             raise ValueError("OverlappedWarp: pattern must be 'auto', 'fused', 'am', 'dag' or 'join'")
         self.pattern = pattern
-        self.images = list(images) if isinstance(images, (list, tuple)) else [images]
-        self.rows = list(rows) if isinstance(rows, (list, tuple)) else [rows]
-        if len(self.images) != len(self.rows) or not self.images:
-            raise ValueError("OverlappedWarp: images and rows must be rings of the same length")
+        self.images = _ring(images, "OverlappedWarp", "images", None, 4, mismatch=ValueError, strided=ValueError)
+        self.rows = _ring(rows, "OverlappedWarp", "attention rows [T,B,heads,kv]", _ATTENTION_DTYPES, 4, strided=ValueError)
+        if len(self.images) != len(self.rows) or self.images[0].shape[0] != self.rows[0].shape[1]:
+            raise ValueError("OverlappedWarp: images and rows must be rings of the same length, of batches of the same size")
         dev = require_gpu(*self.images, *self.rows, starts)
-        if not all(t.is_contiguous() for t in self.images + self.rows + [starts]):
-            raise ValueError("OverlappedWarp: static input buffers must be contiguous (the graph holds raw pointers)")
-        if any(r.dtype not in (torch.float32, torch.float16, torch.bfloat16) or r.dtype != self.rows[0].dtype or r.dim() != 4
-               or r.shape != self.rows[0].shape for r in self.rows):
-            raise TypeError("OverlappedWarp: attention rows [T,B,heads,kv] of one shape and one dtype (float32 / float16 / "
-                            "bfloat16) expected")
-        if any(i.shape != self.images[0].shape or i.dtype != self.images[0].dtype for i in self.images):
-            raise ValueError("OverlappedWarp: every image buffer of the ring must have the same shape and dtype")
+        if not starts.is_contiguous():
+            raise ValueError("OverlappedWarp: starts must be contiguous (the graphs hold raw pointers)")
         self.n = len(self.images)
         self.starts = starts.clone()         # own copy: set_starts() writes into it
         self.channels_last, self.mode = channels_last, mode
         img0 = self.images[0]
-        H, W = (img0.shape[1], img0.shape[2]) if channels_last else (img0.shape[2], img0.shape[3])
+        B, H, W, C = img0.shape if channels_last else (img0.shape[0], img0.shape[2], img0.shape[3], img0.shape[1])
+        Ho, Wo = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        self.B, self.C, self.H, self.W, self.Ho, self.Wo = B, C, H, W, Ho, Wo
         self.size_hw = (H, W)
         self.out_size = out_size
-        T = self.rows[0].shape[0]
-        self.starts_tiled = starts.repeat(T).contiguous()
-        B = img0.shape[0]
-        Ho, Wo = (H, W) if out_size is None else out_size
-        shape = (B, Ho, Wo, img0.shape[3]) if channels_last else (B, img0.shape[1], Ho, Wo)
+        self._T, _, self._heads, self._kv = self.rows[0].shape
+        self.starts_tiled = starts.repeat(self._T).contiguous()
+        shape = (B, Ho, Wo, C) if channels_last else (B, C, Ho, Wo)
         self.outs = [torch.empty(shape, device=dev, dtype=img0.dtype) for _ in range(self.n)]
         self.cur = 0                 # which (steps, maps) buffer set the next resample reads
         self.k = 0                   # ring position of the next resample
         self._dev = dev
         self._sideM = torch.cuda.Stream(device=dev)
         self._sideA = torch.cuda.Stream(device=dev)
-        self._graphs = {}
+        self._init_graphs(dev)
         # both buffer sets, filled once outside capture (allocations, lazily built tables)
         self.steps = [attention_step_maps(self.rows[0], self.starts, ae.NUM_IMAGE_TOKENS, self.starts_tiled) for _ in (0, 1)]
         self.maps = [axis_maps_from_attention_steps(self.steps[i], self.size_hw, self.out_size) for i in (0, 1)]
         cu.remap_separable(self.images[0], *self.maps[0], mode=self.mode, channels_last=self.channels_last, out=self.outs[0])
         torch.cuda.synchronize(dev)
-        g = int(round(ae.NUM_IMAGE_TOKENS ** 0.5))
-        self._inv = (_tables.right_inverse_inv(g, W, 1e-8, dev), _tables.right_inverse_inv(g, H, 1e-8, dev))
+        self._inv = (_tables.right_inverse_inv(GRID, W, 1e-8, dev), _tables.right_inverse_inv(GRID, H, 1e-8, dev))
         if self.pattern == "auto" and img0.dtype == torch.float32 and img0[0].numel() * 4 >= (4 << 20):
             # large images (>= 4 MB each): the resample is > 90 % of a step and keeps its own launch (inside the fused launch it runs 2 %
             # slower); the reduce and the latency-bound map construction share one (attwarp_attn_reduce_and_maps)
@@ -443,22 +528,15 @@ class OverlappedWarp:
         """R(k) | M(k+1) | A(k+2) as ONE launch (block ranges of one grid)."""
         img, out = self.images[k % self.n], self.outs[k % self.n]
         rows = self.rows[(k + 2) % self.n]
-        T, B, heads, kv = rows.shape
-        if self.channels_last:
-            _, H, W, C = img.shape
-            _, Ho, Wo, _ = out.shape
-        else:
-            _, C, H, W = img.shape
-            _, _, Ho, Wo = out.shape
+        T, B = self._T, self.B
         mx, my = self.maps[c]
         nx, ny = self.maps[1 - c]
-        g = int(round(ae.NUM_IMAGE_TOKENS ** 0.5))
         with torch.cuda.device(self._dev):
-            call("attwarp_warp_step_fused", ptr(img), ptr(out), _lib.HWC if self.channels_last else _lib.CHW, B, C, H, W,
-                 Ho, Wo, ptr(mx), ptr(my), _lib.MODE_IDS[self.mode],
-                 _lib.dtype_id(rows), ptr(self.steps[c]), T, g, ptr(self._inv[0]), ptr(self._inv[1]), ptr(nx), ptr(ny),
-                 ptr(rows), T * B, heads, kv, ptr(self.starts_tiled), T * B, ae.NUM_IMAGE_TOKENS, ptr(self.steps[1 - c]),
-                 stream_ptr(self._dev))
+            call("attwarp_warp_step_fused", ptr(img), ptr(out), _lib.HWC if self.channels_last else _lib.CHW, B, self.C, self.H,
+                 self.W, self.Ho, self.Wo, ptr(mx), ptr(my), _lib.MODE_IDS[self.mode],
+                 _lib.dtype_id(rows), ptr(self.steps[c]), T, GRID, ptr(self._inv[0]), ptr(self._inv[1]), ptr(nx), ptr(ny),
+                 ptr(rows), T * B, self._heads, self._kv, ptr(self.starts_tiled), T * B, ae.NUM_IMAGE_TOKENS,
+                 ptr(self.steps[1 - c]), stream_ptr(self._dev))
 
     @property
     def out(self) -> torch.Tensor:
@@ -473,21 +551,18 @@ class OverlappedWarp:
     def _am_launch(self, c, k):
         """A(k+2): rows[k+2] -> steps[1-c]  and  M(k+1): steps[c] -> maps[1-c]  as ONE launch."""
         rows = self.rows[(k + 2) % self.n]
-        T, B, heads, kv = rows.shape
-        H, W = self.size_hw
-        Ho, Wo = (H, W) if self.out_size is None else self.out_size
-        g = int(round(ae.NUM_IMAGE_TOKENS ** 0.5))
+        T, B = self._T, self.B
         nx, ny = self.maps[1 - c]
         with torch.cuda.device(self._dev):
-            call("attwarp_attn_reduce_and_maps", _lib.dtype_id(rows), ptr(rows), T * B, heads, kv, ptr(self.starts_tiled), T * B,
-                 ae.NUM_IMAGE_TOKENS, ptr(self.steps[1 - c]), ptr(self.steps[c]), T, B, g, W, H, Wo, Ho, ptr(self._inv[0]),
-                 ptr(self._inv[1]), ptr(nx), ptr(ny), stream_ptr(self._dev))
+            call("attwarp_attn_reduce_and_maps", _lib.dtype_id(rows), ptr(rows), T * B, self._heads, self._kv,
+                 ptr(self.starts_tiled), T * B, ae.NUM_IMAGE_TOKENS, ptr(self.steps[1 - c]), ptr(self.steps[c]), T, B, GRID,
+                 self.W, self.H, self.Wo, self.Ho, ptr(self._inv[0]), ptr(self._inv[1]), ptr(nx), ptr(ny), stream_ptr(self._dev))
 
     def _reduce(self, i, r):
         """A: rows[r] -> steps[i]"""
-        T, B, heads, kv = self.rows[r].shape
-        ae.attn_reduce_step(self.rows[r].view(T * B, heads, 1, kv), self.starts_tiled, ae.NUM_IMAGE_TOKENS,
-                            out=self.steps[i].view(T * B, ae.NUM_IMAGE_TOKENS))
+        n_rows = self._T * self.B
+        ae.attn_reduce_step(self.rows[r].view(n_rows, self._heads, 1, self._kv), self.starts_tiled, ae.NUM_IMAGE_TOKENS,
+                            out=self.steps[i].view(n_rows, ae.NUM_IMAGE_TOKENS))
 
     def _maps(self, i_steps, i_maps):
         """M: steps[i_steps] -> maps[i_maps]"""
@@ -497,73 +572,60 @@ class OverlappedWarp:
         cu.remap_separable(self.images[r], *self.maps[i], mode=self.mode, channels_last=self.channels_last,
                            out=self.outs[r])
 
-    def _capture(self, c, k, unroll: int = 1):
-        """graph: ``unroll`` consecutive steps starting with buffer set c at ring position k.  Step u launches
+    def _graph_step(self, k, main):
+        """One step inside a capture on ``main``, with the buffer set the stream has reached at ring position k.  It launches
         R(k): resample images[k] with maps[c] | M(k+1): steps[c] -> maps[1-c] | A(k+2): rows[k+2] -> steps[1-c].
         pattern "dag": R and A alternate on ONE stream (both are bandwidth-bound: side by side they would only share
         the same HBM), the latency-bound M runs on a side stream with exactly the edges the buffers need -- M(k+1) after
         A(k+1) and R(k-1) (which read maps[1-c]), R(k+1) after M(k+1), A(k+3) after M(k+1) (which read steps[c]) -- so the
         main stream never waits for a kernel that has not long finished.  pattern "join": three branches forked and
         joined in every step."""
-        g = torch.cuda.CUDAGraph()
-        main = torch.cuda.Stream(device=self._dev)
-        main.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(main):
-            with torch.cuda.graph(g, stream=main):
-                if self.pattern in ("fused", "am"):
-                    for u in range(unroll):
-                        (self._fused_step if self.pattern == "fused" else self._am_step)(c, k)
-                        c ^= 1
-                        k += 1
-                elif self.pattern == "dag":
-                    for u in range(unroll):
-                        # main so far: ..., A(k+1), R(k-1) [previous step: R then A]; side: ..., M(k)
-                        self._sideM.wait_stream(main)                # M(k+1) after A(k+1) and R(k-1)
-                        with torch.cuda.stream(self._sideM):
-                            self._maps(c, 1 - c)
-                        self._resample(c, k % self.n)                # R(k) needs M(k): joined at the end of step u-1
-                        self._reduce(1 - c, (k + 2) % self.n)        # A(k+2) overwrites steps[1-c], read by M(k): done
-                        main.wait_stream(self._sideM)                # next R needs M(k+1); next A overwrites steps[c]
-                        c ^= 1
-                        k += 1
-                else:
-                    for u in range(unroll):
-                        self._sideM.wait_stream(main)                # fork
-                        self._sideA.wait_stream(main)
-                        with torch.cuda.stream(self._sideA):
-                            self._reduce(1 - c, (k + 2) % self.n)
-                        with torch.cuda.stream(self._sideM):
-                            self._maps(c, 1 - c)
-                        self._resample(c, k % self.n)
-                        main.wait_stream(self._sideM)                # join
-                        main.wait_stream(self._sideA)
-                        c ^= 1
-                        k += 1
-        torch.cuda.current_stream().wait_stream(main)
-        return g
+        c = self.cur ^ ((k - self.k) & 1)                    # (cur and k stand still while their graph is captured)
+        if self.pattern == "fused":
+            self._fused_step(c, k)
+        elif self.pattern == "am":
+            self._am_step(c, k)
+        elif self.pattern == "dag":
+            # main so far: ..., A(k+1), R(k-1) [previous step: R then A]; side: ..., M(k)
+            self._sideM.wait_stream(main)                # M(k+1) after A(k+1) and R(k-1)
+            with torch.cuda.stream(self._sideM):
+                self._maps(c, 1 - c)
+            self._resample(c, k % self.n)                # R(k) needs M(k): joined at the end of step u-1
+            self._reduce(1 - c, (k + 2) % self.n)        # A(k+2) overwrites steps[1-c], read by M(k): done
+            main.wait_stream(self._sideM)                # next R needs M(k+1); next A overwrites steps[c]
+        else:
+            self._sideM.wait_stream(main)                # fork
+            self._sideA.wait_stream(main)
+            with torch.cuda.stream(self._sideA):
+                self._reduce(1 - c, (k + 2) % self.n)
+            with torch.cuda.stream(self._sideM):
+                self._maps(c, 1 - c)
+            self._resample(c, k % self.n)
+            main.wait_stream(self._sideM)                # join
+            main.wait_stream(self._sideA)
 
-    def _graph(self, unroll):
-        key = (self.cur, self.k % self.n, unroll)
-        if key not in self._graphs:
-            self._graphs[key] = self._capture(self.cur, self.k % self.n, unroll)
-        return self._graphs[key]
+    def _graph_start(self):
+        return (self.cur, self.k % self.n), self.k           # cur is not the parity of k: flush() advances k alone
+
+    def _advance(self, m):
+        self.cur ^= m & 1
+        self.k += m
+
+    @staticmethod
+    def round_unroll(unroll: int, n: int) -> int:
+        """The graph length run() uses: even, and for a ring of n > 1 buffers a multiple of lcm(2, n) (at least one), so
+        that a graph returns to the state it started from and is re-used; 0 (single steps only) below 2."""
+        unroll -= unroll % 2
+        if unroll >= 2 and n > 1:
+            period = math.lcm(2, n)
+            unroll = max(period, unroll - unroll % period)
+        return unroll if unroll >= 2 else 0
 
     def run(self, n: int, unroll: int = 8) -> torch.Tensor:
         """n steps on the buffers as they are (steady-state measurement / a producer that stays ahead of the ring):
         graphs of ``unroll`` steps (one host call per ``unroll`` steps), then single steps for the remainder.  With a
         ring of n buffers a graph of lcm(2, n)-multiple length returns to the state it started from and is re-used."""
-        unroll -= unroll % 2
-        if unroll >= 2 and self.n > 1:
-            import math
-            period = math.lcm(2, self.n)
-            unroll = max(period, unroll - unroll % period)
-        while unroll >= 2 and n >= unroll:
-            self._graph(unroll).replay()
-            self.cur ^= unroll & 1
-            self.k += unroll
-            n -= unroll
-        for _ in range(n):
-            self.step()
+        self._run(n, self.round_unroll(unroll, self.n))
         return self.out
 
     def set_starts(self, starts: torch.Tensor):
@@ -590,9 +652,7 @@ class OverlappedWarp:
         self._reduce(self.cur, (self.k + 1) % self.n)
 
     def step(self) -> torch.Tensor:
-        self._graph(1).replay()
-        self.cur ^= 1
-        self.k += 1
+        self._play(1)
         return self.out
 
     def flush(self) -> torch.Tensor:
@@ -611,13 +671,10 @@ class OverlappedWarp:
         return self.flush()
 
 
-class _StepSlot(__import__("ctypes").Structure):
-    """``attwarp_step_slot`` of include/attwarp.h (device pointers)."""
-    _fields_ = [(n, __import__("ctypes").c_void_p) for n in ("src", "dst", "map_x", "map_y", "steps_in", "map_x_next", "map_y_next",
-                                                             "rows", "starts", "steps_out")]
+_StepSlot = _lib.StepSlot
 
 
-class PairedStepWarp:
+class PairedStepWarp(_StepGraphs):
     """``OverlappedWarp`` pattern "fused" with TWO batches of the stream per piece and launch
     (attwarp_warp_step_fused_slots):
 
@@ -638,23 +695,21 @@ class PairedStepWarp:
     Bit-identical, batch by batch, to ``warp_from_attention_stack`` (same kernels bodies, same arguments)."""
 
     def __init__(self, images, rows, starts: torch.Tensor, out_size=None, channels_last: bool = False, mode: str = "cv2"):
-        self.images, self.rows = list(images), list(rows)
-        if len(self.images) != len(self.rows) or len(self.images) < 2 or len(self.images) % 2:
-            raise ValueError("PairedStepWarp: images and rows must be rings of the same even length >= 2")
-        dev = require_gpu(*self.images, *self.rows, starts)
+        self.images = _ring(images, "PairedStepWarp", "images", (torch.float32,), 4)
+        self.rows = _ring(rows, "PairedStepWarp", "attention rows [T,B,heads,kv]", _ATTENTION_DTYPES, 4)
         img0, r0 = self.images[0], self.rows[0]
-        if any(i.dtype != torch.float32 or i.shape != img0.shape or not i.is_contiguous() for i in self.images):
-            raise TypeError("PairedStepWarp: contiguous float32 image buffers of one shape expected")
-        if any(r.dtype not in (torch.float32, torch.float16, torch.bfloat16) or r.dtype != r0.dtype or r.shape != r0.shape
-               or r.dim() != 4 or not r.is_contiguous() for r in self.rows):
-            raise TypeError("PairedStepWarp: contiguous attention rows [T,B,heads,kv] of one shape and dtype expected")
+        if len(self.images) != len(self.rows) or len(self.images) % 2 or img0.shape[0] != r0.shape[1]:
+            raise ValueError("PairedStepWarp: images and rows must be rings of the same even length >= 2, of batches of the "
+                             "same size")
+        dev = require_gpu(*self.images, *self.rows, starts)
         self.n = len(self.images)
         self.channels_last, self.mode, self._dev = channels_last, mode, dev
         H, W = (img0.shape[1], img0.shape[2]) if channels_last else (img0.shape[2], img0.shape[3])
         self.C = img0.shape[3] if channels_last else img0.shape[1]
         self.B, self.H, self.W = img0.shape[0], H, W
         self.Ho, self.Wo = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
-        T = r0.shape[0]
+        self._T, _, self._heads, self._kv = r0.shape
+        T = self._T
         self.starts = starts.clone()
         self.starts_tiled = starts.repeat(T).contiguous()
         shape = (self.B, self.Ho, self.Wo, self.C) if channels_last else (self.B, self.C, self.Ho, self.Wo)
@@ -662,18 +717,16 @@ class PairedStepWarp:
         self.steps = [torch.empty(T, self.B, ae.NUM_IMAGE_TOKENS, device=dev, dtype=r0.dtype) for _ in range(4)]
         self.maps = [(torch.empty(self.B, self.Wo, device=dev, dtype=torch.float32),
                       torch.empty(self.B, self.Ho, device=dev, dtype=torch.float32)) for _ in range(4)]
-        g = int(round(ae.NUM_IMAGE_TOKENS ** 0.5))
-        self.g = g
-        self._inv = (_tables.right_inverse_inv(g, W, 1e-8, dev), _tables.right_inverse_inv(g, H, 1e-8, dev))
+        self.g = GRID
+        self._inv = (_tables.right_inverse_inv(GRID, W, 1e-8, dev), _tables.right_inverse_inv(GRID, H, 1e-8, dev))
         self.k = 0
-        self._graphs = {}
+        self._init_graphs(dev)
         self._launch(0)                        # eligibility (raises AttWarpError) + lazy module loading, outside any capture
         torch.cuda.synchronize(dev)
 
     def _launch(self, k):
         """R(k), R(k+1) | M(k+2), M(k+3) | A(k+4), A(k+5)"""
-        import ctypes
-        T, B, heads, kv = self.rows[0].shape
+        T, B = self._T, self.B
         slots = (_StepSlot * 2)()
         for s in (0, 1):
             j = k + s
@@ -685,13 +738,13 @@ class PairedStepWarp:
         with torch.cuda.device(self._dev):
             call("attwarp_warp_step_fused_slots", ctypes.cast(slots, ctypes.c_void_p), 2,
                  _lib.HWC if self.channels_last else _lib.CHW, B, self.C, self.H, self.W, self.Ho, self.Wo, _lib.MODE_IDS[self.mode],
-                 _lib.dtype_id(self.rows[0]), T, self.g, ptr(self._inv[0]), ptr(self._inv[1]), T * B, heads, kv, T * B,
+                 _lib.dtype_id(self.rows[0]), T, self.g, ptr(self._inv[0]), ptr(self._inv[1]), T * B, self._heads, self._kv, T * B,
                  ae.NUM_IMAGE_TOKENS, stream_ptr(self._dev))
 
     def _reduce(self, j):
-        T, B, heads, kv = self.rows[0].shape
-        ae.attn_reduce_step(self.rows[j % self.n].view(T * B, heads, 1, kv), self.starts_tiled, ae.NUM_IMAGE_TOKENS,
-                            out=self.steps[j % 4].view(T * B, ae.NUM_IMAGE_TOKENS))
+        n_rows = self._T * self.B
+        ae.attn_reduce_step(self.rows[j % self.n].view(n_rows, self._heads, 1, self._kv), self.starts_tiled,
+                            ae.NUM_IMAGE_TOKENS, out=self.steps[j % 4].view(n_rows, ae.NUM_IMAGE_TOKENS))
 
     def _maps(self, j):
         axis_maps_from_attention_steps(self.steps[j % 4], (self.H, self.W), (self.Ho, self.Wo), maps_out=self.maps[j % 4])
@@ -709,37 +762,25 @@ class PairedStepWarp:
             self._reduce(j)
         self._maps(k); self._maps(k + 1)
 
-    def _graph(self, pairs):
-        import math
-        key = (self.k % math.lcm(4, self.n), pairs)
-        if key not in self._graphs:
-            g = torch.cuda.CUDAGraph()
-            main = torch.cuda.Stream(device=self._dev)
-            main.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(main):
-                with torch.cuda.graph(g, stream=main):
-                    for q in range(pairs):
-                        self._launch(self.k + 2 * q)
-            torch.cuda.current_stream().wait_stream(main)
-            self._graphs[key] = g
-        return self._graphs[key]
+    # a graph step is one launch = two batches (k stays even); its buffer indices depend on k mod 4 (maps) and k mod n (ring)
+    def _graph_step(self, p, main):
+        self._launch(2 * p)
+
+    def _graph_start(self):
+        return self.k % math.lcm(4, self.n), self.k // 2
+
+    def _advance(self, pairs):
+        self.k += 2 * pairs
 
     def step(self):
         """One launch = two batches."""
-        self._graph(1).replay()
-        self.k += 2
+        self._play(1)
 
     def run(self, n_batches: int, unroll_pairs: int = 4):
         """n_batches (even) batches: graphs of ``unroll_pairs`` launches, then single launches."""
         if n_batches % 2:
             raise ValueError("PairedStepWarp.run: an even number of batches")
-        pairs = n_batches // 2
-        while pairs >= unroll_pairs:
-            self._graph(unroll_pairs).replay()
-            self.k += 2 * unroll_pairs
-            pairs -= unroll_pairs
-        for _ in range(pairs):
-            self.step()
+        self._run(n_batches // 2, unroll_pairs)
 
     def tail(self):
         """The last four batches of a stream that ends: R(k), R(k+1), M + R of k+2, k+3 (their reduce is done)."""
@@ -771,7 +812,7 @@ def pair_slots(ring):
     return out
 
 
-class MaskChainStream:
+class MaskChainStream(_StepGraphs):
     """Steady-state form of :func:`warp_from_masks` -- the chain ``main_batched.py:243-287`` runs per image -- for a STREAM
     of equally shaped batches.  The stages of the chain belong to different batches and are independent:
 
@@ -811,16 +852,12 @@ class MaskChainStream:
                  exp_scale=1.0, exp_divisor=1.0, apply_inverse=False, mode: str = "cv2", pattern: str = "auto"):
         if pattern not in self.PATTERNS:
             raise ValueError(f"MaskChainStream: pattern must be one of {self.PATTERNS}")
-        self.images = list(images) if isinstance(images, (list, tuple)) else [images]
-        self.masks = list(masks) if isinstance(masks, (list, tuple)) else [masks]
-        if len(self.images) != len(self.masks) or not self.images:
+        self.images = _ring(images, "MaskChainStream", "images [B,H,W,C]", (torch.uint8,), 4)
+        self.masks = _ring(masks, "MaskChainStream", "masks [B,n,n]", (torch.float32,), 3)
+        if len(self.images) != len(self.masks):
             raise ValueError("MaskChainStream: images and masks must be rings of the same length")
         dev = require_gpu(*self.images, *self.masks)
         img0, m0 = self.images[0], self.masks[0]
-        if any(i.dtype != torch.uint8 or i.dim() != 4 or i.shape != img0.shape or not i.is_contiguous() for i in self.images):
-            raise TypeError("MaskChainStream: images must be contiguous uint8 [B,H,W,C] tensors of one shape")
-        if any(m.dtype != torch.float32 or m.dim() != 3 or m.shape != m0.shape or not m.is_contiguous() for m in self.masks):
-            raise TypeError("MaskChainStream: masks must be contiguous float32 [B,n,n] tensors of one shape")
         B, H, W, C = img0.shape
         if m0.shape[0] != B or m0.shape[1] != m0.shape[2]:
             raise ValueError("MaskChainStream: masks [B,n,n] must match the image batch")
@@ -831,13 +868,14 @@ class MaskChainStream:
         self.Ho, self.Wo = int(out_size[0]), int(out_size[1])
         self.mode = mode
         self.enhance_coe, self.kernel_size = float(enhance_coe), int(kernel_size)
-        self.transform = transform if transform in nm._KNOWN else "identity"
-        self.exp_scale, self.exp_divisor, self.apply_inverse = float(exp_scale), float(exp_divisor), bool(apply_inverse)
+        xf = _transform_args(transform, exp_scale, exp_divisor, apply_inverse)
+        self.transform, self.exp_scale, self.exp_divisor, self.apply_inverse = xf
+        self._xf = dict(zip(_TRANSFORM_KW, xf))
         self._dev = dev
         lib = _lib.load()
         self.outs = [torch.empty(B, self.Ho, self.Wo, C, device=dev, dtype=torch.uint8) for _ in range(self.n)]
         self.k = 0
-        self._graphs = {}
+        self._init_graphs(dev)
         self._side = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
         self.pattern = pattern
         # the table of the transformed byte values the one-launch steps read for sqrt / exp / log (a constant of the stream)
@@ -878,7 +916,6 @@ class MaskChainStream:
         uses the intermediates of parity j & 1: one RaggedBatch per (slot, parity) that occurs -- n for an even ring, 2 n for
         an odd one -- each with its own table (the table names the slot's images), all batches of one parity SHARING one set
         of intermediates (rev / mota / sums / maps: two sets in all, as the uniform step)."""
-        import math
         self._rb = {}
         first = {}
         for j in range(math.lcm(2, self.n)):
@@ -949,17 +986,14 @@ class MaskChainStream:
 
     def _ragged_launch(self, **stages):
         ragged_chain_launch(**{s: self._ragged(j) for s, j in stages.items()}, enhance_coe=self.enhance_coe, kernel_size=self.kernel_size,
-                            transform=self.transform, exp_scale=self.exp_scale, exp_divisor=self.exp_divisor,
-                            apply_inverse=self.apply_inverse)
+                            **self._xf)
 
     # ---- driving ----
     def prime(self):
         """Everything the first step expects to find done for the batches at ring positions k .. k+depth-1 (serial)."""
         k = self.k
         if self.pattern == "ragged":
-            for j, stages in ((k, "VLPF"), (k + 1, "VLP"), (k + 2, "VL"), (k + 3, "V")):
-                for st in stages:
-                    self._ragged_launch(**{st: j})
+            _ragged_serial(_RAGGED_FILL, k, lambda st, j: self._ragged_launch(**{st: j}))
             return
         if self.pattern == "branches":      # step k runs R(k) | PF(k+1) | VL(k+2)
             self._V(k); self._L(k); self._PF(k)
@@ -981,35 +1015,25 @@ class MaskChainStream:
         else:
             raise RuntimeError("branches are only defined inside a capture")
 
-    def _capture(self, k, unroll):
-        g = torch.cuda.CUDAGraph()
-        main = torch.cuda.Stream(device=self._dev)
-        main.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(main):
-            with torch.cuda.graph(g, stream=main):
-                for u in range(unroll):
-                    if self.pattern == "branches":
-                        s1, s2 = self._side
-                        s1.wait_stream(main); s2.wait_stream(main)          # fork
-                        with torch.cuda.stream(s1):
-                            self._PF(k + 1)
-                        with torch.cuda.stream(s2):
-                            self._V(k + 2); self._L(k + 2)
-                        self._R(k)
-                        main.wait_stream(s1); main.wait_stream(s2)          # join
-                    else:
-                        self._one(k)
-                    k += 1
-        torch.cuda.current_stream().wait_stream(main)
-        return g
+    def _graph_step(self, k, main):
+        """Step k inside a capture on ``main``."""
+        if self.pattern == "branches":
+            s1, s2 = self._side
+            s1.wait_stream(main); s2.wait_stream(main)          # fork
+            with torch.cuda.stream(s1):
+                self._PF(k + 1)
+            with torch.cuda.stream(s2):
+                self._V(k + 2); self._L(k + 2)
+            self._R(k)
+            main.wait_stream(s1); main.wait_stream(s2)          # join
+        else:
+            self._one(k)
 
-    def _graph(self, unroll):
-        # the buffer indices of a step depend on k mod n (ring) and k mod 2 (parity)
-        import math
-        key = (self.k % math.lcm(2, self.n), unroll)
-        if key not in self._graphs:
-            self._graphs[key] = self._capture(self.k, unroll)
-        return self._graphs[key]
+    def _graph_start(self):
+        return self.k % math.lcm(2, self.n), self.k          # the buffer indices of a step depend on k mod n and k mod 2
+
+    def _advance(self, m):
+        self.k += m
 
     @property
     def out(self) -> torch.Tensor:
@@ -1017,21 +1041,19 @@ class MaskChainStream:
         return self.outs[(self.k - 1) % self.n]
 
     def step(self) -> torch.Tensor:
-        self._graph(1).replay()
-        self.k += 1
+        self._play(1)
         return self.out
+
+    @staticmethod
+    def round_unroll(unroll: int) -> int:
+        """The graph length run() uses: even (a graph returns to the parity it started from), at least 2."""
+        return max(2, unroll - unroll % 2)
 
     def run(self, n: int, unroll: int = 8) -> torch.Tensor:
         """n steps on the buffers as they are (steady-state measurement / a producer that stays ahead of the ring): graphs
         of ``unroll`` steps (one host call each), then single steps.  A graph is keyed by the ring position it starts at
         (mod lcm(2, ring length)), so a stream that is reset() and run again replays the graphs of the first pass."""
-        unroll = max(2, unroll - unroll % 2)
-        while n >= unroll:
-            self._graph(unroll).replay()
-            self.k += unroll
-            n -= unroll
-        for _ in range(n):
-            self.step()
+        self._run(n, self.round_unroll(unroll))
         return self.out
 
     def reset(self):
@@ -1041,9 +1063,7 @@ class MaskChainStream:
         """The last ``depth`` batches of a stream that ends (no further masks): the remaining stages, serially."""
         k = self.k
         if self.pattern == "ragged":
-            for j, stages in ((k, "R"), (k + 1, "FR"), (k + 2, "PFR"), (k + 3, "LPFR")):
-                for st in stages:
-                    self._ragged_launch(**{st: j})
+            _ragged_serial(_RAGGED_DRAIN, k, lambda st, j: self._ragged_launch(**{st: j}))
         elif self.pattern == "branches":
             self._R(k); self._PF(k + 1); self._R(k + 1)
         elif self.pattern == "fused":
@@ -1060,16 +1080,30 @@ RAGGED_MAX_ROW_BYTES = 4096          # attwarp_ragged_plan: rows of the integer 
 RAGGED_MAX_SIDE = 8192
 
 
+# the ends of the one-launch-per-step pipeline R(k) | F(k+1) | P(k+2) | L(k+3) | V(k+4), stage by stage: (batch behind k, its
+# stages in launch order).  The fill leaves the four batches ahead of step k where that step expects them; the drain finishes
+# the four batches in flight behind the last step.
+_RAGGED_FILL = ((0, "VLPF"), (1, "VLP"), (2, "VL"), (3, "V"))
+_RAGGED_DRAIN = ((0, "R"), (1, "FR"), (2, "PFR"), (3, "LPFR"))
+
+
+def _ragged_serial(schedule, k: int, launch):
+    """``launch(stage, j)`` -- one stage of batch j alone -- for every entry of a fill / drain schedule at position k."""
+    for d, stages in schedule:
+        for st in stages:
+            launch(st, k + d)
+
+
 def ragged_eligible(h: int, w: int, c: int, g: int = GRID) -> bool:
     """Does an [h,w,c] uint8 image run on the ragged chain kernel (attwarp.h: limits of attwarp_ragged_plan)?"""
     return 4 <= w * c <= RAGGED_MAX_ROW_BYTES and h > g and w > g and max(h, w) <= RAGGED_MAX_SIDE and c <= 4
 
 
-_RAGGED_IMAGE_DTYPE = np.dtype([("image", "<u8"), ("bounds_x", "<u8"), ("kk_x", "<u8"), ("bounds_y", "<u8"), ("kk_y", "<u8"),
-                                ("H", "<i4"), ("W", "<i4"), ("ksize_x", "<i4"), ("reserved", "<i4")])      # attwarp_ragged_image
+_RAGGED_IMAGE_DTYPE = np.dtype(_lib.RaggedImage)       # attwarp_ragged_image as a record array: one column per field
+_RaggedImageDev = _lib.RaggedImageDev
 _AXIS_TABLES: dict = {}
 _STAGING: dict = {}                   # device index -> pinned staging buffers: [tensor, event of the last copy out of it, free]
-_STAGING_LOCK = __import__("threading").Lock()     # (host threads on their own streams share the pool)
+_STAGING_LOCK = threading.Lock()     # (host threads on their own streams share the pool)
 
 
 _AXIS_TABLES_MAX = 4096              # distinct (device, g, size) entries kept (40 KB of device memory each at size 1024)
@@ -1133,7 +1167,6 @@ class RaggedBatch:
                  share: Optional["RaggedBatch"] = None):
         """``share``: a RaggedBatch of the SAME image sizes whose intermediates (rev / mota / sums / maps) this batch adopts
         instead of allocating its own -- the batches of one parity of a stream never have two stages in flight at once."""
-        import ctypes
         images = list(images)
         if not images:
             raise ValueError("RaggedBatch: empty batch")
@@ -1197,20 +1230,10 @@ class RaggedBatch:
 
     def mota_of(self, b: int) -> torch.Tensor:
         """The up-sampled uint8 mask [H_b,W_b] of image b (what blend_mask returns as ``mota_mask``, llava.py:253)."""
-        import ctypes
         rec = (_RaggedImageDev * self.B).from_address(self.table_host.ctypes.data + int(self.header.off_images))
         H, W = int(self.images[b].shape[0]), int(self.images[b].shape[1])
         off = int(rec[b].mota_off)
         return self.mota[off:off + H * W].view(H, W)
-
-
-class _RaggedImageDev(__import__("ctypes").Structure):
-    """The per-image record inside a table (chain_ragged.hip: RaggedImage); read here only for ``mota_off``."""
-    import ctypes as _c
-    _fields_ = [("image", _c.c_void_p), ("bounds_x", _c.c_void_p), ("kk_x", _c.c_void_p), ("bounds_y", _c.c_void_p),
-                ("kk_y", _c.c_void_p), ("H", _c.c_int32), ("W", _c.c_int32), ("ksize_x", _c.c_int32), ("plan_w", _c.c_int32),
-                ("plan_h", _c.c_int32), ("l_nchunks", _c.c_int32), ("l_rows_per_chunk", _c.c_int32), ("ki", _c.c_int32),
-                ("mota_off", _c.c_int64), ("sums_off", _c.c_int64)]
 
 
 def upload_images(images, device=None):
@@ -1251,8 +1274,7 @@ def ragged_chain_launch(R: Optional[RaggedBatch] = None, F: Optional[RaggedBatch
     save_warped_image's keyword arguments (new_method.py:405-411), used by P and F; unknown names mean identity (:400-403)."""
     some = next(b for b in (R, F, P, L, V) if b is not None)
     dev = some._dev
-    if transform not in nm._KNOWN:
-        transform = "identity"
+    transform, exp_scale, exp_divisor, apply_inverse = _transform_args(transform, exp_scale, exp_divisor, apply_inverse)
     lut = _tables.attention_transform_lut(transform, exp_scale, exp_divisor, dev) if P is not None else None
     def tab(b):
         return (None, None) if b is None else (b.table_host.ctypes.data, ptr(b.table_dev))
@@ -1266,7 +1288,7 @@ def ragged_chain_launch(R: Optional[RaggedBatch] = None, F: Optional[RaggedBatch
              *tab(P), ptr(P.mota) if P else None, ptr(P.sums) if P else None,
              *tab(L), ptr(L.rev) if L else None, ptr(L.mota) if L else None,
              ptr(V.masks) if V else None, V.B if V else 0, some.g, int(kernel_size), float(enhance_coe), ptr(V.rev) if V else None,
-             _lib.TRANSFORM_IDS[transform], float(exp_scale), float(exp_divisor), int(bool(apply_inverse)), ptr(lut),
+             _lib.TRANSFORM_IDS[transform], exp_scale, exp_divisor, int(apply_inverse), ptr(lut),
              stream_ptr(dev))
 
 
@@ -1325,7 +1347,7 @@ def warp_from_masks_ragged(images, attn24: torch.Tensor, out_size=(500, 500), en
     return (out, None) if return_batch else out
 
 
-class RaggedMaskChainStream:
+class RaggedMaskChainStream(_StepGraphs):
     """A stream of ragged batches, one launch per batch: R(k) | F(k+1) | P(k+2) | L(k+3) | V(k+4) of
     ``attwarp_mask_chain_ragged`` (the ragged twin of :class:`MaskChainStream`).
 
@@ -1345,10 +1367,8 @@ class RaggedMaskChainStream:
         self.out_size = (int(out_size[0]), int(out_size[1]))
         self.enhance_coe, self.kernel_size, self.g = float(enhance_coe), int(kernel_size), int(g)
         # save_warped_image's keyword arguments (new_method.py:405-411), constants of the stream
-        self._xf = dict(transform=transform if transform in nm._KNOWN else "identity", exp_scale=float(exp_scale),
-                        exp_divisor=float(exp_divisor), apply_inverse=bool(apply_inverse))
+        self._xf = dict(zip(_TRANSFORM_KW, _transform_args(transform, exp_scale, exp_divisor, apply_inverse)))
         self._q = []                       # the batches in flight, oldest first: [k-4 .. k]
-        self._graphs = {}
 
     def _stages(self, **stages):
         ragged_chain_launch(**stages, enhance_coe=self.enhance_coe, kernel_size=self.kernel_size, **self._xf)
@@ -1358,12 +1378,15 @@ class RaggedMaskChainStream:
         if any(b is not None for b in q):
             self._stages(R=q[0], F=q[1], P=q[2], L=q[3], V=q[4])
 
+    def _window(self):
+        """The five [R, F, P, L, V] slots of a launch that takes the youngest batch in flight as V (None: no batch)."""
+        return ([None] * (self.DEPTH + 1) + self._q)[-(self.DEPTH + 1):]
+
     def push(self, images, attn24: torch.Tensor, out: Optional[torch.Tensor] = None):
         rb = RaggedBatch(images, self.out_size, self.g, out=out)
         rb.masks = attn24.float().contiguous()
         self._q.append(rb)
-        q = ([None] * (self.DEPTH + 1) + self._q)[-(self.DEPTH + 1):]
-        self._launch(q)
+        self._launch(self._window())
         if len(self._q) > self.DEPTH:
             return self._q.pop(0)
         return None
@@ -1373,8 +1396,7 @@ class RaggedMaskChainStream:
         done = []
         # the youngest batch in flight has had V only, the one before it V and L, ...: one launch moves every batch one
         # stage on ([R, F, P, L, V] slots, oldest first)
-        q = ([None] * (self.DEPTH + 1) + self._q)[-(self.DEPTH + 1):]
-        q = q[1:] + [None]
+        q = self._window()[1:] + [None]
         while any(b is not None for b in q):
             self._launch(q)
             if q[0] is not None:
@@ -1391,45 +1413,45 @@ class RaggedMaskChainStream:
         if len(self._ring) < self.DEPTH + 1:
             raise ValueError("RaggedMaskChainStream.ring: at least 5 batches")
         self.k = 0
+        self._init_graphs(self._ring[0]._dev)          # (the graphs belong to this ring: a new ring starts without any)
 
     def prime(self):
         """Run V..F of the first four ring slots serially, so that step 0 finds what it expects."""
         r = self._ring
-        for j, stages in ((0, "VLPF"), (1, "VLP"), (2, "VL"), (3, "V")):
-            for s in stages:
-                self._stages(**{s: r[j]})
+        _ragged_serial(_RAGGED_FILL, 0, lambda st, j: self._stages(**{st: r[j]}))
 
-    def _step(self, k):
+    def _step(self, k, main=None):
         r, n = self._ring, len(self._ring)
         self._launch([r[(k + i) % n] for i in range(self.DEPTH + 1)])
 
+    _graph_step = _step
+
+    def _graph_start(self):
+        return self.k % len(self._ring), self.k              # the batches of a step depend on k mod n
+
+    def _advance(self, m):
+        self.k += m
+
+    @staticmethod
+    def round_unroll(unroll: int, n: int) -> int:
+        """The graph length run() uses over a ring of n batches: whole turns of the ring (at least one); 0: no graphs."""
+        return n * max(1, unroll // n) if unroll > 0 else 0
+
     def run(self, n_steps: int, unroll: int = 0):
         """n_steps launches over the ring; unroll > 0: replayed as HIP graphs of ``unroll`` steps (one host call each)."""
-        n = len(self._ring)
-        if unroll > 0:
-            unroll = n * max(1, unroll // n)            # a graph covers whole turns of the ring
-            while n_steps >= unroll:
-                key = (self.k % n, unroll)
-                if key not in self._graphs:
-                    self._graphs[key] = capture_steps(self._step, self.k, unroll, self._ring[0]._dev)
-                self._graphs[key].replay()
-                self.k += unroll
-                n_steps -= unroll
-        for _ in range(n_steps):
+        for _ in range(self._run_graphs(n_steps, self.round_unroll(unroll, len(self._ring)))):
             self._step(self.k)
             self.k += 1
 
     def drain_ring(self):
         """Finish the four batches in flight behind the last step, serially (their outputs then equal the stream's)."""
-        r, n, k = self._ring, len(self._ring), self.k
-        for j, stages in ((k, "R"), (k + 1, "FR"), (k + 2, "PFR"), (k + 3, "LPFR")):
-            for s in stages:
-                self._stages(**{s: r[j % n]})
+        r, n = self._ring, len(self._ring)
+        _ragged_serial(_RAGGED_DRAIN, self.k, lambda st, j: self._stages(**{st: r[j % n]}))
         self.k += self.DEPTH
 
 
 # ---- Jet heat-map overlays (blend_mask's merged image, save_warped_image's masked overlay) ----
-_OVERLAY_IMAGE_DTYPE = np.dtype([("image", "<u8"), ("map", "<u8"), ("out", "<u8"), ("H", "<i4"), ("W", "<i4")])  # attwarp_overlay_image
+_OVERLAY_IMAGE_DTYPE = np.dtype(_lib.OverlayImage)     # attwarp_overlay_image as a record array
 OVERLAY_STYLES = {"blend_mask": _lib.OVERLAY_BLEND_MASK, "save_warped": _lib.OVERLAY_SAVE_WARPED}
 _CHANNEL_ORDERS = {"rgb": _lib.RGB, "bgr": _lib.BGR}
 
@@ -1540,16 +1562,3 @@ def heatmap_overlay_ragged(rb: RaggedBatch, alpha: float = 0.5, order: str = "rg
     _overlay_call(rec, rb._dev, _lib.U8, "blend_mask", alpha, order, out_order)
     views = [packed[o:o + 3 * n].view(h, w, 3) for o, n, h, w in zip(offs.tolist(), npx.tolist(), rec["H"].tolist(), rec["W"].tolist())]
     return packed, views
-
-
-def capture_steps(step_fn, k0: int, n: int, dev: torch.device):
-    """Capture step_fn(k0) .. step_fn(k0 + n - 1) (launches on the current stream, static buffers) as one HIP graph."""
-    g = torch.cuda.CUDAGraph()
-    main = torch.cuda.Stream(device=dev)
-    main.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(main):
-        with torch.cuda.graph(g, stream=main):
-            for u in range(n):
-                step_fn(k0 + u)
-    torch.cuda.current_stream().wait_stream(main)
-    return g

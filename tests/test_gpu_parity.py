@@ -3164,6 +3164,64 @@ def test_mask_chain_two_batches_per_launch(dev):
         pipeline.pair_slots(list(imgs[:3]))                        # odd
 
 
+@pytest.mark.parametrize("n", [5, 6])
+@pytest.mark.parametrize("pattern", ["fused", "branches"])
+def test_mask_chain_stream_replays_cached_graphs_after_reset(dev, pattern, n):
+    """The cycle bench.py repeats -- reset(); prime(); run(K - depth); drain() -- on the uniform patterns (the ragged one has
+    test_ragged_pattern_graphs_replay_more_than_once): K = 13, 13, 7 over static rings of 5 and 6 slots, every slot equal to
+    warp_from_masks after each pass, and the second pass replays the graphs of the first: no new capture."""
+    import weakref
+    from attwarp_amd import pipeline
+    g = torch.Generator(device=dev).manual_seed(60 + n)
+    imgs = [torch.randint(0, 256, (2, 64, 64, 3), device=dev, dtype=torch.uint8, generator=g) for _ in range(n)]
+    msk = [torch.rand(2, 24, 24, device=dev, generator=g) for _ in range(n)]
+    refs = [pipeline.warp_from_masks(imgs[r], msk[r], (48, 52)) for r in range(n)]
+    mc = pipeline.MaskChainStream(imgs, msk, (48, 52), pattern=pattern)
+    assert mc.pattern == pattern
+    captures = []
+    for K in (13, 13, 7):
+        for o in mc.outs:
+            o.zero_()
+        mc.reset(); mc.prime(); mc.run(K - mc.depth); mc.drain()
+        assert mc.k == K
+        for r in range(n):
+            assert torch.equal(mc.outs[r], refs[r]), (K, r)
+        captures.append(mc.graph_captures)
+    assert captures[0] > 0 and captures[1] == captures[0], captures
+    # the stream goes when its last reference goes: no reference cycle keeps its graphs and buffers for the collector, which
+    # might free them in the middle of another stream's capture
+    alive = weakref.ref(mc)
+    del mc
+    assert alive() is None
+
+
+def test_paired_step_warp_replays_cached_graphs_after_reset(dev):
+    """reset(); prime(); run(8); tail() twice on PairedStepWarp over a static ring of 4: every slot equals
+    warp_from_attention_stack both times, and the second pass captures nothing."""
+    import weakref
+    from attwarp_amd import pipeline
+    g = torch.Generator(device=dev).manual_seed(77)
+    n, B = 4, 2
+    imgs = [torch.rand((B, 64, 64, 3), device=dev, generator=g) for _ in range(n)]
+    rows = [torch.softmax(torch.randn(3, B, 8, 600, device=dev, generator=g) * 2, -1).to(torch.float16) for _ in range(n)]
+    starts = (3 + torch.arange(B, device=dev) % 5).to(torch.int32)
+    refs = [pipeline.warp_from_attention_stack(imgs[r], rows[r], starts, channels_last=True) for r in range(n)]
+    pw = pipeline.PairedStepWarp(imgs, rows, starts, channels_last=True)
+    captures = []
+    for _ in (0, 1):
+        for o in pw.outs:
+            o.zero_()
+        pw.reset(); pw.prime(); pw.run(8); pw.tail()
+        assert pw.k == 12
+        for r in range(n):
+            assert torch.equal(pw.outs[r], refs[r]), r
+        captures.append(pw.graph_captures)
+    assert captures[0] > 0 and captures[1] == captures[0], captures
+    alive = weakref.ref(pw)
+    del pw
+    assert alive() is None                      # (no reference cycle: see the MaskChainStream test above)
+
+
 # =============================== unaligned rows and the ragged main_batched chain (round 5) ==============================
 UNALIGNED_SHAPES = [(40, 683, 33, 500, 3), (37, 333, 29, 333, 3), (26, 1023, 31, 1023, 3), (30, 501, 28, 501, 3),
                     (33, 47, 40, 31, 1), (31, 29, 31, 29, 2), (28, 1365, 17, 1365, 3), (25, 4093, 9, 4095, 1), (64, 66, 50, 333, 4)]
@@ -3435,6 +3493,7 @@ def test_ragged_large_batch_of_small_images(dev):
 def test_ragged_falls_back_per_image_outside_its_limits(dev):
     """Images the ragged kernel does not take (rows wider than 4096 bytes, a side <= 24) run through warp_from_masks one by
     one inside warp_from_masks_ragged; the rest of the batch still runs ragged; results are those of the per-image path."""
+    import weakref
     from attwarp_amd import pipeline
     g = torch.Generator(device=dev).manual_seed(77)
     sizes = [(40, 1500), (64, 100), (24, 90), (90, 77)]

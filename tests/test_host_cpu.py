@@ -39,6 +39,19 @@ def test_library_exports_every_declared_symbol(lib):
         return {l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("attwarp_")}
     assert exports(_lib.LIB_PATH) == declared
     assert exports(_lib.TUNING_LIB_PATH) == declared | tuning_only
+    # the caller-side structs: fields in the header's order, and the ctypes layout equal to the numpy record dtype derived from
+    # it, at the size the header's field list gives (five pointers + four int32; ten pointers; three pointers + two int32)
+    import ctypes
+    from attwarp_amd import pipeline
+    for S, cname, dt, size in ((_lib.RaggedImage, "attwarp_ragged_image", pipeline._RAGGED_IMAGE_DTYPE, 56),
+                               (_lib.StepSlot, "attwarp_step_slot", np.dtype(pipeline._StepSlot), 80),
+                               (_lib.OverlayImage, "attwarp_overlay_image", pipeline._OVERLAY_IMAGE_DTYPE, 32)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), hdr, re.S).group(1)
+        names = re.findall(r"(\w+)\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+        assert [n for n, _ in S._fields_] == names == list(dt.names), cname
+        assert ctypes.sizeof(S) == dt.itemsize == size, cname
+        assert [getattr(S, n).offset for n in names] == [dt.fields[n][1] for n in names], cname
+        assert [getattr(S, n).size for n in names] == [dt.fields[n][0].itemsize for n in names], cname
 
 
 def test_debug_override_swaps_to_the_tuning_library_and_restores(lib):
@@ -703,3 +716,82 @@ def test_ragged_stream_schedule_without_gpu(monkeypatch):
         for b in range(nring):
             per = [count.get((b, s), 0) for s in "VLPFR"]
             assert len(set(per)) == 1 and per[0] == (total // nring + (1 if b < total % nring else 0)), (nring, steps, b, per)
+
+
+def test_step_graphs_core_without_gpu(monkeypatch):
+    """pipeline._StepGraphs, the graph cache and replay loop the four stream drivers inherit, is host logic: with the capture
+    replaced by a fake whose "graph" calls the step function n times on replay(), a run executes the steps k0, k0 + 1, ..
+    once each and in order (a cached graph: the steps it was captured as, equal to them modulo the period of its key); a second pass from the same starting state (the reset(); prime(); run() cycle of bench.py)
+    captures nothing new, another starting state does; and the drivers' rules for the graph length give the values of their
+    documentation."""
+    import math
+    from attwarp_amd import pipeline
+
+    class FakeGraph:
+        def __init__(self, step_fn, k0, n, dev):
+            self.args = (step_fn, k0, n)
+
+        def replay(self):
+            step_fn, k0, n = self.args
+            for k in range(k0, k0 + n):
+                step_fn(k, None)
+
+    monkeypatch.setattr(pipeline, "capture_steps", FakeGraph)
+    class Toy(pipeline._StepGraphs):
+        """A driver whose steps only log their k; its graphs are keyed by k mod period (None: by k itself)."""
+        def __init__(self, period):
+            self.period, self.k, self.log = period, 0, []
+            self._init_graphs(None)
+
+        def _graph_step(self, k, main):
+            self.log.append(k)
+
+        def _graph_start(self):
+            return (self.k % self.period if self.period else self.k), self.k
+
+        def _advance(self, m):
+            self.k += m
+
+        def go(self, k0, n, unroll):
+            self.k, self.log = k0, []
+            self._run(n, unroll)
+            assert self.k == k0 + n
+            return self.log
+
+    for ring, unroll in ((1, 0), (1, 1), (1, 2), (3, 6), (4, 8), (5, 10), (2, 26)):
+        period = math.lcm(2, ring)
+        exact, toy = Toy(None), Toy(period)
+        for n in range(26):
+            # keyed by k itself: every step is the one it was captured as
+            assert exact.go(7, n, unroll) == list(range(7, 7 + n)), (ring, unroll, n)
+            # keyed by k mod period: a replayed step is one that touches the same buffers
+            assert [k % period for k in toy.go(0, n, unroll)] == [k % period for k in range(n)], (ring, unroll, n)
+        # every run above started from state 0: at most one graph of `unroll` steps and one single step per state
+        first = toy.graph_captures
+        assert 0 < first <= 2 * period
+        for n in (25, 13, 7):
+            assert [k % period for k in toy.go(0, n, unroll)] == [k % period for k in range(n)], (ring, unroll, n)
+            assert toy.graph_captures == first, (ring, unroll, n)
+        # a state no run has started a graph of this length from: captured
+        fresh, m = Toy(period), max(unroll, 1)
+        fresh.go(0, m, unroll); fresh.go(0, m, unroll)
+        assert fresh.graph_captures == 1
+        assert fresh.go(1, m, unroll) == list(range(1, 1 + m)) and fresh.graph_captures == 2
+    # the graph lengths (0: single steps only / no graphs)
+    ow = pipeline.OverlappedWarp.round_unroll
+    assert [ow(u, n) for u, n in ((8, 1), (9, 1), (1, 1), (8, 2), (8, 3), (8, 4), (8, 5), (3, 4))] == [8, 8, 0, 8, 6, 8, 10, 4]
+    assert [pipeline.MaskChainStream.round_unroll(u) for u in (8, 9, 1, 0)] == [8, 8, 2, 2]
+    rg = pipeline.RaggedMaskChainStream.round_unroll
+    assert [rg(u, n) for u, n in ((8, 5), (12, 5), (3, 7), (0, 5))] == [5, 10, 7, 0]
+    # the ragged ring: graphs of whole turns, then direct launches -- the launches of the direct loop, in its order
+    logs = {}
+    for unroll in (0, 5, 12):
+        launches = []
+        monkeypatch.setattr(pipeline, "ragged_chain_launch", lambda **kw: launches.append({s: kw[s] for s in "RFPLV"}))
+        st = pipeline.RaggedMaskChainStream(out_size=(8, 8))
+        st.ring([type("B", (), {"_dev": None})() for _ in range(5)])
+        st.ring(st._ring)                                   # (adopting a ring starts without graphs)
+        st.run(13, unroll=unroll); st.k = 0; st.run(13, unroll=unroll)
+        assert st.k == 13 and st.graph_captures == (0 if unroll == 0 else 1)      # one graph of 5 or of 10 steps, re-used
+        logs[unroll] = [{s: st._ring.index(b) for s, b in l.items()} for l in launches]
+    assert len(logs[0]) == 26 and logs[5] == logs[0] and logs[12] == logs[0]
