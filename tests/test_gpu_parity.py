@@ -2387,7 +2387,8 @@ def test_clip_preprocess_bit_exact(dev, golden, name):
 ])
 def test_clip_preprocess_staged_equals_generic(dev, shape):
     """The LDS-staged kernels against the one-thread-per-output form (itself pinned to the HF processor by the
-    goldens) and, for RGB, against the oracle: bit-for-bit, float32 and float16."""
+    goldens) and against Pillow itself (tests/clip_ref.py): bit-for-bit, float32 and float16."""
+    import clip_ref
     from attwarp_amd import pipeline
     B, H, W, C, size = shape
     rng = np.random.default_rng(H * 31 + W)
@@ -2399,9 +2400,9 @@ def test_clip_preprocess_staged_equals_generic(dev, shape):
         with _lib.debug_override(clip_variant=1):
             b = pipeline.clip_preprocess(x, size, dt, mean, std)
         assert a.shape == (B, C, size, size) and torch.equal(a, b), (shape, dt)
-    if C == 3 and H * W <= 600 * 600:
-        got = N(pipeline.clip_preprocess(x, size, torch.float32))
-        assert np.array_equal(got[0], O.clip_preprocess(img[0], size))
+    got = N(pipeline.clip_preprocess(x, size, torch.float32, mean, std))
+    for b in range(B):                  # Pillow itself: every shape and channel count, the test's own mean / std
+        assert np.array_equal(got[b], clip_ref.clip_preprocess(img[b], size, mean, std)), (shape, b)
 
 
 @pytest.mark.parametrize("hw", [(300, 420), (421, 300), (336, 336)])
