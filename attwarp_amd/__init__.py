@@ -19,8 +19,9 @@ model/marginalnet_full_dataset/trainer.py   attwarp_amd.optim            (AdamW:
   (the optimiser lines)                       gradient-norm clip and the step in two launches)
 =========================================  =====================================================
 
-plus ``attwarp_amd.pipeline`` (batched device-resident launcher) and ``attwarp_amd.dist``
-(one process per GPU, image shards, one RCCL broadcast of MarginalNet weights).
+plus ``attwarp_amd.pipeline`` (batched device-resident launcher), ``attwarp_amd.png`` (the drivers' PNG files, whole
+ragged batches encoded on the GPU) and ``attwarp_amd.dist`` (one process per GPU, image shards, one RCCL broadcast of
+MarginalNet weights).
 
 Compute happens in hand-written HIP kernels (``attwarp_amd/csrc``) reached through a C ABI
 (``include/attwarp.h``) with ctypes.  There is no CPU fallback.

@@ -152,6 +152,11 @@ SIGNATURES = {
     "attwarp_adamw_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "attwarp_adamw_step": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_size_t, c_void_p]),
+    # PNG files of a ragged batch (png.hip)
+    "attwarp_png_bound": (c_size_t, [c_int, c_int, c_int]),
+    "attwarp_png_table_bytes": (c_size_t, [c_void_p, c_int]),
+    "attwarp_png_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "attwarp_png_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 PIL_LANCZOS, PIL_BICUBIC, PIL_BILINEAR = 0, 1, 2
@@ -159,6 +164,9 @@ RECON_MSE, RECON_L1 = 0, 1                          # attwarp_recon_loss kinds
 TT_IDENTITY, TT_SQRT, TT_NONE = 0, 1, 2              # attwarp_trainer_attention_targets modes
 OVERLAY_BLEND_MASK, OVERLAY_SAVE_WARPED = 0, 1       # attwarp_heatmap_overlay styles
 RGB, BGR = 0, 1
+# attwarp_png_*: filters and limits (ATTWARP_PNG_* of include/attwarp.h)
+PNG_FILTER_IDS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+PNG_SEG_BYTES, PNG_MAX_ROW_BYTES, PNG_SEG_MAX_ROWS, PNG_FILE_OVERHEAD = 24576, 24576, 1024, 68
 
 
 class RaggedImage(ctypes.Structure):
@@ -184,6 +192,20 @@ class StepSlot(ctypes.Structure):
 class OverlayImage(ctypes.Structure):
     """attwarp_overlay_image: one image of an attwarp_heatmap_overlay call, device pointers in a host array."""
     _fields_ = [("image", c_void_p), ("map", c_void_p), ("out", c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+class PngImage(ctypes.Structure):
+    """attwarp_png_image: one image of an attwarp_png_plan call, device pointer in a host array."""
+    _fields_ = [("src", c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("pitch", ctypes.c_int32), ("order", ctypes.c_int32), ("filter", ctypes.c_int32)]
+
+
+class PngHeader(ctypes.Structure):
+    """attwarp_png_header: the first bytes of a table written by attwarp_png_plan."""
+    _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("nseg", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("table_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
+                ("off_images", ctypes.c_uint64), ("off_segs", ctypes.c_uint64),
+                ("crc_pow8", ctypes.c_uint32 * 32), ("idat_head_crc", ctypes.c_uint32), ("reserved2", ctypes.c_uint32)]
 
 
 class RaggedHeader(ctypes.Structure):

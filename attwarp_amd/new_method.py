@@ -98,14 +98,21 @@ def warp_image_by_attention(image: np.ndarray, att_map: np.ndarray, new_width: i
     squeeze = img.ndim == 2
     if squeeze:
         img = img[:, :, None]
-    att = _att_to_device(att_map, dev)
-    if att.dim() != 2 or tuple(att.shape) != img.shape[:2]:
-        raise ValueError(f"attention map {tuple(att.shape)} must match image {img.shape[:2]}")
-    mx, my = attention_axis_maps(att.unsqueeze(0), new_width, new_height, transform, exp_scale, exp_divisor,
-                                 apply_inverse)
-    out = remap_hwc(torch.from_numpy(np.ascontiguousarray(img)).to(dev).unsqueeze(0), mx, my, mode)[0]
+    out = _warp_on_device(torch.from_numpy(np.ascontiguousarray(img)).to(dev), att_map, new_width, new_height, transform,
+                          exp_scale, exp_divisor, apply_inverse, mode)
     res = out.cpu().numpy()
     return res[:, :, 0] if squeeze else res
+
+
+def _warp_on_device(img: torch.Tensor, att_map: np.ndarray, new_width, new_height, transform, exp_scale, exp_divisor,
+                    apply_inverse, mode) -> torch.Tensor:
+    """warp_image_by_attention's compute: img [h,w,C] on the GPU, att_map [h,w] on the host -> [new_height,new_width,C]."""
+    att = _att_to_device(att_map, img.device)
+    if att.dim() != 2 or tuple(att.shape) != tuple(img.shape[:2]):
+        raise ValueError(f"attention map {tuple(att.shape)} must match image {tuple(img.shape[:2])}")
+    mx, my = attention_axis_maps(att.unsqueeze(0), new_width, new_height, transform, exp_scale, exp_divisor,
+                                 apply_inverse)
+    return remap_hwc(img.unsqueeze(0), mx, my, mode)[0]
 
 
 def resize_image_to_match_attmap(image: Optional[np.ndarray], att_map: Optional[np.ndarray], mode: str = "cv2"):
@@ -127,20 +134,26 @@ def resize_image_to_match_attmap(image: Optional[np.ndarray], att_map: Optional[
     squeeze = img.ndim == 2
     if squeeze:
         img = img[:, :, None]
-    src = torch.from_numpy(np.ascontiguousarray(img)).to(dev).unsqueeze(0)
+    out = _resize_on_device(torch.from_numpy(np.ascontiguousarray(img)).to(dev), th, tw, mode).cpu().numpy()
+    return out[:, :, 0] if squeeze else out
+
+
+def _resize_on_device(img: torch.Tensor, th: int, tw: int, mode: str) -> torch.Tensor:
+    """resize_image_to_match_attmap's compute: img [h,w,C] on the GPU (contiguous) -> [th,tw,C]."""
+    dev = img.device
+    ch, cw, C = (int(v) for v in img.shape)
+    src = img.unsqueeze(0)
     if mode == "cv2":
-        out_t = torch.empty((1, th, tw, img.shape[2]), device=dev, dtype=src.dtype)
+        out_t = torch.empty((1, th, tw, C), device=dev, dtype=src.dtype)
         with torch.cuda.device(dev):
-            _lib.call("attwarp_resize_linear", _lib.ptr(src), _lib.ptr(out_t), _lib.dtype_id(src), 1, img.shape[2], ch, cw,
+            _lib.call("attwarp_resize_linear", _lib.ptr(src), _lib.ptr(out_t), _lib.dtype_id(src), 1, C, ch, cw,
                       th, tw, _lib.stream_ptr(dev))
-        out = out_t[0].cpu().numpy()
-    elif mode == "exact":
+        return out_t[0]
+    if mode == "exact":
         mx = ((torch.arange(tw, dtype=torch.float64) + 0.5) * (cw / tw) - 0.5).clamp(0, cw - 1).float().to(dev)[None]
         my = ((torch.arange(th, dtype=torch.float64) + 0.5) * (ch / th) - 0.5).clamp(0, ch - 1).float().to(dev)[None]
-        out = remap_hwc(src, mx, my, "exact")[0].cpu().numpy()
-    else:
-        raise ValueError(f"resize_image_to_match_attmap: unknown mode {mode!r}")
-    return out[:, :, 0] if squeeze else out
+        return remap_hwc(src, mx, my, "exact")[0]
+    raise ValueError(f"resize_image_to_match_attmap: unknown mode {mode!r}")
 
 
 def _coerce_att_map(att_map, width, height):
@@ -164,7 +177,7 @@ def _coerce_att_map(att_map, width, height):
 
 def save_warped_image(image_path, att_map, original_image_save_path, masked_overlay_save_path, output_path,
                       vis_path=None, width=500, height=500, transform="identity", exp_scale=1.0, exp_divisor=1.0,
-                      apply_inverse=False, attention_alpha=0.5, mode="cv2"):
+                      apply_inverse=False, attention_alpha=0.5, mode="cv2", encoder="pillow"):
     """Reference :405-506.  Warps ``image_path`` (path or PIL image) by ``att_map`` and writes the
     result to ``output_path``; returns True, or prints the error and returns False (the reference
     swallows every exception, :504-506).  Images are handled in BGR order like the reference;
@@ -172,9 +185,15 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
     before the warp (:func:`masked_overlay`; an error there returns False before the warp, as in the reference).  The
     visualisation strip is out of scope: ``vis_path`` is accepted and ignored.
     ``mode`` (not in the reference) selects the resample arithmetic: "cv2" (default, what the reference's
-    ``cv2.remap`` call computes) or "exact"."""
+    ``cv2.remap`` call computes) or "exact".
+    ``encoder`` (not in the reference): "pillow" (default) downloads every image and writes it with Pillow, as before;
+    "hip" keeps the image, the overlay and the warped image on the GPU, encodes the requested files in ONE
+    ``png.PngBatch`` (BGR sources swapped while filtering: RGB files, the same decoded pixels) and writes them after the
+    warp -- so an error anywhere leaves no file behind, where the "pillow" route has written the earlier ones."""
     try:
         from PIL import Image
+        if encoder not in ("pillow", "hip"):
+            raise ValueError(f"unknown encoder {encoder!r} ('pillow' or 'hip')")
         if isinstance(image_path, str):
             try:
                 image = np.array(Image.open(image_path).convert("RGB"))[:, :, ::-1]
@@ -183,6 +202,9 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
         else:
             image = _cvt_rgb2bgr(np.array(image_path))
         image = np.ascontiguousarray(image)
+        if encoder == "hip":
+            return _save_warped_hip(image, att_map, original_image_save_path, masked_overlay_save_path, output_path, width,
+                                    height, transform, exp_scale, exp_divisor, apply_inverse, attention_alpha, mode)
         if original_image_save_path:
             _imwrite(original_image_save_path, image)
         att_map = _coerce_att_map(att_map, width, height)
@@ -204,6 +226,30 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
         return False
 
 
+def _save_warped_hip(image, att_map, original_image_save_path, masked_overlay_save_path, output_path, width, height,
+                     transform, exp_scale, exp_divisor, apply_inverse, attention_alpha, mode):
+    """save_warped_image's body for ``encoder="hip"``: the same steps in the same order on GPU tensors, one PNG batch."""
+    from . import png
+    if image.dtype != np.uint8:
+        raise TypeError(f"encoder='hip' writes 8-bit files: uint8 image expected, got {image.dtype}")
+    dev = _lib.default_device()
+    t_img = torch.from_numpy(image).to(dev)                      # BGR [H,W,3]
+    paths, tensors, orders = [], [], []
+    if original_image_save_path:
+        paths.append(original_image_save_path); tensors.append(t_img); orders.append("bgr")
+    att_map = _coerce_att_map(att_map, width, height)
+    if masked_overlay_save_path:
+        paths.append(masked_overlay_save_path); orders.append("rgb")
+        tensors.append(_masked_overlay_on_device(image, att_map, attention_alpha, image_dev=t_img))
+    th, tw = att_map.shape[:2]
+    src = t_img if tuple(image.shape[:2]) == (th, tw) else _resize_on_device(t_img, th, tw, mode)
+    name = set_transform_function(transform, exp_scale, exp_divisor, apply_inverse)
+    paths.append(output_path); orders.append("bgr")
+    tensors.append(_warp_on_device(src, att_map, width, height, name, exp_scale, exp_divisor, apply_inverse, mode))
+    png.write_png(paths, tensors, order=orders)
+    return True
+
+
 def masked_overlay(image_bgr: np.ndarray, att_map: np.ndarray, attention_alpha: float = 0.5) -> np.ndarray:
     """save_warped_image's masked overlay (reference :455-475) on the GPU -> RGB uint8 [H,W,3] (the reference writes the same
     pixels from BGR with cv2.imwrite).  ``cv2.resize(att_map, (W, H), INTER_LINEAR)`` to the image's size (a copy when the
@@ -211,6 +257,11 @@ def masked_overlay(image_bgr: np.ndarray, att_map: np.ndarray, attention_alpha: 
     with EPSILON, COLORMAP_JET, ``addWeighted(heat, alpha, image, 1 - alpha, 0)``.  Maps: uint8, float32, float64; other
     integer maps of at most 32 bits are taken as float64 (exact) at the image's size.  Raises for a non-uint8 image (OpenCV's
     addWeighted refuses mixed depths) and for maps it does not handle."""
+    return _masked_overlay_on_device(image_bgr, att_map, attention_alpha).cpu().numpy()
+
+
+def _masked_overlay_on_device(image_bgr, att_map: np.ndarray, attention_alpha: float = 0.5, image_dev=None) -> torch.Tensor:
+    """:func:`masked_overlay` up to its download; ``image_dev``: the image, already on the GPU."""
     from . import pipeline
     img = np.asarray(image_bgr)
     if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
@@ -231,9 +282,8 @@ def masked_overlay(image_bgr: np.ndarray, att_map: np.ndarray, attention_alpha: 
         with torch.cuda.device(dev):
             call("attwarp_resize_linear", ptr(m), ptr(r), _lib.dtype_id(m), 1, 1, a.shape[0], a.shape[1], H, W, stream_ptr(dev))
         m = r
-    t = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
-    out = pipeline.heatmap_overlay([t], [m], attention_alpha, "save_warped", order="bgr", out_order="rgb")[0]
-    return out.cpu().numpy()
+    t = torch.from_numpy(np.ascontiguousarray(img)).to(dev) if image_dev is None else image_dev
+    return pipeline.heatmap_overlay([t], [m], attention_alpha, "save_warped", order="bgr", out_order="rgb")[0]
 
 
 def _cvt_rgb2bgr(image: np.ndarray) -> np.ndarray:

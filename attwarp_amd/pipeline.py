@@ -1562,3 +1562,23 @@ def heatmap_overlay_ragged(rb: RaggedBatch, alpha: float = 0.5, order: str = "rg
     _overlay_call(rec, rb._dev, _lib.U8, "blend_mask", alpha, order, out_order)
     views = [packed[o:o + 3 * n].view(h, w, 3) for o, n, h, w in zip(offs.tolist(), npx.tolist(), rec["H"].tolist(), rec["W"].tolist())]
     return packed, views
+
+
+def save_png_ragged(rb: RaggedBatch, paths, what: str = "warped", filter: str = "sub", order: str = "rgb"):
+    """The file-writing leg of the driver loop (main_batched.py:243-303) for a whole ragged batch: the warped images
+    (``what="warped"``: ``rb.out``) or the up-sampled masks (``what="mota"``: :meth:`RaggedBatch.mota_of`, grey files) of
+    ``rb`` as PNG files, encoded on the GPU in one :class:`attwarp_amd.png.PngBatch` -- only compressed bytes are copied
+    to the host.  Enqueue it after the launches that produced what it saves; ``order``: channel order of ``rb.images``."""
+    from . import png
+    paths = list(paths)
+    if len(paths) != rb.B:
+        raise ValueError(f"save_png_ragged: {len(paths)} paths for a batch of {rb.B}")
+    if what == "warped":
+        if rb.C not in (1, 3):
+            raise ValueError("save_png_ragged: one- or three-channel images only")
+        images = rb.out
+    elif what == "mota":
+        images, order = [rb.mota_of(b) for b in range(rb.B)], "rgb"
+    else:
+        raise ValueError("save_png_ragged: what is 'warped' or 'mota'")
+    png.write_png(paths, images, filter=filter, order=order)

@@ -707,6 +707,51 @@ ATTWARP_API int attwarp_adamw_step(const attwarp_adamw_tensor* tensors, int n, d
                        const float* grad_scale, const float* found_inf, float* steps, float* grad_norm,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG files of a whole batch of differently sized uint8 images, encoded on the device (png.hip):
+ * what the reference's drivers write per sample with cv2.imwrite (main_batched.py:243-303, new_method.py:405-506).
+ * 8-bit grey (C = 1) or RGB (C = 3), non-interlaced; signature, IHDR, ONE IDAT, IEND.  The zlib stream is 78 01, then
+ * per SEGMENT (whole rows: at most ATTWARP_PNG_SEG_BYTES filtered bytes and ATTWARP_PNG_SEG_MAX_ROWS rows) one
+ * dynamic-Huffman block of literals and distance-1 matches followed by an empty stored block, which ends the segment on
+ * a byte boundary -- or one stored block where that is shorter --, then 01 00 00 FF FF and the Adler-32.  One workgroup
+ * encodes one segment; sizes, offsets, Adler-32 and the IDAT CRC-32 are combined on the device, so a call's launches
+ * depend on nothing the host has to read back and can be captured in a graph.
+ *   1. fill attwarp_png_image[B] (HOST array of DEVICE pointers);
+ *   2. attwarp_png_table_bytes -> size; attwarp_png_plan writes header, records and segments into HOST memory;
+ *   3. copy table_bytes to the device (8-byte aligned);
+ *   4. attwarp_png_encode(host copy, device copy, scratch of header.scratch_bytes (16-byte aligned), out of at least
+ *      header.out_bytes, offsets int64 [B+1], stream): file b is out[offsets[b] .. offsets[b+1]), files back to back.
+ * header.out_bytes is the sum of attwarp_png_bound(H, W, C) over the batch: every segment stored.
+ * Filters: the specification's five, and ADAPTIVE: per row the filter with the smallest sum of |filtered byte as int8|,
+ * ties to the lower number.  order = ATTWARP_BGR swaps the channels of a 3-channel source while filtering (the file is RGB).
+ * Limits (ATTWARP_E_UNSUPPORTED from the planner): 1 + W * C <= ATTWARP_PNG_MAX_ROW_BYTES, C 1 or 3, a file bound below
+ * 2^31, at most 2^24 segments per call; pitch >= W * C is the distance between rows in bytes, any byte address. */
+#define ATTWARP_PNG_SEG_BYTES 24576
+#define ATTWARP_PNG_MAX_ROW_BYTES 24576
+#define ATTWARP_PNG_SEG_MAX_ROWS 1024
+#define ATTWARP_PNG_FILE_OVERHEAD 68  /* bytes of a file that belong to no segment */
+enum { ATTWARP_PNG_NONE = 0, ATTWARP_PNG_SUB = 1, ATTWARP_PNG_UP = 2, ATTWARP_PNG_AVERAGE = 3, ATTWARP_PNG_PAETH = 4,
+       ATTWARP_PNG_ADAPTIVE = 5 };
+typedef struct attwarp_png_image {
+  const uint8_t* src;                              /* device: H rows of W * C bytes, pitch bytes apart */
+  int32_t H, W, C;
+  int32_t pitch;
+  int32_t order;                                   /* ATTWARP_RGB / ATTWARP_BGR (ignored for C = 1) */
+  int32_t filter;                                  /* ATTWARP_PNG_* */
+} attwarp_png_image;
+typedef struct attwarp_png_header {                /* first bytes of a table written by attwarp_png_plan */
+  uint32_t magic;
+  int32_t B, nseg, reserved;
+  uint64_t table_bytes, scratch_bytes, out_bytes;
+  uint64_t off_images, off_segs;
+  uint32_t crc_pow8[32];                           /* x^(8 * 2^k) mod the CRC-32 polynomial, reflected */
+  uint32_t idat_head_crc, reserved2;               /* CRC-32 of "IDAT" 78 01 */
+} attwarp_png_header;
+ATTWARP_API size_t attwarp_png_bound(int H, int W, int C);   /* 0: outside the limits */
+ATTWARP_API size_t attwarp_png_table_bytes(const attwarp_png_image* images, int B);
+ATTWARP_API int attwarp_png_plan(const attwarp_png_image* images, int B, void* table, size_t table_bytes);
+ATTWARP_API int attwarp_png_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
+                       int64_t* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
