@@ -17,6 +17,8 @@ model/marginalnet_full_dataset/             attwarp_amd.dataloader       (prepar
   dataloader.py, data.py                      prepare_attention_maps, collate, transform_for_sample)
 model/marginalnet_full_dataset/trainer.py   attwarp_amd.optim            (AdamW: GradScaler unscale,
   (the optimiser lines)                       gradient-norm clip and the step in two launches)
+model/marginalnet_full_dataset/trainer.py   attwarp_amd.panels           (make_grid_u8, trainer_debug_grid,
+  (the debug / validation panels)             write_trainer_debug: one launch, one PngBatch)
 =========================================  =====================================================
 
 plus ``attwarp_amd.pipeline`` (batched device-resident launcher), ``attwarp_amd.png`` (the drivers' PNG files, whole

@@ -157,6 +157,9 @@ SIGNATURES = {
     "attwarp_png_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_png_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
     "attwarp_png_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # the trainer's debug / validation panels (panel.hip)
+    "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p]),
 }
 
 PIL_LANCZOS, PIL_BICUBIC, PIL_BILINEAR = 0, 1, 2
@@ -167,6 +170,9 @@ RGB, BGR = 0, 1
 # attwarp_png_*: filters and limits (ATTWARP_PNG_* of include/attwarp.h)
 PNG_FILTER_IDS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
 PNG_SEG_BYTES, PNG_MAX_ROW_BYTES, PNG_SEG_MAX_ROWS, PNG_FILE_OVERHEAD = 24576, 24576, 1024, 68
+# attwarp_panel_grid: limits, flags and source kinds (ATTWARP_PANEL_* of include/attwarp.h)
+PANEL_MAX_SRC, PANEL_MAX_HEAT, PANEL_FOR_PNG = 8, 4096, 1
+PANEL_F32, PANEL_U8, PANEL_HEAT = 0, 1, 2
 
 
 class RaggedImage(ctypes.Structure):
@@ -198,6 +204,12 @@ class PngImage(ctypes.Structure):
     """attwarp_png_image: one image of an attwarp_png_plan call, device pointer in a host array."""
     _fields_ = [("src", c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
                 ("pitch", ctypes.c_int32), ("order", ctypes.c_int32), ("filter", ctypes.c_int32)]
+
+
+class PanelSource(ctypes.Structure):
+    """attwarp_panel_source: one row source of an attwarp_panel_grid call, device pointer in a host array."""
+    _fields_ = [("data", c_void_p), ("batch_stride", c_int64), ("kind", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("N", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("clamp", ctypes.c_int32)]
 
 
 class PngHeader(ctypes.Structure):

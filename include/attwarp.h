@@ -752,6 +752,46 @@ ATTWARP_API int attwarp_png_plan(const attwarp_png_image* images, int B, void* t
 ATTWARP_API int attwarp_png_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
                        int64_t* offsets, void* stream);
 
+/* ---- The trainer's debug and validation panels (panel.hip): MN/trainer.py:301-307 and :484-517 --
+ * heat = A / (A.amax + 1e-6) up-sampled with F.interpolate(bilinear, align_corners=False), torch.cat of the first n
+ * samples of every row, (grid * 255).byte() and torchvision.utils.make_grid -- as ONE launch into one uint8 canvas.
+ * sources: HOST array of nsrc <= ATTWARP_PANEL_MAX_SRC records; source r contributes its first n images as cells
+ * r*n .. r*n + n-1.  Planes are dense ([C,H,W] per image), images are batch_stride ELEMENTS apart (a slice of a larger
+ * batch needs no copy).  Kinds:
+ *   ATTWARP_PANEL_F32  float32 [N,C,H,W], C 3 or 1 (one channel fills all three): byte = (unsigned char)(v * 255.0f), one
+ *                      rounded float32 product truncated toward zero; clamp != 0 clamps v to [0, 1] first;
+ *   ATTWARP_PANEL_U8   uint8 [N,C,H,W], C 3 or 1: copied;
+ *   ATTWARP_PANEL_HEAT float32 [N,1,h,w], h * w <= ATTWARP_PANEL_MAX_HEAT, h and w independent of H and W: per image
+ *                      m = max(A) (a NaN propagates), q = A / (m + 1e-6f), then torch's bilinear with align_corners=False in
+ *                      individually rounded float32 operations -- scale = (float)in / (float)out,
+ *                      src = max(scale * (dst + 0.5f) - 0.5f, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0,
+ *                      l0 = 1 - l1, v = l0y * (l0x * q00 + l1x * q01) + l1y * (l0x * q10 + l1x * q11) -- and the byte of
+ *                      v * 255.0f as above, in all three channels.  q lives in LDS only.
+ * Values: the byte is torch's wherever (t).byte() is defined (-1 < t < 256); t <= -1 gives 0, t >= 256 gives 255, NaN
+ * gives 0 (a heat image whose maximum is NaN or +inf is all zeros).
+ * Geometry (torchvision.utils.make_grid): K = nsrc * n cells, xmaps = min(nrow, K), ymaps = ceil(K / xmaps); cell k at
+ * row k / xmaps, column k % xmaps of a canvas of Hg x Wg = (ymaps * (H + padding) + padding) x (xmaps * (W + padding) +
+ * padding) filled with pad_value, each cell offset by padding; K == 1 gives the bare image (no padding).
+ * out: layout ATTWARP_HWC [Hg, Wg + right_margin, 3] or ATTWARP_CHW [3, Hg, Wg + right_margin] uint8, any byte address;
+ * the right_margin columns hold pad_value.  flags: ATTWARP_PANEL_FOR_PNG refuses a canvas whose HWC row does not fit the
+ * PNG encoder (1 + 3 * (Wg + right_margin) > ATTWARP_PNG_MAX_ROW_BYTES).  Every limit is refused before anything is
+ * enqueued; no argument depends on device data, so a call can be captured in a graph. */
+#define ATTWARP_PANEL_MAX_SRC 8
+#define ATTWARP_PANEL_MAX_HEAT 4096   /* h * w of a heat source: one float32 tile in LDS */
+#define ATTWARP_PANEL_FOR_PNG 1
+enum { ATTWARP_PANEL_F32 = 0, ATTWARP_PANEL_U8 = 1, ATTWARP_PANEL_HEAT = 2 };
+typedef struct attwarp_panel_source {
+  const void* data;                                /* device: image 0 of the source */
+  int64_t batch_stride;                            /* elements between images, >= C * H * W (heat: >= h * w) */
+  int32_t kind;                                    /* ATTWARP_PANEL_* */
+  int32_t C;                                       /* 3 or 1 (heat: 1) */
+  int32_t N;                                       /* images the source holds, >= n */
+  int32_t h, w;                                    /* heat: the map's size (other kinds: ignored) */
+  int32_t clamp;                                   /* ATTWARP_PANEL_F32: clamp to [0, 1] before the product */
+} attwarp_panel_source;
+ATTWARP_API int attwarp_panel_grid(const attwarp_panel_source* sources, int nsrc, int n, int H, int W, int nrow, int padding,
+                       int pad_value, int layout, int right_margin, int flags, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
