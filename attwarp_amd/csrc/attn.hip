@@ -2,7 +2,7 @@
 //   A1  BatchMaskHookLogger._process_attention   AGW/attention_extraction/llava.py:385-396
 //   A2  BatchMaskHookLogger.finalize_batch       llava.py:401-411
 //   A3  revise_mask (normalize -> enhance -> box) llava.py:207-238
-//   A4  ToPILImage (x255, truncate) + PIL resize(LANCZOS) llava.py:192-196,243,253
+// (A4, ToPILImage + PIL resize(LANCZOS) of the mask, llava.py:192-196,243,253, is pil8.hip.)
 //
 // A1 is the only bandwidth-relevant one: per generation step it reads heads*ntok elements per
 // sample (T*32*576*elemsize algorithmic bytes per image over a generation) with
@@ -131,262 +131,6 @@ __global__ __launch_bounds__(NT) void mask_postproc_kernel(const float* __restri
   mask_postproc_block(mask, n, ks, coe, out, blockIdx.x, x, red, &fred[0][0]);
 }
 
-// ---- A4: Pillow's 8-bit separable resampler (ImagingResampleHorizontal/Vertical_8bpc); helpers in mask_blocks.hpp ----
-// horizontal pass: tmp[b][y][xx], one thread per output.  grid = (ceil(out_w/NT), h, B)
-__global__ __launch_bounds__(NT) void lanczos_h_kernel(const float* __restrict__ mf, const uint8_t* __restrict__ mu,
-                                                       int h, int w, int out_w, const int32_t* __restrict__ bounds,
-                                                       const int32_t* __restrict__ kk, int ksize,
-                                                       uint8_t* __restrict__ tmp) {
-  const int xx = blockIdx.x * NT + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
-  if (xx >= out_w) return;
-  const int xmin = bounds[2 * xx], cnt = bounds[2 * xx + 1];
-  const int32_t* k = kk + (size_t)xx * ksize;
-  const size_t row = ((size_t)b * h + y) * w;
-  int ss = 1 << (PIL_PRECISION_BITS - 1);
-  for (int x = 0; x < cnt; ++x) {
-    const int px = mf ? (int)to_pil_u8(mf[row + xmin + x]) : (int)mu[row + xmin + x];
-    ss += px * k[x];
-  }
-  tmp[((size_t)b * h + y) * out_w + xx] = pil_clip8(ss);
-}
-
-// vertical pass.  grid = (ceil(out_w/NT), out_h, B)
-__global__ __launch_bounds__(NT) void lanczos_v_kernel(const uint8_t* __restrict__ tmp, int h, int out_w, int out_h,
-                                                       const int32_t* __restrict__ bounds,
-                                                       const int32_t* __restrict__ kk, int ksize,
-                                                       uint8_t* __restrict__ out) {
-  const int xx = blockIdx.x * NT + threadIdx.x, yy = blockIdx.y, b = blockIdx.z;
-  if (xx >= out_w) return;
-  const int ymin = bounds[2 * yy], cnt = bounds[2 * yy + 1];
-  const int32_t* k = kk + (size_t)yy * ksize;
-  int ss = 1 << (PIL_PRECISION_BITS - 1);
-  for (int y = 0; y < cnt; ++y) ss += (int)tmp[((size_t)b * h + ymin + y) * out_w + xx] * k[y];
-  out[((size_t)b * out_h + yy) * out_w + xx] = pil_clip8(ss);
-}
-
-// vertical pass, 4 pixels per thread (out_w % 4 == 0): 4-byte loads and stores, 256 B per wave instruction.
-// grid = (ceil(out_w/4/NT), out_h, B)
-__global__ __launch_bounds__(NT) void lanczos_v4_kernel(const uint8_t* __restrict__ tmp, int h, int out_w, int out_h,
-                                                        const int32_t* __restrict__ bounds,
-                                                        const int32_t* __restrict__ kk, int ksize,
-                                                        uint8_t* __restrict__ out) {
-  const int x4 = blockIdx.x * NT + threadIdx.x, yy = blockIdx.y, b = blockIdx.z;
-  if (x4 * 4 >= out_w) return;
-  const int ymin = bounds[2 * yy], cnt = bounds[2 * yy + 1];
-  const int32_t* k = kk + (size_t)yy * ksize;
-  int s0 = 1 << (PIL_PRECISION_BITS - 1), s1 = s0, s2 = s0, s3 = s0;
-  const uint8_t* col = tmp + ((size_t)b * h + ymin) * out_w + (size_t)x4 * 4;
-  for (int y = 0; y < cnt; ++y) {
-    const uchar4 p = *reinterpret_cast<const uchar4*>(col + (size_t)y * out_w);
-    const int w = k[y];
-    s0 += (int)p.x * w; s1 += (int)p.y * w; s2 += (int)p.z * w; s3 += (int)p.w * w;
-  }
-  uchar4 o;
-  o.x = pil_clip8(s0); o.y = pil_clip8(s1); o.z = pil_clip8(s2); o.w = pil_clip8(s3);
-  *reinterpret_cast<uchar4*>(out + ((size_t)b * out_h + yy) * out_w + (size_t)x4 * 4) = o;
-}
-
-// Both passes in one launch for SMALL sources (the 24 x 24 token grid): the workgroup of (image, block of R output
-// rows) quantises the source rows it needs into LDS, runs the horizontal pass for them into an LDS uint8 tile
-// [h][out_w] and the vertical pass from that tile, 4 output pixels per thread (one ds_read_b32 per tap row, one
-// dword store).  Same integer arithmetic as the two-kernel form; no tmp round trip, one launch instead of two.
-// grid = (ceil(out_h / R), B); out_w % 4 == 0; ksize_x <= KS.  LDS: src[h*w] | tile[h*out_w]
-template <int KS>
-__global__ __launch_bounds__(NT) void lanczos_fused_kernel(const float* __restrict__ mf, const uint8_t* __restrict__ mu,
-                                                           int h, int w, int out_h, int out_w,
-                                                           const int32_t* __restrict__ bounds_x,
-                                                           const int32_t* __restrict__ kk_x, int ksize_x,
-                                                           const int32_t* __restrict__ bounds_y,
-                                                           const int32_t* __restrict__ kk_y, int ksize_y, int R,
-                                                           uint8_t* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lz[];
-  __shared__ int32_t s_ky[64 * 32];                  // vertical coefficients and bounds of the block's rows (R <= 64)
-  __shared__ int32_t s_by[64 * 2];
-  const int srcp = (h * w + 3) & ~3;
-  uint8_t* src = lz;
-  uint8_t* tile = lz + srcp;
-  const int tid = threadIdx.x, b = blockIdx.y;
-  const int yy0 = blockIdx.x * R, yy1 = min(yy0 + R, out_h), nrows = yy1 - yy0;
-  const int ys = bounds_y[2 * yy0];                                          // first / one-past-last source row
-  const int ye = bounds_y[2 * (yy1 - 1)] + bounds_y[2 * (yy1 - 1) + 1];
-  const size_t ib = (size_t)b * h * w;
-  for (int i = ys * w + tid; i < ye * w; i += NT) src[i] = mf ? to_pil_u8(mf[ib + i]) : mu[ib + i];
-  if (ksize_y != 8) {      // only the generic vertical pass reads these (R <= 64 there)
-    for (int i = tid; i < nrows * ksize_y; i += NT) s_ky[i] = kk_y[(size_t)yy0 * ksize_y + i];
-    if (tid < 2 * nrows) s_by[tid] = bounds_y[2 * yy0 + tid];
-  }
-  __syncthreads();
-  for (int xx = tid; xx < out_w; xx += NT) {
-    const int xmin = bounds_x[2 * xx], cnt = bounds_x[2 * xx + 1];
-    int kreg[KS], toff[KS];
-#pragma unroll
-    for (int x = 0; x < KS; ++x) {
-      kreg[x] = (x < cnt) ? kk_x[(size_t)xx * ksize_x + min(x, ksize_x - 1)] : 0;
-      toff[x] = xmin + min(x, cnt - 1);
-    }
-    for (int r = ys; r < ye; ++r) {
-      const uint8_t* row = src + r * w;
-      int ss = 1 << (PIL_PRECISION_BITS - 1);
-#pragma unroll
-      for (int x = 0; x < KS; ++x) ss += __mul24((int)row[toff[x]], kreg[x]);
-      tile[r * out_w + xx] = pil_clip8(ss);
-    }
-  }
-  __syncthreads();
-  // vertical pass.  Everything that depends on the output row only (bounds, the <= 8 coefficients) is wave uniform
-  // and comes from scalar loads; a lane owns one dword column (4 pixels) and keeps the 8 tile rows of the current tap
-  // window UNPACKED in registers, so an output dword costs 32 v_mad_i32_i24 (pixels are 8 bit, coefficients < 2^23)
-  // + clip / pack / one store.  The window slides by one tile row every out_h / h output rows (42 for 24 -> 1024).
-  // Work items = (64-dword column chunk, chunk of the block's rows), dealt to the 4 waves.
-  const int nq = out_w >> 2;
-  if (ksize_y == 8) {       // rows of exactly 8 coefficients: 32-byte scalar loads, masked by the row's tap count
-    const int lane = tid & (WAVE - 1);
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int QW = (nq + WAVE - 1) / WAVE;
-    const int RC = QW >= 3 ? 1 : (NT / WAVE) / QW;               // QW = 1 -> 4 row chunks, 2 -> 2
-    const int rows_per = (nrows + RC - 1) / RC;
-    for (int item = wid; item < QW * RC; item += NT / WAVE) {
-      const int rc = item / QW, qc = item - rc * QW;
-      const int q = qc * WAVE + lane;
-      const int qq = min(q, nq - 1);
-      const int r_beg = rc * rows_per, r_end = min(r_beg + rows_per, nrows);
-      int win[8][4];
-      int base = -0x40000000;
-#pragma unroll
-      for (int y = 0; y < 8; ++y) win[y][0] = win[y][1] = win[y][2] = win[y][3] = 0;
-      auto load_row = [&](int r, int (&dst)[4]) {
-        const uint32_t wv = reinterpret_cast<const uint32_t*>(tile + min(r, h - 1) * out_w)[qq];
-        dst[0] = (int)(wv & 0xffu); dst[1] = (int)((wv >> 8) & 0xffu); dst[2] = (int)((wv >> 16) & 0xffu); dst[3] = (int)(wv >> 24);
-      };
-      // the NEXT row's bounds and coefficients are fetched while the current row is computed
-      // (coefficients past the row's tap count are masked here, so the caller's table need not be zero-padded)
-      int kc[8], ymin_c = 0;
-      if (r_beg < r_end) {
-        ymin_c = bounds_y[2 * (yy0 + r_beg)];
-        const int cnt_c = bounds_y[2 * (yy0 + r_beg) + 1];
-#pragma unroll
-        for (int y = 0; y < 8; ++y) kc[y] = y < cnt_c ? kk_y[(size_t)(yy0 + r_beg) * 8 + y] : 0;
-      }
-      for (int ry = r_beg; ry < r_end; ++ry) {
-        const int yy = yy0 + ry;
-        const int ymin = ymin_c;
-        int kv[8];
-#pragma unroll
-        for (int y = 0; y < 8; ++y) kv[y] = kc[y];
-        const int yn = min(yy + 1, out_h - 1);
-        ymin_c = bounds_y[2 * yn];
-        const int cnt_n = bounds_y[2 * yn + 1];
-#pragma unroll
-        for (int y = 0; y < 8; ++y) kc[y] = y < cnt_n ? kk_y[(size_t)yn * 8 + y] : 0;
-        if (ymin != base) {                                      // wave uniform
-          if (ymin == base + 1) {
-#pragma unroll
-            for (int y = 0; y < 7; ++y) { win[y][0] = win[y + 1][0]; win[y][1] = win[y + 1][1]; win[y][2] = win[y + 1][2]; win[y][3] = win[y + 1][3]; }
-            load_row(ymin + 7, win[7]);
-          } else {
-#pragma unroll
-            for (int y = 0; y < 8; ++y) load_row(ymin + y, win[y]);
-          }
-          base = ymin;
-        }
-        int s0 = 1 << (PIL_PRECISION_BITS - 1), s1 = s0, s2 = s0, s3 = s0;
-#pragma unroll
-        for (int y = 0; y < 8; ++y) {
-          // one v_mad_i32_i24 per tap and pixel (left to itself the compiler pairs v_mul_i32_i24 with v_add3_u32:
-          // 1.5 instructions per tap); the coefficient is wave uniform and sits in an SGPR
-          asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s0) : "v"(win[y][0]), "s"(kv[y]));
-          asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s1) : "v"(win[y][1]), "s"(kv[y]));
-          asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s2) : "v"(win[y][2]), "s"(kv[y]));
-          asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s3) : "v"(win[y][3]), "s"(kv[y]));
-        }
-        if (q < nq) reinterpret_cast<uint32_t*>(out + ((size_t)b * out_h + yy) * out_w)[q] = pil_clip8x4(s0, s1, s2, s3);
-      }
-    }
-    return;
-  }
-  // generic form (more than 8 vertical taps: down-sampling): a thread owns dword q of an output row; rows are spread
-  // over the threads left
-  const int rstep = nq >= NT ? 1 : NT / nq;          // rows in flight per sweep
-  const int q0 = nq >= NT ? tid : tid % nq, r0 = nq >= NT ? 0 : tid / nq;
-  if (r0 < rstep) {
-    for (int ry = r0; ry < nrows; ry += rstep) {
-      const int yy = yy0 + ry;
-      const int ymin = s_by[2 * ry], cnt = s_by[2 * ry + 1];
-      const int32_t* k = s_ky + ry * ksize_y;
-      for (int q = q0; q < nq; q += NT) {
-        int s0 = 1 << (PIL_PRECISION_BITS - 1), s1 = s0, s2 = s0, s3 = s0;
-        for (int y = 0; y < cnt; ++y) {
-          const uint32_t wv = reinterpret_cast<const uint32_t*>(tile + (ymin + y) * out_w)[q];
-          const int kv = k[y];
-          s0 += (int)(wv & 0xffu) * kv;
-          s1 += (int)((wv >> 8) & 0xffu) * kv;
-          s2 += (int)((wv >> 16) & 0xffu) * kv;
-          s3 += (int)(wv >> 24) * kv;
-        }
-        reinterpret_cast<uint32_t*>(out + ((size_t)b * out_h + yy) * out_w)[q] = pil_clip8x4(s0, s1, s2, s3);
-      }
-    }
-  }
-}
-
-// Up-sampling form of the fused kernel (<= 8 taps on both axes): body lanczos_strip_block (mask_blocks.hpp).
-// grid = (nstrips * nchunks, B).  LDS: src[h*w] | tile[h][256].   kk_y rows hold exactly 8 coefficients (zero padded).
-template <int KS, bool UA>
-__global__ __launch_bounds__(NT) void lanczos_strip_kernel(const LanczosStripArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lz[];
-  const int b = blockIdx.y;
-  lanczos_strip_block<KS, UA>(a, blockIdx.x, (size_t)b * a.h * a.w, a.out + (size_t)b * a.out_h * a.out_w, lz);
-}
-
-// copy / quantise pass used when an axis keeps its size (Pillow skips that pass)
-__global__ __launch_bounds__(NT) void quantise_copy_kernel(const float* __restrict__ mf, const uint8_t* __restrict__ mu,
-                                                           size_t n, uint8_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
-  if (i < n) out[i] = mf ? to_pil_u8(mf[i]) : mu[i];
-}
-
-// ---- "next" row 3: warped uint8 RGB image -> CLIP-ready tensor (HF CLIPImageProcessor, PIL backend) ----
-// horizontal pass of Pillow's 8-bit resampler on interleaved C-channel images, restricted to the output
-// columns [left, left+ow):  tmp[b][y][xx][c].   grid = (ceil(ow*C/NT), h, B)
-__global__ __launch_bounds__(NT) void resample8_h_kernel(const uint8_t* __restrict__ src, int h, int w, int C,
-                                                         int left, int ow, const int32_t* __restrict__ bounds,
-                                                         const int32_t* __restrict__ kk, int ksize,
-                                                         uint8_t* __restrict__ tmp) {
-  const int e = blockIdx.x * NT + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
-  if (e >= ow * C) return;
-  const int xx = e / C, c = e - xx * C;
-  const int xo = left + xx;
-  const int xmin = bounds[2 * xo], cnt = bounds[2 * xo + 1];
-  const int32_t* k = kk + (size_t)xo * ksize;
-  const uint8_t* row = src + ((size_t)b * h + y) * w * C + c;
-  int ss = 1 << (PIL_PRECISION_BITS - 1);
-  for (int x = 0; x < cnt; ++x) ss += (int)row[(size_t)(xmin + x) * C] * k[x];
-  tmp[((size_t)b * h + y) * ow * C + e] = pil_clip8(ss);
-}
-
-// vertical pass for the output rows [top, top+oh) fused with the CLIP epilogue:
-//   u8 -> float32(float64(u8) * (1/255)) -> (x - mean[c]) / std[c] in float32 -> planar [B,C,oh,ow] (f32 or f16)
-// grid = (ceil(ow/NT), oh, B)
-template <typename OutT>
-__global__ __launch_bounds__(NT) void clip_v_kernel(const uint8_t* __restrict__ tmp, int h, int C, int top, int oh,
-                                                    int ow, const int32_t* __restrict__ bounds,
-                                                    const int32_t* __restrict__ kk, int ksize, float m0, float m1,
-                                                    float m2, float m3, float s0, float s1, float s2, float s3,
-                                                    OutT* __restrict__ out) {
-  const int xx = blockIdx.x * NT + threadIdx.x, yy = blockIdx.y, b = blockIdx.z;
-  if (xx >= ow) return;
-  const int yo = top + yy;
-  const int ymin = bounds[2 * yo], cnt = bounds[2 * yo + 1];
-  const int32_t* k = kk + (size_t)yo * ksize;
-  const float mean[4] = {m0, m1, m2, m3}, stdv[4] = {s0, s1, s2, s3};
-  for (int c = 0; c < C; ++c) {
-    int ss = 1 << (PIL_PRECISION_BITS - 1);
-    for (int y = 0; y < cnt; ++y) ss += (int)tmp[(((size_t)b * h + ymin + y) * ow + xx) * C + c] * k[y];
-    const float x = (float)((double)pil_clip8(ss) * (1.0 / 255.0));
-    const float v = fsub(x, mean[c]) / stdv[c];
-    out[(((size_t)b * C + c) * oh + yy) * ow + xx] = from_f32<OutT>(v);
-  }
-}
 
 template <typename T>
 static int launch_step(const void* attn, int nb, int heads, int64_t sb, int64_t sh, int64_t row_off, int64_t skv,
@@ -506,105 +250,3 @@ extern "C" int attwarp_mask_postproc(const float* mask, int B, int n, int kernel
                      out);
   return check_launch("mask_postproc_kernel");
 }
-
-extern "C" int attwarp_mask_upsample_lanczos(const float* mask_f32, const uint8_t* mask_u8, int B, int h, int w,
-                                             int out_h, int out_w, const int32_t* bounds_x, const int32_t* kk_x,
-                                             int ksize_x, const int32_t* bounds_y, const int32_t* kk_y, int ksize_y,
-                                             uint8_t* tmp, uint8_t* out, void* stream) {
-  ATTWARP_REQUIRE((mask_f32 != nullptr) != (mask_u8 != nullptr), "mask_upsample_lanczos: pass exactly one of mask_f32 / mask_u8");
-  ATTWARP_REQUIRE(out, "mask_upsample_lanczos: null output");
-  ATTWARP_REQUIRE(B > 0 && h > 0 && w > 0 && out_h > 0 && out_w > 0, "mask_upsample_lanczos: non-positive size");
-  if (B > 65535 || h > 65535 || out_h > 65535) return fail(ATTWARP_E_UNSUPPORTED, "mask_upsample_lanczos: dims > 65535");
-  const bool need_h = out_w != w, need_v = out_h != h;
-  ATTWARP_REQUIRE(!need_h || (bounds_x && kk_x && ksize_x > 0), "mask_upsample_lanczos: missing x coefficients");
-  ATTWARP_REQUIRE(!need_v || (bounds_y && kk_y && ksize_y > 0), "mask_upsample_lanczos: missing y coefficients");
-  ATTWARP_REQUIRE(!(need_h && need_v) || tmp, "mask_upsample_lanczos: tmp workspace required for a two-pass resize");
-  hipStream_t st = as_stream(stream);
-  if (!need_h && !need_v) {
-    const size_t n = (size_t)B * h * w;
-    hipLaunchKernelGGL(quantise_copy_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, st, mask_f32, mask_u8, n, out);
-    return check_launch("quantise_copy_kernel");
-  }
-  // up-sampling of a small source with <= 8 taps per axis (the 24 x 24 token grid): column-strip kernel
-  if (need_h && need_v && tune(TUNE_LANCZOS_VARIANT) <= 0 && (long long)h * w <= 4096 && ksize_x <= 8 &&
-      ksize_y == 8 && (size_t)((h * w + 3) & ~3) + (size_t)h * NT <= 48 * 1024) {
-    // rows that do not start on dword boundaries (out_w % 4 != 0, e.g. the mask of a 683-pixel-wide image): the UA form
-    const bool ua = out_w % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 3u) != 0;
-    const int nstrips = (out_w + NT - 1) / NT;
-    // enough workgroups to fill the chip (~4096: measured 1024x1024 B=256, rows per chunk 512 / 256 / 128 / 64:
-    // 108 / 105 / 111 / 127 us), at least 16 rows per wave
-    long long nchunks = (4096 + (long long)B * nstrips - 1) / ((long long)B * nstrips);
-    const int max_chunks = (out_h + 63) / 64;
-    if (nchunks > max_chunks) nchunks = max_chunks;
-    if (nchunks < 1) nchunks = 1;
-    const int rows_per_chunk = (int)((out_h + nchunks - 1) / nchunks);
-    nchunks = (out_h + rows_per_chunk - 1) / rows_per_chunk;
-    const size_t lds = (size_t)((h * w + 3) & ~3) + (size_t)h * NT;
-    LanczosStripArgs la{mask_f32, mask_u8, h, w, out_h, out_w, bounds_x, kk_x, ksize_x, bounds_y, kk_y, (int)nchunks, rows_per_chunk, out};
-    if (ua) hipLaunchKernelGGL((lanczos_strip_kernel<8, true>), dim3((unsigned)(nstrips * nchunks), B), dim3(NT), lds, st, la);
-    else hipLaunchKernelGGL((lanczos_strip_kernel<8, false>), dim3((unsigned)(nstrips * nchunks), B), dim3(NT), lds, st, la);
-    return check_launch("lanczos_strip_kernel");
-  }
-  // small source and both passes needed, any tap count: one fused launch (row-block form)
-  {
-    const bool two_kernel = tune(TUNE_LANCZOS_VARIANT) == 1;      // 2: the row-block fused kernel
-    const size_t lds = (size_t)((h * w + 3) & ~3) + (size_t)h * out_w;
-    if (need_h && need_v && !two_kernel && (long long)h * w <= 4096 && out_w % 4 == 0 && ksize_x <= 8 &&
-        ksize_y <= 32 &&
-        lds <= 48 * 1024 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0) {
-      const int R = out_h >= 448 ? 64 : 32;   // measured: 24->336 R=32 27 us (two-kernel form 34), 24->1024 B=256 R=64 258 us (287)
-      hipLaunchKernelGGL((lanczos_fused_kernel<8>), dim3((out_h + R - 1) / R, B), dim3(NT), lds, st, mask_f32, mask_u8,
-                         h, w, out_h, out_w, bounds_x, kk_x, ksize_x, bounds_y, kk_y, ksize_y, R, out);
-      return check_launch("lanczos_fused_kernel");
-    }
-  }
-  const uint8_t* vsrc = mask_u8;
-  if (need_h) {
-    uint8_t* hdst = need_v ? tmp : out;
-    hipLaunchKernelGGL(lanczos_h_kernel, dim3((out_w + NT - 1) / NT, h, B), dim3(NT), 0, st, mask_f32, mask_u8, h, w,
-                       out_w, bounds_x, kk_x, ksize_x, hdst);
-    int rc = check_launch("lanczos_h_kernel");
-    if (rc) return rc;
-    vsrc = hdst;
-  } else if (mask_f32) {
-    ATTWARP_REQUIRE(tmp, "mask_upsample_lanczos: tmp workspace required to quantise a float mask");
-    const size_t n = (size_t)B * h * w;
-    hipLaunchKernelGGL(quantise_copy_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, st, mask_f32, nullptr, n, tmp);
-    int rc = check_launch("quantise_copy_kernel");
-    if (rc) return rc;
-    vsrc = tmp;
-  }
-  if (need_v) {
-    const bool vec4 = (out_w % 4 == 0) && ((reinterpret_cast<uintptr_t>(vsrc) | reinterpret_cast<uintptr_t>(out)) % 4 == 0);
-    if (vec4)
-      hipLaunchKernelGGL(lanczos_v4_kernel, dim3((out_w / 4 + NT - 1) / NT, out_h, B), dim3(NT), 0, st, vsrc, h, out_w,
-                         out_h, bounds_y, kk_y, ksize_y, out);
-    else
-      hipLaunchKernelGGL(lanczos_v_kernel, dim3((out_w + NT - 1) / NT, out_h, B), dim3(NT), 0, st, vsrc, h, out_w,
-                         out_h, bounds_y, kk_y, ksize_y, out);
-    return check_launch("lanczos_v_kernel");
-  }
-  return ATTWARP_OK;
-}
-
-namespace attwarp {
-// Generic two-kernel form (one thread per output element, global byte taps): any size; clip.hip holds the
-// LDS-staged kernels that take the common shapes and calls this one otherwise.
-int clip_preprocess_generic(const uint8_t* src, int B, int h, int w, int C, int top, int left, int size,
-                            const int32_t* bounds_x, const int32_t* kk_x, int ksize_x, const int32_t* bounds_y,
-                            const int32_t* kk_y, int ksize_y, const float* m, const float* s, uint8_t* tmp, void* out,
-                            int out_dtype, hipStream_t st) {
-  hipLaunchKernelGGL(resample8_h_kernel, dim3((size * C + NT - 1) / NT, h, B), dim3(NT), 0, st, src, h, w, C, left, size,
-                     bounds_x, kk_x, ksize_x, tmp);
-  int rc = check_launch("resample8_h_kernel");
-  if (rc) return rc;
-  const dim3 grid((size + NT - 1) / NT, size, B);
-  if (out_dtype == ATTWARP_F32)
-    hipLaunchKernelGGL((clip_v_kernel<float>), grid, dim3(NT), 0, st, tmp, h, C, top, size, size, bounds_y, kk_y,
-                       ksize_y, m[0], m[1], m[2], m[3], s[0], s[1], s[2], s[3], (float*)out);
-  else
-    hipLaunchKernelGGL((clip_v_kernel<__half>), grid, dim3(NT), 0, st, tmp, h, C, top, size, size, bounds_y, kk_y,
-                       ksize_y, m[0], m[1], m[2], m[3], s[0], s[1], s[2], s[3], (__half*)out);
-  return check_launch("clip_v_kernel");
-}
-}  // namespace attwarp

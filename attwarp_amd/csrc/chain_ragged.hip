@@ -193,25 +193,6 @@ __global__ __launch_bounds__(RAGGED_NT, RAGGED_WAVES) void mask_chain_ragged_ker
 #endif
 }
 
-// ---- host: Pillow's coefficient tables (ImagingResample precompute_coeffs + normalize_coeffs_8bpc, Resample.c) -------
-static double pil_sinc(double x) {
-  if (x == 0.0) return 1.0;
-  x *= M_PI;
-  return sin(x) / x;
-}
-static double pil_lanczos3(double x) { return (-3.0 <= x && x < 3.0) ? pil_sinc(x) * pil_sinc(x / 3.0) : 0.0; }
-static double pil_bicubic(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-static double pil_bilinear(double x) {
-  if (x < 0.0) x = -x;
-  return x < 1.0 ? 1.0 - x : 0.0;
-}
-
 // ---- host: the table of one batch ----------------------------------------------------------------------------------
 struct RaggedLayout {
   attwarp_ragged_header h;
@@ -359,52 +340,6 @@ static int launch_ragged(const RaggedStepArgs& a, size_t lds, unsigned grid, hip
 }  // namespace attwarp
 
 using namespace attwarp;
-
-extern "C" int attwarp_pil_coeffs_8bpc(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk, int kk_cols) try {
-  ATTWARP_REQUIRE(bounds && kk, "pil_coeffs_8bpc: null pointer");
-  ATTWARP_REQUIRE(in_size > 0 && out_size > 0 && kk_cols > 0, "pil_coeffs_8bpc: non-positive size");
-  ATTWARP_REQUIRE(filter == ATTWARP_PIL_LANCZOS || filter == ATTWARP_PIL_BICUBIC || filter == ATTWARP_PIL_BILINEAR,
-                  "pil_coeffs_8bpc: unknown filter %d", filter);
-  double (*fn)(double) = filter == ATTWARP_PIL_LANCZOS ? pil_lanczos3 : filter == ATTWARP_PIL_BICUBIC ? pil_bicubic : pil_bilinear;
-  const double support0 = filter == ATTWARP_PIL_LANCZOS ? 3.0 : filter == ATTWARP_PIL_BICUBIC ? 2.0 : 1.0;
-  constexpr int PRECISION_BITS = 32 - 8 - 2;
-  if (in_size == out_size) {     // Pillow skips the pass; an identity table makes clip8((v << 22 + 2^21) >> 22) == v
-    for (int o = 0; o < out_size; ++o) {
-      bounds[2 * o] = o; bounds[2 * o + 1] = 1;
-      for (int i = 0; i < kk_cols; ++i) kk[(size_t)o * kk_cols + i] = i == 0 ? (1 << PRECISION_BITS) : 0;
-    }
-    return 1;
-  }
-  const double scale = (double)in_size / (double)out_size;
-  const double fscale = scale < 1.0 ? 1.0 : scale;
-  const double support = support0 * fscale;
-  const int ksize = (int)ceil(support) * 2 + 1;
-  if (ksize > kk_cols) return fail(ATTWARP_E_ARG, "pil_coeffs_8bpc: %d taps do not fit %d columns", ksize, kk_cols);
-  const double ss = 1.0 / fscale;
-  std::vector<double> w((size_t)ksize);
-  for (int o = 0; o < out_size; ++o) {
-    const double center = (o + 0.5) * scale;
-    int lo = (int)(center - support + 0.5);
-    if (lo < 0) lo = 0;
-    int hi = (int)(center + support + 0.5);
-    if (hi > in_size) hi = in_size;
-    const int cnt = hi - lo;
-    double tot = 0.0;
-    for (int i = 0; i < cnt; ++i) {
-      w[i] = fn((i + lo - center + 0.5) * ss);
-      tot += w[i];
-    }
-    for (int i = 0; i < cnt; ++i)
-      if (tot != 0.0) w[i] /= tot;
-    int32_t* row = kk + (size_t)o * kk_cols;
-    for (int i = 0; i < kk_cols; ++i) row[i] = 0;
-    for (int i = 0; i < cnt; ++i) row[i] = (int32_t)((w[i] < 0 ? -0.5 : 0.5) + w[i] * (1 << PRECISION_BITS));
-    bounds[2 * o] = lo; bounds[2 * o + 1] = cnt;
-  }
-  return ksize;
-} catch (...) {
-  return fail(ATTWARP_E_UNSUPPORTED, "pil_coeffs_8bpc: out of host memory");
-}
 
 // (the host helpers allocate std::vectors: an allocation failure must not travel through the C ABI as an exception)
 extern "C" size_t attwarp_ragged_table_bytes(const attwarp_ragged_image* images, int B, int C, int g, int H_out, int W_out) try {

@@ -5,7 +5,7 @@
 // (x - mean) / std in float32, channels first.  The coefficient tables are Pillow's, computed on the host
 // (attwarp_amd/_tables.py) and shared by every image of the batch.
 //
-// Two LDS-staged kernels (the generic one-thread-per-output form in attn.hip costs 0.20 + 0.12 ms for 64 images
+// Two LDS-staged kernels (the generic one-thread-per-output form below costs 0.20 + 0.12 ms for 64 images
 // 500x500 -> 336x336, bound by global byte loads: 14 and 8 load instructions per output byte):
 //   clip_h_rows_kernel : a workgroup stages the coefficient table of the cropped columns and RB source rows in LDS
 //                        (coalesced dword loads), computes RB x ow pixels from LDS, writes the uint8 rows back
@@ -15,27 +15,13 @@
 //                        each thread accumulates 4 interleaved bytes per tap row from one dword load, looks the
 //                        result up and the row is written planar through an LDS transpose.
 #include "common.hpp"
+#include "pil8.hpp"
 
 namespace attwarp {
-
-int clip_preprocess_generic(const uint8_t* src, int B, int h, int w, int C, int top, int left, int size,
-                            const int32_t* bounds_x, const int32_t* kk_x, int ksize_x, const int32_t* bounds_y,
-                            const int32_t* kk_y, int ksize_y, const float* m, const float* s, uint8_t* tmp, void* out,
-                            int out_dtype, hipStream_t st);
-
 namespace clip {
 
 constexpr int NT = 256;
-constexpr int PIL_PRECISION_BITS = 32 - 8 - 2;
 constexpr int RV = 8;            // output rows per workgroup of the vertical pass (the per-workgroup table and index set-up is amortised over them)
-
-__device__ __forceinline__ uint8_t clip8(int v) { return (uint8_t)min(max(v >> PIL_PRECISION_BITS, 0), 255); }
-// acc += pixel * coefficient with ONE full-rate instruction: pixels are 8 bit, Pillow's coefficients |k| <= 2^22, so the
-// 24-bit multiply-add is exact (left to itself the compiler emits the quarter-rate v_mul_lo_u32 + an add: the
-// horizontal pass spent 24 of those per pixel and row)
-__device__ __forceinline__ void mad24(int& acc, int px, int k) { asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(acc) : "v"(px), "v"(k)); }
-// the same with a wave-uniform coefficient (an SGPR operand: no v_mov per tap)
-__device__ __forceinline__ void mad24s(int& acc, int px, int k) { asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(acc) : "v"(px), "s"(k)); }
 
 // grid = (ceil(h / RB), B), NTH threads.  LDS: srow[RB][wcp] | orow[RB][ocp]  (row bytes rounded up to 4).
 // A thread owns output pixel xx (and xx + NTH, ...): its first tap and its <= KS coefficients stay in registers
@@ -73,12 +59,7 @@ __global__ __launch_bounds__(NTH) void clip_h_rows_kernel(const uint8_t* __restr
   }
   __syncthreads();
 
-  // The KS taps x C channels of a pixel are KS*C CONSECUTIVE bytes of the source row starting at xmin*C: they are read
-  // as KS*C/4 + 1 dwords, shifted into place with v_alignbyte_b32 and consumed with a static byte extract + one
-  // v_mad_i32_i24 each (byte reads made the LDS the bottleneck: 24 ds_read_u8 per pixel and row for RGB, 41 % of the
-  // LDS cycles bank conflicts -- profiles/round2_clip_pmc.txt).  Taps past the pixel's count carry a zero coefficient;
-  // the bytes they multiply may lie past the row (the next row, or the slack behind the last one).
-  constexpr int NB = KS * C, NA = NB / 4, NW = NA + 1;
+  // horizontal pass from LDS: the byte window of pil8.hpp (its over-read lands in the next row or in H_SLACK)
   for (int xx = tid; xx < ow; xx += NTH) {
     const int xo = left + xx;
     const int xmin = bounds[2 * xo], cnt = bounds[2 * xo + 1];
@@ -87,27 +68,9 @@ __global__ __launch_bounds__(NTH) void clip_h_rows_kernel(const uint8_t* __restr
     for (int x = 0; x < KS; ++x) kreg[x] = (x < cnt) ? kk[(size_t)xo * ksize + min(x, ksize - 1)] : 0;
     const int o = xmin * C, sh = o & 3;
     const uint8_t* first = srow + (o & ~3);
-    for (int r = 0; r < nrows; ++r) {
-      const uint32_t* rw = reinterpret_cast<const uint32_t*>(first + (size_t)r * wcp);
-      uint32_t wv[NW], a[NA];
-#pragma unroll
-      for (int i = 0; i < NW; ++i) wv[i] = rw[i];
-#pragma unroll
-      for (int i = 0; i < NA; ++i) a[i] = __builtin_amdgcn_alignbyte(wv[i + 1], wv[i], sh);
-      int ss[C];
-#pragma unroll
-      for (int c = 0; c < C; ++c) ss[c] = 1 << (PIL_PRECISION_BITS - 1);
-#pragma unroll
-      for (int x = 0; x < KS; ++x)
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          const int j = x * C + c;
-          mad24(ss[c], (int)((a[j >> 2] >> (8 * (j & 3))) & 0xffu), kreg[x]);
-        }
-      uint8_t* op = orow + (size_t)r * ocp + xx * C;
-#pragma unroll
-      for (int c = 0; c < C; ++c) op[c] = clip8(ss[c]);
-    }
+    for (int r = 0; r < nrows; ++r)
+      pil_h_window<C, KS>(reinterpret_cast<const uint32_t*>(first + (size_t)r * wcp), sh, kreg,
+                          orow + (size_t)r * ocp + xx * C);
   }
   __syncthreads();
 
@@ -143,7 +106,7 @@ __global__ __launch_bounds__(NT) void clip_v_rows_kernel(const uint8_t* __restri
     const float mean[4] = {m0, m1, m2, m3}, stdv[4] = {s0, s1, s2, s3};
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const float x = (float)((double)tid * (1.0 / 255.0));        // rescale: float32(float64(u8) * (1/255))
+      const float x = pil_u8_to_unit(tid);                         // rescale
       lut[c * 256 + tid] = fsub(x, mean[c]) / stdv[c];             // normalize in float32
     }
   }
@@ -180,7 +143,7 @@ __global__ __launch_bounds__(NT) void clip_v_rows_kernel(const uint8_t* __restri
     for (int n = 0; n < NQ; ++n) {
       const int q = tid + NT * n;
       if (q < nq) {
-        int a0 = 1 << (PIL_PRECISION_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
+        int a0 = PIL_ROUND_HALF, a1 = a0, a2 = a0, a3 = a0;
         if (ksize == 8) {
           // rows of exactly 8 coefficients: one 32-byte scalar load, masked by the row's tap count (the caller's table
           // need not be zero-padded), and 8 row loads without a branch (row indices clamped to the image)
@@ -217,10 +180,10 @@ __global__ __launch_bounds__(NT) void clip_v_rows_kernel(const uint8_t* __restri
             mad24s(a3, (int)(wv[i] >> 24), kv[i]);
           }
         }
-        tile[toff[n][0]] = from_f32<OutT>(lut[lbase[n][0] + clip8(a0)]);
-        tile[toff[n][1]] = from_f32<OutT>(lut[lbase[n][1] + clip8(a1)]);
-        tile[toff[n][2]] = from_f32<OutT>(lut[lbase[n][2] + clip8(a2)]);
-        tile[toff[n][3]] = from_f32<OutT>(lut[lbase[n][3] + clip8(a3)]);
+        tile[toff[n][0]] = from_f32<OutT>(lut[lbase[n][0] + pil_clip8(a0)]);
+        tile[toff[n][1]] = from_f32<OutT>(lut[lbase[n][1] + pil_clip8(a1)]);
+        tile[toff[n][2]] = from_f32<OutT>(lut[lbase[n][2] + pil_clip8(a2)]);
+        tile[toff[n][3]] = from_f32<OutT>(lut[lbase[n][3] + pil_clip8(a3)]);
       }
     }
     __syncthreads();
@@ -234,6 +197,67 @@ __global__ __launch_bounds__(NT) void clip_v_rows_kernel(const uint8_t* __restri
 }
 
 }  // namespace clip
+
+using clip::NT;
+
+// ---- the generic two-kernel form (one thread per output element, global byte taps): any size ----
+// horizontal pass of Pillow's 8-bit resampler on interleaved C-channel images, restricted to the output
+// columns [left, left+ow):  tmp[b][y][xx][c].   grid = (ceil(ow*C/NT), h, B)
+__global__ __launch_bounds__(NT) void resample8_h_kernel(const uint8_t* __restrict__ src, int h, int w, int C,
+                                                         int left, int ow, const int32_t* __restrict__ bounds,
+                                                         const int32_t* __restrict__ kk, int ksize,
+                                                         uint8_t* __restrict__ tmp) {
+  const int e = blockIdx.x * NT + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+  if (e >= ow * C) return;
+  const int xx = e / C, c = e - xx * C;
+  const int xo = left + xx;
+  const int xmin = bounds[2 * xo], cnt = bounds[2 * xo + 1];
+  const uint8_t* row = src + ((size_t)b * h + y) * w * C + c;
+  tmp[((size_t)b * h + y) * ow * C + e] = pil_tap_sum(row + (size_t)xmin * C, (size_t)C, kk + (size_t)xo * ksize, cnt);
+}
+
+// vertical pass for the output rows [top, top+oh) fused with the CLIP epilogue:
+//   u8 -> pil_u8_to_unit -> (x - mean[c]) / std[c] in float32 -> planar [B,C,oh,ow] (f32 or f16)
+// grid = (ceil(ow/NT), oh, B)
+template <typename OutT>
+__global__ __launch_bounds__(NT) void clip_v_kernel(const uint8_t* __restrict__ tmp, int h, int C, int top, int oh,
+                                                    int ow, const int32_t* __restrict__ bounds,
+                                                    const int32_t* __restrict__ kk, int ksize, float m0, float m1,
+                                                    float m2, float m3, float s0, float s1, float s2, float s3,
+                                                    OutT* __restrict__ out) {
+  const int xx = blockIdx.x * NT + threadIdx.x, yy = blockIdx.y, b = blockIdx.z;
+  if (xx >= ow) return;
+  const int yo = top + yy;
+  const int ymin = bounds[2 * yo], cnt = bounds[2 * yo + 1];
+  const int32_t* k = kk + (size_t)yo * ksize;
+  const float mean[4] = {m0, m1, m2, m3}, stdv[4] = {s0, s1, s2, s3};
+  const uint8_t* col = tmp + (((size_t)b * h + ymin) * ow + xx) * C;
+  for (int c = 0; c < C; ++c) {
+    const float x = pil_u8_to_unit(pil_tap_sum(col + c, (size_t)ow * C, k, cnt));
+    const float v = fsub(x, mean[c]) / stdv[c];
+    out[(((size_t)b * C + c) * oh + yy) * ow + xx] = from_f32<OutT>(v);
+  }
+}
+
+// the LDS-staged kernels above take the common shapes; the entry point calls this one otherwise
+static int clip_preprocess_generic(const uint8_t* src, int B, int h, int w, int C, int top, int left, int size,
+                                   const int32_t* bounds_x, const int32_t* kk_x, int ksize_x, const int32_t* bounds_y,
+                                   const int32_t* kk_y, int ksize_y, const float* m, const float* s, uint8_t* tmp,
+                                   void* out, int out_dtype, hipStream_t st) {
+  hipLaunchKernelGGL(resample8_h_kernel, dim3((size * C + NT - 1) / NT, h, B), dim3(NT), 0, st, src, h, w, C, left, size,
+                     bounds_x, kk_x, ksize_x, tmp);
+  int rc = check_launch("resample8_h_kernel");
+  if (rc) return rc;
+  const dim3 grid((size + NT - 1) / NT, size, B);
+  if (out_dtype == ATTWARP_F32)
+    hipLaunchKernelGGL((clip_v_kernel<float>), grid, dim3(NT), 0, st, tmp, h, C, top, size, size, bounds_y, kk_y,
+                       ksize_y, m[0], m[1], m[2], m[3], s[0], s[1], s[2], s[3], (float*)out);
+  else
+    hipLaunchKernelGGL((clip_v_kernel<__half>), grid, dim3(NT), 0, st, tmp, h, C, top, size, size, bounds_y, kk_y,
+                       ksize_y, m[0], m[1], m[2], m[3], s[0], s[1], s[2], s[3], (__half*)out);
+  return check_launch("clip_v_kernel");
+}
+
 }  // namespace attwarp
 
 using namespace attwarp;

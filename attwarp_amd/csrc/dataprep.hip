@@ -14,11 +14,12 @@
 //
 // prep_fused_kernel: a workgroup owns one (image, band of output rows) item of a host-built list.  It stages the source
 // rows the band's vertical taps need into LDS RB rows at a time (dword loads at any byte address), runs the horizontal
-// pass from LDS with the byte-window + v_mad_i32_i24 idiom of clip.hip into uint8 rows of S_w*C bytes that stay in LDS,
+// pass from LDS with the byte window of pil8.hpp (as clip.hip does) into uint8 rows of S_w*C bytes that stay in LDS,
 // then the vertical pass from those rows through the 256-entry /255 table, each lane storing four consecutive floats of
 // one plane.  The band height follows the image's vertical scale: neighbouring bands recompute the 2 * support source
 // rows they share, which the host keeps near an eighth of a band's rows.
 #include "common.hpp"
+#include "pil8.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -29,7 +30,6 @@ namespace prep {
 
 constexpr uint32_t PREP_MAGIC = 0x50455250u;       // "PREP"
 constexpr int NT = 256;                            // == entries of the /255 table: thread t writes entry t
-constexpr int PIL_PRECISION_BITS = 32 - 8 - 2;
 constexpr int LUT_BYTES = 256 * 4;
 constexpr int SLACK = 128;                         // behind the staged rows: the byte window of the last pixels reads past the row
 constexpr int SPLIT_H_ROWS = 16, SPLIT_V_ROWS = 8; // rows per item of the two-launch route
@@ -42,12 +42,6 @@ struct PrepImageDev {                              // the per-image record insid
   int32_t fused, ny, rb, nr_cap;                   // one-launch route: band height, staged rows per round, LDS rows of the band
 };
 struct PrepItem { int32_t img, y0, ny, reserved; };
-
-__device__ __forceinline__ uint8_t clip8(int v) { return (uint8_t)min(max(v >> PIL_PRECISION_BITS, 0), 255); }
-// acc += pixel * coefficient in one full-rate instruction (8-bit pixels, |k| <= 2^22: the 24-bit multiply-add is exact)
-__device__ __forceinline__ void mad24(int& acc, int px, int k) { asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(acc) : "v"(px), "v"(k)); }
-__device__ __forceinline__ void mad24s(int& acc, int px, int k) { asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(acc) : "v"(px), "s"(k)); }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // grid = items, NT threads.  LDS: lut[256] float | inter[nr_cap][ocp] | srow[rb][wcp] | SLACK   (row bytes rounded up to 4)
 template <int C, int KS>
@@ -63,7 +57,7 @@ __global__ __launch_bounds__(NT) void prep_fused_kernel(const PrepImageDev* __re
   float* lut = reinterpret_cast<float*>(lds_b);
   uint8_t* inter = lds_b + LUT_BYTES;
   uint8_t* srow = inter + (size_t)im.nr_cap * ocp;
-  lut[tid] = (float)((double)tid * (1.0 / 255.0));
+  lut[tid] = pil_u8_to_unit(tid);
 
   const int32_t* __restrict__ by = im.r.bounds_y;
   const int y0 = it.y0, y1 = it.y0 + it.ny;
@@ -85,7 +79,6 @@ __global__ __launch_bounds__(NT) void prep_fused_kernel(const PrepImageDev* __re
   const int ndw = wcp >> 2, full = wc >> 2, ksx = im.r.ksize_x;
   const int32_t* __restrict__ bx = im.r.bounds_x;
   const int32_t* __restrict__ kx = im.r.kk_x;
-  constexpr int NB = KS * C, NA = (NB + 3) / 4, NW = NA + 1;
   for (int rs = 0; rs < nr; rs += RB) {
     const int nrows = min(RB, nr - rs);
     const uint8_t* sp = im.r.image + (size_t)(r0 + rs) * wc;
@@ -102,8 +95,7 @@ __global__ __launch_bounds__(NT) void prep_fused_kernel(const PrepImageDev* __re
       reinterpret_cast<uint32_t*>(srow + (size_t)r * wcp)[d] = v;
     }
     __syncthreads();
-    // the KS taps x C channels of a pixel are consecutive bytes of the staged row from xmin*C on: NW dwords, shifted into
-    // place with v_alignbyte_b32; taps past the pixel's count carry a zero coefficient and may multiply bytes past the row
+    // the byte window of pil8.hpp; its over-read lands in the next staged row or in SLACK
     for (int xx = tid; xx < S_w; xx += NT) {
       const int xmin = clampi(bx[2 * xx], 0, W - 1), cnt = bx[2 * xx + 1];
       int kreg[KS];
@@ -111,27 +103,9 @@ __global__ __launch_bounds__(NT) void prep_fused_kernel(const PrepImageDev* __re
       for (int x = 0; x < KS; ++x) kreg[x] = (x < cnt && x < ksx) ? kx[(size_t)xx * ksx + x] : 0;
       const int o = xmin * C, sh = o & 3;
       const uint8_t* first = srow + (o & ~3);
-      for (int r = 0; r < nrows; ++r) {
-        const uint32_t* rw = reinterpret_cast<const uint32_t*>(first + (size_t)r * wcp);
-        uint32_t wv[NW], a[NA];
-#pragma unroll
-        for (int i = 0; i < NW; ++i) wv[i] = rw[i];
-#pragma unroll
-        for (int i = 0; i < NA; ++i) a[i] = __builtin_amdgcn_alignbyte(wv[i + 1], wv[i], sh);
-        int ss[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) ss[c] = 1 << (PIL_PRECISION_BITS - 1);
-#pragma unroll
-        for (int x = 0; x < KS; ++x)
-#pragma unroll
-          for (int c = 0; c < C; ++c) {
-            const int j = x * C + c;
-            mad24(ss[c], (int)((a[j >> 2] >> (8 * (j & 3))) & 0xffu), kreg[x]);
-          }
-        uint8_t* op = inter + (size_t)(rs + r) * ocp + xx * C;
-#pragma unroll
-        for (int c = 0; c < C; ++c) op[c] = clip8(ss[c]);
-      }
+      for (int r = 0; r < nrows; ++r)
+        pil_h_window<C, KS>(reinterpret_cast<const uint32_t*>(first + (size_t)r * wcp), sh, kreg,
+                            inter + (size_t)(rs + r) * ocp + xx * C);
     }
     __syncthreads();
   }
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(NT) void prep_fused_kernel(const PrepImageDev* __re
       const uint8_t* col = inter + xx * C + c;
       float* o = oimg + ((size_t)c * S_h + yy) * S_w + xx;
       if (vec) {
-        int a0 = 1 << (PIL_PRECISION_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
+        int a0 = PIL_ROUND_HALF, a1 = a0, a2 = a0, a3 = a0;
         for (int t = 0; t < cnt; ++t) {
           const int kv = __builtin_amdgcn_readfirstlane(k[t]);
           const uint8_t* row = col + (size_t)clampi(rel + t, 0, nr - 1) * ocp;
@@ -159,14 +133,15 @@ __global__ __launch_bounds__(NT) void prep_fused_kernel(const PrepImageDev* __re
           mad24s(a2, row[2 * C], kv);
           mad24s(a3, row[3 * C], kv);
         }
-        *reinterpret_cast<float4*>(o) = make_float4(lut[clip8(a0)], lut[clip8(a1)], lut[clip8(a2)], lut[clip8(a3)]);
+        *reinterpret_cast<float4*>(o) =
+            make_float4(lut[pil_clip8(a0)], lut[pil_clip8(a1)], lut[pil_clip8(a2)], lut[pil_clip8(a3)]);
       } else {
-        int a0 = 1 << (PIL_PRECISION_BITS - 1);
+        int a0 = PIL_ROUND_HALF;
         for (int t = 0; t < cnt; ++t) {
           const int kv = __builtin_amdgcn_readfirstlane(k[t]);
           mad24s(a0, col[(size_t)clampi(rel + t, 0, nr - 1) * ocp], kv);
         }
-        *o = lut[clip8(a0)];
+        *o = lut[pil_clip8(a0)];
       }
     }
   }
@@ -180,11 +155,7 @@ __device__ __forceinline__ SplitTaps split_taps(const int32_t* bounds, const int
   const int lo = clampi(bounds[2 * o], 0, n_in - 1);
   return SplitTaps{base + lo * step, kk + (size_t)o * ksize, min(min(bounds[2 * o + 1], ksize), n_in - lo), step};
 }
-__device__ __forceinline__ uint8_t split_sum(const SplitTaps& t) {
-  int ss = 1 << (PIL_PRECISION_BITS - 1);
-  for (int i = 0; i < t.cnt; ++i) ss += (int)t.p[i * t.step] * t.k[i];
-  return clip8(ss);
-}
+__device__ __forceinline__ uint8_t split_sum(const SplitTaps& t) { return pil_tap_sum(t.p, t.step, t.k, t.cnt); }
 
 __global__ __launch_bounds__(NT) void prep_split_first_kernel(const PrepImageDev* __restrict__ images,
                                                               const PrepItem* __restrict__ items, int C, int S_w,
@@ -207,7 +178,7 @@ __global__ __launch_bounds__(NT) void prep_split_second_kernel(const PrepImageDe
                                                                const PrepItem* __restrict__ items, int C, int S_h, int S_w,
                                                                const uint8_t* __restrict__ tmp, float* __restrict__ out) {
   __shared__ float lut[256];
-  lut[threadIdx.x] = (float)((double)threadIdx.x * (1.0 / 255.0));
+  lut[threadIdx.x] = pil_u8_to_unit(threadIdx.x);
   __syncthreads();
   const PrepItem it = items[blockIdx.x];
   const PrepImageDev& im = images[it.img];
@@ -256,7 +227,7 @@ __global__ __launch_bounds__(NT) void prep_att_gather_kernel(const attwarp_prep_
                                                              const float* __restrict__ ws, int S_h, int S_w, int nblk,
                                                              float* __restrict__ out) {
   __shared__ float lut[256];
-  lut[threadIdx.x] = (float)((double)threadIdx.x * (1.0 / 255.0));
+  lut[threadIdx.x] = pil_u8_to_unit(threadIdx.x);
   const int b = blockIdx.x / nblk, y0 = (blockIdx.x - b * nblk) * ATT_ROWS, rows = min(ATT_ROWS, S_h - y0);
   const attwarp_prep_attention m = maps[b];
   float mx = -INFINITY;

@@ -22,6 +22,7 @@
 // the same bits, and the dense and fused paths -- the same kernel body with another value source -- give identical bits on
 // identical values.
 #include "common.hpp"
+#include "pil8.hpp"          // clampi
 #include "resize_axis.hpp"
 
 #include <algorithm>
@@ -48,7 +49,6 @@ struct Part {                  // one workgroup's partial (32 bytes)
 
 inline int tiles_of(int W) { return (W + TILE - 1) / TILE; }
 inline int bands_of(int H) { return (H + BAND - 1) / BAND; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // np.argmax's order: a NaN beats every number and the first NaN wins; otherwise the larger value, the first index on ties
 // (-0.0 == 0.0).  (v, i) takes (v2, i2) when that is the earlier element of this order; i < 0 marks "no candidate".

@@ -1,9 +1,10 @@
 // A3 (revise_mask, AGW/attention_extraction/llava.py:207-238) and A4 (ToPILImage x255 + PIL LANCZOS up-sampling of the
-// 24 x 24 mask, llava.py:192-196,243,253) as device BLOCKS: bodies shared by the stand-alone kernels of attn.hip and the
-// one-launch step of the main_batched chain (chain_step.hip), which runs them as block ranges of one grid.  LDS comes
-// from the caller so that the chain kernel can give every body the same pool.
+// 24 x 24 mask, llava.py:192-196,243,253) as device BLOCKS: bodies shared by the stand-alone kernels of attn.hip and
+// pil8.hip and the one-launch step of the main_batched chain (chain_step.hip), which runs them as block ranges of one
+// grid.  LDS comes from the caller so that the chain kernel can give every body the same pool.
 #pragma once
 #include "common.hpp"
+#include "pil8.hpp"
 
 namespace attwarp {
 
@@ -79,26 +80,7 @@ __device__ __forceinline__ void mask_postproc_block(const float* __restrict__ ma
   }
 }
 
-// ---- A4: Pillow's 8-bit separable resampler (ImagingResampleHorizontal/Vertical_8bpc) ----
-constexpr int PIL_PRECISION_BITS = 32 - 8 - 2;
-
-__device__ __forceinline__ uint8_t pil_clip8(int v) { return (uint8_t)min(max(v >> PIL_PRECISION_BITS, 0), 255); }
-// four clip8 results packed into a dword: gfx950's v_ashr_pk_u8_i32 shifts, saturates to [0,255] and packs two
-// values into the low 16 bits.  Used through the builtin with an explicit 16-bit mask: when the compiler forms the
-// instruction by itself from `clip8(a) | clip8(b) << 8 | clip8(c) << 16 | ...` it omits that mask (ROCm 7.2) and the
-// stale upper half of the destination register corrupts bytes 2 and 3.
-__device__ __forceinline__ uint32_t pil_clip8x4(int s0, int s1, int s2, int s3) {
-  const uint32_t lo = (uint32_t)(uint16_t)__builtin_amdgcn_ashr_pk_u8_i32(s0, s1, PIL_PRECISION_BITS);
-  const uint32_t hi = (uint32_t)(uint16_t)__builtin_amdgcn_ashr_pk_u8_i32(s2, s3, PIL_PRECISION_BITS);
-  return lo | (hi << 16);
-}
-
-// ToPILImage on a float tensor: pic.mul(255).byte()  (truncating cast)
-__device__ __forceinline__ uint8_t to_pil_u8(float v) {
-  const float s = fmul(v, 255.0f);
-  return (uint8_t)min(max((int)truncf(s), 0), 255);
-}
-
+// ---- A4: Pillow's 8-bit separable resampler (arithmetic: pil8.hpp) ----
 // Up-sampling form of the fused kernel (<= 8 taps on both axes: the 24 x 24 token grid blown up to the image size).
 // The cost is the vertical pass -- out_h * out_w outputs of <= 8 taps each -- so the decomposition is chosen for it:
 //   * a workgroup owns a COLUMN STRIP of 256 pixels (64 dwords, one per lane) and a chunk of the output rows; its
@@ -160,7 +142,7 @@ __device__ __forceinline__ void lanczos_strip_block(const LanczosStripArgs& a, i
     }
     for (int r = ys; r < ye; ++r) {
       const uint8_t* row = src + r * w;
-      int ss = 1 << (PIL_PRECISION_BITS - 1);
+      int ss = PIL_ROUND_HALF;
 #pragma unroll
       for (int x = 0; x < KS; ++x) ss += __mul24((int)row[toff[x]], kreg[x]);
       tile[r * SW + tid] = pil_clip8(ss);
@@ -190,7 +172,7 @@ __device__ __forceinline__ void lanczos_strip_block(const LanczosStripArgs& a, i
   // (UA: a narrow last strip may have no whole dword at all: nq == 0)
   uint8_t* __restrict__ orow = out_img + (size_t)r_beg * out_w + 4 * (UA ? min(q, nq) : min(q, nq - 1));
   const int tail_bytes = (UA && q == nq) ? (out_w & 3) : 0;
-  int round_half = 1 << (PIL_PRECISION_BITS - 1);
+  int round_half = PIL_ROUND_HALF;
   asm volatile("" : "+v"(round_half));                      // one register for the whole loop (not an inline constant: VOP3 takes none)
   for (int yy = r_beg; yy < r_end; ++yy) {
     const int ymin = ymin_c;
@@ -227,10 +209,10 @@ __device__ __forceinline__ void lanczos_strip_block(const LanczosStripArgs& a, i
       // is Pillow's allocation bound): the zero 7th and the padded 8th are skipped (wave uniform; adding 0 * pixel is exact)
       if (y == 6 && kv[6] == 0 && kv[7] == 0) break;
       if (y == 7 && kv[7] == 0) break;
-      asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s0) : "v"(win[y][0]), "s"(kv[y]));
-      asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s1) : "v"(win[y][1]), "s"(kv[y]));
-      asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s2) : "v"(win[y][2]), "s"(kv[y]));
-      asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s3) : "v"(win[y][3]), "s"(kv[y]));
+      mad24s(s0, win[y][0], kv[y]);
+      mad24s(s1, win[y][1], kv[y]);
+      mad24s(s2, win[y][2], kv[y]);
+      mad24s(s3, win[y][3], kv[y]);
     }
     // (written once by this kernel: nontemporal -- 24 -> 1024 B=256 109.9 -> 106.2 us, 24 -> 336 40.6 -> 36.6, and the
     // marginals kernel that reads the mask next is not slower for it)
@@ -242,6 +224,5 @@ __device__ __forceinline__ void lanczos_strip_block(const LanczosStripArgs& a, i
     orow += out_w;
   }
 }
-
 
 }  // namespace attwarp

@@ -19,6 +19,7 @@
 // OpenCV's arithmetic is restated from its published source; OpenCV is absent where this is built, so parity with it is
 // unpinned (tests/test_sdwarp_vs_opencv.py reports the distance where cv2 imports).  Bit-exact with tests/sdwarp_ref.py.
 #include "common.hpp"
+#include "pil8.hpp"          // clampi
 #include "resize_axis.hpp"
 
 #include <algorithm>
@@ -173,7 +174,6 @@ typedef attwarp_cubic_map CMap;
 
 inline int ctiles_of(int W) { return (W + TILE - 1) / TILE; }
 inline int cbands_of(int H) { return (H + BAND - 1) / BAND; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // OpenCV's interpolateCubic (imgproc/src/resize.cpp), float32, one rounding per operation (host code is built with
 // -ffp-contract=off as well)

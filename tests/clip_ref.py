@@ -4,7 +4,7 @@ oracle.warp_oracle is read here, so an error those two share cannot hide.  tests
 to oracle.clip_preprocess (which the goldens tie to the HF processor) on every RGB case below.
 
 Also here: the seeded input patterns of the sweep, route() -- the launcher's choice between the LDS-staged kernels
-(csrc/clip.hip) and the one-thread-per-output pair (csrc/attn.hip) restated in Python, so that every case can assert that
+and the one-thread-per-output pair (both csrc/clip.hip) restated in Python, so that every case can assert that
 it reaches the path it is named for -- and the case lists that tests/test_clip_sweep_gpu.py runs."""
 import math
 from collections import namedtuple

@@ -1,6 +1,6 @@
 """GPU sweep of pipeline.clip_preprocess against Pillow itself (tests/clip_ref.py) on every route its launcher takes: the
 LDS-staged kernels of csrc/clip.hip with 8 and with 16 coefficient registers, and the one-thread-per-output pair of
-csrc/attn.hip.  tests/test_gpu_parity.py pins the operating point (500 x 500 -> 336, RGB, noise) to the HF processor; here
+the same file.  tests/test_gpu_parity.py pins the operating point (500 x 500 -> 336, RGB, noise) to the HF processor; here
 are the tap counts where the variant changes, up-scaling and one-pixel sources, C = 1, 2, 4, outputs wider than one pass of
 either staged kernel, every rows-per-workgroup class of the LDS budget, and source pointers off a 4-byte boundary.
 

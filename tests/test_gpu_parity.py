@@ -517,6 +517,34 @@ def test_mask_upsample_lanczos_bit_exact(dev, golden, wh, variant):
         assert np.array_equal(got_f, ref) and np.array_equal(got_u, ref)
 
 
+@pytest.fixture(scope="module")
+def shrink_masks():
+    """Two random uint8 24 x 24 masks and float masks that ToPILImage truncates to exactly them."""
+    u8 = np.random.default_rng(24).integers(0, 256, (2, 24, 24), dtype=np.uint8)
+    f32 = np.minimum((u8.astype(np.float32) + np.float32(0.5)) / np.float32(255.0), np.float32(1.0))
+    assert np.array_equal(O.mask_to_u8(f32), u8)
+    return u8, f32
+
+
+# masks that shrink vertically while they grow horizontally: more than 8 vertical taps, which the column-strip kernel
+# does not take.  (W, H) -> vertical taps -> route: (48, 17) 11, (28, 23) 9 and (100, 9) 17: row-block fused kernel;
+# (64, 5) 31: that kernel's limit of 32 taps; (64, 4) 37: lanczos_h + lanczos_v4; (50, 5) 31, width not a multiple of
+# 4: lanczos_h + lanczos_v
+@pytest.mark.parametrize("wh", [(48, 17), (28, 23), (64, 5), (64, 4), (50, 5), (100, 9)])
+def test_mask_upsample_lanczos_shrinking_axis_bit_exact(dev, shrink_masks, wh):
+    from attwarp_amd import attention_extraction as ae
+    u8, f32 = shrink_masks
+    w, h = wh
+    ref = np.stack([O.lanczos_resize_u8(m, w, h) for m in u8])
+    for variant in (-1, 1, 2):      # automatic / two-kernel form / row-block fused kernel: equal to the oracle, so to each other
+        with _lib.debug_override(lanczos_variant=variant):
+            got_f = N(ae.upsample_mask_lanczos(T(f32, dev), (w, h)))
+            got_u = N(ae.upsample_mask_lanczos(T(u8, dev), (w, h)))
+        assert got_f.shape == ref.shape and got_u.shape == ref.shape, variant
+        assert np.array_equal(got_u, ref), variant
+        assert np.array_equal(got_f, ref), variant
+
+
 def test_blend_mask_surface(dev, golden):
     from PIL import Image
     from attwarp_amd import attention_extraction as ae
