@@ -148,6 +148,10 @@ SIGNATURES = {
     "attwarp_pil_nearest_index": (c_int, [c_int, c_int, c_void_p]),
     "attwarp_prep_attention_workspace_bytes": (c_size_t, [c_int]),
     "attwarp_prep_attention_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # the first visit to CLIP: ragged batches, pad-to-square included (clip_ragged.hip)
+    "attwarp_clip_images_table_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "attwarp_clip_images_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t]),
+    "attwarp_clip_images_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     # the trainer's optimiser step (optim.hip)
     "attwarp_adamw_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "attwarp_adamw_step": (c_int, [c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -238,6 +242,23 @@ class PrepHeader(ctypes.Structure):
                 ("S_w", ctypes.c_int32), ("n_fused_images", ctypes.c_int32), ("n_fused_items", ctypes.c_int32),
                 ("n_split_images", ctypes.c_int32), ("n_h_items", ctypes.c_int32), ("n_v_items", ctypes.c_int32),
                 ("ks", ctypes.c_int32), ("n_wide_items", ctypes.c_int32),
+                ("table_bytes", ctypes.c_uint64), ("tmp_bytes", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64),
+                ("off_images", ctypes.c_uint64), ("off_items", ctypes.c_uint64)]
+
+
+class ClipImage(ctypes.Structure):
+    """attwarp_clip_image (include/attwarp.h): one image of a ragged CLIP batch, device pointers in a host array."""
+    _fields_ = [("image", c_void_p), ("bounds_x", c_void_p), ("kk_x", c_void_p), ("bounds_y", c_void_p), ("kk_y", c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("H", "W", "ksize_x", "ksize_y", "pad_x", "pad_y", "canvas_w", "canvas_h", "nw", "nh",
+                                              "left", "top", "vertical_first", "reserved")]
+
+
+class ClipHeader(ctypes.Structure):
+    """attwarp_clip_header: the first bytes of a table written by attwarp_clip_images_plan."""
+    _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("C", ctypes.c_int32), ("size", ctypes.c_int32),
+                ("n_fused_images", ctypes.c_int32), ("n_fused_items", ctypes.c_int32), ("n_wide_items", ctypes.c_int32),
+                ("n_split_images", ctypes.c_int32), ("n_h_items", ctypes.c_int32), ("n_v_items", ctypes.c_int32),
+                ("ks", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("table_bytes", ctypes.c_uint64), ("tmp_bytes", ctypes.c_uint64), ("lds_bytes", ctypes.c_uint64),
                 ("off_images", ctypes.c_uint64), ("off_items", ctypes.c_uint64)]
 

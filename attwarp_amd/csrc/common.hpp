@@ -182,6 +182,7 @@ enum TuneKey {
   TUNE_TRACE_LO,            // block timeline of the one-launch steps (tools/gantt.py): bits 0..23 and 24..47 of the address of a
   TUNE_TRACE_HI,            //   device buffer of TRACE_WORDS x uint64 per block (layout below)
   TUNE_PREP_VARIANT,        // 1: attwarp_prep_images_plan sends every image down the two-launch route (uint8 intermediate in memory)
+  TUNE_CLIP_RAGGED_VARIANT,  // 1: attwarp_clip_images_plan sends every image down the two-launch route (uint8 intermediate in memory)
   TUNE_COUNT
 };
 #ifdef ATTWARP_TUNING

@@ -1,8 +1,8 @@
 // Pillow's 8-bit two-pass resampler (ImagingResampleHorizontal/Vertical_8bpc, Resample.c) as device arithmetic: 22-bit
 // fixed-point coefficients, sum = 2^21 + sum(pixel * k), >> 22, clip to a byte, uint8 between the passes.  Every kernel
 // that has to be bit-identical to Image.resize takes its pieces from here: the LANCZOS mask up-sampling (pil8.hip,
-// mask_blocks.hpp), the CLIP preprocess (clip.hip), the trainer's data preparation (dataprep.hip) and, through the strip
-// block, the two chains.  The coefficient tables come from attwarp_pil_coeffs_8bpc (pil8.hip).
+// mask_blocks.hpp), the CLIP preprocess (clip.hip, clip_ragged.hip), the trainer's data preparation (dataprep.hip) and,
+// through the strip block, the two chains.  The coefficient tables come from attwarp_pil_coeffs_8bpc (pil8.hip).
 #pragma once
 #include "common.hpp"
 

@@ -269,6 +269,204 @@ def clip_preprocess(images_u8: torch.Tensor, size: int = 336, dtype: torch.dtype
     return out
 
 
+_CLIP_IMAGE_DTYPE = np.dtype(_lib.ClipImage)            # attwarp_clip_image as a record array: one column per field
+# the per-image record inside a planned table (clip_ragged.hip: ClipImageDev): the caller's record + the launcher's choices
+_CLIP_RECORD_DTYPE = np.dtype(_CLIP_IMAGE_DTYPE.descr + [("tmp_off", "<i8"), ("fused", "<i4"), ("ny", "<i4"), ("rb", "<i4"),
+                                                         ("nr_cap", "<i4"), ("window", "<i4"), ("reserved2", "<i4")])
+
+
+def _clip_tables(n_in: int, n_out: int, device: torch.device):
+    """Pillow's 8-bit BICUBIC tables n_in -> n_out on the device, at their own tap count (identity tables for
+    n_in == n_out): (bounds int32 [n_out,2], kk int32 [n_out,ksize], ksize)."""
+    key = ("clip_bicubic", n_in, n_out, str(device))
+    t = _tables._DEV_CACHE.get(key)
+    if t is None:
+        bounds, kk, ksize = _tables._lanczos_tables_host(n_in, n_out, "bicubic")
+        kk = np.ascontiguousarray(kk[:, :ksize])
+        t = _tables._cache_put(key, (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize))
+    return t
+
+
+def clip_geometry(H: int, W: int, size: int, pad_to_square: bool) -> dict:
+    """The geometry columns of one image's attwarp_clip_image record.  ``pad_to_square``: LLaVA's expand2square canvas of
+    side max(H, W) with the image centred on it (offset ``(n - short) // 2``), resized to size x size.  Otherwise the HF
+    processor's own route: shorter edge to ``size``, longer edge to ``int(size * long / short)``, centre crop; Pillow runs
+    the vertical pass first on a source more than 100 times as high as wide that it shrinks vertically."""
+    if pad_to_square:
+        n = max(H, W)
+        return dict(canvas_w=n, canvas_h=n, pad_x=(n - W) // 2, pad_y=(n - H) // 2, nw=size, nh=size, left=0, top=0,
+                    vertical_first=0)
+    short, long_ = (H, W) if H <= W else (W, H)
+    new_long = int(size * long_ / short)
+    nh, nw = (size, new_long) if H <= W else (new_long, size)
+    return dict(canvas_w=W, canvas_h=H, pad_x=0, pad_y=0, nw=nw, nh=nh, left=(nw - size) // 2, top=(nh - size) // 2,
+                vertical_first=int(H > 100 * W and nh < H))
+
+
+class ClipBatch:
+    """One batch of uint8 [H_i,W_i,C] GPU images planned for ``attwarp_clip_images_u8``: the coefficient
+    tables (cached per distinct ``(n_in, n_out)``), the record table (host copy + device copy, uploaded through the pinned
+    staging pool), the uint8 intermediate of the images that take the two-launch route and the output [B,C,size,size].
+    ``run()`` enqueues the launch(es) on the current stream -- any stream: it first waits for the event recorded behind the
+    uploads of the constructor -- and may be captured in a graph; a capture cannot wait for that event, so it must begin
+    after the constructing stream's work (``capture_step`` does that).  The images are referenced, not copied: keep them
+    alive and unchanged until the launch has run, and let the stream that wrote them be ordered before the one ``run()`` is
+    called on.  The padded canvas of ``pad_to_square`` is never built: the kernels read the background where a tap leaves
+    the image."""
+
+    def __init__(self, images, size: int = 336, dtype: torch.dtype = torch.float16, mean=OPENAI_CLIP_MEAN,
+                 std=OPENAI_CLIP_STD, pad_to_square: bool = True, background=None, out: Optional[torch.Tensor] = None):
+        size = int(size)
+        if size < 1:
+            raise ValueError(f"ClipBatch: size must be positive (got {size})")
+        if dtype not in (torch.float32, torch.float16):
+            raise TypeError("ClipBatch: dtype must be float32 or float16")
+        images = list(images)
+        if not images:
+            raise ValueError("ClipBatch: empty batch")
+        for im in images:
+            if not isinstance(im, torch.Tensor):
+                raise TypeError("ClipBatch: uint8 [H,W,C] GPU tensors expected (clip_preprocess_ragged uploads host images)")
+        dev = require_gpu(*images)
+        for im in images:
+            if im.dtype != torch.uint8:
+                raise TypeError(f"ClipBatch: images must be uint8 (got {im.dtype})")
+            if im.dim() != 3:
+                raise ValueError(f"ClipBatch: images must be [H,W,C] (got {tuple(im.shape)})")
+        C = int(images[0].shape[2])
+        if C not in (1, 3) or any(int(im.shape[2]) != C for im in images):
+            raise ValueError("ClipBatch: every image must have the same channel count, 1 or 3")
+        if any(im.numel() == 0 for im in images):
+            raise ValueError("ClipBatch: empty image")
+        if len(mean) < C or len(std) < C:
+            raise ValueError(f"ClipBatch: mean and std need {C} channel values")
+        if background is None:
+            background = tuple(int(float(m) * 255) for m in mean[:C])
+        if len(background) < C or any(not 0 <= int(v) <= 255 for v in background[:C]):
+            raise ValueError(f"ClipBatch: background needs {C} channel values in 0 .. 255")
+        self.images = [im if im.is_contiguous() else im.contiguous() for im in images]
+        self.B, self.C, self.size, self.dtype, self._dev = len(images), C, size, dtype, dev
+        self.pad_to_square = bool(pad_to_square)
+        rec = np.zeros(self.B, dtype=_CLIP_IMAGE_DTYPE)
+        geo = [clip_geometry(int(im.shape[0]), int(im.shape[1]), size, self.pad_to_square) for im in self.images]
+        tx = [_clip_tables(g["canvas_w"], g["nw"], dev) for g in geo]
+        ty = [_clip_tables(g["canvas_h"], g["nh"], dev) for g in geo]
+        rec["image"] = [im.data_ptr() for im in self.images]
+        rec["H"] = [int(im.shape[0]) for im in self.images]
+        rec["W"] = [int(im.shape[1]) for im in self.images]
+        for k in geo[0]:
+            rec[k] = [g[k] for g in geo]
+        rec["bounds_x"] = [t[0].data_ptr() for t in tx]; rec["kk_x"] = [t[1].data_ptr() for t in tx]
+        rec["bounds_y"] = [t[0].data_ptr() for t in ty]; rec["kk_y"] = [t[1].data_ptr() for t in ty]
+        rec["ksize_x"] = [t[2] for t in tx]; rec["ksize_y"] = [t[2] for t in ty]
+        self._keep = tx + ty
+        lib = _lib.load()
+        rp = ctypes.c_void_p(rec.ctypes.data)
+        nbytes = lib.attwarp_clip_images_table_bytes(rp, self.B, C, size)
+        if nbytes == 0:
+            raise _lib.AttWarpError("attwarp_clip_images_table_bytes: " + lib.attwarp_last_error().decode("utf-8", "replace"))
+        self.table_host = np.empty(nbytes, dtype=np.uint8)
+        call("attwarp_clip_images_plan", rp, self.B, C, size, self.table_host.ctypes.data, nbytes)
+        self.header = _lib.ClipHeader.from_address(self.table_host.ctypes.data)
+        self.table_dev = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            _upload(self.table_host, self.table_dev)
+        self.tmp = torch.empty(int(self.header.tmp_bytes), device=dev, dtype=torch.uint8) if self.header.tmp_bytes else None
+        if out is None:
+            out = torch.empty(self.B, C, size, size, device=dev, dtype=dtype)
+        elif tuple(out.shape) != (self.B, C, size, size) or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+            raise ValueError("ClipBatch: out must be a dense (B,C,size,size) tensor of `dtype` on the images' device")
+        self.out = out
+        self._mean = (ctypes.c_float * C)(*[float(v) for v in mean[:C]])
+        self._std = (ctypes.c_float * C)(*[float(v) for v in std[:C]])
+        self._bg = (ctypes.c_uint8 * C)(*[int(v) for v in background[:C]])
+        self._ready = torch.cuda.Event()
+        self._ready.record(torch.cuda.current_stream(dev))
+
+    @property
+    def plan(self) -> np.ndarray:
+        """What the launcher chose per image (structured array): the geometry columns, ``fused`` (1: the one-launch kernel),
+        its register ``window`` (8 or 16 taps), band height ``ny``, staged canvas rows per round ``rb`` and LDS rows
+        ``nr_cap``; ``fused`` 0, ``window`` 0 and ``tmp_off`` on the two-launch route."""
+        off = int(self.header.off_images)
+        return self.table_host[off:off + self.B * _CLIP_RECORD_DTYPE.itemsize].view(_CLIP_RECORD_DTYPE)
+
+    @property
+    def algorithmic_bytes(self) -> int:
+        """Sources read once, the batch written once."""
+        return sum(im.numel() for im in self.images) + self.out.numel() * self.out.element_size()
+
+    def run(self) -> torch.Tensor:
+        with torch.cuda.device(self._dev):
+            if not torch.cuda.is_current_stream_capturing():        # (a capture begins after the constructing stream's work)
+                torch.cuda.current_stream(self._dev).wait_event(self._ready)
+            call("attwarp_clip_images_u8", self.table_host.ctypes.data, ptr(self.table_dev),
+                 ctypes.cast(self._mean, ctypes.c_void_p), ctypes.cast(self._std, ctypes.c_void_p),
+                 ctypes.cast(self._bg, ctypes.c_void_p), ptr(self.tmp), ptr(self.out),
+                 _lib.F32 if self.dtype == torch.float32 else _lib.F16, stream_ptr(self._dev))
+        return self.out
+
+
+def clip_preprocess_ragged(images, size: int = 336, dtype: torch.dtype = torch.float16, mean=OPENAI_CLIP_MEAN,
+                           std=OPENAI_CLIP_STD, pad_to_square: bool = True, background=None) -> torch.Tensor:
+    """A batch of images of their own sizes -> CLIP-ready [B,C,size,size] on the GPU, the whole batch per call: what
+    LLaVA-1.5's ``process_images`` computes on the CPU one PIL image at a time (functions.py:262-271), bit for bit.
+    ``images``: uint8 [H_i,W_i,C] GPU tensors (for instance the views of :func:`upload_images`), or, all of them, host
+    images (PIL or numpy), which go through ``upload_images`` first (one transfer).  ``pad_to_square=True`` is
+    ``image_aspect_ratio == "pad"`` (``background`` defaults to ``int(mean * 255)`` per channel); ``False`` the HF processor's
+    shorter-edge resize + centre crop that :func:`clip_preprocess` computes for a dense batch."""
+    images = list(images)
+    if not images:
+        raise ValueError("clip_preprocess_ragged: empty batch")
+    if not any(isinstance(im, torch.Tensor) for im in images):
+        images = upload_images(images)
+    return ClipBatch(images, size, dtype, mean, std, pad_to_square, background).run()
+
+
+def _field(obj, key):
+    """``obj[key]`` or ``obj.key`` (HF size dictionaries come as either), None when absent."""
+    if obj is None:
+        return None
+    try:
+        return obj[key]
+    except (KeyError, TypeError, IndexError, AttributeError):
+        return getattr(obj, key, None)
+
+
+def process_images(images, image_processor, model_cfg, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Duck-typed drop-in for LLaVA's ``process_images(images, image_processor, model_cfg)`` (the call at
+    AGW/attention_extraction/functions.py:270) on the GPU: ``image_mean``, ``image_std``, the shortest-edge / crop size are
+    read from ``image_processor``, ``image_aspect_ratio`` from ``model_cfg``.  ``"pad"`` pads to a square of
+    ``int(mean * 255)`` first; an absent or any other plain mode is the processor alone (resize + centre crop).  Returns
+    float32 [B,3,size,size] as LLaVA's does (the caller casts; ``dtype=torch.float16`` gives the cast result directly)."""
+    mode = getattr(model_cfg, "image_aspect_ratio", None)
+    if isinstance(mode, str) and mode.startswith("anyres"):
+        raise NotImplementedError("process_images: image_aspect_ratio == 'anyres' (multi-patch inputs) is not implemented")
+    size = getattr(image_processor, "size", None)
+    short = size if isinstance(size, int) else _field(size, "shortest_edge")
+    if short is None and _field(size, "height") is not None and _field(size, "height") == _field(size, "width"):
+        short = _field(size, "height") if mode == "pad" else None          # a fixed (h, w) resize is another arithmetic unless the source is square
+    crop = getattr(image_processor, "crop_size", None)
+    ch, cw = (crop, crop) if isinstance(crop, int) else (_field(crop, "height"), _field(crop, "width"))
+    if ch is None:
+        ch = cw = short
+    if short is None or int(ch) != int(short) or int(cw) != int(short):
+        raise NotImplementedError(f"process_images: needs a shortest-edge resize and a square centre crop of one size "
+                                  f"(got size={size}, crop_size={crop})")
+    for flag in ("do_resize", "do_center_crop", "do_rescale", "do_normalize"):
+        if getattr(image_processor, flag, True) is False:
+            raise NotImplementedError(f"process_images: {flag}=False is not implemented")
+    resample = getattr(image_processor, "resample", 3)
+    if resample is not None and int(resample) != 3:
+        raise NotImplementedError(f"process_images: resample must be PIL BICUBIC (3), got {resample}")
+    factor = getattr(image_processor, "rescale_factor", 1 / 255)
+    if factor is not None and float(factor) != 1 / 255:
+        raise NotImplementedError(f"process_images: rescale_factor must be 1/255, got {factor}")
+    mean = tuple(float(v) for v in image_processor.image_mean)
+    std = tuple(float(v) for v in image_processor.image_std)
+    return clip_preprocess_ragged(images, int(short), dtype, mean, std, pad_to_square=(mode == "pad"))
+
+
 def random_clip_vision_tower(device, dtype: torch.dtype = torch.float16, seed: int = 0):
     """The architecture of LLaVA-1.5's vision tower (openai/clip-vit-large-patch14-336: ViT-L/14 at 336 x 336, 24 layers,
     hidden 1024, 16 heads, MLP 4096) from ``transformers`` with SEEDED RANDOM weights -- the checkpoint, the ``llava``

@@ -679,6 +679,59 @@ ATTWARP_API size_t attwarp_prep_attention_workspace_bytes(int B);
 ATTWARP_API int attwarp_prep_attention_f32(const attwarp_prep_attention* maps_dev, int B, int S_h, int S_w, void* ws, float* out,
                                void* stream);
 
+/* ---- the first visit to CLIP (AGW/attention_extraction/functions.py:262-271: LLaVA's process_images on a batch of images
+ * of their own sizes): per image expand2square (image_aspect_ratio == "pad") or nothing, the HF CLIPImageProcessor's PIL
+ * BICUBIC resize, centre crop to size x size, float32(float64(u8) * (1/255)), (x - mean) / std in float32, channels first:
+ * out [B,C,size,size] float32 or float16 (the float32 value rounded once), bit for bit what Pillow + the processor compute.
+ *
+ * The table pattern of attwarp_prep_images_*:
+ *   1. fill attwarp_clip_image[B] (HOST array of DEVICE pointers).  The source Pillow resizes is a canvas_w x canvas_h
+ *      canvas of the background colour with the image at (pad_x, pad_y) -- the canvas is never stored, taps outside the
+ *      image read the background -- or, without padding, the image itself (canvas == image, pads 0).  Tables:
+ *      attwarp_pil_coeffs_8bpc(canvas_w, nw, ATTWARP_PIL_BICUBIC, ...) and (canvas_h, nh, ...), identity tables on an axis
+ *      that keeps its size (Pillow skips that pass); (left, top) is the crop's origin in the nh x nw resized image;
+ *   2. attwarp_clip_images_table_bytes(...) -> size; attwarp_clip_images_plan(...) writes header, records and the work
+ *      items (image, band of output rows) into HOST memory; header.tmp_bytes is the uint8 intermediate the caller provides;
+ *   3. copy table_bytes to the device (8-byte aligned); 4. attwarp_clip_images_u8(host copy, device copy, ...).
+ * An image runs on the one-launch kernel (both passes, the uint8 intermediate in LDS) when its horizontal taps fit the
+ * 16-tap register window (canvas_w <= 3.5 nw: 1176 -> 336), a band of 8 output rows fits the LDS and the horizontal pass
+ * comes first; images with 9 .. 16 taps run as a second launch of that kernel (n_wide_items).  The others (and every image
+ * in the tuning library under clip_ragged_variant = 1) take two launches with the intermediate in `tmp`.  Both routes
+ * compute the same bytes.  The LDS rows of a band are bounded on the host from canvas_h, nh and ksize_y, which holds for
+ * the tables of attwarp_pil_coeffs_8bpc; a band whose tables reach further is written as NaN, never computed from clamped
+ * taps.
+ * Limits (ATTWARP_E_UNSUPPORTED from the plan, with a message): C 1 or 3, canvas_w, canvas_h <= 8192, size <= 4096,
+ * nw, nh <= 2^20, B <= 2^20.  A vertical-first image cannot be padded (a padded canvas is square). */
+typedef struct attwarp_clip_image {
+  const uint8_t* image;                            /* device: [H,W,C] uint8 interleaved, any byte address */
+  const int32_t* bounds_x; const int32_t* kk_x;    /* device: canvas_w -> nw: int32 [nw,2], int32 [nw,ksize_x] */
+  const int32_t* bounds_y; const int32_t* kk_y;    /* device: canvas_h -> nh: int32 [nh,2], int32 [nh,ksize_y] */
+  int32_t H, W, ksize_x, ksize_y;
+  int32_t pad_x, pad_y;                            /* where the image's first pixel lies on the canvas */
+  int32_t canvas_w, canvas_h;
+  int32_t nw, nh;                                  /* size the canvas is resized to */
+  int32_t left, top;                               /* origin of the size x size crop in the resized image */
+  int32_t vertical_first, reserved;                /* 1: vertical pass first (what PIL.Image.resize does when H > 100 * W and
+                                                      nh < H); such an image takes the two-launch route */
+} attwarp_clip_image;
+typedef struct attwarp_clip_header {               /* first bytes of a table written by attwarp_clip_images_plan */
+  uint32_t magic;
+  int32_t B, C, size;
+  int32_t n_fused_images, n_fused_items;           /* images / (image, band) items of the one-launch kernel */
+  int32_t n_wide_items;                            /* the last n_wide_items of n_fused_items: images with 9 .. 16 horizontal taps */
+  int32_t n_split_images, n_h_items, n_v_items;    /* the two-launch route: its images, row-block items of either pass */
+  int32_t ks, reserved;                            /* widest register window of the batch: 8 or 16 taps */
+  uint64_t table_bytes, tmp_bytes, lds_bytes;
+  uint64_t off_images, off_items;
+} attwarp_clip_header;
+ATTWARP_API size_t attwarp_clip_images_table_bytes(const attwarp_clip_image* images, int B, int C, int size);
+ATTWARP_API int attwarp_clip_images_plan(const attwarp_clip_image* images, int B, int C, int size, void* table,
+                             size_t table_bytes);
+/* mean, stdv: HOST, C floats each; background: HOST, C bytes (read only where an image is padded); tmp: header.tmp_bytes
+ * bytes (may be NULL when that is 0); out: 16-byte aligned; out_dtype ATTWARP_F32 or ATTWARP_F16. */
+ATTWARP_API int attwarp_clip_images_u8(const void* table_host, const void* table_dev, const float* mean, const float* stdv,
+                           const uint8_t* background, uint8_t* tmp, void* out, int out_dtype, void* stream);
+
 /* ---- the trainer's optimiser step (MN/trainer.py:259-264): GradScaler unscale, global L2 gradient norm, clip and
  * torch.optim.AdamW (decoupled weight decay, no amsgrad, no maximize) in two kernels per group of 64 tensors.
  *   g = g_raw * inv_scale, inv_scale = float32(1 / float64(*grad_scale)) (1 when grad_scale is NULL);
