@@ -161,6 +161,10 @@ SIGNATURES = {
     "attwarp_png_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_png_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
     "attwarp_png_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # PNG files decoded on the device (pngdec.hip)
+    "attwarp_pngdec_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "attwarp_pngdec_plan": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t]),
+    "attwarp_pngdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),
@@ -174,6 +178,13 @@ RGB, BGR = 0, 1
 # attwarp_png_*: filters and limits (ATTWARP_PNG_* of include/attwarp.h)
 PNG_FILTER_IDS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
 PNG_SEG_BYTES, PNG_MAX_ROW_BYTES, PNG_SEG_MAX_ROWS, PNG_FILE_OVERHEAD = 24576, 24576, 1024, 68
+# attwarp_pngdec_*: modes, limits and status codes (ATTWARP_PNGDEC_* of include/attwarp.h)
+PNGDEC_MODE_IDS = {"RGB": 0, "L": 1, "keep": 2}
+PNGDEC_MAX_UNITS, PNGDEC_MAX_ROW_BYTES = 256, 49152
+PNGDEC_STATUS_NAMES = ("OK", "E_CRC", "E_ZLIB_HEADER", "E_TRUNCATED", "E_BLOCK_TYPE", "E_STORED_LEN", "E_CODE_LENGTHS", "E_SYMBOL",
+                       "E_DISTANCE", "E_OVERFLOW", "E_UNDERFLOW", "E_ADLER", "E_FILTER")
+(PNGDEC_OK, PNGDEC_E_CRC, PNGDEC_E_ZLIB_HEADER, PNGDEC_E_TRUNCATED, PNGDEC_E_BLOCK_TYPE, PNGDEC_E_STORED_LEN, PNGDEC_E_CODE_LENGTHS,
+ PNGDEC_E_SYMBOL, PNGDEC_E_DISTANCE, PNGDEC_E_OVERFLOW, PNGDEC_E_UNDERFLOW, PNGDEC_E_ADLER, PNGDEC_E_FILTER) = range(13)
 # attwarp_panel_grid: limits, flags and source kinds (ATTWARP_PANEL_* of include/attwarp.h)
 PANEL_MAX_SRC, PANEL_MAX_HEAT, PANEL_FOR_PNG = 8, 4096, 1
 PANEL_F32, PANEL_U8, PANEL_HEAT = 0, 1, 2
@@ -208,6 +219,27 @@ class PngImage(ctypes.Structure):
     """attwarp_png_image: one image of an attwarp_png_plan call, device pointer in a host array."""
     _fields_ = [("src", c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
                 ("pitch", ctypes.c_int32), ("order", ctypes.c_int32), ("filter", ctypes.c_int32)]
+
+
+class PngDecImage(ctypes.Structure):
+    """attwarp_pngdec_image: one file of an attwarp_pngdec_plan call, offsets into the packed stream buffer."""
+    _fields_ = [("stream_off", ctypes.c_uint64), ("stream_len", ctypes.c_uint64), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("color_type", ctypes.c_int32), ("mode", ctypes.c_int32), ("order", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class PngDecChunk(ctypes.Structure):
+    """attwarp_pngdec_chunk: one IDAT chunk's payload in the packed stream buffer and the CRC-32 its file states."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("image", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class PngDecHeader(ctypes.Structure):
+    """attwarp_pngdec_header: the first bytes of a table written by attwarp_pngdec_plan."""
+    _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("nchunks", ctypes.c_int32), ("check_crc", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("table_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
+                ("stream_bytes", ctypes.c_uint64), ("off_images", ctypes.c_uint64), ("off_chunks", ctypes.c_uint64),
+                ("crc_pow8", ctypes.c_uint32 * 32), ("idat_crc", ctypes.c_uint32), ("reserved2", ctypes.c_uint32)]
 
 
 class PanelSource(ctypes.Structure):

@@ -183,6 +183,7 @@ enum TuneKey {
   TUNE_TRACE_HI,            //   device buffer of TRACE_WORDS x uint64 per block (layout below)
   TUNE_PREP_VARIANT,        // 1: attwarp_prep_images_plan sends every image down the two-launch route (uint8 intermediate in memory)
   TUNE_CLIP_RAGGED_VARIANT,  // 1: attwarp_clip_images_plan sends every image down the two-launch route (uint8 intermediate in memory)
+  TUNE_PNGDEC_ROUTE,         // 1: attwarp_pngdec_decode sends every image down the serial route (one wave from the stream's start)
   TUNE_COUNT
 };
 #ifdef ATTWARP_TUNING

@@ -1327,11 +1327,18 @@ def _upload(host: "np.ndarray", dst: torch.Tensor):
     (one pool per device: a slot's event is recorded on, and queried against, the stream that carries its copy).
     Refuses to run inside a stream capture: the copy would become a graph node and be re-executed on every replay from a
     staging buffer that has long been reused."""
+    def fill(buf):
+        buf[:] = host
+    _upload_filled(host.size, fill, dst)
+
+
+def _upload_filled(n: int, fill, dst: torch.Tensor):
+    """:func:`_upload` for bytes that are assembled in place: ``fill(buf)`` writes the n bytes straight into the pinned
+    staging slot (a uint8 numpy view), so data gathered from many sources crosses host memory once."""
     dev = dst.device
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("attwarp_amd: a host-to-device table upload inside a stream capture (build RaggedBatch objects / call "
                            "upload_images before capturing; a captured copy would replay from a reused staging buffer)")
-    n = host.size
     with torch.cuda.device(dev):
         with _STAGING_LOCK:
             pool = _STAGING.setdefault(dev.index, [])
@@ -1348,7 +1355,7 @@ def _upload(host: "np.ndarray", dst: torch.Tensor):
                 pool.append(slot)
             slot[2] = False                       # taken: nobody else may pick it until its copy has been enqueued and recorded
         try:
-            slot[0][:n].numpy()[:] = host
+            fill(slot[0][:n].numpy())
             dst.copy_(slot[0][:n], non_blocking=True)
             slot[1].record(torch.cuda.current_stream(dev))
         finally:
@@ -1461,6 +1468,15 @@ def upload_images(images, device=None):
         out.append(flat[off:off + n].view(*a.shape))
         off += n
     return out
+
+
+def upload_png_files(files_or_paths, device=None):
+    """:func:`upload_images` for a batch still in its PNG files (bytes-like or paths; the warped, overlay and attention-map
+    files the drivers wrote, or anyone's 8-bit non-interlaced PNG): the COMPRESSED bytes go up in one transfer and are decoded
+    on the GPU (attwarp_amd.png.decode_png) -> list of uint8 [H_i,W_i,3] RGB GPU tensors, views into one packed buffer, as
+    ``Image.open(f).convert("RGB")`` gives them.  OSError for a broken file, ValueError for an unsupported one."""
+    from .png import decode_png
+    return decode_png(files_or_paths, "RGB", "rgb", device)
 
 
 def ragged_chain_launch(R: Optional[RaggedBatch] = None, F: Optional[RaggedBatch] = None, P: Optional[RaggedBatch] = None,

@@ -1,4 +1,8 @@
-"""PNG files of a whole ragged batch, encoded on the GPU (csrc/png.hip): what the reference's drivers
+"""PNG files of a whole ragged batch, encoded and decoded on the GPU.  Decoding (csrc/pngdec.hip) is the
+reading half: what the reference does per file with ``Image.open(...).convert(...)`` (evaluate_accuracy.py:157-158,
+MN/dataloader.py:171-382); only compressed bytes cross to the device.  8-bit grey, grey + alpha, RGB, RGBA, non-interlaced.
+
+Encoding: PNG files of a whole ragged batch, encoded on the GPU (csrc/png.hip): what the reference's drivers
 write per sample with ``cv2.imwrite`` (main_batched.py:243-303, new_method.py:405-506).  Only compressed bytes cross to
 the host.  8-bit grey or RGB, non-interlaced; OpenCV's writer defaults (SUB filter, distance-1 matches) are the defaults
 here.  The files decode to the source pixels; their bytes are this encoder's own (tests/png_ref.py restates them).
@@ -6,6 +10,9 @@ here.  The files decode to the source pixels; their bytes are this encoder's own
 from __future__ import annotations
 
 import ctypes
+import os
+import struct
+import zlib
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -150,3 +157,208 @@ def write_png(paths, images, filter="sub", order="rgb") -> None:
     for p, f in zip(paths, files):
         with open(p, "wb") as fh:
             fh.write(f)
+
+
+# ---- decoding ---------------------------------------------------------------------------------------------------------------
+PNGDEC_MAX_UNITS = _lib.PNGDEC_MAX_UNITS                # decoding units (sync points) kept per image
+PNGDEC_MAX_ROW_BYTES = _lib.PNGDEC_MAX_ROW_BYTES        # 1 + W * channels at most
+STATUS_NAMES = _lib.PNGDEC_STATUS_NAMES
+_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
+_PNGDEC_IMAGE_DTYPE = np.dtype(_lib.PngDecImage)
+_PNGDEC_CHUNK_DTYPE = np.dtype(_lib.PngDecChunk)
+
+
+def parse_png(data, index: int = 0):
+    """The host's whole part of decoding one file: the chunk walk.  bytes-like -> ``(W, H, colour type, [(offset, length,
+    stated CRC-32) of every IDAT payload])``.  Signature, IHDR first (its CRC and IEND's are checked here: tens of bytes),
+    consecutive IDATs, IEND; ancillary chunks are skipped.  No compressed byte is looked at.  ValueError names the field."""
+    mv = memoryview(data).cast("B")
+    n = len(mv)
+
+    def bad(what):
+        return ValueError(f"png: file {index}: {what}")
+
+    if n < 8 or bytes(mv[:8]) != _SIGNATURE:
+        raise bad("bad signature")
+    pos, ihdr, spans, idat_done, iend = 8, None, [], False, False
+    while pos < n:
+        if pos + 12 > n:
+            raise bad("truncated chunk")
+        ln, kind = struct.unpack_from(">I4s", mv, pos)
+        if pos + 12 + ln > n:
+            raise bad(f"truncated {kind!r} chunk")
+        crc = struct.unpack_from(">I", mv, pos + 8 + ln)[0]
+        if ihdr is None and kind != b"IHDR":
+            raise bad(f"IHDR is not the first chunk ({kind!r} is)")
+        if kind == b"IHDR":
+            if ihdr is not None or ln != 13:
+                raise bad("misplaced IHDR")
+            if zlib.crc32(mv[pos + 4:pos + 8 + ln]) != crc:
+                raise bad("IHDR CRC")
+            ihdr = struct.unpack_from(">IIBBBBB", mv, pos + 8)
+        elif kind == b"IDAT":
+            if idat_done:
+                raise bad("IDAT chunks are not consecutive")
+            spans.append((pos + 8, ln, crc))
+        elif kind == b"IEND":
+            if not spans:
+                raise bad("IDAT missing before IEND")
+            if ln != 0 or zlib.crc32(b"IEND") != crc:
+                raise bad("IEND CRC")
+            iend = True
+            break
+        else:
+            idat_done = bool(spans)
+            if not (kind[0] & 32) and kind != b"PLTE":        # (a suggested palette is legal in colour files)
+                raise bad(f"unknown critical chunk {kind!r}")
+        pos += 12 + ln
+    if ihdr is None:
+        raise bad("IHDR missing")
+    if not iend:
+        raise bad("IEND missing")
+    W, H, depth, ctype, comp, filt, lace = ihdr
+    if depth != 8:
+        raise bad(f"bit depth {depth} (8 only)")
+    if ctype not in _CHANNELS:
+        raise bad(f"colour type {ctype} (0, 2, 4 or 6; palette files are not decoded)")
+    if comp != 0 or filt != 0:
+        raise bad("unknown compression / filter method")
+    if lace != 0:
+        raise bad("interlace (non-interlaced files only)")
+    if W == 0 or H == 0:
+        raise bad(f"size {W} x {H}")
+    rb = 1 + W * _CHANNELS[ctype]
+    if rb > PNGDEC_MAX_ROW_BYTES or H * rb >= 1 << 31 or sum(s[1] for s in spans) >= 1 << 31:
+        raise bad(f"size limit: {W} x {H} x {_CHANNELS[ctype]} (rows of at most {PNGDEC_MAX_ROW_BYTES} bytes, images and streams below 2 GiB)")
+    return W, H, ctype, spans
+
+
+def _file_bytes(f):
+    if isinstance(f, (str, os.PathLike)):
+        with open(f, "rb") as fh:
+            return fh.read()
+    return f
+
+
+class PngFiles:
+    """One batch of PNG files planned for ``attwarp_pngdec_decode``: ``files`` is a list of bytes / bytearray / memoryview /
+    paths.  The host walks the chunks (:func:`parse_png`), packs every IDAT payload of every file back to back and uploads
+    them in ONE transfer; the plan depends only on what IHDR and the chunk lengths say.  ``mode``: "RGB" (what
+    ``Image.open(f).convert("RGB")`` gives), "L" (``.convert("L")``) or "keep" (the file's channels without alpha);
+    ``order="bgr"`` swaps a 3-channel result.  ``out``: a uint8 device buffer of at least :attr:`out_bytes` bytes.
+    Unsupported files raise ValueError before any launch."""
+
+    def __init__(self, files, mode: str = "RGB", order: str = "rgb", check_crc: bool = True, out: Optional[torch.Tensor] = None,
+                 device=None):
+        from .pipeline import _upload_filled
+        files = [_file_bytes(f) for f in files]
+        if not files:
+            raise ValueError("PngFiles: empty batch")
+        if mode not in _lib.PNGDEC_MODE_IDS or order not in _ORDERS:
+            raise ValueError(f"PngFiles: mode must be one of {sorted(_lib.PNGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
+        parsed = [parse_png(f, i) for i, f in enumerate(files)]
+        B = len(files)
+        nchunks = sum(len(p[3]) for p in parsed)
+        rec = np.zeros(B, dtype=_PNGDEC_IMAGE_DTYPE)
+        chunks = np.zeros(max(nchunks, 1), dtype=_PNGDEC_CHUNK_DTYPE)
+        lens = [sum(s[1] for s in p[3]) for p in parsed]
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        spans_of = []                     # per file: (source bytes, [(offset in the file, offset in the packed buffer, length)])
+        c = 0
+        for b, (f, (W, H, ctype, spans)) in enumerate(zip(files, parsed)):
+            at = int(offs[b])
+            moves = []
+            for off, ln, crc in spans:
+                moves.append((off, at, ln))
+                chunks[c] = (at, ln, crc, b, 0)
+                at += ln
+                c += 1
+            spans_of.append((np.frombuffer(f, dtype=np.uint8), moves))
+        rec["stream_off"] = offs[:-1]; rec["stream_len"] = lens
+        rec["W"] = [p[0] for p in parsed]; rec["H"] = [p[1] for p in parsed]; rec["color_type"] = [p[2] for p in parsed]
+        rec["mode"] = _lib.PNGDEC_MODE_IDS[mode]; rec["order"] = _ORDERS[order]
+        dev = torch.device(device) if device is not None else (out.device if out is not None else _lib.default_device())
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        lib = _lib.load()
+        rp, cp = ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(chunks.ctypes.data)
+        nbytes = lib.attwarp_pngdec_table_bytes(rp, B, nchunks)
+        if nbytes == 0:
+            raise ValueError("PngFiles: " + lib.attwarp_last_error().decode("utf-8", "replace"))
+        self.table_host = np.empty(nbytes, dtype=np.uint8)
+        try:
+            call("attwarp_pngdec_plan", rp, B, cp, nchunks, int(bool(check_crc)), self.table_host.ctypes.data, nbytes)
+        except _lib.AttWarpError as e:
+            raise ValueError(f"PngFiles: {e}") from None
+        self.header = _lib.PngDecHeader.from_address(self.table_host.ctypes.data)
+        self.B, self._dev, self.mode, self.order = B, dev, mode, order
+        self.shapes = [(p[1], p[0], 1 if mode == "L" else 3 if mode == "RGB" else (1 if _CHANNELS[p[2]] <= 2 else 3)) for p in parsed]
+        self.compressed_bytes = int(offs[-1])
+        with torch.cuda.device(dev):
+            # ONE transfer: the table, then (256-byte aligned) every IDAT payload, gathered straight into the pinned slot
+            pad = -nbytes % 256
+            total = nbytes + pad + max(self.compressed_bytes, 1)
+
+            def fill(buf):
+                buf[:nbytes] = self.table_host
+                body = buf[nbytes + pad:]
+                for src, moves in spans_of:
+                    for off, at, ln in moves:
+                        body[at:at + ln] = src[off:off + ln]
+            self._uploaded = torch.empty(total, device=dev, dtype=torch.uint8)
+            _upload_filled(total, fill, self._uploaded)
+            self.table_dev = self._uploaded[:nbytes]
+            self.stream = self._uploaded[nbytes + pad:]
+            self.scratch = torch.empty(int(self.header.scratch_bytes), device=dev, dtype=torch.uint8)
+            if out is None:
+                out = torch.empty(max(self.out_bytes, 1), device=dev, dtype=torch.uint8)
+            elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < self.out_bytes:
+                raise ValueError(f"PngFiles: out must be a dense uint8 buffer of at least {self.out_bytes} bytes on the device")
+            self.buffer = out
+            self.status = torch.empty(B, device=dev, dtype=torch.int32)
+
+    @property
+    def out_bytes(self) -> int:
+        """Bytes of all decoded images, back to back: the capacity ``out`` needs."""
+        return int(self.header.out_bytes)
+
+    def views(self) -> List[torch.Tensor]:
+        """uint8 [H_i, W_i, C] views into the packed output buffer, in the convention of ``pipeline.upload_images``."""
+        out, off = [], 0
+        for H, W, C in self.shapes:
+            out.append(self.buffer[off:off + H * W * C].view(H, W, C))
+            off += H * W * C
+        return out
+
+    def routes(self):
+        """After a :meth:`run` (synchronises): per image ``(route, units on the chain, sync points kept)``; route 0 is the
+        unit route, 1 the serial one, 2 none (the zlib header failed).  For measurements and tests."""
+        st = self.scratch[:self.B * 32].cpu().numpy().view(np.uint32).reshape(self.B, 8)
+        return [(int(r[1]), int(r[7]), int(r[0])) for r in st]
+
+    def run(self):
+        """Seven launches on the current stream -> ``(views, status)``: the images, and an int32 [B] device tensor (0: ok,
+        else ``STATUS_NAMES[code]``; such an image's pixels are unspecified).  No host synchronisation and no host-dependent
+        argument: capturable in a graph."""
+        with torch.cuda.device(self._dev):
+            call("attwarp_pngdec_decode", self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.stream), ptr(self.scratch),
+                 ptr(self.buffer), self.buffer.numel(), ptr(self.status), stream_ptr(self._dev))
+        return self.views(), self.status
+
+
+def decode_png(files, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+    """PNG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
+    first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all."""
+    views, status = PngFiles(files, mode, order, device=device).run()
+    st = status.cpu().tolist()
+    for i, s in enumerate(st):
+        if s:
+            name = STATUS_NAMES[s] if 0 <= s < len(STATUS_NAMES) else str(s)
+            raise OSError(f"png: file {i} of {len(st)} is broken: {name}")
+    return views
+
+
+def read_png(paths, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+    """:func:`decode_png` of the files at ``paths``."""
+    return decode_png([os.fspath(p) for p in paths], mode, order, device)

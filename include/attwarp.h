@@ -845,6 +845,74 @@ typedef struct attwarp_panel_source {
 ATTWARP_API int attwarp_panel_grid(const attwarp_panel_source* sources, int nsrc, int n, int H, int W, int nrow, int padding,
                        int pad_value, int layout, int right_margin, int flags, uint8_t* out, void* stream);
 
+/* ---- PNG files of a whole batch DECODED on the device (pngdec.hip): the reading half of attwarp_png_*.
+ * 8-bit, non-interlaced, colour types 0 (grey), 2 (RGB), 4 (grey + alpha), 6 (RGBA).  The HOST walks the chunks only and
+ * packs the IDAT payloads of all files back to back into one buffer, so every image's zlib stream is contiguous; the
+ * device inflates (all of RFC 1951), verifies zlib header, Adler-32, final size and, with check_crc, the CRC-32 of every
+ * IDAT chunk, undoes the five filters and converts.
+ *   1. fill attwarp_pngdec_image[B] and attwarp_pngdec_chunk[nchunks] (HOST arrays, offsets into the packed stream buffer);
+ *   2. attwarp_pngdec_table_bytes -> size; attwarp_pngdec_plan writes header, records and chunks into HOST memory;
+ *   3. copy the table (8-byte aligned) and header.stream_bytes packed stream bytes to the device;
+ *   4. attwarp_pngdec_decode(host copy, device copy, the packed stream, scratch of header.scratch_bytes (16-byte
+ *      aligned), out of at least header.out_bytes, status int32 [B], stream): image b is the dense [H, W, out_channels]
+ *      block at out + sum of the blocks before it; status[b] is ATTWARP_PNGDEC_OK or the FIRST failing check in the order
+ *      CRC, inflate (the codes from ZLIB_HEADER to UNDERFLOW), ADLER, FILTER.  A failing image touches nothing but its own
+ *      scratch and output block, whose content is then unspecified; the other images are unaffected.
+ * mode: ATTWARP_PNGDEC_RGB (3 channels: grey replicated, alpha dropped), ATTWARP_PNGDEC_L (1 channel: colour files give
+ * (19595 R + 38470 G + 7471 B + 32768) >> 16, Pillow's), ATTWARP_PNGDEC_KEEP (the file's channels without alpha).  order =
+ * ATTWARP_BGR swaps the channels of a 3-channel output.
+ * Sync points: per image the stream's start and the first ATTWARP_PNGDEC_MAX_UNITS - 1 byte positions behind a
+ * 00 00 FF FF start one decoding unit (one workgroup) each; a 1024 x 1024 x 3 file of attwarp_png_encode has 147 segments
+ * and 149 such positions.  Later positions are ignored: the last kept unit decodes on to the end.
+ * Limits (ATTWARP_E_UNSUPPORTED from the planner): 1 + W * channels <= ATTWARP_PNGDEC_MAX_ROW_BYTES (the unfilter kernel
+ * keeps one row in LDS); H * (1 + W * channels) and an image's stream below 2^31 bytes (positions inside an image are
+ * uint32; offsets between images are uint64); at most 2^20 images and 2^26 chunks per call.  No launch depends on
+ * anything the host reads back: a call can be captured in a graph. */
+#define ATTWARP_PNGDEC_MAX_UNITS 256
+#define ATTWARP_PNGDEC_MAX_ROW_BYTES 49152
+enum { ATTWARP_PNGDEC_RGB = 0, ATTWARP_PNGDEC_L = 1, ATTWARP_PNGDEC_KEEP = 2 };
+enum { ATTWARP_PNGDEC_OK = 0,
+       ATTWARP_PNGDEC_E_CRC = 1,           /* an IDAT chunk's CRC-32 */
+       ATTWARP_PNGDEC_E_ZLIB_HEADER = 2,   /* CM / CINFO / FCHECK / FDICT */
+       ATTWARP_PNGDEC_E_TRUNCATED = 3,     /* a read past the stream's end (the Adler-32's four bytes included) */
+       ATTWARP_PNGDEC_E_BLOCK_TYPE = 4,    /* BTYPE 3 */
+       ATTWARP_PNGDEC_E_STORED_LEN = 5,    /* LEN != ~NLEN */
+       ATTWARP_PNGDEC_E_CODE_LENGTHS = 6,  /* over-subscribed or incomplete set, bad repeat, too many symbols, no end of block */
+       ATTWARP_PNGDEC_E_SYMBOL = 7,        /* bits that are no code of the table, length symbol > 285, distance symbol > 29 */
+       ATTWARP_PNGDEC_E_DISTANCE = 8,      /* a match that starts before the first byte */
+       ATTWARP_PNGDEC_E_OVERFLOW = 9,      /* more than H * (1 + W * channels) bytes */
+       ATTWARP_PNGDEC_E_UNDERFLOW = 10,    /* fewer */
+       ATTWARP_PNGDEC_E_ADLER = 11,
+       ATTWARP_PNGDEC_E_FILTER = 12 };     /* a filter byte above 4 */
+typedef struct attwarp_pngdec_image {
+  uint64_t stream_off;                             /* the image's zlib stream in the packed buffer */
+  uint64_t stream_len;
+  int32_t H, W;
+  int32_t color_type;                              /* 0, 2, 4, 6 */
+  int32_t mode;                                    /* ATTWARP_PNGDEC_RGB / L / KEEP */
+  int32_t order;                                   /* ATTWARP_RGB / ATTWARP_BGR */
+  int32_t reserved;
+} attwarp_pngdec_image;
+typedef struct attwarp_pngdec_chunk {              /* one IDAT chunk: its payload in the packed buffer, the CRC-32 the file states */
+  uint64_t off;
+  uint32_t len, crc;
+  int32_t image, reserved;
+} attwarp_pngdec_chunk;
+typedef struct attwarp_pngdec_header {             /* first bytes of a table written by attwarp_pngdec_plan */
+  uint32_t magic;
+  int32_t B, nchunks, check_crc;
+  int32_t lds_bytes, reserved;
+  uint64_t table_bytes, scratch_bytes, out_bytes, stream_bytes;
+  uint64_t off_images, off_chunks;
+  uint32_t crc_pow8[32];
+  uint32_t idat_crc, reserved2;                    /* CRC-32 of "IDAT" */
+} attwarp_pngdec_header;
+ATTWARP_API size_t attwarp_pngdec_table_bytes(const attwarp_pngdec_image* images, int B, int nchunks);
+ATTWARP_API int attwarp_pngdec_plan(const attwarp_pngdec_image* images, int B, const attwarp_pngdec_chunk* chunks, int nchunks,
+                       int check_crc, void* table, size_t table_bytes);
+ATTWARP_API int attwarp_pngdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                       uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
