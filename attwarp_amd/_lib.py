@@ -165,6 +165,10 @@ SIGNATURES = {
     "attwarp_pngdec_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "attwarp_pngdec_plan": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t]),
     "attwarp_pngdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # baseline JPEG files decoded on the device (jpegdec.hip)
+    "attwarp_jpegdec_table_bytes": (c_size_t, [c_void_p, c_int]),
+    "attwarp_jpegdec_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "attwarp_jpegdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),
@@ -185,6 +189,11 @@ PNGDEC_STATUS_NAMES = ("OK", "E_CRC", "E_ZLIB_HEADER", "E_TRUNCATED", "E_BLOCK_T
                        "E_DISTANCE", "E_OVERFLOW", "E_UNDERFLOW", "E_ADLER", "E_FILTER")
 (PNGDEC_OK, PNGDEC_E_CRC, PNGDEC_E_ZLIB_HEADER, PNGDEC_E_TRUNCATED, PNGDEC_E_BLOCK_TYPE, PNGDEC_E_STORED_LEN, PNGDEC_E_CODE_LENGTHS,
  PNGDEC_E_SYMBOL, PNGDEC_E_DISTANCE, PNGDEC_E_OVERFLOW, PNGDEC_E_UNDERFLOW, PNGDEC_E_ADLER, PNGDEC_E_FILTER) = range(13)
+# attwarp_jpegdec_*: modes, limits and status codes (ATTWARP_JPEGDEC_* of include/attwarp.h)
+JPEGDEC_MODE_IDS = {"RGB": 0, "L": 1, "keep": 2}
+JPEGDEC_MAX_UNITS, JPEGDEC_MAX_BLOCKS = 65536, 1 << 24
+JPEGDEC_STATUS_NAMES = ("OK", "E_TRUNCATED", "E_HUFFMAN", "E_COEFF", "E_RESTART", "E_NO_EOI")
+(JPEGDEC_OK, JPEGDEC_E_TRUNCATED, JPEGDEC_E_HUFFMAN, JPEGDEC_E_COEFF, JPEGDEC_E_RESTART, JPEGDEC_E_NO_EOI) = range(6)
 # attwarp_panel_grid: limits, flags and source kinds (ATTWARP_PANEL_* of include/attwarp.h)
 PANEL_MAX_SRC, PANEL_MAX_HEAT, PANEL_FOR_PNG = 8, 4096, 1
 PANEL_F32, PANEL_U8, PANEL_HEAT = 0, 1, 2
@@ -240,6 +249,23 @@ class PngDecHeader(ctypes.Structure):
                 ("table_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
                 ("stream_bytes", ctypes.c_uint64), ("off_images", ctypes.c_uint64), ("off_chunks", ctypes.c_uint64),
                 ("crc_pow8", ctypes.c_uint32 * 32), ("idat_crc", ctypes.c_uint32), ("reserved2", ctypes.c_uint32)]
+
+
+class JpegDecImage(ctypes.Structure):
+    """attwarp_jpegdec_image: one file of an attwarp_jpegdec_plan call; the tables are the scan's, resolved per component."""
+    _fields_ = [("stream_off", ctypes.c_uint64), ("stream_len", ctypes.c_uint64), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("order", ctypes.c_int32), ("qt", ctypes.c_uint16 * 64 * 3),
+                ("dc_counts", ctypes.c_uint8 * 16 * 3), ("ac_counts", ctypes.c_uint8 * 16 * 3),
+                ("dc_symbols", ctypes.c_uint8 * 256 * 3), ("ac_symbols", ctypes.c_uint8 * 256 * 3)]
+
+
+class JpegDecHeader(ctypes.Structure):
+    """attwarp_jpegdec_header: the first bytes of a table written by attwarp_jpegdec_plan."""
+    _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("total_units", ctypes.c_int32), ("idct_tiles", ctypes.c_int32),
+                ("color_tiles", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("table_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
+                ("stream_bytes", ctypes.c_uint64), ("off_images", ctypes.c_uint64)]
 
 
 class PanelSource(ctypes.Structure):

@@ -1,0 +1,303 @@
+"""Baseline JPEG files of a whole ragged batch, decoded on the GPU (csrc/jpegdec.hip): what the reference
+does per file with ``Image.open(path).convert('RGB')`` (main_batched.py:95-98, main.py:148-152, functions.py:36,
+MN/dataloader.py:216,368).  Only compressed bytes cross to the device; the pixels are Pillow's, bit for bit.
+SOF0 / SOF1, 8 bits, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, any restart interval.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import struct
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call, ptr, stream_ptr
+
+JPEGDEC_MAX_UNITS = _lib.JPEGDEC_MAX_UNITS              # restart intervals per image
+JPEGDEC_MAX_BLOCKS = _lib.JPEGDEC_MAX_BLOCKS            # 8x8 blocks per image, all components (exclusive)
+STATUS_NAMES = _lib.JPEGDEC_STATUS_NAMES
+_ORDERS = {"rgb": _lib.RGB, "bgr": _lib.BGR}
+_IMAGE_DTYPE = np.dtype(_lib.JpegDecImage)
+_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_UNSUPPORTED_FRAMES = {0xC2: "progressive", 0xC3: "lossless", 0xC5: "hierarchical", 0xC6: "hierarchical", 0xC7: "hierarchical",
+                       0xC9: "arithmetic", 0xCA: "arithmetic", 0xCB: "arithmetic", 0xCD: "arithmetic", 0xCE: "arithmetic",
+                       0xCF: "arithmetic"}
+
+
+def parse_jpeg(data, index: int = 0) -> dict:
+    """The host's whole part of decoding one file: the walk over the marker segments up to the SOS header.  bytes-like ->
+    ``dict(W, H, ncomp, hs, vs, ri, qt, dc, ac, data_off)``: luma sampling factors, the restart interval (0: none), per
+    component the quantisation table (64 values, natural order) and the (counts, symbols) of its DC and AC Huffman tables,
+    and the offset of the first byte behind the SOS header.  No entropy-coded byte is looked at.  ValueError names what
+    is not decoded; a file that ends inside its headers raises OSError."""
+    mv = memoryview(data).cast("B")
+    n = len(mv)
+
+    def bad(what):
+        return ValueError(f"jpeg: file {index}: {what}")
+
+    def need(upto):
+        if upto > n:
+            raise OSError(f"jpeg: file {index}: the file ends inside its headers")
+
+    need(2)
+    if mv[0] != 0xFF or mv[1] != 0xD8:
+        raise bad("bad signature")
+    pos = 2
+    qts, dcs, acs = {}, {}, {}
+    frame, ri, jfif, adobe = None, 0, False, None
+    while True:
+        need(pos + 1)
+        if mv[pos] != 0xFF:
+            raise bad("a marker was expected")
+        while mv[pos] == 0xFF:                            # fill bytes
+            pos += 1
+            need(pos + 1)
+        m = mv[pos]
+        pos += 1
+        if m in _UNSUPPORTED_FRAMES:
+            raise bad(f"{_UNSUPPORTED_FRAMES[m]} frame (sequential Huffman only)")
+        if m == 0xCC:
+            raise bad("arithmetic conditioning")
+        if m in (0x00, 0x01, 0xD8, 0xD9) or 0xD0 <= m <= 0xD7:
+            raise bad(f"marker {m:02x} in the headers")
+        need(pos + 2)
+        L = mv[pos] << 8 | mv[pos + 1]
+        if L < 2:
+            raise bad("segment length below 2")
+        need(pos + L)
+        seg = bytes(mv[pos + 2:pos + L])
+        pos += L
+        if m in (0xC0, 0xC1):
+            if frame is not None:
+                raise bad("a second frame (hierarchical)")
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                raise bad("bad frame header")
+            prec, H, W, nf = struct.unpack(">BHHB", seg[:6])
+            if prec != 8:
+                raise bad(f"precision {prec} (8 only)")
+            if H == 0 or W == 0:
+                raise bad(f"size {W} x {H}")
+            if nf not in (1, 3):
+                raise bad(f"{nf} components (1 or 3)")
+            frame = (W, H, [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(nf)])
+        elif m == 0xC4:
+            q = 0
+            while q < len(seg):
+                if q + 17 > len(seg):
+                    raise bad("DHT runs past its segment")
+                tc, th = seg[q] >> 4, seg[q] & 15
+                if tc > 1 or th > 3:
+                    raise bad("DHT class / id")
+                counts = seg[q + 1:q + 17]
+                left = 1
+                for c in counts:
+                    left = 2 * left - c
+                    if left < 0:
+                        raise bad("DHT over-subscribed")
+                ns = sum(counts)
+                if ns > 256 or q + 17 + ns > len(seg):
+                    raise bad("DHT symbols exceed 256 or run past the segment")
+                syms = seg[q + 17:q + 17 + ns]
+                if tc == 0 and any(s > 15 for s in syms):
+                    raise bad("DHT with a DC category above 15")
+                (acs if tc else dcs)[th] = (counts, syms)
+                q += 17 + ns
+        elif m == 0xDB:
+            q = 0
+            while q < len(seg):
+                pq, tq = seg[q] >> 4, seg[q] & 15
+                if pq == 1:
+                    raise bad("16-bit quantisation table")
+                if pq > 1 or tq > 3 or q + 65 > len(seg):
+                    raise bad("bad DQT")
+                t = [0] * 64
+                for k in range(64):
+                    t[_ZIGZAG[k]] = seg[q + 1 + k]
+                qts[tq] = t
+                q += 65
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise bad("bad DRI")
+            ri = seg[0] << 8 | seg[1]
+        elif m == 0xE0:
+            jfif = jfif or seg[:5] == b"JFIF\0"
+        elif m == 0xEE:
+            if seg[:5] == b"Adobe" and len(seg) >= 12:
+                adobe = seg[11]
+        elif m in (0xDC, 0xDE, 0xDF):
+            raise bad("DNL / hierarchical marker")
+        elif m == 0xDA:
+            break
+    if frame is None:
+        raise bad("SOS before the frame header")
+    W, H, comps = frame
+    nf = len(comps)
+    if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+        raise bad("bad scan header")
+    if seg[0] != nf or [seg[1 + 2 * i] for i in range(nf)] != [c[0] for c in comps]:
+        raise bad("the scan does not hold all components in frame order (more than one scan)")
+    if tuple(seg[1 + 2 * nf:]) != (0, 63, 0):
+        raise bad("spectral selection / successive approximation")
+    hs = vs = 1
+    if nf == 3:
+        if adobe == 0 or (adobe is None and not jfif and bytes(c[0] for c in comps) == b"RGB"):
+            raise bad("RGB-coded file (YCbCr only)")
+        samp = [(c[1], c[2]) for c in comps]
+        if samp[1] != (1, 1) or samp[2] != (1, 1) or samp[0] not in ((1, 1), (2, 1), (2, 2)):
+            raise bad(f"sampling layout {samp} (4:4:4, 4:2:2, 4:2:0)")
+        hs, vs = samp[0]
+    qt, dc, ac = [], [], []
+    for i, c in enumerate(comps):
+        td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
+        if c[3] not in qts or td not in dcs or ta not in acs:
+            raise bad("the scan names a table never defined")
+        qt.append(qts[c[3]]); dc.append(dcs[td]); ac.append(acs[ta])
+    mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
+    units = -(-mcus // ri) if ri else 1
+    blocks = mcus * (hs * vs + nf - 1)
+    if units > JPEGDEC_MAX_UNITS or blocks >= JPEGDEC_MAX_BLOCKS or n - pos >= 1 << 31:
+        raise bad(f"size limit: {units} restart intervals (at most {JPEGDEC_MAX_UNITS}), {blocks} blocks (below {JPEGDEC_MAX_BLOCKS})")
+    return dict(W=W, H=H, ncomp=nf, hs=hs, vs=vs, ri=ri, qt=qt, dc=dc, ac=ac, data_off=pos, units=units)
+
+
+def _file_bytes(f):
+    if isinstance(f, (str, os.PathLike)):
+        with open(f, "rb") as fh:
+            return fh.read()
+    return f
+
+
+def plan(files, mode: str = "RGB", order: str = "rgb"):
+    """Host only (no device is touched): files -> ``(parsed, table, header)``: :func:`parse_jpeg` of every file and the table
+    ``attwarp_jpegdec_plan`` writes for them, which depends on the headers alone."""
+    if mode not in _lib.JPEGDEC_MODE_IDS or order not in _ORDERS:
+        raise ValueError(f"jpeg: mode must be one of {sorted(_lib.JPEGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
+    files = [_file_bytes(f) for f in files]
+    parsed = [parse_jpeg(f, i) for i, f in enumerate(files)]
+    B = len(parsed)
+    rec = np.zeros(B, dtype=_IMAGE_DTYPE)
+    lens = [len(memoryview(f).cast("B")) - p["data_off"] for f, p in zip(files, parsed)]
+    rec["stream_off"] = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    rec["stream_len"] = lens
+    for key, name in (("H", "H"), ("W", "W"), ("ncomp", "ncomp"), ("hs", "hs"), ("vs", "vs"), ("restart_interval", "ri")):
+        rec[key] = [p[name] for p in parsed]
+    rec["mode"] = _lib.JPEGDEC_MODE_IDS[mode]; rec["order"] = _ORDERS[order]
+    for b, p in enumerate(parsed):
+        for c in range(p["ncomp"]):
+            rec["qt"][b, c] = p["qt"][c]
+            for kind, tabs in (("dc", p["dc"]), ("ac", p["ac"])):
+                counts, syms = tabs[c]
+                rec[kind + "_counts"][b, c] = list(counts)
+                rec[kind + "_symbols"][b, c, :len(syms)] = list(syms)
+    lib = _lib.load()
+    rp = ctypes.c_void_p(rec.ctypes.data)
+    nbytes = lib.attwarp_jpegdec_table_bytes(rp, B)
+    if nbytes == 0:
+        raise ValueError("jpeg: " + lib.attwarp_last_error().decode("utf-8", "replace"))
+    table = np.empty(nbytes, dtype=np.uint8)
+    try:
+        call("attwarp_jpegdec_plan", rp, B, table.ctypes.data, nbytes)
+    except _lib.AttWarpError as e:
+        raise ValueError(f"jpeg: {e}") from None
+    return parsed, table, _lib.JpegDecHeader.from_address(table.ctypes.data)
+
+
+class JpegFiles:
+    """One batch of JPEG files planned for ``attwarp_jpegdec_decode``: ``files`` is a list of bytes / bytearray / memoryview /
+    paths.  The host walks the marker segments (:func:`parse_jpeg`), packs everything behind every file's SOS header back
+    to back and uploads it, with the table, in ONE transfer; the plan depends only on what the headers say.  ``mode``:
+    "RGB" (what ``Image.open(f).convert("RGB")`` gives), "L" (``.convert("L")``) or "keep" (grey files one channel, colour
+    files three); ``order="bgr"`` swaps a 3-channel result.  ``out``: a uint8 device buffer of at least :attr:`out_bytes`
+    bytes.  Unsupported files raise ValueError before any launch."""
+
+    def __init__(self, files, mode: str = "RGB", order: str = "rgb", out: Optional[torch.Tensor] = None, device=None):
+        from .pipeline import _upload_filled
+        files = [_file_bytes(f) for f in files]
+        if not files:
+            raise ValueError("JpegFiles: empty batch")
+        parsed, self.table_host, self.header = plan(files, mode, order)
+        B = len(files)
+        dev = torch.device(device) if device is not None else (out.device if out is not None else _lib.default_device())
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.B, self._dev, self.mode, self.order = B, dev, mode, order
+        self.parsed = parsed
+        self.shapes = [(p["H"], p["W"], 1 if mode == "L" else 3 if mode == "RGB" else p["ncomp"]) for p in parsed]
+        srcs = [np.frombuffer(f, dtype=np.uint8)[p["data_off"]:] for f, p in zip(files, parsed)]
+        self.compressed_bytes = int(self.header.stream_bytes)
+        nbytes = self.table_host.size
+        with torch.cuda.device(dev):
+            pad = -nbytes % 256
+            total = nbytes + pad + max(self.compressed_bytes, 1)
+
+            def fill(buf):
+                buf[:nbytes] = self.table_host
+                at = nbytes + pad
+                for s in srcs:
+                    buf[at:at + s.size] = s
+                    at += s.size
+            self._uploaded = torch.empty(total, device=dev, dtype=torch.uint8)
+            _upload_filled(total, fill, self._uploaded)
+            self.table_dev = self._uploaded[:nbytes]
+            self.stream = self._uploaded[nbytes + pad:]
+            self.scratch = torch.empty(int(self.header.scratch_bytes), device=dev, dtype=torch.uint8)
+            if out is None:
+                out = torch.empty(max(self.out_bytes, 1), device=dev, dtype=torch.uint8)
+            elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < self.out_bytes:
+                raise ValueError(f"JpegFiles: out must be a dense uint8 buffer of at least {self.out_bytes} bytes on the device")
+            self.buffer = out
+            self.status = torch.empty(B, device=dev, dtype=torch.int32)
+
+    @property
+    def out_bytes(self) -> int:
+        """Bytes of all decoded images, back to back: the capacity ``out`` needs."""
+        return int(self.header.out_bytes)
+
+    def views(self) -> List[torch.Tensor]:
+        """uint8 [H_i, W_i, C] views into the packed output buffer, in the convention of ``pipeline.upload_images``."""
+        out, off = [], 0
+        for H, W, C in self.shapes:
+            out.append(self.buffer[off:off + H * W * C].view(H, W, C))
+            off += H * W * C
+        return out
+
+    def units(self) -> List[int]:
+        """Decoding units (restart intervals) planned per image, from the headers alone: one wave each."""
+        return [p["units"] for p in self.parsed]
+
+    def restarts(self) -> List[int]:
+        """After a :meth:`run` (synchronises): restart markers the device found in front of each image's data end; units - 1
+        in a file that decodes.  For measurements and tests."""
+        st = self.scratch[:self.B * 16].cpu().numpy().view(np.uint32).reshape(self.B, 4)
+        return [int(r[3]) for r in st]
+
+    def run(self):
+        """Four launches on the current stream -> ``(views, status)``: the images, and an int32 [B] device tensor (0: ok,
+        else ``STATUS_NAMES[code]``; such an image's pixels are unspecified).  No host synchronisation and no host-dependent
+        argument: capturable in a graph."""
+        with torch.cuda.device(self._dev):
+            call("attwarp_jpegdec_decode", self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.stream), ptr(self.scratch),
+                 ptr(self.buffer), self.buffer.numel(), ptr(self.status), stream_ptr(self._dev))
+        return self.views(), self.status
+
+
+def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+    """JPEG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
+    first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all."""
+    views, status = JpegFiles(files, mode, order, device=device).run()
+    st = status.cpu().tolist()
+    for i, s in enumerate(st):
+        if s:
+            name = STATUS_NAMES[s] if 0 <= s < len(STATUS_NAMES) else str(s)
+            raise OSError(f"jpeg: file {i} of {len(st)} is broken: {name}")
+    return views
+
+
+def read_jpeg(paths, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+    """:func:`decode_jpeg` of the files at ``paths``."""
+    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device)

@@ -1479,6 +1479,39 @@ def upload_png_files(files_or_paths, device=None):
     return decode_png(files_or_paths, "RGB", "rgb", device)
 
 
+def upload_jpeg_files(files_or_paths, device=None):
+    """:func:`upload_images` for a batch still in its JPEG files (bytes-like or paths; the TextVQA / GQA images the drivers and
+    the MarginalNet loader open, or anyone's baseline JPEG): the COMPRESSED bytes go up in one transfer and are decoded on
+    the GPU (attwarp_amd.jpeg.decode_jpeg) -> list of uint8 [H_i,W_i,3] RGB GPU tensors, views into one packed buffer, as
+    ``Image.open(f).convert("RGB")`` gives them.  OSError for a broken file, ValueError for an unsupported one."""
+    from .jpeg import decode_jpeg
+    return decode_jpeg(files_or_paths, "RGB", "rgb", device)
+
+
+def upload_image_files(files_or_paths, device=None):
+    """A batch of image files of either kind (bytes-like or paths), each sent by its signature to the PNG or the JPEG decoder
+    (:func:`upload_png_files`, :func:`upload_jpeg_files`): one transfer and one decode per kind -> the uint8 [H_i,W_i,3] RGB
+    GPU tensors in input order.  ValueError for a file that is neither."""
+    from .jpeg import _file_bytes
+    files = [_file_bytes(f) for f in files_or_paths]
+    kinds = []
+    for i, f in enumerate(files):
+        head = bytes(memoryview(f).cast("B")[:8])
+        if head == b"\x89PNG\r\n\x1a\n":
+            kinds.append("png")
+        elif head[:2] == b"\xff\xd8":
+            kinds.append("jpeg")
+        else:
+            raise ValueError(f"upload_image_files: file {i} is neither a PNG nor a JPEG file")
+    out = [None] * len(files)
+    for kind, decode in (("png", upload_png_files), ("jpeg", upload_jpeg_files)):
+        idx = [i for i, k in enumerate(kinds) if k == kind]
+        if idx:
+            for i, v in zip(idx, decode([files[i] for i in idx], device)):
+                out[i] = v
+    return out
+
+
 def ragged_chain_launch(R: Optional[RaggedBatch] = None, F: Optional[RaggedBatch] = None, P: Optional[RaggedBatch] = None,
                         L: Optional[RaggedBatch] = None, V: Optional[RaggedBatch] = None, enhance_coe=10, kernel_size=3,
                         transform="identity", exp_scale=1.0, exp_divisor=1.0, apply_inverse=False):

@@ -913,6 +913,68 @@ ATTWARP_API int attwarp_pngdec_plan(const attwarp_pngdec_image* images, int B, c
 ATTWARP_API int attwarp_pngdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
 
+/* ---- baseline JPEG files of a whole batch DECODED on the device (jpegdec.hip).  SOF0 / SOF1 (sequential
+ * Huffman, 8 bits), one component (grey) or three (YCbCr, luma 1x1, 2x1 or 2x2 and chroma 1x1: 4:4:4, 4:2:2, 4:2:0), one
+ * interleaved scan.  The HOST walks the marker segments only and packs, per file, everything behind the SOS header into
+ * one buffer; the device finds the restart markers, decodes the entropy data (one wave per restart interval),
+ * dequantises, runs libjpeg's integer IDCT, "fancy" chroma up-sampling and YCbCr -> RGB: the pixels of
+ * Pillow's Image.open(f).convert(mode), bit for bit.
+ *   1. fill attwarp_jpegdec_image[B] (a HOST array: sizes, sampling, the tables the scan names, resolved per component);
+ *   2. attwarp_jpegdec_table_bytes -> size; attwarp_jpegdec_plan writes header and records into HOST memory;
+ *   3. copy the table (8-byte aligned) and header.stream_bytes packed bytes to the device;
+ *   4. attwarp_jpegdec_decode(host copy, device copy, the packed bytes, scratch of header.scratch_bytes (256-byte
+ *      aligned), out of at least header.out_bytes, status int32 [B], stream): four launches, none with an argument that
+ *      depends on anything read back, so a call can be captured in a graph.  Image b is the dense [H, W, out_channels]
+ *      block at out + sum of the blocks before it.
+ * Units: with a restart interval Ri an image has ceil(MCUs / Ri) units (else one), known from the headers; the k-th restart
+ * marker of the data starts unit k + 1.  The data ends at the first FF that is followed by neither 00 nor D0..D7.
+ * status[b], in this precedence: E_RESTART (the markers in front of the data's end do not number units - 1 with indices
+ * cycling 0..7; nothing is resynchronised and no unit is decoded), then the status of the LOWEST failing unit
+ * (E_TRUNCATED: a code or value needs bits behind the unit's end, which read as zero; E_HUFFMAN: 16 bits that start no
+ * code; E_COEFF: a run that leaves coefficient 63), then E_NO_EOI (the marker behind the data is not EOI; fill bytes are
+ * skipped).  Bytes between the last MCU and the next marker are tolerated.  A failing image touches nothing but its own
+ * scratch and output block, whose content is then unspecified.
+ * Hostile values: the DC predictor is a 32-bit sum that wraps; the coefficient stored is its low 16 bits; dequantisation
+ * and IDCT are 32-bit with wrap-around; the final clamp to 0..255 saturates.  Every file gets the same pixels on every run.
+ * mode: ATTWARP_JPEGDEC_RGB (3 channels, grey replicated), ATTWARP_JPEGDEC_L (1 channel: colour files give
+ * (19595 R + 38470 G + 7471 B + 32768) >> 16 of the RGB pixel, grey files the plane), ATTWARP_JPEGDEC_KEEP (1 or 3).
+ * order = ATTWARP_BGR swaps a 3-channel output.
+ * Limits (ATTWARP_E_UNSUPPORTED from the planner): at most ATTWARP_JPEGDEC_MAX_UNITS units and fewer than
+ * ATTWARP_JPEGDEC_MAX_BLOCKS 8x8 blocks per image (offsets inside an image stay below 2^31: 128 bytes of coefficients
+ * per block), an image's data below 2^31 bytes, at most 2^20 images and 2^30 units per call. */
+#define ATTWARP_JPEGDEC_MAX_UNITS 65536
+#define ATTWARP_JPEGDEC_MAX_BLOCKS 16777216
+enum { ATTWARP_JPEGDEC_RGB = 0, ATTWARP_JPEGDEC_L = 1, ATTWARP_JPEGDEC_KEEP = 2 };
+enum { ATTWARP_JPEGDEC_OK = 0,
+       ATTWARP_JPEGDEC_E_TRUNCATED = 1,    /* a code or value needs bits behind the unit's end */
+       ATTWARP_JPEGDEC_E_HUFFMAN = 2,      /* no code of <= 16 bits matches */
+       ATTWARP_JPEGDEC_E_COEFF = 3,        /* a run past coefficient 63 */
+       ATTWARP_JPEGDEC_E_RESTART = 4,      /* restart markers: wrong number or wrong index */
+       ATTWARP_JPEGDEC_E_NO_EOI = 5 };     /* the first marker behind the data is not EOI */
+typedef struct attwarp_jpegdec_image {
+  uint64_t stream_off;                             /* the image's entropy data in the packed buffer */
+  uint64_t stream_len;
+  int32_t H, W;
+  int32_t ncomp;                                   /* 1 or 3 */
+  int32_t hs, vs;                                  /* luma sampling: 1x1, 2x1, 2x2 (grey: 1x1) */
+  int32_t restart_interval;                        /* MCUs, 0: none */
+  int32_t mode;                                    /* ATTWARP_JPEGDEC_RGB / L / KEEP */
+  int32_t order;                                   /* ATTWARP_RGB / ATTWARP_BGR */
+  uint16_t qt[3][64];                              /* per component, natural (de-zigzagged) order, 0..255 */
+  uint8_t dc_counts[3][16], ac_counts[3][16];      /* DHT: codes of each length 1..16 */
+  uint8_t dc_symbols[3][256], ac_symbols[3][256];  /* DHT: symbols by (length, code); DC symbols are categories <= 15 */
+} attwarp_jpegdec_image;
+typedef struct attwarp_jpegdec_header {            /* first bytes of a table written by attwarp_jpegdec_plan */
+  uint32_t magic;
+  int32_t B, total_units, idct_tiles, color_tiles, reserved;
+  uint64_t table_bytes, scratch_bytes, out_bytes, stream_bytes;
+  uint64_t off_images;
+} attwarp_jpegdec_header;
+ATTWARP_API size_t attwarp_jpegdec_table_bytes(const attwarp_jpegdec_image* images, int B);
+ATTWARP_API int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes);
+ATTWARP_API int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                       uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
