@@ -168,6 +168,8 @@ SIGNATURES = {
     # baseline JPEG files decoded on the device (jpegdec.hip)
     "attwarp_jpegdec_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_jpegdec_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "attwarp_jpegdec_plan_ex": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int]),
+    "attwarp_jpegdec_info_offset": (ctypes.c_uint64, [c_void_p]),
     "attwarp_jpegdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,

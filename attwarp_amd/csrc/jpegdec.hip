@@ -1,9 +1,13 @@
 // Baseline JPEG files of a whole ragged batch decoded on the device (include/attwarp.h).  The host walks
-// the marker segments and packs everything behind each SOS header; everything per byte happens here.  Four launches,
+// the marker segments and packs everything behind each SOS header; everything per byte happens here.  Five launches,
 // none with a host-dependent argument:
 //   jpegdec_scan_kernel     one workgroup per IMAGE: the FF D0..D7 positions in order (the k-th starts unit k + 1), the
 //                           data's end (the first other marker), whether that marker is EOI; E_RESTART unless the markers
 //                           number units - 1 with indices cycling 0..7;
+//   jpegdec_substream_kernel one workgroup per marker-less IMAGE planned for it: the unit is cut into byte segments, every lane
+//                           decodes segments from guessed states until every segment enters where the one before it
+//                           leaves (jd_decode_segment, Jacobi rounds under a cap), then the blocks are written with their
+//                           true indices and DC predictors; an image it accepts is flagged and skipped by the next kernel;
 //   jpegdec_entropy_kernel  one wave per UNIT (restart interval): the wave builds the image's decode tables in LDS and
 //                           keeps a ring of the unit's bytes filled; lane 0 decodes block after block with the shared core
 //                           (jpegdec_blocks.hpp); the wave stores each block as one 128-byte row of int16[64];
@@ -12,7 +16,7 @@
 //   jpegdec_color_kernel    one thread per output pixel (eight pixels, a workgroup apart): chroma up-sampling, YCbCr -> RGB,
 //                           mode and order, the store; the first thread of every image writes its status.
 // Every loop is bounded by a header-derived count (units, MCUs per unit, blocks per MCU), by 64 coefficients or 16 bits,
-// or by the stream's length.
+// by the stream's length, or by the plan's cap on rounds.
 #include <algorithm>
 #include <cstring>
 
@@ -27,6 +31,28 @@ constexpr int JD_MAX_B = 1 << 20, JD_MAX_TOTAL_UNITS = 1 << 30;
 constexpr int JD_RING = 2048, JD_CHUNK = WAVE * 4;        // bytes of the entropy kernel's ring / loaded per step
 constexpr int JD_IDCT_TILE = JD_NT;                       // blocks per workgroup
 constexpr int JD_CPX = 8, JD_COLOR_TILE = JD_NT * JD_CPX;  // pixels per thread / workgroup
+constexpr int JD_SUB_MAX_SEGS = 1 << 14, JD_SUB_MAX_ROUNDS = 1 << 16;
+constexpr int JD_SUB_BLK = 66;                            // int16 per lane's block in LDS: 33 dwords, so lanes spread over the banks
+
+struct JdSub {                         // behind the image records of a table, one per image
+  uint64_t seg_off;                    // the image's JdSegState[nseg], then JdSegment[nseg], in the scratch buffer
+  uint64_t info_off;                   // JdSubInfo[B] in the scratch buffer (the same in every record)
+  uint32_t nseg;                       // planned segments; 0: the image is decoded sequentially
+  uint32_t segment_bytes, max_rounds;
+  int32_t image;                       // record w: the image that workgroup w of the sub-stream launch decodes
+};
+static_assert(sizeof(JdSub) == 32, "record layout");
+struct JdSubInfo {                     // per image (scratch), written on every run
+  uint32_t nseg, rounds, accepted, pad;
+};
+struct JdSegState {                    // per segment (scratch)
+  JdSync entry;
+  uint32_t dirty;                      // the entry changed in the last round
+  uint32_t before;                     // blocks that start in front of the segment
+  uint32_t pred[3];                    // the DC predictors at its start
+  uint32_t pad;
+};
+static_assert(sizeof(JdSegState) == 32, "segment layout");
 
 __host__ __device__ inline uint64_t jd_align(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 // the scratch buffer: states, unit starts, unit ends, then every image's coefficients and planes (JdImage::coef_off, plane_off)
@@ -37,11 +63,15 @@ __host__ __device__ inline uint64_t jd_data_base(int B, int units) { return jd_a
 struct JdView {
   const attwarp_jpegdec_header* hdr;
   const JdImage* images;
+  const JdSub* subs;
+  JdSubInfo* infos;
   JdState* states;
   uint32_t *starts, *ends;
   __device__ __forceinline__ JdView(const uint8_t* table, uint8_t* scratch) {
     hdr = reinterpret_cast<const attwarp_jpegdec_header*>(table);
     images = reinterpret_cast<const JdImage*>(table + hdr->off_images);
+    subs = reinterpret_cast<const JdSub*>(table + hdr->off_images + (uint64_t)hdr->B * sizeof(JdImage));
+    infos = reinterpret_cast<JdSubInfo*>(scratch + subs[0].info_off);
     states = reinterpret_cast<JdState*>(scratch);
     starts = reinterpret_cast<uint32_t*>(scratch + jd_starts_off(hdr->B));
     ends = reinterpret_cast<uint32_t*>(scratch + jd_ends_off(hdr->B, hdr->total_units));
@@ -132,6 +162,113 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_scan_kernel(const uint8_t* __re
     st.nrst = running;
     if (!st.st_scan) ends[nunits - 1u] = term;
     v.states[b] = st;
+    JdSubInfo info;
+    info.nseg = v.subs[b].nseg; info.rounds = 0; info.accepted = 0; info.pad = 0;
+    v.infos[b] = info;
+  }
+}
+
+// grid: one workgroup per image planned for sub-streams (at least one workgroup, which then has nothing to do).
+__global__ __launch_bounds__(JD_NT) void jpegdec_substream_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                                  uint8_t* scratch) {
+  __shared__ JdHuff s_dc[3], s_ac[3];
+  __shared__ int16_t s_blk[JD_NT][JD_SUB_BLK];
+  __shared__ uint32_t s_tmp[JD_NT];
+  __shared__ uint8_t s_zz[64];
+  const int tid = threadIdx.x;
+  const JdView v(table, scratch);
+  if ((int)blockIdx.x >= v.hdr->reserved) return;
+  const int b = v.subs[blockIdx.x].image;
+  if (b < 0 || b >= v.hdr->B) return;
+  const JdImage* im = v.images + b;
+  const JdSub sub = v.subs[b];
+  if (v.states[b].st_scan != 0 || sub.nseg == 0) return;      // (uniform) the info record already says "not accepted"
+  const uint32_t n = im->stream_len, nseg = sub.nseg, S = sub.segment_bytes;
+  uint32_t uend = v.ends[im->unit0];
+  if (uend > n) uend = n;
+  const int ncomp = im->ncomp;
+  for (int c = 0; c < ncomp; ++c) {
+    if (tid == 0) { jd_huff_ranges(s_dc[c], im->dc_counts[c]); jd_huff_ranges(s_ac[c], im->ac_counts[c]); }
+    jd_huff_clear(s_dc[c], im->dc_symbols[c], jd_nsym(im->dc_counts[c]), tid, JD_NT);
+    jd_huff_clear(s_ac[c], im->ac_symbols[c], jd_nsym(im->ac_counts[c]), tid, JD_NT);
+  }
+  if (tid < 64) s_zz[tid] = JD_ZIGZAG[tid];
+  __syncthreads();
+  for (int c = 0; c < ncomp; ++c) {
+    jd_huff_fill(s_dc[c], im->dc_counts[c], tid, JD_NT);
+    jd_huff_fill(s_ac[c], im->ac_counts[c], tid, JD_NT);
+  }
+  __syncthreads();
+  // the stream is read in place: p is the dword in front of the image's first byte, lo that byte's offset in it
+  const uint8_t* data = stream + im->stream_off;
+  const uint32_t lo = (uint32_t)(reinterpret_cast<uintptr_t>(data) & 3u);
+  const uint8_t* p = data - lo;
+  JdSegState* seg = reinterpret_cast<JdSegState*>(scratch + sub.seg_off);
+  JdSegment* res = reinterpret_cast<JdSegment*>(scratch + sub.seg_off + (uint64_t)nseg * sizeof(JdSegState));
+  const uint32_t nb0 = (uint32_t)(im->hs * im->vs), nblk = nb0 + (uint32_t)ncomp - 1u;
+  const uint32_t expected = (uint32_t)im->mcux * (uint32_t)im->mcuy * nblk;
+  // every loop over segments below gives segment s to lane s % JD_NT, so a lane reads back its own entry and dirty flag
+  for (uint32_t s = tid; s < nseg; s += JD_NT) {
+    seg[s].entry = jd_segment_guess(data, s, S, uend);
+    seg[s].dirty = 1u;
+  }
+  uint32_t rounds = 0;
+  bool converged = false;
+  while (rounds < sub.max_rounds) {                          // (uniform)
+    ++rounds;
+    for (uint32_t s = tid; s < nseg; s += JD_NT)
+      if (seg[s].dirty) {
+        JdSegment r;
+        jd_decode_segment(p, lo, seg[s].entry, jd_segment_end(s, S, uend), uend, s_dc, s_ac, nb0, nblk, r);
+        res[s] = r;
+      }
+    __syncthreads();                                         // every exit of this round is written
+    int changed = 0;
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      uint32_t d = 0;
+      if (s > 0) {
+        const JdSync e = res[s - 1].exit;
+        if (!jd_sync_equal(e, seg[s].entry)) { seg[s].entry = e; d = 1u; changed = 1; }
+      }
+      seg[s].dirty = d;
+    }
+    if (!__syncthreads_or(changed)) { converged = true; break; }
+  }
+  // exclusive sums of (owned blocks, DC differences) over the segments: lane t sums segments t * chunk .. in order
+  const uint32_t chunk = (nseg + JD_NT - 1) / JD_NT;
+  const uint32_t s0 = min((uint32_t)tid * chunk, nseg), s1 = min(s0 + chunk, nseg);
+  uint32_t sum[4] = {0, 0, 0, 0};
+  for (uint32_t s = s0; s < s1; ++s) {
+    const JdSegment r = res[s];
+    sum[0] += r.owned; sum[1] += r.dc[0]; sum[2] += r.dc[1]; sum[3] += r.dc[2];
+  }
+  uint32_t total;
+  for (int e = 0; e < 4; ++e) sum[e] = jd_excl_sum(sum[e], s_tmp, total);
+  uint32_t flags = 0;
+  for (uint32_t s = s0; s < s1; ++s) {
+    const JdSegment r = res[s];
+    seg[s].before = sum[0];
+    seg[s].pred[0] = sum[1]; seg[s].pred[1] = sum[2]; seg[s].pred[2] = sum[3];
+    flags |= jd_segment_check(seg[s].entry, r, sum[0], expected, nblk);
+    sum[0] += r.owned; sum[1] += r.dc[0]; sum[2] += r.dc[1]; sum[3] += r.dc[2];
+  }
+  const int bad = __syncthreads_or((int)(flags & 1u));
+  const int found = __syncthreads_or((int)(flags & 2u));       // (and every `before` and predictor is written)
+  bool accepted = converged && found && !bad;
+  if (accepted) {                                            // (uniform)
+    int16_t* coef = reinterpret_cast<int16_t*>(scratch + im->coef_off);
+    uint32_t werr = 0;
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      const JdSegState e = seg[s];
+      werr |= jd_write_segment(p, lo, e.entry, uend, s_dc, s_ac, *im, nb0, nblk, e.before, e.pred, res[s].owned, expected, s_blk[tid], s_zz,
+                               coef);
+    }
+    if (__syncthreads_or((int)werr)) accepted = false;       // (never, after the checks: the sequential decode then redoes it)
+  }
+  if (tid == 0) {
+    JdSubInfo info;
+    info.nseg = nseg; info.rounds = rounds; info.accepted = accepted ? 1u : 0u; info.pad = 0;
+    v.infos[b] = info;
   }
 }
 
@@ -150,6 +287,7 @@ __global__ __launch_bounds__(WAVE) void jpegdec_entropy_kernel(const uint8_t* __
   const JdImage* im = v.images + b;
   JdState* state = v.states + b;
   if (state->st_scan != 0) return;                           // (uniform) the units' limits were never written
+  if (v.infos[b].accepted != 0) return;                      // (uniform) the sub-stream kernel decoded this image's only unit
   const uint32_t k = (uint32_t)(u - im->unit0), n = im->stream_len;
   const int ncomp = im->ncomp;
   uint32_t start = v.starts[u], end = v.ends[u];
@@ -371,7 +509,10 @@ static int jpegdec_geom(const attwarp_jpegdec_image& d, int b, JdGeom& g) {
   return ATTWARP_OK;
 }
 
-static size_t jpegdec_bytes(int B) { return (size_t)(jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JdImage)); }
+// header, image records, sub-stream records (always present, so that the size depends on B alone)
+static size_t jpegdec_bytes(int B) {
+  return (size_t)(jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JdImage) + (uint64_t)B * sizeof(JdSub));
+}
 
 extern "C" size_t attwarp_jpegdec_table_bytes(const attwarp_jpegdec_image* images, int B) {
   if (!images || B <= 0 || B > JD_MAX_B) {
@@ -382,7 +523,18 @@ extern "C" size_t attwarp_jpegdec_table_bytes(const attwarp_jpegdec_image* image
 }
 
 extern "C" int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes) {
+  return attwarp_jpegdec_plan_ex(images, B, table, table_bytes, 0, 0);
+}
+
+extern "C" int attwarp_jpegdec_plan_ex(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes, int segment_bytes,
+                                       int max_rounds) {
   ATTWARP_REQUIRE(images, "jpegdec: null image array");
+  const bool substreams = segment_bytes != 0 || max_rounds != 0;
+  if (substreams) {
+    ATTWARP_REQUIRE(segment_bytes >= 32 && segment_bytes <= 512 && (segment_bytes & (segment_bytes - 1)) == 0,
+                    "jpegdec: segment_bytes=%d must be a power of two in 32..512", segment_bytes);
+    ATTWARP_REQUIRE(max_rounds >= 1 && max_rounds <= JD_SUB_MAX_ROUNDS, "jpegdec: max_rounds=%d outside 1..%d", max_rounds, JD_SUB_MAX_ROUNDS);
+  }
   ATTWARP_REQUIRE(B > 0, "jpegdec: non-positive batch size");
   if (B > JD_MAX_B) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: B=%d > 2^20", B);
   ATTWARP_REQUIRE(table, "jpegdec_plan: null table");
@@ -410,6 +562,8 @@ extern "C" int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, 
   h.table_bytes = need;
   h.off_images = jd_align(sizeof(attwarp_jpegdec_header), 16);
   JdImage* im = reinterpret_cast<JdImage*>(t + h.off_images);
+  JdSub* sub = reinterpret_cast<JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JdImage));
+  int32_t nsub = 0;
   uint64_t soff = jd_data_base(B, (int)units), ooff = 0, stream_bytes = 0;
   int32_t u0 = 0, it0 = 0, ct0 = 0;
   for (int b = 0; b < B; ++b) {
@@ -444,12 +598,39 @@ extern "C" int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, 
     it0 += (int32_t)((g.nblocks + JD_IDCT_TILE - 1) / JD_IDCT_TILE);
     ct0 += (int32_t)(((int64_t)d.H * d.W + JD_COLOR_TILE - 1) / JD_COLOR_TILE);
     stream_bytes = std::max(stream_bytes, d.stream_off + d.stream_len);
+    // sub-streams: a marker-less image (one unit) whose data is at least two segments long
+    const uint64_t nseg = substreams ? (d.stream_len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes : 0;
+    sub[b].segment_bytes = (uint32_t)segment_bytes;
+    sub[b].max_rounds = (uint32_t)max_rounds;
+    if (substreams && g.nunits == 1 && d.stream_len >= 2u * (uint64_t)segment_bytes && nseg <= (uint64_t)JD_SUB_MAX_SEGS) {
+      sub[b].nseg = (uint32_t)nseg;
+      sub[nsub++].image = b;
+    }
   }
+  // behind everything there was: the per-image sub-stream results, then the segments of every image planned for them
+  const uint64_t info_off = soff;
+  soff += jd_align((uint64_t)B * sizeof(JdSubInfo), 256);
+  for (int b = 0; b < B; ++b) {
+    sub[b].info_off = info_off;
+    sub[b].seg_off = soff;
+    soff += jd_align((uint64_t)sub[b].nseg * (sizeof(JdSegState) + sizeof(JdSegment)), 256);
+  }
+  h.reserved = nsub;
   h.scratch_bytes = soff;
   h.out_bytes = ooff;
   h.stream_bytes = stream_bytes;
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
+}
+
+extern "C" uint64_t attwarp_jpegdec_info_offset(const void* table_host) {
+  if (!table_host) return 0;
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, table_host, sizeof h);
+  if (h.magic != JD_MAGIC || h.B <= 0 || h.B > JD_MAX_B) return 0;
+  JdSub s;
+  std::memcpy(&s, static_cast<const uint8_t*>(table_host) + h.off_images + (uint64_t)h.B * sizeof(JdImage), sizeof s);
+  return s.info_off;
 }
 
 extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
@@ -458,7 +639,8 @@ extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_
   attwarp_jpegdec_header h;
   std::memcpy(&h, table_host, sizeof h);
   ATTWARP_REQUIRE(h.magic == JD_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.total_units >= h.B && h.total_units <= JD_MAX_TOTAL_UNITS &&
-                      h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS && h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS,
+                      h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS && h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS &&
+                      h.reserved >= 0 && h.reserved <= h.B,
                   "jpegdec_decode: not a table of attwarp_jpegdec_plan");
   ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegdec_decode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
   ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
@@ -469,6 +651,8 @@ extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_
   uint8_t* sc = static_cast<uint8_t*>(scratch);
   hipLaunchKernelGGL(jpegdec_scan_kernel, dim3(h.B), dim3(JD_NT), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegdec_scan_kernel")) return rc;
+  hipLaunchKernelGGL(jpegdec_substream_kernel, dim3(std::max(h.reserved, 1)), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch("jpegdec_substream_kernel")) return rc;
   hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegdec_entropy_kernel")) return rc;
   hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);

@@ -222,6 +222,192 @@ JD_FN uint32_t jd_block_index(const JdImage& im, int c, uint32_t m, int yy, int 
   return jd_block_at(im.block0[c], (uint32_t)im.bw[c], c == 0 ? im.hs : 1, c == 0 ? im.vs : 1, mx, my, yy, xx);
 }
 
+// ---- self-synchronising sub-streams: a marker-less unit cut into byte segments, one decoder each ----------------
+// A decoder's state between two symbols: where the next bit lies in the raw (stuffed) stream, which block of the MCU it
+// belongs to and the zigzag index of the next coefficient (0: a DC symbol is next).  The position is canonical: the offset
+// of the byte that holds the next bit, never a stuffed 00, and the bit's index in it (0: the top bit); at the unit's end
+// it is (end, 0).  Two decoders that consumed the same bits report the same state.
+struct JdSync {
+  uint32_t byte;                       // relative to the image's data
+  uint32_t bsk;                        // bit << 16 | slot << 8 | k
+};
+JD_FN bool jd_sync_equal(const JdSync& a, const JdSync& b) { return a.byte == b.byte && a.bsk == b.bsk; }
+
+constexpr uint32_t JD_NO_ERROR = 0xffffffffu;
+struct JdSegment {                     // what one segment's decode found (scratch, 32 bytes)
+  JdSync exit;                         // the state at the first symbol that starts at or behind the segment's end
+  uint32_t owned;                      // blocks whose DC symbol starts in the segment
+  uint32_t nend;                       // blocks that end in its decode
+  uint32_t eclean;                     // blocks that ended before its first error; JD_NO_ERROR: no error
+  uint32_t dc[3];                      // per component, the wrapping sum of the owned blocks' DC differences
+};
+static_assert(sizeof(JdSegment) == 32, "segment layout");
+
+// The reader's canonical position, in the reader's own coordinates (>= lo, the first byte of the image's data).  The bits
+// still in acc came from the cnt / 8 (rounded up) data bytes in front of the next raw byte; each step back over a data
+// byte also steps over the stuffed 00 behind an FF.
+JD_FN void jd_sync_position(const JdBits& br, uint32_t lo, uint32_t& byte, uint32_t& bit) {
+  uint32_t q = br.pos;                                        // (the next raw byte: pos counts bytes handed out, not loaded)
+  const uint32_t nb = (br.cnt + 7u) >> 3;                     // <= 7
+  for (uint32_t i = 0; i < nb && q > lo; ++i) {
+    --q;
+    if (q > lo && br.p[q & br.mask] == 0u && br.p[(q - 1u) & br.mask] == 0xffu) --q;
+  }
+  byte = q;
+  bit = (8u - (br.cnt & 7u)) & 7u;
+}
+
+// Where segment `seg` starts before anything is known: its first byte, one later if that is the 00 behind an FF; a block
+// is assumed to start there.  s: the image's data.
+JD_FN JdSync jd_segment_guess(const uint8_t* s, uint32_t seg, uint32_t segment_bytes, uint32_t uend) {
+  uint64_t b = (uint64_t)seg * segment_bytes;
+  if (b >= uend) b = uend;
+  else if (b > 0 && s[b] == 0u && s[b - 1] == 0xffu) ++b;     // (b + 1 <= uend)
+  JdSync e;
+  e.byte = (uint32_t)b;
+  e.bsk = 0;
+  return e;
+}
+JD_FN uint32_t jd_segment_end(uint32_t seg, uint32_t segment_bytes, uint32_t uend) {
+  const uint64_t e = ((uint64_t)seg + 1u) * segment_bytes;
+  return e < uend ? (uint32_t)e : uend;
+}
+
+JD_FN void jd_sync_open(JdBits& br, const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t uend) {
+  br.init(p, 0xffffffffu, lo + (entry.byte < uend ? entry.byte : uend), lo + uend);
+  br.refill();
+  const uint32_t bit = (entry.bsk >> 16) & 7u;
+  br.skip(bit < br.cnt ? bit : br.cnt);                       // (an entry in front of the end has a whole byte behind it)
+}
+
+// One segment, symbol by symbol, from `entry` until the position reaches seg_end.  p + lo: the image's data, p dword
+// aligned; uend: the unit's end, nothing at or behind it is read.  nb0 / nblk: luma blocks / all blocks of an MCU.  An
+// invalid code or a run past 63 marks the decode, skips one bit and starts a new block in the next slot, so a decoder that
+// began in the wrong place goes on until it falls in step; a code or value that needs bits behind the unit's end marks it
+// and ends at the unit's end.  Every turn of the loop consumes at least one bit.
+JD_FN void jd_decode_segment(const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t seg_end, uint32_t uend, const JdHuff* dc,
+                             const JdHuff* ac, uint32_t nb0, uint32_t nblk, JdSegment& r) {
+  JdBits br;
+  jd_sync_open(br, p, lo, entry, uend);
+  uint32_t slot = (entry.bsk >> 8) & 255u, k = entry.bsk & 63u;
+  if (slot >= nblk) slot = 0;
+  r.owned = 0; r.nend = 0; r.eclean = JD_NO_ERROR;
+  r.dc[0] = 0; r.dc[1] = 0; r.dc[2] = 0;
+  const uint32_t from = entry.byte < seg_end ? entry.byte : seg_end;
+  const uint32_t limit = (seg_end - from) * 8u + 8u;
+  uint32_t byte = 0, bit = 0;
+  bool at_end = false;
+  for (uint32_t it = 0; it < limit; ++it) {
+    br.refill();
+    if (br.pos - ((br.cnt + 7u) >> 3) >= lo + seg_end) {          // (an upper bound of the position)
+      jd_sync_position(br, lo, byte, bit);
+      if (byte >= lo + seg_end) break;
+    }
+    const uint32_t c = slot < nb0 ? 0u : slot - nb0 + 1u;
+    uint32_t st, s = 0, v = 0;
+    bool endblk = false;
+    if (k == 0) {
+      st = jd_symbol(br, dc[c], s);
+      s &= 15u;
+      if (!st && !br.bits(s, v)) st = ATTWARP_JPEGDEC_E_TRUNCATED;
+      if (!st) {
+        ++r.owned;
+        r.dc[c] += (uint32_t)jd_extend(v, s);
+        k = 1;
+      }
+    } else {
+      uint32_t rs = 0;
+      st = jd_symbol(br, ac[c], rs);
+      if (!st) {
+        const uint32_t run = rs >> 4;
+        s = rs & 15u;
+        if (s == 0) {
+          if (run != 15u) endblk = true;
+          else if (k + 16u > 64u) st = ATTWARP_JPEGDEC_E_COEFF;
+          else k += 16u;
+        } else if (k + run > 63u) st = ATTWARP_JPEGDEC_E_COEFF;
+        else if (!br.bits(s, v)) st = ATTWARP_JPEGDEC_E_TRUNCATED;
+        else k += run + 1u;
+      }
+      if (!st && k >= 64u) endblk = true;
+    }
+    if (st) {
+      if (r.eclean == JD_NO_ERROR) r.eclean = r.nend;
+      br.refill();
+      if (st == (uint32_t)ATTWARP_JPEGDEC_E_TRUNCATED || br.cnt == 0) { at_end = true; break; }
+      br.skip(1);
+      slot = slot + 1u == nblk ? 0u : slot + 1u;
+      k = 0;
+    } else if (endblk) {
+      ++r.nend;
+      slot = slot + 1u == nblk ? 0u : slot + 1u;
+      k = 0;
+    }
+  }
+  if (at_end) { byte = lo + uend; bit = 0; }
+  else jd_sync_position(br, lo, byte, bit);
+  r.exit.byte = byte - lo;
+  r.exit.bsk = bit << 16 | slot << 8 | k;
+}
+
+// What the converged states must satisfy, segment by segment: `before` blocks start in front of the segment.  Bit 0: the
+// segment contradicts a sequential decode of `expected` blocks (an error in front of the end of block expected - 1, or an
+// entry slot that does not follow from the count); bit 1: block expected - 1 ends in this segment, cleanly.
+JD_FN uint32_t jd_segment_check(const JdSync& entry, const JdSegment& r, uint32_t before, uint32_t expected, uint32_t nblk) {
+  const uint32_t inprog = (entry.bsk & 63u) != 0u;
+  if (before < inprog) return 1u;
+  const uint32_t done = before - inprog;                     // blocks that ended in front of the segment
+  if (done >= expected) return 0u;                           // behind the last block: whatever follows it is tolerated
+  if (((entry.bsk >> 8) & 255u) != done % nblk) return 1u;
+  const uint32_t last = expected - 1u - done;
+  if (last < r.nend) return r.eclean > last ? 2u : 1u;
+  return r.eclean == JD_NO_ERROR ? 0u : 1u;
+}
+
+// The write pass of one segment from its TRUE entry: the rest of a block begun earlier is skipped, then every owned block
+// is decoded in full (reading past the segment's end until it ends) and stored whole at its true index.  pred: the
+// predictors at the segment's start (the sums of all DC differences in front of it), before: the owned blocks in front of
+// it; blocks with ordinal >= expected are dropped.  blk: 64 int16 of the caller's (dword aligned).  -> status
+JD_FN uint32_t jd_write_segment(const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t uend, const JdHuff* dc, const JdHuff* ac,
+                                const JdImage& im, uint32_t nb0, uint32_t nblk, uint32_t before, const uint32_t* pred0, uint32_t owned,
+                                uint32_t expected, int16_t* blk, const uint8_t* zz, int16_t* coef) {
+  if (before >= expected || owned == 0) return 0;
+  JdBits br;
+  jd_sync_open(br, p, lo, entry, uend);
+  uint32_t slot = (entry.bsk >> 8) & 255u, k = entry.bsk & 63u;
+  if (slot >= nblk) slot = 0;
+  if (k != 0) {
+    const uint32_t c = slot < nb0 ? 0u : slot - nb0 + 1u;
+    for (int it = 0; it < 63 && k < 64u; ++it) {
+      uint32_t rs, v;
+      if (const uint32_t st = jd_symbol(br, ac[c], rs)) return st;
+      const uint32_t run = rs >> 4, s = rs & 15u;
+      if (s == 0) {
+        if (run != 15u) break;
+        if (k + 16u > 64u) return ATTWARP_JPEGDEC_E_COEFF;
+        k += 16u;
+        continue;
+      }
+      if (k + run > 63u) return ATTWARP_JPEGDEC_E_COEFF;
+      if (!br.bits(s, v)) return ATTWARP_JPEGDEC_E_TRUNCATED;
+      k += run + 1u;
+    }
+    slot = slot + 1u == nblk ? 0u : slot + 1u;
+  }
+  int32_t pred[3] = {(int32_t)pred0[0], (int32_t)pred0[1], (int32_t)pred0[2]};
+  const uint32_t n = owned < expected - before ? owned : expected - before;
+  const uint32_t hs = (uint32_t)im.hs;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t o = before + i, m = o / nblk, j = o - m * nblk;
+    const uint32_t c = j < nb0 ? 0u : j - nb0 + 1u;
+    __builtin_memset(blk, 0, 128);
+    if (const uint32_t st = jd_decode_block(br, dc[c], ac[c], pred[c], blk, zz)) return st;
+    const uint32_t bi = jd_block_index(im, (int)c, m, c == 0 ? (int)(j / hs) : 0, c == 0 ? (int)(j % hs) : 0);
+    if (bi < im.nblocks) __builtin_memcpy(coef + (size_t)bi * 64u, blk, 128);
+  }
+  return 0;
+}
+
 // ---- the integer IDCT of jidctint.c (CONST_BITS 13, PASS1_BITS 2), 32-bit wrap-around arithmetic ---------------------------------
 JD_FN int32_t jd_sra(uint32_t x, int n) { return (int32_t)x >> n; }
 JD_FN void jd_idct_1d(const uint32_t i[8], int shift, int32_t o[8]) {

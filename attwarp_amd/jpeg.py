@@ -21,6 +21,9 @@ JPEGDEC_MAX_BLOCKS = _lib.JPEGDEC_MAX_BLOCKS            # 8x8 blocks per image, 
 STATUS_NAMES = _lib.JPEGDEC_STATUS_NAMES
 _ORDERS = {"rgb": _lib.RGB, "bgr": _lib.BGR}
 _IMAGE_DTYPE = np.dtype(_lib.JpegDecImage)
+SEGMENT_BYTES = 256                                     # the sub-streams' defaults: bytes per segment,
+MAX_ROUNDS = 64                                         # rounds after which an image falls back to the sequential decode
+MAX_SEGMENTS = 1 << 14                                  # an image with more segments is decoded sequentially
 _ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
            35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
 _UNSUPPORTED_FRAMES = {0xC2: "progressive", 0xC3: "lossless", 0xC5: "hierarchical", 0xC6: "hierarchical", 0xC7: "hierarchical",
@@ -172,11 +175,29 @@ def _file_bytes(f):
     return f
 
 
-def plan(files, mode: str = "RGB", order: str = "rgb"):
+def _substream_plan(substreams, segment_bytes, max_rounds):
+    if substreams not in ("auto", True, False):
+        raise ValueError("jpeg: substreams must be 'auto', True or False")
+    if substreams is False:
+        return 0, 0
+    sb = SEGMENT_BYTES if segment_bytes is None else int(segment_bytes)
+    mr = MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    if sb not in (32, 64, 128, 256, 512) or not 1 <= mr <= 65536:
+        raise ValueError(f"jpeg: segment_bytes={sb} must be a power of two in 32..512, max_rounds={mr} in 1..65536")
+    return sb, mr
+
+
+def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segment_bytes: Optional[int] = None,
+         max_rounds: Optional[int] = None):
     """Host only (no device is touched): files -> ``(parsed, table, header)``: :func:`parse_jpeg` of every file and the table
-    ``attwarp_jpegdec_plan`` writes for them, which depends on the headers alone."""
+    ``attwarp_jpegdec_plan_ex`` writes for them, which depends on the headers and the files' lengths alone.  ``substreams``:
+    "auto" / True cut every marker-less file of at least two segments into ``segment_bytes`` (a power of two in 32..512,
+    default :data:`SEGMENT_BYTES`) decoded by one lane each, in at most ``max_rounds`` rounds (default :data:`MAX_ROUNDS`);
+    False plans every file for the sequential decode, one wave per restart interval.  Each ``parsed[i]["segments"]`` holds
+    the segments planned (0: sequential)."""
     if mode not in _lib.JPEGDEC_MODE_IDS or order not in _ORDERS:
         raise ValueError(f"jpeg: mode must be one of {sorted(_lib.JPEGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
+    sb, mr = _substream_plan(substreams, segment_bytes, max_rounds)
     files = [_file_bytes(f) for f in files]
     parsed = [parse_jpeg(f, i) for i, f in enumerate(files)]
     B = len(parsed)
@@ -201,9 +222,12 @@ def plan(files, mode: str = "RGB", order: str = "rgb"):
         raise ValueError("jpeg: " + lib.attwarp_last_error().decode("utf-8", "replace"))
     table = np.empty(nbytes, dtype=np.uint8)
     try:
-        call("attwarp_jpegdec_plan", rp, B, table.ctypes.data, nbytes)
+        call("attwarp_jpegdec_plan_ex", rp, B, table.ctypes.data, nbytes, sb, mr)
     except _lib.AttWarpError as e:
         raise ValueError(f"jpeg: {e}") from None
+    for p, n in zip(parsed, lens):
+        nseg = -(-n // sb) if sb else 0
+        p["segments"] = nseg if p["units"] == 1 and n >= 2 * sb and nseg <= MAX_SEGMENTS else 0
     return parsed, table, _lib.JpegDecHeader.from_address(table.ctypes.data)
 
 
@@ -213,14 +237,18 @@ class JpegFiles:
     to back and uploads it, with the table, in ONE transfer; the plan depends only on what the headers say.  ``mode``:
     "RGB" (what ``Image.open(f).convert("RGB")`` gives), "L" (``.convert("L")``) or "keep" (grey files one channel, colour
     files three); ``order="bgr"`` swaps a 3-channel result.  ``out``: a uint8 device buffer of at least :attr:`out_bytes`
-    bytes.  Unsupported files raise ValueError before any launch."""
+    bytes.  ``substreams``, ``segment_bytes``, ``max_rounds``: see :func:`plan`; ``substreams=False`` decodes every file
+    sequentially.  Pixels and statuses do not depend on them.  Unsupported files raise ValueError before any launch."""
 
-    def __init__(self, files, mode: str = "RGB", order: str = "rgb", out: Optional[torch.Tensor] = None, device=None):
+    def __init__(self, files, mode: str = "RGB", order: str = "rgb", out: Optional[torch.Tensor] = None, device=None,
+                 substreams="auto", segment_bytes: Optional[int] = None, max_rounds: Optional[int] = None):
         from .pipeline import _upload_filled
         files = [_file_bytes(f) for f in files]
         if not files:
             raise ValueError("JpegFiles: empty batch")
-        parsed, self.table_host, self.header = plan(files, mode, order)
+        parsed, self.table_host, self.header = plan(files, mode, order, substreams, segment_bytes, max_rounds)
+        self.segment_bytes, self.max_rounds = _substream_plan(substreams, segment_bytes, max_rounds)      # (0, 0): off
+        self._info_off = int(_lib.load().attwarp_jpegdec_info_offset(self.table_host.ctypes.data))
         B = len(files)
         dev = torch.device(device) if device is not None else (out.device if out is not None else _lib.default_device())
         if dev.type == "cuda" and dev.index is None:
@@ -270,6 +298,18 @@ class JpegFiles:
         """Decoding units (restart intervals) planned per image, from the headers alone: one wave each."""
         return [p["units"] for p in self.parsed]
 
+    def substreams(self) -> List[int]:
+        """Segments planned per image, from the headers and the files' lengths alone; 0: the image is decoded sequentially
+        (it has restart intervals, is shorter than two segments, or sub-streams are off)."""
+        return [p["segments"] for p in self.parsed]
+
+    def substream_info(self) -> List[tuple]:
+        """After a :meth:`run` (synchronises): per image ``(segments, rounds, accepted)`` as the device left them: the
+        segments planned, the rounds its workgroup ran, and 1 if the sub-streams decoded the image, 0 if the sequential
+        decode did.  For measurements and tests."""
+        raw = self.scratch[self._info_off:self._info_off + self.B * 16].cpu().numpy().view(np.uint32).reshape(self.B, 4)
+        return [(int(r[0]), int(r[1]), int(r[2])) for r in raw]
+
     def restarts(self) -> List[int]:
         """After a :meth:`run` (synchronises): restart markers the device found in front of each image's data end; units - 1
         in a file that decodes.  For measurements and tests."""
@@ -277,7 +317,7 @@ class JpegFiles:
         return [int(r[3]) for r in st]
 
     def run(self):
-        """Four launches on the current stream -> ``(views, status)``: the images, and an int32 [B] device tensor (0: ok,
+        """Five launches on the current stream -> ``(views, status)``: the images, and an int32 [B] device tensor (0: ok,
         else ``STATUS_NAMES[code]``; such an image's pixels are unspecified).  No host synchronisation and no host-dependent
         argument: capturable in a graph."""
         with torch.cuda.device(self._dev):
@@ -286,10 +326,11 @@ class JpegFiles:
         return self.views(), self.status
 
 
-def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto") -> List[torch.Tensor]:
     """JPEG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
-    first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all."""
-    views, status = JpegFiles(files, mode, order, device=device).run()
+    first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all.
+    ``substreams``: see :func:`plan`."""
+    views, status = JpegFiles(files, mode, order, device=device, substreams=substreams).run()
     st = status.cpu().tolist()
     for i, s in enumerate(st):
         if s:
@@ -298,6 +339,6 @@ def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None) -> Li
     return views
 
 
-def read_jpeg(paths, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+def read_jpeg(paths, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto") -> List[torch.Tensor]:
     """:func:`decode_jpeg` of the files at ``paths``."""
-    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device)
+    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device, substreams)

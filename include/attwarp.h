@@ -923,7 +923,7 @@ ATTWARP_API int attwarp_pngdec_decode(const void* table_host, const void* table_
  *   2. attwarp_jpegdec_table_bytes -> size; attwarp_jpegdec_plan writes header and records into HOST memory;
  *   3. copy the table (8-byte aligned) and header.stream_bytes packed bytes to the device;
  *   4. attwarp_jpegdec_decode(host copy, device copy, the packed bytes, scratch of header.scratch_bytes (256-byte
- *      aligned), out of at least header.out_bytes, status int32 [B], stream): four launches, none with an argument that
+ *      aligned), out of at least header.out_bytes, status int32 [B], stream): five launches, none with an argument that
  *      depends on anything read back, so a call can be captured in a graph.  Image b is the dense [H, W, out_channels]
  *      block at out + sum of the blocks before it.
  * Units: with a restart interval Ri an image has ceil(MCUs / Ri) units (else one), known from the headers; the k-th restart
@@ -939,6 +939,22 @@ ATTWARP_API int attwarp_pngdec_decode(const void* table_host, const void* table_
  * mode: ATTWARP_JPEGDEC_RGB (3 channels, grey replicated), ATTWARP_JPEGDEC_L (1 channel: colour files give
  * (19595 R + 38470 G + 7471 B + 32768) >> 16 of the RGB pixel, grey files the plane), ATTWARP_JPEGDEC_KEEP (1 or 3).
  * order = ATTWARP_BGR swaps a 3-channel output.
+ * Sub-streams (attwarp_jpegdec_plan_ex; attwarp_jpegdec_plan plans without them): an image of ONE unit (no restart
+ * interval, or one of at least all its MCUs) whose data is at least two segments of segment_bytes long (and at most 16384
+ * of them) is cut into such segments, known from the headers and the length alone.  The second of the five launches gives
+ * it one workgroup (the launch always happens; header.reserved holds the workgroups that have work).  A lane decodes a
+ * segment from a guessed state (a block starts at the segment's first byte), and every round hands each segment's exit
+ * state (position in the raw stream, block of the MCU, coefficient index) to the next segment as its entry, until no
+ * entry changes: after round r segments 0..r enter where a sequential decoder would, so a fixed point is the sequential
+ * decode.  A decoder that meets an invalid code goes on one bit later, so a wrong guess falls in step instead of dying.
+ * The unit is ACCEPTED only if the rounds end within max_rounds, block MCUs x blocks-per-MCU - 1 ends inside the data,
+ * no segment up to that one met an error in front of it, and every entry's block slot follows from the count of blocks in
+ * front of it; then the blocks are written with their true indices and DC predictors, and the one-wave-per-unit kernel
+ * skips the image.  FALLBACK: any other image, a rejected one included, is decoded by that kernel exactly as without
+ * sub-streams; the sub-stream path never sets a status, so status[] and the pixels do not depend on the plan.  The time
+ * of a workgroup is bounded by max_rounds x ceil(segments / 256) segment decodes.  Scratch: the states stay at offset 0;
+ * per image 16 bytes (uint32 segments planned, rounds run, accepted, 0), written on every run, lie at the offset held
+ * in the sub-stream records, which follow the image records in the table (one per image, always present).
  * Limits (ATTWARP_E_UNSUPPORTED from the planner): at most ATTWARP_JPEGDEC_MAX_UNITS units and fewer than
  * ATTWARP_JPEGDEC_MAX_BLOCKS 8x8 blocks per image (offsets inside an image stay below 2^31: 128 bytes of coefficients
  * per block), an image's data below 2^31 bytes, at most 2^20 images and 2^30 units per call. */
@@ -966,12 +982,18 @@ typedef struct attwarp_jpegdec_image {
 } attwarp_jpegdec_image;
 typedef struct attwarp_jpegdec_header {            /* first bytes of a table written by attwarp_jpegdec_plan */
   uint32_t magic;
-  int32_t B, total_units, idct_tiles, color_tiles, reserved;
+  int32_t B, total_units, idct_tiles, color_tiles;
+  int32_t reserved;                                /* workgroups of the sub-stream launch that have an image; 0: none planned */
   uint64_t table_bytes, scratch_bytes, out_bytes, stream_bytes;
   uint64_t off_images;
 } attwarp_jpegdec_header;
 ATTWARP_API size_t attwarp_jpegdec_table_bytes(const attwarp_jpegdec_image* images, int B);
 ATTWARP_API int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes);
+/* The same with sub-streams: segment_bytes a power of two in 32..512, max_rounds in 1..65536; (0, 0): attwarp_jpegdec_plan. */
+ATTWARP_API int attwarp_jpegdec_plan_ex(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes, int segment_bytes,
+                       int max_rounds);
+/* Where a table keeps, per image, the uint32[4] (segments planned, rounds, accepted, 0) in the scratch buffer. */
+ATTWARP_API uint64_t attwarp_jpegdec_info_offset(const void* table_host);
 ATTWARP_API int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
 

@@ -5,13 +5,16 @@
 Cases: B = 32 and B = 256 files of a TextVQA-like size mix (1024 x 768, 768 x 1024, 1024 x 683, 1024 x 1024, 800 x 600,
 640 x 480, cycling), and 256 files of 1024 x 1024; photo-like content (tests/png_cases.photo, eight prototypes per size
 rolled to B different images), written by Pillow at quality 75, 4:2:0.  File kinds:
-  plain    Pillow's default: no restart markers, ONE decoding unit (one wave, one lane) per file;
+  plain    Pillow's default: no restart markers, ONE decoding unit per file: self-synchronising sub-streams (one workgroup
+           per file, one lane per segment), or with them off one wave, one lane per file;
   rows     restart_marker_rows=1: one unit per MCU row.
 Per case and kind, one process, ONE run:
-  * JpegFiles.run on a planned batch (HIP events around the four launches; the compressed bytes are already on the device);
+  * JpegFiles.run on a planned batch (HIP events around the five launches; the compressed bytes are already on the device);
+    for plain files also with substreams=False ("run_substreams_off") and over --sweep segment sizes, with the rounds and
+    accepted counts the device reports;
   * a plain streaming launch (csrc/calib.hip, tuning flavour) that reads and writes as many bytes as the decoded pixels: the ruler;
   * the route users take today: Image.open(...).convert("RGB") on 16 threads + pipeline.upload_images, against
-    decode_jpeg (marker walk, ONE upload of the compressed bytes, four launches, the status read back), both on the host
+    decode_jpeg (marker walk, ONE upload of the compressed bytes, five launches, the status read back), both on the host
     clock around a synchronise, both including their upload.
 --only runs JpegFiles.run of one kind and case N times and nothing else: the workload for a kernel trace, in a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/jpegdec_bench.py --only plain:mix_B256 --loops 3
@@ -86,13 +89,35 @@ def make_files(kind, imgs):
         return list(pool.map(one, imgs))
 
 
-def measure(dev, kind, files):
+def substream_summary(jf):
+    info = jf.substream_info()
+    planned = [i for i in info if i[0]]
+    return {"segment_bytes": jf.segment_bytes, "max_rounds": jf.max_rounds, "images_planned": len(planned),
+            "images_accepted": int(sum(i[2] for i in planned)), "segments_mean": float(np.mean([i[0] for i in planned])) if planned else 0.0,
+            "rounds_max": max([i[1] for i in planned], default=0), "rounds_mean": float(np.mean([i[1] for i in planned])) if planned else 0.0}
+
+
+def measure(dev, kind, files, sweep=()):
     from PIL import Image
     from attwarp_amd import _lib, jpeg, pipeline
     res = {"kind": kind, "file_bytes": int(sum(len(f) for f in files))}
+    if kind == "plain":
+        off = jpeg.JpegFiles(files, device=dev, substreams=False)
+        res["run_substreams_off"] = timed(off.run, n=1, groups=3)
+        first = off.buffer.clone()
+        del off
+        res["sweep"] = []
+        for sb in sweep:
+            sw = jpeg.JpegFiles(files, device=dev, segment_bytes=sb)
+            entry = timed(sw.run)
+            entry.update(substream_summary(sw), equals_substreams_off=bool(torch.equal(sw.buffer, first)))
+            res["sweep"].append(entry)
+            del sw
+        del first
     jf = jpeg.JpegFiles(files, device=dev)
     views, status = jf.run()
     assert status.cpu().tolist() == [0] * len(files)
+    res["substreams"] = substream_summary(jf)
     res["equals_pillow"] = bool(all(np.array_equal(v.cpu().numpy(), np.asarray(Image.open(io.BytesIO(f)).convert("RGB")))
                                     for v, f in list(zip(views, files))[:6]))
     res["units_per_image_mean"] = float(np.mean(jf.units()))
@@ -151,6 +176,8 @@ def main():
     ap.add_argument("--only", default=None, help="KIND:CASE -- run JpegFiles.run of that batch --loops times and exit (for a kernel trace)")
     ap.add_argument("--loops", type=int, default=3)
     ap.add_argument("--cases", default=",".join(CASES), help="comma-separated subset of " + ", ".join(CASES))
+    ap.add_argument("--sweep", default="64,128,256", help="segment sizes the plain rows are also run with ('' for none)")
+    ap.add_argument("--substreams", default="auto", choices=("auto", "off"), help="with --only: the plan of the traced run")
     ap.add_argument("--shares", nargs="+", default=None, help="KIND=kernel_trace.csv ...: write the per-kernel shares file and exit")
     args = ap.parse_args()
     if args.shares:
@@ -163,7 +190,7 @@ def main():
     if args.only:
         kind, case = args.only.split(":")
         B, sizes = CASES[case]
-        jf = jpeg.JpegFiles(make_files(kind, images(B, sizes)), device=dev)
+        jf = jpeg.JpegFiles(make_files(kind, images(B, sizes)), device=dev, substreams="auto" if args.substreams == "auto" else False)
         for _ in range(args.loops):
             jf.run()
         torch.cuda.synchronize()
@@ -175,7 +202,7 @@ def main():
         imgs = images(B, sizes)
         entry = {"case": case, "B": B, "sizes_HW": [list(s) for s in sizes], "kinds": []}
         for kind in KINDS:
-            entry["kinds"].append(measure(dev, kind, make_files(kind, imgs)))
+            entry["kinds"].append(measure(dev, kind, make_files(kind, imgs), [int(s) for s in args.sweep.split(",") if s]))
             print(json.dumps({"case": case, **entry["kinds"][-1]}), flush=True)
             torch.cuda.empty_cache()
         res["cases"].append(entry)
