@@ -433,9 +433,12 @@ JD_FN void jd_idct_1d(const uint32_t i[8], int shift, int32_t o[8]) {
 JD_FN uint32_t jd_clamp8(int32_t v) { return v < 0 ? 0u : v > 255 ? 255u : (uint32_t)v; }
 
 // ---- chroma up-sampling ("fancy", jdsample.c) and colour (jdcolor.c) -----------------------------------------------------------
-// p: the plane (pitch bytes per row), dw x dh its true size; (x, y) an output pixel.
+// p: the plane (pitch bytes per row), dw x dh its true size; (x, y) an output pixel.  libjpeg picks the triangle filter
+// only for a component with `downsampled_width > 2` (jinit_upsampler in jdsample.c); a plane of one or two columns is
+// replicated instead, in both directions: sample (x >> 1, y >> 1) at 2 x 2, (x >> 1, y) at 2 x 1.
 JD_FN int32_t jd_chroma(const uint8_t* p, int pitch, int dw, int dh, int hs, int vs, int x, int y) {
   if (hs == 1) return p[(size_t)y * pitch + x];
+  if (dw <= 2) return p[(size_t)(vs == 2 ? y >> 1 : y) * pitch + (x >> 1)];
   const int i = x >> 1;
   const int in = (x & 1) ? (i + 1 < dw ? i + 1 : i) : (i > 0 ? i - 1 : 0);
   if (vs == 1) {

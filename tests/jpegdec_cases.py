@@ -193,13 +193,21 @@ class BitWriter:
         return bytes(out)
 
 
-def tiny_file(W, H, data, q=1):
-    """A grey file with DC_TINY / AC_TINY, a constant quantisation table and the given entropy data."""
+def hand_file(W, H, data, dc=DC_TINY, ac=AC_TINY, q=1, ri=0, eoi=b"\xff\xd9"):
+    """A grey file with the (counts, symbols) tables dc / ac, a constant quantisation table, a DRI segment if ri, the given
+    entropy data and whatever is to stand where the EOI does."""
     segs = [(0xE0, b"JFIF\0\x01\x01\0\0\x01\0\x01\0\0"), (0xDB, bytes([0]) + bytes([q]) * 64),
             (0xC0, struct.pack(">BHHB", 8, H, W, 1) + bytes([1, 0x11, 0])),
-            (0xC4, bytes([0x00]) + bytes(DC_TINY[0]) + bytes(DC_TINY[1]) + bytes([0x10]) + bytes(AC_TINY[0]) + bytes(AC_TINY[1])),
-            (0xDA, bytes([1, 1, 0x00, 0, 63, 0]))]
-    return join(segs, data + b"\xff\xd9")
+            (0xC4, bytes([0x00]) + bytes(dc[0]) + bytes(dc[1]) + bytes([0x10]) + bytes(ac[0]) + bytes(ac[1]))]
+    if ri:
+        segs.append((0xDD, struct.pack(">H", ri)))
+    segs.append((0xDA, bytes([1, 1, 0x00, 0, 63, 0])))
+    return join(segs, data + eoi)
+
+
+def tiny_file(W, H, data, q=1):
+    """A grey file with DC_TINY / AC_TINY, a constant quantisation table and the given entropy data."""
+    return hand_file(W, H, data, q=q)
 
 
 def _dc15(w, v):

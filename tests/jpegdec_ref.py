@@ -380,11 +380,14 @@ def idct_planes(p, planes):
 
 
 def upsample(pl, hs, vs, W, H):
-    """"Fancy" up-sampling of a chroma plane (already cropped to its true size) by hs x vs, cropped to W x H."""
+    """"Fancy" up-sampling of a chroma plane (already cropped to its true size) by hs x vs, cropped to W x H.  A plane of
+    one or two columns is replicated instead: jdsample.c takes the triangle filter only when downsampled_width > 2."""
     p = pl.astype(np.int32)
     dh, dw = p.shape
     if hs == 1 and vs == 1:
         return p[:H, :W]
+    if dw <= 2:
+        return np.repeat(np.repeat(p, vs, 0), hs, 1)[:H, :W]
     if vs == 2:
         up = np.concatenate([p[:1], p[:-1]])
         dn = np.concatenate([p[1:], p[-1:]])

@@ -9,7 +9,7 @@ import functools
 import jpegdec_cases as C
 import jpegdec_ref as D
 
-SEGMENT_BYTES = (32, 64, 128, 256)
+SEGMENT_BYTES = (32, 64, 128, 256, 512)
 MAX_ROUNDS = 256                                           # the slowest file here needs 233 rounds at 32 bytes
 STRADDLE = "smooth_512x384_q90_s2"                          # FF | 00 across a boundary at 32, 64 and 128 bytes
 LARGE = "smooth_400x300_q95_s0"                             # >= 33 KB, quick to synchronise: the stride loop at 32 bytes

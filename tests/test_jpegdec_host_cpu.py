@@ -1,6 +1,6 @@
 """The JPEG decoder's shared host / device core (attwarp_amd/csrc/jpegdec_blocks.hpp) on the CPU under AddressSanitizer and
 UndefinedBehaviorSanitizer: tests/jpegdec_host_main.cpp is compiled as a stand-alone program and run as a child process
-over the whole corpus, the malformed files included.  It must end clean and print, per file, the restatement's status,
+over the whole corpus, the malformed files and the longest hand-written blocks (tests/jpegdec_limit_cases.py) included.  It must end clean and print, per file, the restatement's status,
 the CRC-32 of the coefficients and the planned units."""
 import os
 import shutil
@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 import jpegdec_cases as C
+import jpegdec_limit_cases as L
 import jpegdec_ref as D
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,8 +37,9 @@ def test_host_core_under_sanitizers_equals_the_restatement(tmp_path):
     subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined",
                     "-Xarch_host", "-fno-sanitize-recover=undefined", "-I" + CSRC, os.path.join(HERE, "jpegdec_host_main.cpp"), "-o", str(exe)],
                    check=True, capture_output=True, text=True, timeout=600)
-    names = [n for n, _ in C.good()] + [n for n, _, _ in C.malformed()]
-    files = [f for _, f in C.good()] + [f for _, f, _ in C.malformed()]
+    limits = L.long_files() + L.long_cuts()                  # blocks as long as a block can be, whole and cut short
+    names = [n for n, _ in C.good()] + [n for n, _, _ in C.malformed()] + [n for n, _ in limits]
+    files = [f for _, f in C.good()] + [f for _, f, _ in C.malformed()] + [f for _, f in limits]
     (tmp_path / "corpus.bin").write_bytes(corpus(files))
     r = subprocess.run([str(exe), str(tmp_path / "corpus.bin")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stderr == "", r.stderr[-4000:]

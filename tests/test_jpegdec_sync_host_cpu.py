@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import jpegdec_cases as C
+import jpegdec_limit_cases as L
 import jpegdec_ref as D
 import jpegdec_sync_cases as SC
 import jpegdec_sync_ref as R
@@ -25,6 +26,7 @@ def test_sub_stream_core_under_sanitizers_equals_the_restatement(tmp_path):
                     "-Xarch_host", "-fno-sanitize-recover=undefined", "-I" + CSRC, os.path.join(HERE, "jpegdec_sync_host_main.cpp"), "-o", str(exe)],
                    check=True, capture_output=True, text=True, timeout=600)
     named = list(C.good()) + list(SC.good()) + [(n, f) for n, f, _ in C.malformed()]
+    named += [(n, f) for n, f in L.long_files() + L.long_cuts() if D.parse(f)["ri"] == 0]      # many segments inside one block
     (tmp_path / "corpus.bin").write_bytes(corpus([f for _, f in named]))
     seen = set()
     for S in (32, 128):
