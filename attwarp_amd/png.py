@@ -337,6 +337,15 @@ class PngFiles:
         st = self.scratch[:self.B * 32].cpu().numpy().view(np.uint32).reshape(self.B, 8)
         return [(int(r[1]), int(r[7]), int(r[0])) for r in st]
 
+    def kept(self):
+        """After a :meth:`run` (synchronises): per image the byte positions the marker scan kept, the stream's start first
+        (empty when the zlib header failed).  For measurements and tests."""
+        B, U = self.B, PNGDEC_MAX_UNITS
+        nunits = self.scratch[:B * 32].cpu().numpy().view(np.uint32).reshape(B, 8)[:, 0]
+        off = -(-B * 32 // 16) * 16 + B * U * 32                 # behind the states and the unit records (pd_kept_off)
+        pos = self.scratch[off:off + B * U * 4].cpu().numpy().view(np.uint32).reshape(B, U)
+        return [pos[b, :int(nunits[b])].tolist() for b in range(B)]
+
     def run(self):
         """Seven launches on the current stream -> ``(views, status)``: the images, and an int32 [B] device tensor (0: ok,
         else ``STATUS_NAMES[code]``; such an image's pixels are unspecified).  No host synchronisation and no host-dependent

@@ -141,7 +141,7 @@ def build(lens, allow_single):
     return tab
 
 
-def _decode(br, tab):
+def _decode(br, tab, used=None):
     br.refill()
     e = tab[br.acc & 0x7FFF]
     if e is None:
@@ -151,6 +151,8 @@ def _decode(br, tab):
         return E_TRUNCATED, 0
     br.acc >>= l
     br.cnt -= l
+    if used is not None:
+        used.add(l)
     return OK, sym
 
 
@@ -168,6 +170,7 @@ class Result:
     def __init__(self, start):
         self.status, self.start, self.end, self.out, self.final, self.dependent = OK, start, start, bytearray(), 0, 0
         self.seen = set()             # (length, distance) of every match: the tests' token walk
+        self.lit_lens, self.dist_lens = set(), set()   # code lengths of the literals and length symbols / distances decoded
 
     @property
     def out_len(self):
@@ -267,9 +270,12 @@ def inflate(s, start, cap, kept=None, write=True):
                 if lit is None:
                     return fail(E_CODE_LENGTHS)
             while True:
-                rc, sym = _decode(br, lit)
+                eob = set()
+                rc, sym = _decode(br, lit, eob)
                 if rc:
                     return fail(rc)
+                if sym != 256:
+                    R_.lit_lens |= eob
                 if sym < 256:
                     if len(out) >= cap:
                         return fail(E_OVERFLOW)
@@ -284,7 +290,7 @@ def inflate(s, start, cap, kept=None, write=True):
                 if v is None:
                     return fail(E_TRUNCATED)
                 ln = R.LEN_BASE[sym] + v
-                rc, sym = _decode(br, dist)
+                rc, sym = _decode(br, dist, R_.dist_lens)
                 if rc:
                     return fail(rc)
                 if sym >= 30:
