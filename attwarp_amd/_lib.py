@@ -171,6 +171,10 @@ SIGNATURES = {
     "attwarp_jpegdec_plan_ex": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int]),
     "attwarp_jpegdec_info_offset": (ctypes.c_uint64, [c_void_p]),
     "attwarp_jpegdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # progressive files: every scan planned, scans by dependency level
+    "attwarp_jpegdec_scans_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "attwarp_jpegdec_plan_scans": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int]),
+    "attwarp_jpegdec_decode_scans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),
@@ -194,6 +198,8 @@ PNGDEC_STATUS_NAMES = ("OK", "E_CRC", "E_ZLIB_HEADER", "E_TRUNCATED", "E_BLOCK_T
 # attwarp_jpegdec_*: modes, limits and status codes (ATTWARP_JPEGDEC_* of include/attwarp.h)
 JPEGDEC_MODE_IDS = {"RGB": 0, "L": 1, "keep": 2}
 JPEGDEC_MAX_UNITS, JPEGDEC_MAX_BLOCKS = 65536, 1 << 24
+JPEGDEC_MAX_SCANS = 64
+JPEGDEC_RECORD_BYTES = 2152                              # one image record of a planned table (JdImage of jpegdec_blocks.hpp)
 JPEGDEC_STATUS_NAMES = ("OK", "E_TRUNCATED", "E_HUFFMAN", "E_COEFF", "E_RESTART", "E_NO_EOI")
 (JPEGDEC_OK, JPEGDEC_E_TRUNCATED, JPEGDEC_E_HUFFMAN, JPEGDEC_E_COEFF, JPEGDEC_E_RESTART, JPEGDEC_E_NO_EOI) = range(6)
 # attwarp_panel_grid: limits, flags and source kinds (ATTWARP_PANEL_* of include/attwarp.h)
@@ -260,6 +266,13 @@ class JpegDecImage(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("order", ctypes.c_int32), ("qt", ctypes.c_uint16 * 64 * 3),
                 ("dc_counts", ctypes.c_uint8 * 16 * 3), ("ac_counts", ctypes.c_uint8 * 16 * 3),
                 ("dc_symbols", ctypes.c_uint8 * 256 * 3), ("ac_symbols", ctypes.c_uint8 * 256 * 3)]
+
+
+class JpegDecScan(ctypes.Structure):
+    """attwarp_jpegdec_scan: one scan of a progressive file of an attwarp_jpegdec_plan_scans call."""
+    _fields_ = [("image", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("comp", ctypes.c_int32 * 3), ("ss", ctypes.c_int32),
+                ("se", ctypes.c_int32), ("ah", ctypes.c_int32), ("al", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("stream_off", ctypes.c_uint64), ("counts", ctypes.c_uint8 * 16 * 3), ("symbols", ctypes.c_uint8 * 256 * 3)]
 
 
 class JpegDecHeader(ctypes.Structure):

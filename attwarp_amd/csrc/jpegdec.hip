@@ -17,10 +17,17 @@
 //                           mode and order, the store; the first thread of every image writes its status.
 // Every loop is bounded by a header-derived count (units, MCUs per unit, blocks per MCU), by 64 coefficients or 16 bits,
 // by the stream's length, or by the plan's cap on rounds.
+// Progressive files (attwarp_jpegdec_plan_scans / attwarp_jpegdec_decode_scans) keep the last two launches
+// and put in front of them
+//   jpegprog_clear_kernel   the coefficient memory of every image zeroed (the scans only refine it), the states opened;
+//   jpegprog_scan_kernel    one workgroup per SCAN: the restart-marker rule above (jd_scan_units) for the scan's own data;
+//   jpegprog_entropy_kernel one launch per dependency level of the scans, one wave per (scan, unit): the four block routines
+//                           of jpegprog_blocks.hpp; a wave stores only the int16s of its band Ss..Se (the band rule).
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
-#include "jpegdec_blocks.hpp"
+#include "jpegprog_blocks.hpp"
 
 namespace attwarp {
 
@@ -104,19 +111,15 @@ __device__ __forceinline__ uint32_t jd_excl_sum(uint32_t v, uint32_t* tmp, uint3
   return incl - v;
 }
 
-__global__ __launch_bounds__(JD_NT) void jpegdec_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
-                                                             uint8_t* __restrict__ scratch) {
-  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const JdView v(table, scratch);
-  const JdImage* im = v.images + b;
-  const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off;
-  const uint32_t n = im->stream_len, nunits = (uint32_t)im->nunits;
-  uint32_t* starts = v.starts + im->unit0;
-  uint32_t* ends = v.ends + im->unit0;
+// The restart-marker scan of one run of entropy data by one workgroup: s[0 .. n), planned for nunits units.  Writes the
+// units' starts and all ends but the last, -> the markers found in front of the data's end (running) and that end (term);
+// s_bad: an index out of its cycle.  Ends behind a barrier.
+__device__ __forceinline__ void jd_scan_units(const JD_G uint8_t* s, uint32_t n, uint32_t nunits, uint32_t* starts, uint32_t* ends,
+                                              uint32_t* s_tmp, uint32_t& s_term, uint32_t& s_bad, uint32_t& running, uint32_t& term) {
+  const int tid = threadIdx.x;
   if (tid == 0) { s_term = 0xffffffffu; s_bad = 0; starts[0] = 0; }
   __syncthreads();
-  uint32_t running = 0, term = n;
+  running = 0; term = n;
   constexpr uint32_t PER = 8, TILE = JD_NT * PER;
   for (uint32_t base = 0; base < n; base += TILE) {
     const uint32_t i0 = base + tid * PER;
@@ -152,6 +155,19 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_scan_kernel(const uint8_t* __re
     if (T != 0xffffffffu) { term = T; break; }                // (uniform: T comes from LDS behind a barrier)
   }
   __syncthreads();
+}
+
+__global__ __launch_bounds__(JD_NT) void jpegdec_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                             uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const JdView v(table, scratch);
+  const JdImage* im = v.images + b;
+  const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off;
+  const uint32_t n = im->stream_len, nunits = (uint32_t)im->nunits;
+  uint32_t* ends = v.ends + im->unit0;
+  uint32_t running, term;
+  jd_scan_units(s, n, nunits, v.starts + im->unit0, ends, s_tmp, s_term, s_bad, running, term);
   if (tid == 0) {
     uint32_t q = term;
     while (q < n && s[q] == 0xffu) ++q;                        // fill bytes in front of the marker's code
@@ -272,6 +288,21 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_substream_kernel(const uint8_t*
   }
 }
 
+// One wave keeps its ring of the unit's bytes filled: chunks of JD_CHUNK bytes from `loaded` on, while they land on ring
+// bytes behind the reader (base: the reader's position, rounded down to a dword).  Nothing at or behind `end` is loaded.
+__device__ __forceinline__ void jd_ring_fill(uint32_t* s_ring, const JD_G uint8_t* s, uint32_t& loaded, uint32_t base, uint32_t end, int lane) {
+  for (int it = 0; it < JD_RING / JD_CHUNK && loaded < end && loaded - base <= (uint32_t)(JD_RING - JD_CHUNK); ++it) {
+    const uint32_t q = loaded + (uint32_t)lane * 4u;
+    uint32_t w = 0;
+    if (q < end && end - q >= 4u) w = *(const JD_G u32_una*)(s + q);
+    else
+      for (uint32_t e = 0; e < 4; ++e)
+        if (q + e < end) w |= (uint32_t)s[q + e] << (8 * e);
+    s_ring[(q & (uint32_t)(JD_RING - 1)) >> 2] = w;
+    loaded += JD_CHUNK;
+  }
+}
+
 // grid: one wave per planned unit of the call.
 __global__ __launch_bounds__(WAVE) void jpegdec_entropy_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
                                                                uint8_t* __restrict__ scratch) {
@@ -325,16 +356,7 @@ __global__ __launch_bounds__(WAVE) void jpegdec_entropy_kernel(const uint8_t* __
       // keep the ring filled: a block takes at most 64 x (16 + 16) bits = 256 bytes, 512 with stuffing, and the reader looks
       // 8 more bytes ahead; after this loop more than JD_RING - JD_CHUNK bytes lie ahead of it, or the whole unit.  A chunk
       // only ever lands on ring bytes behind the reader: loaded - base <= JD_RING - JD_CHUNK.
-      for (int it = 0; it < JD_RING / JD_CHUNK && loaded < end && loaded - base <= (uint32_t)(JD_RING - JD_CHUNK); ++it) {
-        const uint32_t q = loaded + (uint32_t)lane * 4u;
-        uint32_t w = 0;
-        if (q < end && end - q >= 4u) w = *(const JD_G u32_una*)(s + q);
-        else
-          for (uint32_t e = 0; e < 4; ++e)
-            if (q + e < end) w |= (uint32_t)s[q + e] << (8 * e);
-        s_ring[(q & (uint32_t)(JD_RING - 1)) >> 2] = w;
-        loaded += JD_CHUNK;
-      }
+      jd_ring_fill(s_ring, s, loaded, base, end, lane);
       s_blk[lane] = 0;
       __syncthreads();
       if (lane == 0) {
@@ -452,6 +474,167 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_color_kernel(const uint8_t* __r
     if (to_luma) d[0] = (uint8_t)jd_luma(r, g, bl);
     else { d[0] = (uint8_t)(swap ? bl : r); d[1] = (uint8_t)g; d[2] = (uint8_t)(swap ? r : bl); }
   }
+}
+
+// ---- progressive files: a table of attwarp_jpegdec_plan_scans is a baseline table of B one-unit images (what
+// the IDCT and colour kernels read) with a JpHeader and the scan records behind it, sorted by (level, image, position) ---------
+constexpr uint32_t JP_MAGIC = 0x4745504bu;
+struct JpHeader {
+  uint32_t magic;
+  int32_t nscans, nlevels, total_units;
+  uint64_t off_scans;                  // JpScan[nscans] in the table
+  uint64_t starts_off;                 // uint32 starts[total_units], ends[total_units] in the scratch buffer
+  uint64_t clear_off, clear_bytes;     // every image's coefficients (and planes) in the scratch buffer, multiples of 16
+  int32_t level_scan0[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // the first record of each level
+  int32_t level_waves[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // waves of each level's launch
+};
+static_assert(sizeof(JpHeader) % 8 == 0, "record layout");
+__host__ __device__ inline uint64_t jp_header_off(int B) {
+  return jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JdImage) + (uint64_t)B * sizeof(JdSub);
+}
+
+// The coefficient memory of every image zeroed (the scans only refine it) and the per-image states opened.
+__global__ __launch_bounds__(JD_NT) void jpegprog_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  const JdView v(table, scratch);
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  uint4* d = reinterpret_cast<uint4*>(scratch + ph->clear_off);
+  const uint64_t n = ph->clear_bytes / 16u;
+  for (uint64_t i = (uint64_t)blockIdx.x * JD_NT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * JD_NT) d[i] = make_uint4(0, 0, 0, 0);
+  for (int b = (int)(blockIdx.x * JD_NT + threadIdx.x); b < v.hdr->B; b += (int)(gridDim.x * JD_NT)) {
+    JdState st;
+    st.st_scan = 0; st.eoi = 0; st.fail = 0xffffffffu; st.nrst = 0;
+    v.states[b] = st;
+    JdSubInfo info;
+    info.nseg = 0; info.rounds = 0; info.accepted = 0; info.pad = 0;
+    v.infos[b] = info;
+  }
+}
+
+// grid: one workgroup per SCAN; the rule of jpegdec_scan_kernel for the scan's own data and units.
+__global__ __launch_bounds__(JD_NT) void jpegprog_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                              uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
+  const JdView v(table, scratch);
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  const JpScan* sc = reinterpret_cast<const JpScan*>(table + ph->off_scans) + blockIdx.x;
+  if (sc->image >= (uint32_t)v.hdr->B) return;
+  const JdImage* im = v.images + sc->image;
+  const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len;
+  const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off + off;
+  const uint32_t n = im->stream_len - off, nunits = sc->nunits;
+  uint32_t* starts = reinterpret_cast<uint32_t*>(scratch + ph->starts_off) + sc->unit0;
+  uint32_t* ends = starts + ph->total_units;
+  uint32_t running, term;
+  jd_scan_units(s, n, nunits, starts, ends, s_tmp, s_term, s_bad, running, term);
+  if (threadIdx.x == 0) {
+    JdState* st = v.states + sc->image;
+    if (running + 1u != nunits || s_bad) st->st_scan = (uint32_t)ATTWARP_JPEGDEC_E_RESTART;   // (every writer stores this value)
+    else ends[nunits - 1u] = term;
+    atomicAdd(&st->nrst, running);
+    if (sc->last) {
+      uint32_t q = term;
+      while (q < n && s[q] == 0xffu) ++q;
+      st->eoi = q > term && q < n && s[q] == 0xd9u;
+    }
+  }
+}
+
+// grid: one wave per (scan, unit) of the launch's level.  The band rule: a wave may LOAD a block's whole row for its
+// history, but stores only the int16s at zigzag positions Ss..Se, one 2-byte store per lane: another wave of the level may
+// be refining another band of the same block.
+__global__ __launch_bounds__(WAVE) void jpegprog_entropy_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                                uint8_t* scratch, int level) {
+  __shared__ JdHuff s_h[3];
+  __shared__ uint32_t s_ring[JD_RING / 4];
+  __shared__ int16_t s_blk[64];
+  __shared__ int32_t s_pred[4];
+  __shared__ uint8_t s_zz[64];
+  __shared__ uint32_t s_pos, s_err, s_run;
+  const int lane = threadIdx.x, w = blockIdx.x;
+  const JdView v(table, scratch);
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  const JpScan* scans = reinterpret_cast<const JpScan*>(table + ph->off_scans);
+  int lo = ph->level_scan0[level], hi = ph->level_scan0[level + 1] - 1;
+  if (hi < lo) return;
+  for (int it = 0; it < 32 && lo < hi; ++it) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (scans[mid].wave0 <= (uint32_t)w) lo = mid;
+    else hi = mid - 1;
+  }
+  const JpScan* sc = scans + lo;
+  if (sc->image >= (uint32_t)v.hdr->B) return;
+  const JdImage* im = v.images + sc->image;
+  JdState* state = v.states + sc->image;
+  if (state->st_scan != 0) return;                           // (uniform) some scan's limits were never written
+  const uint32_t k = (uint32_t)w - sc->wave0;
+  if (k >= sc->nunits) return;
+  const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len, n = im->stream_len - off;
+  const uint32_t* pstarts = reinterpret_cast<const uint32_t*>(scratch + ph->starts_off) + sc->unit0;
+  uint32_t start = pstarts[k], end = pstarts[ph->total_units + k];
+  if (end > n) end = n;
+  if (start > end) start = end;
+  const uint32_t kind = sc->kind, ss = sc->ss, se = sc->se < 63u ? sc->se : 63u, al = sc->al < 15u ? sc->al : 15u;
+  const int ntab = kind == JP_DC_FIRST ? 3 : kind == JP_DC_REFINE ? 0 : 1;
+  for (int c = 0; c < ntab; ++c) {
+    if (lane == 0) jd_huff_ranges(s_h[c], sc->counts[c]);
+    jd_huff_clear(s_h[c], sc->symbols[c], jd_nsym(sc->counts[c]), lane, WAVE);
+  }
+  s_zz[lane] = JD_ZIGZAG[lane];
+  if (lane == 0) { s_pos = start; s_err = 0; s_run = 0; }
+  if (lane < 4) s_pred[lane] = 0;
+  __syncthreads();
+  for (int c = 0; c < ntab; ++c) jd_huff_fill(s_h[c], sc->counts[c], lane, WAVE);
+  const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off + off;
+  JD_G int16_t* coef = (JD_G int16_t*)(scratch + im->coef_off);
+  const uint32_t nslot = sc->nslot >= 1u && sc->nslot <= 6u ? sc->nslot : 1u, nblocks = im->nblocks;
+  const uint32_t nmcu = sc->nmcu, ri = sc->ri;
+  const uint32_t m0 = k * ri, m1 = m0 + ri < nmcu ? m0 + ri : nmcu;
+  const uint32_t iend = m1 * nslot;
+  const bool dc = kind <= JP_DC_REFINE;
+  JdBits br;
+  br.init(reinterpret_cast<const uint8_t*>(s_ring), JD_RING - 1, start, end);
+  uint32_t loaded = start & ~3u, err = 0, eobrun = 0;
+  for (uint32_t i = m0 * nslot; i < iend;) {
+    const uint32_t m = i / nslot, j = i - m * nslot;
+    const uint32_t bi = jp_block_index(*im, *sc, m, j);
+    __syncthreads();                                         // s_pos of the block before; the tables the first time
+    jd_ring_fill(s_ring, s, loaded, s_pos & ~3u, end, lane);  // a block takes at most 64 x 16 + 64 + 14 bits: the baseline's bound holds
+    int16_t have = 0;
+    if (bi < nblocks && (kind == JP_AC_REFINE || (kind == JP_DC_REFINE && lane == 0))) have = coef[(size_t)bi * 64u + lane];
+    s_blk[lane] = have;
+    __syncthreads();
+    if (lane == 0) {
+      br.end = loaded < end ? loaded : end;
+      uint32_t st;
+      if (kind == JP_DC_FIRST) {
+        const int t = sc->slot_t[j & 7u] % 3;
+        int32_t p = s_pred[t];
+        st = jp_dc_first(br, s_h[t], p, al, s_blk[0]);
+        s_pred[t] = p;
+      } else if (kind == JP_DC_REFINE) st = jp_dc_refine(br, al, s_blk[0]);
+      else if (kind == JP_AC_FIRST) st = jp_ac_first(br, s_h[0], ss, se, al, eobrun, s_blk, s_zz);
+      else st = jp_ac_refine(br, s_h[0], ss, se, al, eobrun, s_blk, s_zz);
+      s_pos = br.pos;
+      s_run = eobrun;
+      if (st) s_err = st;
+    }
+    __syncthreads();
+    err = s_err;
+    if (err) break;                                          // (uniform)
+    if (bi < nblocks && (dc ? lane == 0 : ((uint32_t)lane >= ss && (uint32_t)lane <= se))) {
+      const uint32_t at = s_zz[lane] & 63u;
+      coef[(size_t)bi * 64u + at] = s_blk[at];
+    }
+    eobrun = s_run;
+    uint32_t adv = 1;
+    if (kind == JP_AC_FIRST && eobrun > 0) {                 // the blocks of the run are skipped without touching memory
+      const uint32_t skip = eobrun < iend - i - 1u ? eobrun : iend - i - 1u;
+      adv += skip;
+      eobrun -= skip;                                        // (what is left at the unit's end is dropped with the unit)
+    }
+    i += adv;
+  }
+  if (err && lane == 0) atomicMin(&state->fail, sc->index << 24 | k << 8 | err);
 }
 
 }  // namespace attwarp
@@ -655,6 +838,193 @@ extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_
   if (const int rc = check_launch("jpegdec_substream_kernel")) return rc;
   hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegdec_entropy_kernel")) return rc;
+  hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegdec_idct_kernel")) return rc;
+  hipLaunchKernelGGL(jpegdec_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
+  return check_launch("jpegdec_color_kernel");
+}
+
+// ---- progressive files: the plan over all scans ---------------------------------------------------------------------------------------
+static size_t jpegprog_bytes(int B, int nscans) { return (size_t)(jp_header_off(B) + sizeof(JpHeader) + (uint64_t)nscans * sizeof(JpScan)); }
+
+extern "C" size_t attwarp_jpegdec_scans_table_bytes(const attwarp_jpegdec_image* images, int B, int nscans) {
+  if (!images || B <= 0 || B > JD_MAX_B || nscans < B || (int64_t)nscans > (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS) {
+    fail(ATTWARP_E_ARG, "jpegdec_scans_table_bytes: B=%d, %d scans outside the limits", B, nscans);
+    return 0;
+  }
+  return jpegprog_bytes(B, nscans);
+}
+
+extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
+                                          void* table, size_t table_bytes, int by_level) {
+  ATTWARP_REQUIRE(images && scans && table, "jpegdec_plan_scans: null pointer");
+  ATTWARP_REQUIRE(B > 0 && B <= JD_MAX_B && nscans >= B && (int64_t)nscans <= (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS,
+                  "jpegdec_plan_scans: B=%d, %d scans outside the limits", B, nscans);
+  const size_t need = jpegprog_bytes(B, nscans);
+  ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan_scans: table of %zu bytes, %zu needed", table_bytes, need);
+  for (int b = 0; b < B; ++b)
+    ATTWARP_REQUIRE(images[b].restart_interval == 0, "jpegdec_plan_scans: image %d: the restart interval belongs to the scans", b);
+  // everything is checked before anything is written: the scans come image by image, in file order
+  std::vector<JpScan> rec((size_t)nscans);
+  std::vector<int> count(B, 0);
+  int64_t total_units = 0;
+  int nlevels = 0, prev = -1;
+  for (int i = 0, first = 0; i < nscans; ++i) {
+    const attwarp_jpegdec_scan& d = scans[i];
+    ATTWARP_REQUIRE(d.image >= 0 && d.image < B && d.image >= prev, "jpegdec_plan_scans: scan %d: image %d out of order", i, d.image);
+    if (d.image != prev) { first = i; prev = d.image; }
+    const attwarp_jpegdec_image& img = images[d.image];
+    const int index = i - first;
+    if (index >= ATTWARP_JPEGDEC_MAX_SCANS)
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: more than %d scans", d.image, ATTWARP_JPEGDEC_MAX_SCANS);
+    ++count[d.image];
+    ATTWARP_REQUIRE(d.ncomp >= 1 && d.ncomp <= img.ncomp, "jpegdec: image %d scan %d: %d components", d.image, index, d.ncomp);
+    for (int c = 0; c < d.ncomp; ++c)
+      ATTWARP_REQUIRE(d.comp[c] >= 0 && d.comp[c] < img.ncomp && (c == 0 || d.comp[c] > d.comp[c - 1]),
+                      "jpegdec: image %d scan %d: components not in frame order", d.image, index);
+    ATTWARP_REQUIRE(d.ss >= 0 && d.ss <= d.se && d.se <= 63 && (d.ss != 0 || d.se == 0) && (d.ss == 0 || d.ncomp == 1) && d.al >= 0 &&
+                        d.al <= 13 && d.ah >= 0 && d.ah <= 14 && (d.ah == 0 || d.al == d.ah - 1),
+                    "jpegdec: image %d scan %d: bad progression Ss=%d Se=%d Ah=%d Al=%d", d.image, index, d.ss, d.se, d.ah, d.al);
+    ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d scan %d: restart interval %d", d.image, index,
+                    d.restart_interval);
+    ATTWARP_REQUIRE(d.stream_off <= img.stream_len, "jpegdec: image %d scan %d: data outside the image's", d.image, index);
+    JdGeom g;
+    if (const int rc = jpegdec_geom(img, d.image, g)) return rc;
+    JpScan& r = rec[(size_t)i];
+    std::memset(&r, 0, sizeof r);
+    r.image = (uint32_t)d.image; r.index = (uint32_t)index; r.off = (uint32_t)d.stream_off;
+    r.kind = (uint32_t)((d.ss ? 2 : 0) + (d.ah ? 1 : 0));
+    r.ss = (uint32_t)d.ss; r.se = (uint32_t)d.se; r.al = (uint32_t)d.al;
+    const int ntab = d.ss ? 1 : d.ncomp;
+    for (int t = 0; t < ntab; ++t) {
+      int left = 1, n = 0;
+      for (int l = 0; l < 16; ++l) {
+        left = 2 * left - d.counts[t][l];
+        n += d.counts[t][l];
+        ATTWARP_REQUIRE(left >= 0, "jpegdec: image %d scan %d: an over-subscribed Huffman table", d.image, index);
+      }
+      ATTWARP_REQUIRE(n <= 256, "jpegdec: image %d scan %d: a Huffman table of %d symbols", d.image, index, n);
+      if (!d.ss)
+        for (int k = 0; k < n; ++k) ATTWARP_REQUIRE(d.symbols[t][k] <= 15, "jpegdec: image %d scan %d: a DC category above 15", d.image, index);
+      std::memcpy(r.counts[t], d.counts[t], 16);
+      std::memcpy(r.symbols[t], d.symbols[t], 256);
+    }
+    if (d.ncomp == 1) {                                        // not interleaved: the blocks that cover the component's true size
+      const int c = d.comp[0], h = c == 0 ? img.hs : 1, vv = c == 0 ? img.vs : 1;
+      const int cw = (img.W * h + img.hs - 1) / img.hs, ch = (img.H * vv + img.vs - 1) / img.vs;
+      r.nslot = 1;
+      r.mcux = (uint32_t)((cw + 7) / 8);
+      r.nmcu = r.mcux * (uint32_t)((ch + 7) / 8);
+      r.slot_c[0] = (uint8_t)c;
+    } else {
+      r.mcux = (uint32_t)g.mcux;
+      r.nmcu = (uint32_t)g.mcux * (uint32_t)g.mcuy;
+      for (int t = 0; t < d.ncomp; ++t) {
+        const int c = d.comp[t], h = c == 0 ? img.hs : 1, vv = c == 0 ? img.vs : 1;
+        for (int y = 0; y < vv; ++y)
+          for (int x = 0; x < h; ++x) {
+            r.slot_c[r.nslot] = (uint8_t)c; r.slot_y[r.nslot] = (uint8_t)y; r.slot_x[r.nslot] = (uint8_t)x; r.slot_t[r.nslot] = (uint8_t)t;
+            ++r.nslot;
+          }
+      }
+    }
+    r.ri = d.restart_interval ? (uint32_t)d.restart_interval : r.nmcu;
+    r.nunits = (r.nmcu + r.ri - 1) / r.ri;
+    // the level: behind every earlier scan of the image that shares a component and overlaps the band
+    uint32_t level = by_level ? 0u : (uint32_t)index;
+    if (by_level)
+      for (int j = first; j < i; ++j) {
+        const attwarp_jpegdec_scan& e = scans[j];
+        bool share = false;
+        for (int a = 0; a < d.ncomp; ++a)
+          for (int bb = 0; bb < e.ncomp; ++bb) share = share || d.comp[a] == e.comp[bb];
+        if (share && e.ss <= d.se && d.ss <= e.se) level = std::max(level, rec[(size_t)j].level + 1u);
+      }
+    r.level = level;
+    nlevels = std::max(nlevels, (int)level + 1);
+    total_units += r.nunits;
+  }
+  for (int b = 0; b < B; ++b) ATTWARP_REQUIRE(count[b] >= 1, "jpegdec_plan_scans: image %d has no scan", b);
+  {                                                            // the units of an image, over all its scans
+    std::vector<int64_t> per(B, 0);
+    for (int i = 0; i < nscans; ++i) per[scans[i].image] += rec[(size_t)i].nunits;
+    for (int b = 0; b < B; ++b)
+      if (per[b] > ATTWARP_JPEGDEC_MAX_UNITS)
+        return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld units over its scans (> %d)", b, (long long)per[b], ATTWARP_JPEGDEC_MAX_UNITS);
+  }
+  if (total_units > JD_MAX_TOTAL_UNITS) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units in one call (> 2^30)", (long long)total_units);
+  if (const int rc = attwarp_jpegdec_plan_ex(images, B, table, table_bytes, 0, 0)) return rc;
+  uint8_t* t = static_cast<uint8_t*>(table);
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, t, sizeof h);
+  JpHeader ph;
+  std::memset(&ph, 0, sizeof ph);
+  ph.magic = JP_MAGIC;
+  ph.nscans = nscans; ph.nlevels = nlevels; ph.total_units = (int32_t)total_units;
+  ph.off_scans = jp_header_off(B) + sizeof(JpHeader);
+  const JdSub* sub = reinterpret_cast<const JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JdImage));
+  ph.clear_off = jd_data_base(B, h.total_units);
+  ph.clear_bytes = sub[0].info_off - ph.clear_off;             // (both are multiples of 256)
+  ph.starts_off = jd_align(h.scratch_bytes, 256);
+  h.scratch_bytes = ph.starts_off + jd_align((uint64_t)total_units * 8u, 256);
+  h.table_bytes = need;
+  // records sorted by (level, image, position): a stable pass per level over the input order
+  JpScan* out = reinterpret_cast<JpScan*>(t + ph.off_scans);
+  uint32_t unit0 = 0;
+  for (int i = 0; i < nscans; ++i) {
+    rec[(size_t)i].unit0 = unit0;
+    unit0 += rec[(size_t)i].nunits;
+    rec[(size_t)i].last = i + 1 == nscans || scans[i + 1].image != scans[i].image;
+  }
+  int at = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    ph.level_scan0[l] = at;
+    uint32_t wave = 0;
+    for (int i = 0; i < nscans; ++i)
+      if ((int)rec[(size_t)i].level == l) {
+        rec[(size_t)i].wave0 = wave;
+        wave += rec[(size_t)i].nunits;
+        std::memcpy(out + at++, &rec[(size_t)i], sizeof(JpScan));
+      }
+    ph.level_waves[l] = (int32_t)wave;
+  }
+  ph.level_scan0[nlevels] = at;
+  std::memcpy(t + jp_header_off(B), &ph, sizeof ph);
+  std::memcpy(t, &h, sizeof h);
+  return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                            uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "jpegdec_decode_scans: null pointer");
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, table_host, sizeof h);
+  ATTWARP_REQUIRE(h.magic == JD_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.total_units == h.B && h.idct_tiles >= h.B &&
+                      h.idct_tiles <= JD_MAX_TOTAL_UNITS && h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS && h.reserved == 0 &&
+                      h.table_bytes >= jp_header_off(h.B) + sizeof(JpHeader),
+                  "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
+  JpHeader ph;
+  std::memcpy(&ph, static_cast<const uint8_t*>(table_host) + jp_header_off(h.B), sizeof ph);
+  ATTWARP_REQUIRE(ph.magic == JP_MAGIC && ph.nscans >= h.B && ph.nlevels >= 1 && ph.nlevels <= ATTWARP_JPEGDEC_MAX_SCANS &&
+                      ph.total_units >= ph.nscans && ph.total_units <= JD_MAX_TOTAL_UNITS,
+                  "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
+  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegdec_decode_scans: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
+  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
+                      reinterpret_cast<uintptr_t>(status) % 4 == 0,
+                  "jpegdec_decode_scans: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned");
+  hipStream_t st = as_stream(stream);
+  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  const uint64_t clear_groups = std::min<uint64_t>(std::max<uint64_t>((ph.clear_bytes / 16u + JD_NT - 1) / JD_NT, (uint64_t)(h.B + JD_NT - 1) / JD_NT), 4096);
+  hipLaunchKernelGGL(jpegprog_clear_kernel, dim3((unsigned)clear_groups), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegprog_clear_kernel")) return rc;
+  hipLaunchKernelGGL(jpegprog_scan_kernel, dim3(ph.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch("jpegprog_scan_kernel")) return rc;
+  for (int l = 0; l < ph.nlevels; ++l) {
+    ATTWARP_REQUIRE(ph.level_waves[l] >= 1, "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
+    hipLaunchKernelGGL(jpegprog_entropy_kernel, dim3(ph.level_waves[l]), dim3(WAVE), 0, st, td, stream_bytes, sc, l);
+    if (const int rc = check_launch("jpegprog_entropy_kernel")) return rc;
+  }
   hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
   if (const int rc = check_launch("jpegdec_idct_kernel")) return rc;
   hipLaunchKernelGGL(jpegdec_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);

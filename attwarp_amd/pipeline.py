@@ -1479,20 +1479,21 @@ def upload_png_files(files_or_paths, device=None):
     return decode_png(files_or_paths, "RGB", "rgb", device)
 
 
-def upload_jpeg_files(files_or_paths, device=None, substreams="auto"):
+def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressive=False):
     """:func:`upload_images` for a batch still in its JPEG files (bytes-like or paths; the TextVQA / GQA images the drivers and
     the MarginalNet loader open, or anyone's baseline JPEG): the COMPRESSED bytes go up in one transfer and are decoded on
     the GPU (attwarp_amd.jpeg.decode_jpeg) -> list of uint8 [H_i,W_i,3] RGB GPU tensors, views into one packed buffer, as
     ``Image.open(f).convert("RGB")`` gives them.  OSError for a broken file, ValueError for an unsupported one.
-    ``substreams``: marker-less files as self-synchronising sub-streams (jpeg.plan); the pixels do not depend on it."""
+    ``substreams``: marker-less files as self-synchronising sub-streams (jpeg.plan); the pixels do not depend on it.
+    ``progressive=True`` also takes progressive files (jpeg.JpegFiles); without it they raise ValueError."""
     from .jpeg import decode_jpeg
-    return decode_jpeg(files_or_paths, "RGB", "rgb", device, substreams)
+    return decode_jpeg(files_or_paths, "RGB", "rgb", device, substreams, progressive)
 
 
-def upload_image_files(files_or_paths, device=None, substreams="auto"):
+def upload_image_files(files_or_paths, device=None, substreams="auto", progressive=False):
     """A batch of image files of either kind (bytes-like or paths), each sent by its signature to the PNG or the JPEG decoder
     (:func:`upload_png_files`, :func:`upload_jpeg_files`): one transfer and one decode per kind -> the uint8 [H_i,W_i,3] RGB
-    GPU tensors in input order.  ValueError for a file that is neither."""
+    GPU tensors in input order.  ValueError for a file that is neither.  ``progressive``: see :func:`upload_jpeg_files`."""
     from .jpeg import _file_bytes
     files = [_file_bytes(f) for f in files_or_paths]
     kinds = []
@@ -1505,7 +1506,7 @@ def upload_image_files(files_or_paths, device=None, substreams="auto"):
         else:
             raise ValueError(f"upload_image_files: file {i} is neither a PNG nor a JPEG file")
     out = [None] * len(files)
-    for kind, decode in (("png", upload_png_files), ("jpeg", lambda f, d: upload_jpeg_files(f, d, substreams))):
+    for kind, decode in (("png", upload_png_files), ("jpeg", lambda f, d: upload_jpeg_files(f, d, substreams, progressive))):
         idx = [i for i, k in enumerate(kinds) if k == kind]
         if idx:
             for i, v in zip(idx, decode([files[i] for i in idx], device)):

@@ -997,6 +997,41 @@ ATTWARP_API uint64_t attwarp_jpegdec_info_offset(const void* table_host);
 ATTWARP_API int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
 
+/* ---- PROGRESSIVE files (SOF2) of a whole batch, scans by dependency level (jpegdec.hip).  The same frames
+ * as above; the HOST walks every marker of the file, applies DHT / DRI in file order and describes every scan: its
+ * components (indices in frame order, ascending), band Ss..Se, Ah, Al, the restart interval in force at its SOS (MCUs of
+ * THAT scan, 0: none), where its entropy data starts inside the image's packed data (everything behind the first SOS
+ * header, as above), and the tables it names (one DC table per component of a DC scan, [0] the AC table of an AC scan).
+ * attwarp_jpegdec_image carries sizes, sampling, qt, mode and order; its tables and restart_interval stay zero.  The scans
+ * are passed image by image, in file order.  The table is a table of attwarp_jpegdec_plan (what the IDCT and colour
+ * launches read) followed by the scan records; it depends on the headers, the scan records and the lengths alone.
+ * Geometry: a scan of several components walks the frame's MCUs; a scan of one component walks the ceil(cw / 8) x
+ * ceil(ch / 8) blocks that cover the component's true size (cw = ceil(W h / hmax)), in raster order, and its restart
+ * interval counts those.  Units of a scan: ceil(MCUs / Ri), one wave each; predictors and the EOB run reset per unit.
+ * Level of a scan: 0 if no earlier scan of the image shares a component with it and overlaps its band, else 1 + the
+ * largest level among those; by_level = 0 plans one level per scan position instead (for tests: pixels, statuses and
+ * coefficients do not depend on it).  Launches: one clear (the coefficient memory is zeroed on every run), one restart scan
+ * (per SCAN the rule above), one entropy launch per level of the call's deepest image, IDCT, colour: constant per plan.
+ * The planner checks what the kernels' bounds rest on (Ss <= Se <= 63, Ss = 0 only with Se = 0, an AC scan of one
+ * component, Al <= 13, Ah = 0 or Al + 1, at most ATTWARP_JPEGDEC_MAX_SCANS scans and ATTWARP_JPEGDEC_MAX_UNITS units per
+ * image over all its scans); whether the scans form a complete, consistent progression is the caller's to check.
+ * status[b]: E_RESTART from any scan first, then the status of the lowest failing (scan in file order, unit), then
+ * E_NO_EOI by the marker behind the LAST scan.  E_COEFF also names a refinement symbol whose size is not 1. */
+#define ATTWARP_JPEGDEC_MAX_SCANS 64
+typedef struct attwarp_jpegdec_scan {
+  int32_t image;                                   /* index into the images of the call; ascending over the array */
+  int32_t ncomp, comp[3];                          /* components of the scan, indices in frame order */
+  int32_t ss, se, ah, al;
+  int32_t restart_interval;                        /* MCUs of this scan, 0: none */
+  uint64_t stream_off;                             /* its entropy data, relative to the image's stream_off */
+  uint8_t counts[3][16], symbols[3][256];          /* DHT of the tables it names */
+} attwarp_jpegdec_scan;
+ATTWARP_API size_t attwarp_jpegdec_scans_table_bytes(const attwarp_jpegdec_image* images, int B, int nscans);
+ATTWARP_API int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
+                       void* table, size_t table_bytes, int by_level);
+ATTWARP_API int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                       uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
