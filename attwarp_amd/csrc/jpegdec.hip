@@ -24,6 +24,7 @@
 //   jpegprog_entropy_kernel one launch per dependency level of the scans, one wave per (scan, unit): the four block routines
 //                           of jpegprog_blocks.hpp; a wave stores only the int16s of its band Ss..Se (the band rule).
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -489,6 +490,7 @@ struct JpHeader {
   int32_t level_waves[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // waves of each level's launch
 };
 static_assert(sizeof(JpHeader) % 8 == 0, "record layout");
+// (behind a baseline table: header, image records, sub-stream records, always present: attwarp_jpegdec_table_bytes is this sum)
 __host__ __device__ inline uint64_t jp_header_off(int B) {
   return jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JdImage) + (uint64_t)B * sizeof(JdSub);
 }
@@ -647,6 +649,18 @@ struct JdGeom {
   uint32_t block0[3], nblocks;
 };
 
+// What is wrong with a Huffman table (counts per length, symbols), in words for the caller's message; nullptr: nothing.
+static const char* jd_huffman_fault(const uint8_t* counts, const uint8_t* symbols, bool dc, char (&what)[48]) {
+  int left = 1, n = 0;
+  for (int l = 0; l < 16 && left >= 0; ++l) { left = 2 * left - counts[l]; n += counts[l]; }
+  if (left < 0) return "an over-subscribed Huffman table";
+  std::snprintf(what, sizeof what, "a Huffman table of %d symbols", n);
+  if (n > 256) return what;
+  for (int k = 0; dc && k < n; ++k)
+    if (symbols[k] > 15) return "a DC category above 15";
+  return nullptr;
+}
+
 static int jpegdec_geom(const attwarp_jpegdec_image& d, int b, JdGeom& g) {
   ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1 && d.H <= 65535 && d.W <= 65535, "jpegdec: image %d: size %d x %d outside 1..65535", b, d.H, d.W);
   ATTWARP_REQUIRE(d.ncomp == 1 || d.ncomp == 3, "jpegdec: image %d: %d components (1 or 3)", b, d.ncomp);
@@ -658,16 +672,9 @@ static int jpegdec_geom(const attwarp_jpegdec_image& d, int b, JdGeom& g) {
   for (int c = 0; c < d.ncomp; ++c) {
     for (int k = 0; k < 64; ++k) ATTWARP_REQUIRE(d.qt[c][k] <= 255, "jpegdec: image %d: a quantisation value above 255", b);
     for (int t = 0; t < 2; ++t) {
-      const uint8_t* counts = t ? d.ac_counts[c] : d.dc_counts[c];
-      int left = 1, n = 0;
-      for (int l = 0; l < 16; ++l) {
-        left = 2 * left - counts[l];
-        n += counts[l];
-        ATTWARP_REQUIRE(left >= 0, "jpegdec: image %d: an over-subscribed Huffman table", b);
-      }
-      ATTWARP_REQUIRE(n <= 256, "jpegdec: image %d: a Huffman table of %d symbols", b, n);
-      if (!t)
-        for (int k = 0; k < n; ++k) ATTWARP_REQUIRE(d.dc_symbols[c][k] <= 15, "jpegdec: image %d: a DC category above 15", b);
+      char what[48];
+      const char* fault = t ? jd_huffman_fault(d.ac_counts[c], d.ac_symbols[c], false, what) : jd_huffman_fault(d.dc_counts[c], d.dc_symbols[c], true, what);
+      ATTWARP_REQUIRE(!fault, "jpegdec: image %d: %s", b, fault);
     }
   }
   g.mcux = (d.W + 8 * d.hs - 1) / (8 * d.hs);
@@ -692,17 +699,12 @@ static int jpegdec_geom(const attwarp_jpegdec_image& d, int b, JdGeom& g) {
   return ATTWARP_OK;
 }
 
-// header, image records, sub-stream records (always present, so that the size depends on B alone)
-static size_t jpegdec_bytes(int B) {
-  return (size_t)(jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JdImage) + (uint64_t)B * sizeof(JdSub));
-}
-
 extern "C" size_t attwarp_jpegdec_table_bytes(const attwarp_jpegdec_image* images, int B) {
   if (!images || B <= 0 || B > JD_MAX_B) {
     fail(ATTWARP_E_ARG, "jpegdec_table_bytes: B=%d outside the limits", B);
     return 0;
   }
-  return jpegdec_bytes(B);
+  return (size_t)jp_header_off(B);
 }
 
 extern "C" int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes) {
@@ -721,7 +723,7 @@ extern "C" int attwarp_jpegdec_plan_ex(const attwarp_jpegdec_image* images, int 
   ATTWARP_REQUIRE(B > 0, "jpegdec: non-positive batch size");
   if (B > JD_MAX_B) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: B=%d > 2^20", B);
   ATTWARP_REQUIRE(table, "jpegdec_plan: null table");
-  const size_t need = jpegdec_bytes(B);
+  const size_t need = (size_t)jp_header_off(B);
   ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan: table of %zu bytes, %zu needed", table_bytes, need);
   int64_t units = 0, itiles = 0, ctiles = 0;
   for (int b = 0; b < B; ++b) {                              // everything is checked before anything is written
@@ -816,19 +818,43 @@ extern "C" uint64_t attwarp_jpegdec_info_offset(const void* table_host) {
   return s.info_off;
 }
 
-extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
-                                      uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
-  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "jpegdec_decode: null pointer");
-  attwarp_jpegdec_header h;
+// What both decode entry points (`who`) check: pointers, the table of `planner` (-> h; `ph`: and its scan header), sizes, alignment.
+static int jd_decode_args(const char* who, const char* planner, const void* table_host, const void* table_dev, const uint8_t* stream_bytes,
+                          const void* scratch, const uint8_t* out, size_t out_bytes, const int32_t* status, attwarp_jpegdec_header& h,
+                          JpHeader* ph) {
+  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "%s: null pointer", who);
   std::memcpy(&h, table_host, sizeof h);
-  ATTWARP_REQUIRE(h.magic == JD_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.total_units >= h.B && h.total_units <= JD_MAX_TOTAL_UNITS &&
-                      h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS && h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS &&
-                      h.reserved >= 0 && h.reserved <= h.B,
-                  "jpegdec_decode: not a table of attwarp_jpegdec_plan");
-  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegdec_decode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
+  bool ok = h.magic == JD_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS &&
+            h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS;
+  if (!ph) ok = ok && h.total_units >= h.B && h.total_units <= JD_MAX_TOTAL_UNITS && h.reserved >= 0 && h.reserved <= h.B;
+  else ok = ok && h.total_units == h.B && h.reserved == 0 && h.table_bytes >= jp_header_off(h.B) + sizeof(JpHeader);
+  if (ok && ph) {
+    std::memcpy(ph, static_cast<const uint8_t*>(table_host) + jp_header_off(h.B), sizeof *ph);
+    ok = ph->magic == JP_MAGIC && ph->nscans >= h.B && ph->nlevels >= 1 && ph->nlevels <= ATTWARP_JPEGDEC_MAX_SCANS &&
+         ph->total_units >= ph->nscans && ph->total_units <= JD_MAX_TOTAL_UNITS;
+  }
+  ATTWARP_REQUIRE(ok, "%s: not a table of %s", who, planner);
+  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "%s: out of %zu bytes, %llu needed", who, out_bytes, (unsigned long long)h.out_bytes);
   ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
                       reinterpret_cast<uintptr_t>(status) % 4 == 0,
-                  "jpegdec_decode: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned");
+                  "%s: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned", who);
+  return ATTWARP_OK;
+}
+
+// The last two launches of both entry points: coefficients -> planes -> pixels and statuses.
+static int jd_launch_idct_color(const attwarp_jpegdec_header& h, const uint8_t* td, uint8_t* sc, uint8_t* out, int32_t* status, hipStream_t st) {
+  hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegdec_idct_kernel")) return rc;
+  hipLaunchKernelGGL(jpegdec_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
+  return check_launch("jpegdec_color_kernel");
+}
+
+extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                      uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  attwarp_jpegdec_header h;
+  if (const int rc = jd_decode_args("jpegdec_decode", "attwarp_jpegdec_plan", table_host, table_dev, stream_bytes, scratch, out, out_bytes,
+                                    status, h, nullptr))
+    return rc;
   hipStream_t st = as_stream(stream);
   const uint8_t* td = static_cast<const uint8_t*>(table_dev);
   uint8_t* sc = static_cast<uint8_t*>(scratch);
@@ -838,10 +864,7 @@ extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_
   if (const int rc = check_launch("jpegdec_substream_kernel")) return rc;
   hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegdec_entropy_kernel")) return rc;
-  hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegdec_idct_kernel")) return rc;
-  hipLaunchKernelGGL(jpegdec_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
-  return check_launch("jpegdec_color_kernel");
+  return jd_launch_idct_color(h, td, sc, out, status, st);
 }
 
 // ---- progressive files: the plan over all scans ---------------------------------------------------------------------------------------
@@ -897,15 +920,9 @@ extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, i
     r.ss = (uint32_t)d.ss; r.se = (uint32_t)d.se; r.al = (uint32_t)d.al;
     const int ntab = d.ss ? 1 : d.ncomp;
     for (int t = 0; t < ntab; ++t) {
-      int left = 1, n = 0;
-      for (int l = 0; l < 16; ++l) {
-        left = 2 * left - d.counts[t][l];
-        n += d.counts[t][l];
-        ATTWARP_REQUIRE(left >= 0, "jpegdec: image %d scan %d: an over-subscribed Huffman table", d.image, index);
-      }
-      ATTWARP_REQUIRE(n <= 256, "jpegdec: image %d scan %d: a Huffman table of %d symbols", d.image, index, n);
-      if (!d.ss)
-        for (int k = 0; k < n; ++k) ATTWARP_REQUIRE(d.symbols[t][k] <= 15, "jpegdec: image %d scan %d: a DC category above 15", d.image, index);
+      char what[48];
+      const char* fault = jd_huffman_fault(d.counts[t], d.symbols[t], !d.ss, what);
+      ATTWARP_REQUIRE(!fault, "jpegdec: image %d scan %d: %s", d.image, index, fault);
       std::memcpy(r.counts[t], d.counts[t], 16);
       std::memcpy(r.symbols[t], d.symbols[t], 256);
     }
@@ -996,22 +1013,11 @@ extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, i
 
 extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                                             uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
-  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "jpegdec_decode_scans: null pointer");
   attwarp_jpegdec_header h;
-  std::memcpy(&h, table_host, sizeof h);
-  ATTWARP_REQUIRE(h.magic == JD_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.total_units == h.B && h.idct_tiles >= h.B &&
-                      h.idct_tiles <= JD_MAX_TOTAL_UNITS && h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS && h.reserved == 0 &&
-                      h.table_bytes >= jp_header_off(h.B) + sizeof(JpHeader),
-                  "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
   JpHeader ph;
-  std::memcpy(&ph, static_cast<const uint8_t*>(table_host) + jp_header_off(h.B), sizeof ph);
-  ATTWARP_REQUIRE(ph.magic == JP_MAGIC && ph.nscans >= h.B && ph.nlevels >= 1 && ph.nlevels <= ATTWARP_JPEGDEC_MAX_SCANS &&
-                      ph.total_units >= ph.nscans && ph.total_units <= JD_MAX_TOTAL_UNITS,
-                  "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
-  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegdec_decode_scans: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
-  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
-                      reinterpret_cast<uintptr_t>(status) % 4 == 0,
-                  "jpegdec_decode_scans: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned");
+  if (const int rc = jd_decode_args("jpegdec_decode_scans", "attwarp_jpegdec_plan_scans", table_host, table_dev, stream_bytes, scratch, out,
+                                    out_bytes, status, h, &ph))
+    return rc;
   hipStream_t st = as_stream(stream);
   const uint8_t* td = static_cast<const uint8_t*>(table_dev);
   uint8_t* sc = static_cast<uint8_t*>(scratch);
@@ -1025,8 +1031,5 @@ extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* 
     hipLaunchKernelGGL(jpegprog_entropy_kernel, dim3(ph.level_waves[l]), dim3(WAVE), 0, st, td, stream_bytes, sc, l);
     if (const int rc = check_launch("jpegprog_entropy_kernel")) return rc;
   }
-  hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegdec_idct_kernel")) return rc;
-  hipLaunchKernelGGL(jpegdec_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
-  return check_launch("jpegdec_color_kernel");
+  return jd_launch_idct_color(h, td, sc, out, status, st);
 }

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, _tables, pipeline
+from ._batch import TABLE, packed_views, planned_table, uploaded
 from ._lib import call, ptr, require_gpu, stream_ptr
 
 _PREP_IMAGE_DTYPE = np.dtype([("image", "<u8"), ("bounds_x", "<u8"), ("kk_x", "<u8"), ("bounds_y", "<u8"), ("kk_y", "<u8"),
@@ -60,15 +61,6 @@ def _nearest_table(n_in: int, n_out: int, device: torch.device) -> torch.Tensor:
         call("attwarp_pil_nearest_index", int(n_in), int(n_out), idx.ctypes.data)
         t = _tables._cache_put(key, torch.from_numpy(idx).to(device))
     return t
-
-
-def _pinned_upload(host: np.ndarray, device: torch.device) -> torch.Tensor:
-    """A per-batch record table -> device bytes with one pinned asynchronous copy (the launch does not wait for the host;
-    the caching host allocator keeps the pinned buffer until the copy has run)."""
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("attwarp_amd.dataloader: the per-batch record table cannot be uploaded inside a stream capture "
-                           "(capture prepared PreparedImages / PreparedAttention objects instead)")
-    return torch.from_numpy(host.view(np.uint8).reshape(-1)).pin_memory().to(device, non_blocking=True)
 
 
 def _uploads_done(device: torch.device) -> torch.cuda.Event:
@@ -130,15 +122,11 @@ class PreparedImages:
         # vertically (two calls of the resampler); the intermediate is uint8 either way, so the order shows in the bytes
         rec["vertical_first"] = [int(h > 100 * w and sh < h) for h, w in zip(hs, ws)]
         self._keep = tx + ty
-        lib = _lib.load()
         rp = ctypes.c_void_p(rec.ctypes.data)
-        nbytes = lib.attwarp_prep_images_table_bytes(rp, self.B, C, sh, sw)
-        if nbytes == 0:
-            raise _lib.AttWarpError("attwarp_prep_images_table_bytes: " + lib.attwarp_last_error().decode("utf-8", "replace"))
-        self.table_host = np.empty(nbytes, dtype=np.uint8)
-        call("attwarp_prep_images_plan", rp, self.B, C, sh, sw, self.table_host.ctypes.data, nbytes)
-        self.header = _lib.PrepHeader.from_address(self.table_host.ctypes.data)
-        self.table_dev = _pinned_upload(self.table_host, dev)
+        self.table_host, self.header = planned_table(
+            ("attwarp_prep_images_table_bytes", rp, self.B, C, sh, sw), ("attwarp_prep_images_plan", rp, self.B, C, sh, sw, TABLE),
+            _lib.PrepHeader, _lib.AttWarpError, "attwarp_prep_images_table_bytes: ")
+        self.table_dev = uploaded(self.table_host, dev)
         self.tmp = torch.empty(int(self.header.tmp_bytes), device=dev, dtype=torch.uint8) if self.header.tmp_bytes else None
         if out is None:
             out = torch.empty(self.B, C, sh, sw, device=dev, dtype=torch.float32)
@@ -196,7 +184,7 @@ class PreparedAttention:
         rec["h"] = [int(m.shape[0]) for m in self.maps]; rec["w"] = [int(m.shape[1]) for m in self.maps]
         rec["normalize"] = int(bool(normalize))
         self._keep = ix + iy
-        self.records = _pinned_upload(rec, dev)
+        self.records = uploaded(rec, dev)
         self.ws = torch.empty(int(_lib.load().attwarp_prep_attention_workspace_bytes(self.B)), device=dev, dtype=torch.uint8)
         if out is None:
             out = torch.empty(self.B, 1, sh, sw, device=dev, dtype=torch.float32)
@@ -263,15 +251,8 @@ def prepare_attention_maps(maps, image_size=512, normalize: bool = True) -> torc
             if a.size == 0:
                 raise ValueError("prepare_attention_maps: empty map")
         dev = _lib.default_device()
-        sizes = [a.size * 4 for a in arrs]
         host = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrs])
-        flat = torch.empty(int(sum(sizes)), device=dev, dtype=torch.uint8)
-        with torch.cuda.device(dev):
-            pipeline._upload(host, flat)
-        maps, off = [], 0
-        for a, n in zip(arrs, sizes):
-            maps.append(flat[off:off + n].view(torch.float32).view(*a.shape))
-            off += n
+        maps = packed_views(uploaded(host, dev).view(torch.float32), [a.shape for a in arrs])
     return PreparedAttention(maps, image_size, normalize).run()
 
 

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, _tables
+from ._batch import uploaded as _upload_records
 from ._lib import call, ptr, require_gpu, stream_ptr
 from .attention_extraction import NUM_IMAGE_TOKENS, kv_begin_from_mask, probe_head_mean
 
@@ -131,13 +132,6 @@ def _boxes(rec, boxes, sizes, who: str):
     rec["box_x"], rec["box_y"], rec["box_w"], rec["box_h"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
     sl = np.array([box_slice(box, H, W) for box, (W, H) in zip(b.tolist(), sizes)], dtype=np.int32)
     rec["r0"], rec["r1"], rec["c0"], rec["c1"] = sl[:, 0], sl[:, 1], sl[:, 2], sl[:, 3]
-
-
-def _upload_records(rec: np.ndarray, dev: torch.device) -> torch.Tensor:
-    from .pipeline import _upload
-    rec_dev = torch.empty(rec.nbytes, device=dev, dtype=torch.uint8)
-    _upload(rec.view(np.uint8), rec_dev)
-    return rec_dev
 
 
 def _packed(sizes, dev):

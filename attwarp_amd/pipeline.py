@@ -26,7 +26,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, _tables
+from . import _lib, _tables, jpeg, png
+from ._batch import TABLE, _upload, _upload_filled, file_bytes, packed_views, per_kind, planned_table, uploaded      # noqa: F401 (the pool's old home)
 from ._lib import call, ptr, require_gpu, stream_ptr
 from . import attention_extraction as ae
 from . import checkpoint_utils as cu
@@ -360,17 +361,11 @@ class ClipBatch:
         rec["bounds_y"] = [t[0].data_ptr() for t in ty]; rec["kk_y"] = [t[1].data_ptr() for t in ty]
         rec["ksize_x"] = [t[2] for t in tx]; rec["ksize_y"] = [t[2] for t in ty]
         self._keep = tx + ty
-        lib = _lib.load()
         rp = ctypes.c_void_p(rec.ctypes.data)
-        nbytes = lib.attwarp_clip_images_table_bytes(rp, self.B, C, size)
-        if nbytes == 0:
-            raise _lib.AttWarpError("attwarp_clip_images_table_bytes: " + lib.attwarp_last_error().decode("utf-8", "replace"))
-        self.table_host = np.empty(nbytes, dtype=np.uint8)
-        call("attwarp_clip_images_plan", rp, self.B, C, size, self.table_host.ctypes.data, nbytes)
-        self.header = _lib.ClipHeader.from_address(self.table_host.ctypes.data)
-        self.table_dev = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        with torch.cuda.device(dev):
-            _upload(self.table_host, self.table_dev)
+        self.table_host, self.header = planned_table(
+            ("attwarp_clip_images_table_bytes", rp, self.B, C, size), ("attwarp_clip_images_plan", rp, self.B, C, size, TABLE),
+            _lib.ClipHeader, _lib.AttWarpError, "attwarp_clip_images_table_bytes: ")
+        self.table_dev = uploaded(self.table_host, dev)
         self.tmp = torch.empty(int(self.header.tmp_bytes), device=dev, dtype=torch.uint8) if self.header.tmp_bytes else None
         if out is None:
             out = torch.empty(self.B, C, size, size, device=dev, dtype=dtype)
@@ -1300,8 +1295,7 @@ def ragged_eligible(h: int, w: int, c: int, g: int = GRID) -> bool:
 _RAGGED_IMAGE_DTYPE = np.dtype(_lib.RaggedImage)       # attwarp_ragged_image as a record array: one column per field
 _RaggedImageDev = _lib.RaggedImageDev
 _AXIS_TABLES: dict = {}
-_STAGING: dict = {}                   # device index -> pinned staging buffers: [tensor, event of the last copy out of it, free]
-_STAGING_LOCK = threading.Lock()     # (host threads on their own streams share the pool)
+_AXIS_TABLES_LOCK = threading.Lock()     # (host threads share the cache: insert + evict under one lock)
 
 
 _AXIS_TABLES_MAX = 4096              # distinct (device, g, size) entries kept (40 KB of device memory each at size 1024)
@@ -1315,51 +1309,11 @@ def _axis_tables(g: int, n: int, dev: torch.device):
     if t is None:
         b, k, ks = _tables.lanczos_tables(g, n, dev)
         t = (b.data_ptr(), k.data_ptr(), ks, b, k)
-        with _STAGING_LOCK:                   # (host threads share the cache: insert + evict under one lock)
+        with _AXIS_TABLES_LOCK:
             while len(_AXIS_TABLES) >= _AXIS_TABLES_MAX:
                 _AXIS_TABLES.pop(next(iter(_AXIS_TABLES)), None)
             _AXIS_TABLES[key] = t
     return t
-
-
-def _upload(host: "np.ndarray", dst: torch.Tensor):
-    """host bytes -> dst (device uint8), asynchronously on the current stream of dst's device through a pooled pinned buffer
-    (one pool per device: a slot's event is recorded on, and queried against, the stream that carries its copy).
-    Refuses to run inside a stream capture: the copy would become a graph node and be re-executed on every replay from a
-    staging buffer that has long been reused."""
-    def fill(buf):
-        buf[:] = host
-    _upload_filled(host.size, fill, dst)
-
-
-def _upload_filled(n: int, fill, dst: torch.Tensor):
-    """:func:`_upload` for bytes that are assembled in place: ``fill(buf)`` writes the n bytes straight into the pinned
-    staging slot (a uint8 numpy view), so data gathered from many sources crosses host memory once."""
-    dev = dst.device
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("attwarp_amd: a host-to-device table upload inside a stream capture (build RaggedBatch objects / call "
-                           "upload_images before capturing; a captured copy would replay from a reused staging buffer)")
-    with torch.cuda.device(dev):
-        with _STAGING_LOCK:
-            pool = _STAGING.setdefault(dev.index, [])
-            slot = None
-            for s in pool:
-                if s[0].numel() >= n and s[2] and s[1].query():
-                    slot = s
-                    break
-            if slot is None:
-                if len(pool) >= 64:               # (only if nothing ever completes: keep the pool bounded)
-                    torch.cuda.synchronize(dev)
-                    del pool[1:]
-                slot = [torch.empty(max(n, 1 << 16), dtype=torch.uint8).pin_memory(), torch.cuda.Event(), True]
-                pool.append(slot)
-            slot[2] = False                       # taken: nobody else may pick it until its copy has been enqueued and recorded
-        try:
-            fill(slot[0][:n].numpy())
-            dst.copy_(slot[0][:n], non_blocking=True)
-            slot[1].record(torch.cuda.current_stream(dev))
-        finally:
-            slot[2] = True
 
 
 class RaggedBatch:
@@ -1384,7 +1338,6 @@ class RaggedBatch:
         self.B, self.C, self.g = len(images), C, int(g)
         self.Ho, self.Wo = int(out_size[0]), int(out_size[1])
         self._dev = dev
-        lib = _lib.load()
         # the caller-side records (attwarp_ragged_image) as one structured array: pointers and sizes column by column
         rec = np.zeros(self.B, dtype=_RAGGED_IMAGE_DTYPE)
         rec["image"] = [im.data_ptr() for im in images]
@@ -1398,16 +1351,12 @@ class RaggedBatch:
         rec["bounds_y"] = [t[0] for t in ty]; rec["kk_y"] = [t[1] for t in ty]
         self._keep = [t[3:] for t in tx] + [t[3:] for t in ty]      # the coefficient tensors the table points to
         rp = ctypes.c_void_p(rec.ctypes.data)
-        nbytes = lib.attwarp_ragged_table_bytes(rp, self.B, C, self.g, self.Ho, self.Wo)
-        if nbytes == 0:
-            raise _lib.AttWarpError("attwarp_ragged_table_bytes: " + lib.attwarp_last_error().decode("utf-8", "replace"))
         # host copy: a plain buffer this batch keeps (the entry point reads the header from it at every launch); the upload
         # goes through a pooled pinned staging buffer (allocating pinned memory per batch costs more than the five launches)
-        self.table_host = np.empty(nbytes, dtype=np.uint8)
-        call("attwarp_ragged_plan", rp, self.B, C, self.g, self.Ho, self.Wo, self.table_host.ctypes.data, nbytes)
-        self.header = _lib.RaggedHeader.from_address(self.table_host.ctypes.data)
-        self.table_dev = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        _upload(self.table_host, self.table_dev)
+        shape = (rp, self.B, C, self.g, self.Ho, self.Wo)
+        self.table_host, self.header = planned_table(("attwarp_ragged_table_bytes",) + shape, ("attwarp_ragged_plan",) + shape + (TABLE,),
+                                                     _lib.RaggedHeader, _lib.AttWarpError, "attwarp_ragged_table_bytes: ")
+        self.table_dev = uploaded(self.table_host, dev)
         h = self.header
         if share is not None:
             if (share.B, share.g, share.Ho, share.Wo, int(share.header.mota_bytes), int(share.header.sums_bytes)) != \
@@ -1460,14 +1409,7 @@ def upload_images(images, device=None):
     for a, n in zip(arrs, sizes):
         host[off:off + n] = a.reshape(-1)
         off += n
-    flat = torch.empty(total, device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        _upload(host, flat)
-    out, off = [], 0
-    for a, n in zip(arrs, sizes):
-        out.append(flat[off:off + n].view(*a.shape))
-        off += n
-    return out
+    return packed_views(uploaded(host, dev), [a.shape for a in arrs])
 
 
 def upload_png_files(files_or_paths, device=None):
@@ -1475,8 +1417,7 @@ def upload_png_files(files_or_paths, device=None):
     files the drivers wrote, or anyone's 8-bit non-interlaced PNG): the COMPRESSED bytes go up in one transfer and are decoded
     on the GPU (attwarp_amd.png.decode_png) -> list of uint8 [H_i,W_i,3] RGB GPU tensors, views into one packed buffer, as
     ``Image.open(f).convert("RGB")`` gives them.  OSError for a broken file, ValueError for an unsupported one."""
-    from .png import decode_png
-    return decode_png(files_or_paths, "RGB", "rgb", device)
+    return png.decode_png(files_or_paths, "RGB", "rgb", device)
 
 
 def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressive=False):
@@ -1486,16 +1427,14 @@ def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressiv
     ``Image.open(f).convert("RGB")`` gives them.  OSError for a broken file, ValueError for an unsupported one.
     ``substreams``: marker-less files as self-synchronising sub-streams (jpeg.plan); the pixels do not depend on it.
     ``progressive=True`` also takes progressive files (jpeg.JpegFiles); without it they raise ValueError."""
-    from .jpeg import decode_jpeg
-    return decode_jpeg(files_or_paths, "RGB", "rgb", device, substreams, progressive)
+    return jpeg.decode_jpeg(files_or_paths, "RGB", "rgb", device, substreams, progressive)
 
 
 def upload_image_files(files_or_paths, device=None, substreams="auto", progressive=False):
     """A batch of image files of either kind (bytes-like or paths), each sent by its signature to the PNG or the JPEG decoder
     (:func:`upload_png_files`, :func:`upload_jpeg_files`): one transfer and one decode per kind -> the uint8 [H_i,W_i,3] RGB
     GPU tensors in input order.  ValueError for a file that is neither.  ``progressive``: see :func:`upload_jpeg_files`."""
-    from .jpeg import _file_bytes
-    files = [_file_bytes(f) for f in files_or_paths]
+    files = [file_bytes(f) for f in files_or_paths]
     kinds = []
     for i, f in enumerate(files):
         head = bytes(memoryview(f).cast("B")[:8])
@@ -1505,13 +1444,8 @@ def upload_image_files(files_or_paths, device=None, substreams="auto", progressi
             kinds.append("jpeg")
         else:
             raise ValueError(f"upload_image_files: file {i} is neither a PNG nor a JPEG file")
-    out = [None] * len(files)
-    for kind, decode in (("png", upload_png_files), ("jpeg", lambda f, d: upload_jpeg_files(f, d, substreams, progressive))):
-        idx = [i for i, k in enumerate(kinds) if k == kind]
-        if idx:
-            for i, v in zip(idx, decode([files[i] for i in idx], device)):
-                out[i] = v
-    return out
+    decode = {"png": upload_png_files, "jpeg": lambda f, d: upload_jpeg_files(f, d, substreams, progressive)}
+    return per_kind(files, kinds, ("png", "jpeg"), lambda kind, group: decode[kind](group, device))
 
 
 def ragged_chain_launch(R: Optional[RaggedBatch] = None, F: Optional[RaggedBatch] = None, P: Optional[RaggedBatch] = None,
@@ -1743,8 +1677,7 @@ def _overlay_call(rec: np.ndarray, dev: torch.device, map_dtype: int, style, alp
     B = int(rec.shape[0])
     lib = _lib.load()
     with torch.cuda.device(dev):
-        rec_dev = torch.empty(rec.nbytes, device=dev, dtype=torch.uint8)
-        _upload(rec.view(np.uint8), rec_dev)
+        rec_dev = uploaded(rec, dev)
         ws = torch.empty(lib.attwarp_overlay_workspace_bytes(B), device=dev, dtype=torch.uint8)
         call("attwarp_heatmap_overlay", rec.ctypes.data, ptr(rec_dev), B, map_dtype, OVERLAY_STYLES[style],
              float(alpha), _CHANNEL_ORDERS[order], _CHANNEL_ORDERS[out_order], ptr(ws), stream_ptr(dev))
@@ -1818,7 +1751,6 @@ def save_png_ragged(rb: RaggedBatch, paths, what: str = "warped", filter: str = 
     (``what="warped"``: ``rb.out``) or the up-sampled masks (``what="mota"``: :meth:`RaggedBatch.mota_of`, grey files) of
     ``rb`` as PNG files, encoded on the GPU in one :class:`attwarp_amd.png.PngBatch` -- only compressed bytes are copied
     to the host.  Enqueue it after the launches that produced what it saves; ``order``: channel order of ``rb.images``."""
-    from . import png
     paths = list(paths)
     if len(paths) != rb.B:
         raise ValueError(f"save_png_ragged: {len(paths)} paths for a batch of {rb.B}")

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._batch import TABLE, FileBatch, file_bytes, indexed_device, planned_table, raise_first_broken, uploaded
 from ._lib import call, ptr, stream_ptr
 
 PNG_SEG_BYTES = _lib.PNG_SEG_BYTES              # filtered bytes one workgroup encodes at most
@@ -76,7 +77,6 @@ class PngBatch:
 
     def __init__(self, images, filter: Union[str, Sequence[str]] = "sub", order: Union[str, Sequence[str]] = "rgb",
                  out: Optional[torch.Tensor] = None):
-        from .pipeline import _upload
         images = _views(images)
         if not images:
             raise ValueError("PngBatch: empty batch")
@@ -92,18 +92,12 @@ class PngBatch:
         rec["pitch"] = [g[3] for g in geo]
         rec["order"] = [_ORDERS[o] for o in orders]
         rec["filter"] = [_lib.PNG_FILTER_IDS[f] for f in filters]
-        lib = _lib.load()
         rp = ctypes.c_void_p(rec.ctypes.data)
-        nbytes = lib.attwarp_png_table_bytes(rp, B)
-        if nbytes == 0:
-            raise ValueError("PngBatch: " + lib.attwarp_last_error().decode("utf-8", "replace"))
-        self.table_host = np.empty(nbytes, dtype=np.uint8)
-        call("attwarp_png_plan", rp, B, self.table_host.ctypes.data, nbytes)
-        self.header = _lib.PngHeader.from_address(self.table_host.ctypes.data)
+        self.table_host, self.header = planned_table(("attwarp_png_table_bytes", rp, B), ("attwarp_png_plan", rp, B, TABLE),
+                                                     _lib.PngHeader, ValueError, "PngBatch: ")
         self._pixels = sum(g[0] * g[1] * g[2] for g in geo)
         with torch.cuda.device(dev):
-            self.table_dev = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-            _upload(self.table_host, self.table_dev)
+            self.table_dev = uploaded(self.table_host, dev)
             self.scratch = torch.empty(int(self.header.scratch_bytes), device=dev, dtype=torch.uint8)
             if out is None:
                 out = torch.empty(self.bound, device=dev, dtype=torch.uint8)
@@ -234,25 +228,18 @@ def parse_png(data, index: int = 0):
     return W, H, ctype, spans
 
 
-def _file_bytes(f):
-    if isinstance(f, (str, os.PathLike)):
-        with open(f, "rb") as fh:
-            return fh.read()
-    return f
-
-
-class PngFiles:
+class PngFiles(FileBatch):
     """One batch of PNG files planned for ``attwarp_pngdec_decode``: ``files`` is a list of bytes / bytearray / memoryview /
     paths.  The host walks the chunks (:func:`parse_png`), packs every IDAT payload of every file back to back and uploads
     them in ONE transfer; the plan depends only on what IHDR and the chunk lengths say.  ``mode``: "RGB" (what
     ``Image.open(f).convert("RGB")`` gives), "L" (``.convert("L")``) or "keep" (the file's channels without alpha);
     ``order="bgr"`` swaps a 3-channel result.  ``out``: a uint8 device buffer of at least :attr:`out_bytes` bytes.
-    Unsupported files raise ValueError before any launch."""
+    Unsupported files raise ValueError before any launch.  :meth:`run` is seven launches."""
+    _entry = "attwarp_pngdec_decode"
 
     def __init__(self, files, mode: str = "RGB", order: str = "rgb", check_crc: bool = True, out: Optional[torch.Tensor] = None,
                  device=None):
-        from .pipeline import _upload_filled
-        files = [_file_bytes(f) for f in files]
+        files = [file_bytes(f) for f in files]
         if not files:
             raise ValueError("PngFiles: empty batch")
         if mode not in _lib.PNGDEC_MODE_IDS or order not in _ORDERS:
@@ -278,58 +265,20 @@ class PngFiles:
         rec["stream_off"] = offs[:-1]; rec["stream_len"] = lens
         rec["W"] = [p[0] for p in parsed]; rec["H"] = [p[1] for p in parsed]; rec["color_type"] = [p[2] for p in parsed]
         rec["mode"] = _lib.PNGDEC_MODE_IDS[mode]; rec["order"] = _ORDERS[order]
-        dev = torch.device(device) if device is not None else (out.device if out is not None else _lib.default_device())
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        lib = _lib.load()
+        dev = indexed_device(device, out)
         rp, cp = ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(chunks.ctypes.data)
-        nbytes = lib.attwarp_pngdec_table_bytes(rp, B, nchunks)
-        if nbytes == 0:
-            raise ValueError("PngFiles: " + lib.attwarp_last_error().decode("utf-8", "replace"))
-        self.table_host = np.empty(nbytes, dtype=np.uint8)
-        try:
-            call("attwarp_pngdec_plan", rp, B, cp, nchunks, int(bool(check_crc)), self.table_host.ctypes.data, nbytes)
-        except _lib.AttWarpError as e:
-            raise ValueError(f"PngFiles: {e}") from None
-        self.header = _lib.PngDecHeader.from_address(self.table_host.ctypes.data)
+        self.table_host, self.header = planned_table(
+            ("attwarp_pngdec_table_bytes", rp, B, nchunks), ("attwarp_pngdec_plan", rp, B, cp, nchunks, int(bool(check_crc)), TABLE),
+            _lib.PngDecHeader, ValueError, "PngFiles: ", wrap_plan=True)
         self.B, self._dev, self.mode, self.order = B, dev, mode, order
         self.shapes = [(p[1], p[0], 1 if mode == "L" else 3 if mode == "RGB" else (1 if _CHANNELS[p[2]] <= 2 else 3)) for p in parsed]
         self.compressed_bytes = int(offs[-1])
-        with torch.cuda.device(dev):
-            # ONE transfer: the table, then (256-byte aligned) every IDAT payload, gathered straight into the pinned slot
-            pad = -nbytes % 256
-            total = nbytes + pad + max(self.compressed_bytes, 1)
 
-            def fill(buf):
-                buf[:nbytes] = self.table_host
-                body = buf[nbytes + pad:]
-                for src, moves in spans_of:
-                    for off, at, ln in moves:
-                        body[at:at + ln] = src[off:off + ln]
-            self._uploaded = torch.empty(total, device=dev, dtype=torch.uint8)
-            _upload_filled(total, fill, self._uploaded)
-            self.table_dev = self._uploaded[:nbytes]
-            self.stream = self._uploaded[nbytes + pad:]
-            self.scratch = torch.empty(int(self.header.scratch_bytes), device=dev, dtype=torch.uint8)
-            if out is None:
-                out = torch.empty(max(self.out_bytes, 1), device=dev, dtype=torch.uint8)
-            elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < self.out_bytes:
-                raise ValueError(f"PngFiles: out must be a dense uint8 buffer of at least {self.out_bytes} bytes on the device")
-            self.buffer = out
-            self.status = torch.empty(B, device=dev, dtype=torch.int32)
-
-    @property
-    def out_bytes(self) -> int:
-        """Bytes of all decoded images, back to back: the capacity ``out`` needs."""
-        return int(self.header.out_bytes)
-
-    def views(self) -> List[torch.Tensor]:
-        """uint8 [H_i, W_i, C] views into the packed output buffer, in the convention of ``pipeline.upload_images``."""
-        out, off = [], 0
-        for H, W, C in self.shapes:
-            out.append(self.buffer[off:off + H * W * C].view(H, W, C))
-            off += H * W * C
-        return out
+        def fill(body):                   # every IDAT payload, gathered straight into the pinned slot
+            for src, moves in spans_of:
+                for off, at, ln in moves:
+                    body[at:at + ln] = src[off:off + ln]
+        self._to_device(fill, out)
 
     def routes(self):
         """After a :meth:`run` (synchronises): per image ``(route, units on the chain, sync points kept)``; route 0 is the
@@ -346,25 +295,12 @@ class PngFiles:
         pos = self.scratch[off:off + B * U * 4].cpu().numpy().view(np.uint32).reshape(B, U)
         return [pos[b, :int(nunits[b])].tolist() for b in range(B)]
 
-    def run(self):
-        """Seven launches on the current stream -> ``(views, status)``: the images, and an int32 [B] device tensor (0: ok,
-        else ``STATUS_NAMES[code]``; such an image's pixels are unspecified).  No host synchronisation and no host-dependent
-        argument: capturable in a graph."""
-        with torch.cuda.device(self._dev):
-            call("attwarp_pngdec_decode", self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.stream), ptr(self.scratch),
-                 ptr(self.buffer), self.buffer.numel(), ptr(self.status), stream_ptr(self._dev))
-        return self.views(), self.status
-
 
 def decode_png(files, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
     """PNG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
     first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all."""
     views, status = PngFiles(files, mode, order, device=device).run()
-    st = status.cpu().tolist()
-    for i, s in enumerate(st):
-        if s:
-            name = STATUS_NAMES[s] if 0 <= s < len(STATUS_NAMES) else str(s)
-            raise OSError(f"png: file {i} of {len(st)} is broken: {name}")
+    raise_first_broken(status, STATUS_NAMES, "png")
     return views
 
 
