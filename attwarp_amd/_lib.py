@@ -165,6 +165,8 @@ SIGNATURES = {
     "attwarp_pngdec_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "attwarp_pngdec_plan": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t]),
     "attwarp_pngdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "attwarp_pngdec_table_bytes_formats": (c_size_t, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    "attwarp_pngdec_plan_formats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t]),
     # baseline JPEG files decoded on the device (jpegdec.hip)
     "attwarp_jpegdec_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_jpegdec_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
@@ -253,10 +255,16 @@ class PngDecChunk(ctypes.Structure):
 class PngDecHeader(ctypes.Structure):
     """attwarp_pngdec_header: the first bytes of a table written by attwarp_pngdec_plan."""
     _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("nchunks", ctypes.c_int32), ("check_crc", ctypes.c_int32),
-                ("lds_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int32), ("formats", ctypes.c_int32),
                 ("table_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
                 ("stream_bytes", ctypes.c_uint64), ("off_images", ctypes.c_uint64), ("off_chunks", ctypes.c_uint64),
                 ("crc_pow8", ctypes.c_uint32 * 32), ("idat_crc", ctypes.c_uint32), ("reserved2", ctypes.c_uint32)]
+
+
+class PngDecFormat(ctypes.Structure):
+    """attwarp_pngdec_format: what IHDR and PLTE say besides, parallel to the images of attwarp_pngdec_plan_formats."""
+    _fields_ = [("depth", ctypes.c_int32), ("interlace", ctypes.c_int32), ("palette_entries", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("palette", ctypes.c_uint8 * 768)]
 
 
 class JpegDecImage(ctypes.Structure):

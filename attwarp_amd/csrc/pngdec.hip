@@ -12,11 +12,13 @@
 //   pngdec_adler_kernel     one workgroup per image: Adler-32 of the filtered bytes against the stream's;
 //   pngdec_unfilter_kernel  one wave per image: 64 rows in flight, skewed by one pixel per lane, so that the row above is one
 //                           lane away; reconstructs, converts and writes the pixels, then the image's status.
+// A table of attwarp_pngdec_plan_formats with the format flag (palette, 1 / 2 / 4 / 16 bits, Adam7: DESIGN.md 3.18) takes, in
+// place of the last launch, pngdec_unfilter_formats_kernel (one wave per image and PASS) and pngdec_status_formats_kernel.
 // Every loop is bounded by a constant, by a size the planner checked, or by the stream's bits (pngdec_blocks.hpp).
 #include <algorithm>
 #include <cstring>
 
-#include "pngdec_blocks.hpp"
+#include "pngfmt_blocks.hpp"
 
 namespace attwarp {
 
@@ -30,6 +32,10 @@ __host__ __device__ inline uint64_t pd_align(uint64_t v, uint64_t a) { return (v
 __host__ __device__ inline uint64_t pd_units_off(int B) { return pd_align((uint64_t)B * sizeof(PdState), 16); }
 __host__ __device__ inline uint64_t pd_kept_off(int B) { return pd_units_off(B) + (uint64_t)B * PD_MAX_UNITS * sizeof(PdUnit); }
 __host__ __device__ inline uint64_t pd_filt_base(int B) { return pd_align(pd_kept_off(B) + (uint64_t)B * PD_MAX_UNITS * 4u, 256); }
+// a table with the format flag: the format records stand behind the chunks, the palettes behind them
+__host__ __device__ inline uint64_t pf_formats_off(const attwarp_pngdec_header& h) {
+  return pd_align(h.off_chunks + (uint64_t)h.nchunks * sizeof(attwarp_pngdec_chunk), 16);
+}
 
 struct PdView {
   const attwarp_pngdec_header* hdr;
@@ -323,11 +329,99 @@ __global__ __launch_bounds__(WAVE) void pngdec_unfilter_kernel(const uint8_t* __
   if (lane == 0) status[b] = (int32_t)stat;
 }
 
+// The same skewed scheme for every format of the specification.  Grid (B, 7), one wave per (image, pass):
+// the passes of an interlaced image are filtered on their own, so they are independent once inflated; a non-interlaced
+// image is its slot 0 and the other slots exit.  Lane l reconstructs row r0 + l of the PASS, one filter unit of 1 .. 8 bytes
+// per step (packed into 64 bits), and scatters the converted pixels to ((y0 + r dy) W + x0 + x dx) oc; a unit below 8 bits
+// holds up to 8 pixels, clipped at the pass's width.  LDS: the converted palette (1 KiB), then lane 63's row.
+// A bad filter byte raises st_filter with an atomic max; pngdec_status_formats_kernel then states the image's status.
+__global__ __launch_bounds__(WAVE) void pngdec_unfilter_formats_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch,
+                                                                       uint8_t* __restrict__ out) {
+  extern __shared__ uint8_t s_dyn[];
+  uint32_t* s_pal = reinterpret_cast<uint32_t*>(s_dyn);
+  uint8_t* s_carry = s_dyn + PF_PALETTE_LDS;
+  const int lane = threadIdx.x, b = blockIdx.x, p = blockIdx.y;
+  const PdView v(table, scratch);
+  PdState* st = v.states + b;
+  if (st->st_crc || st->st_inflate || st->st_adler) return;   // (uniform)
+  const PdImage im = v.images[b];
+  const PfImage fm = reinterpret_cast<const PfImage*>(table + pf_formats_off(*v.hdr))[b];
+  const int W = im.W, ch = im.ch, oc = im.oc, depth = fm.depth, ctype = fm.ctype;
+  const PfPass g = pf_pass(fm.interlace, p, W, im.H);
+  if (g.w <= 0 || g.h <= 0) return;                         // (uniform)
+  const bool swap = im.swap != 0;
+  if (ctype == 3) {
+    const uint8_t* pal = table + fm.pal_off;
+    for (int i = lane; i < 256; i += WAVE) s_pal[i] = pf_palette_entry(pal, i, oc, swap);
+    __syncthreads();
+  }
+  const int unit = pf_unit(ch, depth), ppu = pf_unit_pixels(depth);
+  const int RB = (int)pf_row_bytes(g.w, ch, depth), nu = (RB - 1) / unit;
+  const PD_G uint8_t* filt = (const PD_G uint8_t*)scratch + im.filt_off + pf_pass_offset(fm.interlace, p, W, im.H, ch, depth);
+  PD_G uint8_t* o = (PD_G uint8_t*)out + im.out_off;
+  for (int r0 = 0; r0 < g.h; r0 += WAVE) {
+    const int r = r0 + lane;
+    const bool active = r < g.h;
+    const PD_G uint8_t* frow = filt + (size_t)(active ? r : r0) * RB;
+    const int ft = frow[0];
+    if (__ballot(active && ft > 4) != 0ull) {
+      if (lane == 0) atomicMax(&st->st_filter, (uint32_t)ATTWARP_PNGDEC_E_FILTER);
+      return;
+    }
+    const int rows = min(WAVE, g.h - r0), steps = nu + rows - 1;
+    const bool keep = r0 + WAVE < g.h;                      // a later batch needs this one's last row
+    const size_t orow = ((size_t)(g.y0 + r * g.dy) * W + g.x0) * oc;
+    uint64_t cur = 0, up = 0, upleft = 0;
+    for (int s = 0; s < steps; ++s) {
+      const int x = s - lane;
+      const bool on = active && x >= 0 && x < nu;
+      const uint32_t alo = __shfl_up((uint32_t)cur, 1, WAVE), ahi = __shfl_up((uint32_t)(cur >> 32), 1, WAVE);
+      upleft = up;
+      up = (uint64_t)ahi << 32 | alo;
+      if (lane == 0) {
+        up = 0;
+        if (r0 > 0 && on)
+          for (int k = 0; k < unit; ++k) up |= (uint64_t)s_carry[x * unit + k] << (8 * k);
+      }
+      if (on) {
+        const uint64_t left = cur;
+        uint64_t px = 0;
+        for (int k = 0; k < unit; ++k) {
+          const uint32_t f = frow[1 + x * unit + k];
+          px |= (uint64_t)pd_recon(ft, f, (int)((left >> (8 * k)) & 255u), (int)((up >> (8 * k)) & 255u), (int)((upleft >> (8 * k)) & 255u)) << (8 * k);
+        }
+        cur = px;
+        if (keep && lane == WAVE - 1)
+          for (int k = 0; k < unit; ++k) s_carry[x * unit + k] = (uint8_t)(px >> (8 * k));
+        const int n = min(ppu, g.w - x * ppu);              // pixels of this unit inside the pass
+        for (int j = 0; j < n; ++j) {
+          const uint32_t q = pf_output(ctype, pf_pixel(ctype, depth, px, j), oc, swap, s_pal);
+          PD_G uint8_t* d = o + orow + (size_t)(x * ppu + j) * g.dx * oc;
+          d[0] = (uint8_t)q;
+          if (oc == 3) { d[1] = (uint8_t)(q >> 8); d[2] = (uint8_t)(q >> 16); }
+        }
+      }
+    }
+  }
+}
+
+// One thread per image: the first failing check in the order CRC, inflate, Adler, filter, as pngdec_unfilter_kernel states it.
+__global__ __launch_bounds__(WAVE) void pngdec_status_formats_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
+                                                                     int32_t* __restrict__ status) {
+  const attwarp_pngdec_header* hdr = reinterpret_cast<const attwarp_pngdec_header*>(table);
+  const int b = blockIdx.x * WAVE + threadIdx.x;
+  if (b >= hdr->B) return;
+  const PdState st = reinterpret_cast<const PdState*>(scratch)[b];
+  status[b] = (int32_t)(st.st_crc ? st.st_crc : st.st_inflate ? st.st_inflate : st.st_adler ? st.st_adler : st.st_filter);
+}
+
 }  // namespace attwarp
 
 using namespace attwarp;
 
-static int pngdec_check(const attwarp_pngdec_image* images, int B, const attwarp_pngdec_chunk* chunks, int nchunks) {
+// formats == nullptr: the 8-bit, non-interlaced records of attwarp_pngdec_plan
+static int pngdec_check(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B, const attwarp_pngdec_chunk* chunks,
+                        int nchunks) {
   ATTWARP_REQUIRE(images, "pngdec: null image array");
   ATTWARP_REQUIRE(B > 0, "pngdec: non-positive batch size");
   ATTWARP_REQUIRE(nchunks >= 0 && (nchunks == 0 || chunks), "pngdec: null chunk array");
@@ -336,15 +430,26 @@ static int pngdec_check(const attwarp_pngdec_image* images, int B, const attwarp
   for (int b = 0; b < B; ++b) {
     const attwarp_pngdec_image& d = images[b];
     ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1, "pngdec: image %d: non-positive size %d x %d", b, d.H, d.W);
-    ATTWARP_REQUIRE(d.color_type == 0 || d.color_type == 2 || d.color_type == 4 || d.color_type == 6,
-                    "pngdec: image %d: colour type %d (0, 2, 4 or 6)", b, d.color_type);
+    int depth = 8, lace = 0;
+    if (formats) {
+      const attwarp_pngdec_format& f = formats[b];
+      depth = f.depth;
+      lace = f.interlace;
+      ATTWARP_REQUIRE(pf_valid(depth, d.color_type), "pngdec: image %d: bit depth %d with colour type %d", b, depth, d.color_type);
+      ATTWARP_REQUIRE(lace == 0 || lace == 1, "pngdec: image %d: interlace method %d (0 or 1)", b, lace);
+      ATTWARP_REQUIRE(d.color_type == 3 ? f.palette_entries >= 1 && f.palette_entries <= 256 : f.palette_entries >= 0 && f.palette_entries <= 256,
+                      "pngdec: image %d: a PLTE of %d entries", b, f.palette_entries);
+    } else {
+      ATTWARP_REQUIRE(d.color_type == 0 || d.color_type == 2 || d.color_type == 4 || d.color_type == 6,
+                      "pngdec: image %d: colour type %d (0, 2, 4 or 6)", b, d.color_type);
+    }
     ATTWARP_REQUIRE(d.mode >= ATTWARP_PNGDEC_RGB && d.mode <= ATTWARP_PNGDEC_KEEP, "pngdec: image %d: unknown mode %d", b, d.mode);
     ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "pngdec: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
-    const int64_t ch = d.color_type == 0 ? 1 : d.color_type == 2 ? 3 : d.color_type == 4 ? 2 : 4;
-    const int64_t rb = 1 + (int64_t)d.W * ch;
+    const int ch = pf_channels(d.color_type);
+    const int64_t rb = pf_row_bytes(d.W, ch, depth);
     if (rb > ATTWARP_PNGDEC_MAX_ROW_BYTES)
       return fail(ATTWARP_E_UNSUPPORTED, "pngdec: image %d: row of %lld bytes (> %d)", b, (long long)rb, ATTWARP_PNGDEC_MAX_ROW_BYTES);
-    if ((int64_t)d.H * rb >= ((int64_t)1 << 31))
+    if (pf_pass_offset(lace, PF_PASSES, d.W, d.H, ch, depth) >= ((int64_t)1 << 31))
       return fail(ATTWARP_E_UNSUPPORTED, "pngdec: image %d: %d x %d x %lld is 2 GiB or more", b, d.H, d.W, (long long)ch);
     if (d.stream_len >= ((uint64_t)1 << 31) || d.stream_off >= ((uint64_t)1 << 62))
       return fail(ATTWARP_E_UNSUPPORTED, "pngdec: image %d: a zlib stream of 2 GiB or more", b);
@@ -359,24 +464,49 @@ static int pngdec_check(const attwarp_pngdec_image* images, int B, const attwarp
   return ATTWARP_OK;
 }
 
-static size_t pngdec_bytes(int B, int nchunks) {
-  return (size_t)(pd_align(sizeof(attwarp_pngdec_header), 16) + pd_align((uint64_t)B * sizeof(PdImage), 16) +
-                  (uint64_t)nchunks * sizeof(attwarp_pngdec_chunk));
+// the format flag: at least one image that pngdec_unfilter_kernel does not decode
+static bool pngdec_needs_formats(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B) {
+  if (!formats) return false;
+  for (int b = 0; b < B; ++b)
+    if (!pf_plain(formats[b].depth, images[b].color_type, formats[b].interlace)) return true;
+  return false;
+}
+
+static size_t pngdec_bytes(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B, int nchunks) {
+  uint64_t n = pd_align(sizeof(attwarp_pngdec_header), 16) + pd_align((uint64_t)B * sizeof(PdImage), 16) +
+               (uint64_t)nchunks * sizeof(attwarp_pngdec_chunk);
+  if (pngdec_needs_formats(images, formats, B)) {
+    n = pd_align(n, 16) + (uint64_t)B * sizeof(PfImage);
+    for (int b = 0; b < B; ++b)
+      if (images[b].color_type == 3) n += 768;
+  }
+  return (size_t)n;
+}
+
+static bool pngdec_bytes_args(const void* images, int B, int nchunks) {
+  if (images && B > 0 && B <= PD_MAX_B && nchunks >= 0 && nchunks <= PD_MAX_CHUNKS) return true;
+  fail(ATTWARP_E_ARG, "pngdec_table_bytes: B=%d, nchunks=%d outside the limits", B, nchunks);
+  return false;
 }
 
 extern "C" size_t attwarp_pngdec_table_bytes(const attwarp_pngdec_image* images, int B, int nchunks) {
-  if (!images || B <= 0 || B > PD_MAX_B || nchunks < 0 || nchunks > PD_MAX_CHUNKS) {
-    fail(ATTWARP_E_ARG, "pngdec_table_bytes: B=%d, nchunks=%d outside the limits", B, nchunks);
-    return 0;
-  }
-  return pngdec_bytes(B, nchunks);
+  return pngdec_bytes_args(images, B, nchunks) ? pngdec_bytes(images, nullptr, B, nchunks) : 0;
 }
 
-extern "C" int attwarp_pngdec_plan(const attwarp_pngdec_image* images, int B, const attwarp_pngdec_chunk* chunks, int nchunks,
-                                   int check_crc, void* table, size_t table_bytes) {
-  if (const int rc = pngdec_check(images, B, chunks, nchunks)) return rc;
+extern "C" size_t attwarp_pngdec_table_bytes_formats(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                                                     const attwarp_pngdec_chunk* chunks, int nchunks) {
+  (void)chunks;
+  if (!pngdec_bytes_args(images, B, nchunks)) return 0;
+  if (!formats) { fail(ATTWARP_E_ARG, "pngdec_table_bytes_formats: null format array"); return 0; }
+  return pngdec_bytes(images, formats, B, nchunks);
+}
+
+static int pngdec_plan(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B, const attwarp_pngdec_chunk* chunks,
+                       int nchunks, int check_crc, void* table, size_t table_bytes) {
+  if (const int rc = pngdec_check(images, formats, B, chunks, nchunks)) return rc;
   ATTWARP_REQUIRE(table, "pngdec_plan: null table");
-  const size_t need = pngdec_bytes(B, nchunks);
+  const bool fmt = pngdec_needs_formats(images, formats, B);
+  const size_t need = pngdec_bytes(images, formats, B, nchunks);
   ATTWARP_REQUIRE(table_bytes >= need, "pngdec_plan: table of %zu bytes, %zu needed", table_bytes, need);
   uint8_t* t = static_cast<uint8_t*>(table);
   std::memset(t, 0, need);
@@ -386,6 +516,7 @@ extern "C" int attwarp_pngdec_plan(const attwarp_pngdec_image* images, int B, co
   h.B = B;
   h.nchunks = nchunks;
   h.check_crc = check_crc != 0;
+  h.formats = fmt ? 1 : 0;
   h.table_bytes = need;
   h.off_images = pd_align(sizeof(attwarp_pngdec_header), 16);
   h.off_chunks = h.off_images + pd_align((uint64_t)B * sizeof(PdImage), 16);
@@ -395,33 +526,55 @@ extern "C" int attwarp_pngdec_plan(const attwarp_pngdec_image* images, int B, co
   const uint8_t idat[4] = {'I', 'D', 'A', 'T'};
   h.idat_crc = crc_bytes(idat, 4);
   PdImage* im = reinterpret_cast<PdImage*>(t + h.off_images);
-  uint64_t soff = pd_filt_base(B), ooff = 0, stream_bytes = 0;
+  PfImage* fm = fmt ? reinterpret_cast<PfImage*>(t + pf_formats_off(h)) : nullptr;
+  uint64_t soff = pd_filt_base(B), ooff = 0, stream_bytes = 0, poff = fmt ? pf_formats_off(h) + (uint64_t)B * sizeof(PfImage) : 0;
   int lds = 16;
   for (int b = 0; b < B; ++b) {
     const attwarp_pngdec_image& d = images[b];
+    const int depth = formats ? formats[b].depth : 8, lace = formats ? formats[b].interlace : 0;
     PdImage& r = im[b];
-    r.ch = d.color_type == 0 ? 1 : d.color_type == 2 ? 3 : d.color_type == 4 ? 2 : 4;
-    r.oc = pd_out_channels(r.ch, d.mode);
+    r.ch = pf_channels(d.color_type);
+    r.oc = pf_out_channels(d.color_type, d.mode);
     r.H = d.H; r.W = d.W;
-    r.swap = r.oc == 3 && r.ch >= 3 && d.order == ATTWARP_BGR;
-    r.row_bytes = 1 + d.W * r.ch;
+    r.swap = r.oc == 3 && (r.ch >= 3 || d.color_type == 3) && d.order == ATTWARP_BGR;
+    r.row_bytes = (int32_t)pf_row_bytes(d.W, r.ch, depth);
     r.stream_off = d.stream_off;
     r.stream_len = (uint32_t)d.stream_len;
-    r.filt_bytes = (uint32_t)((uint64_t)d.H * (uint64_t)r.row_bytes);
+    r.filt_bytes = (uint32_t)pf_pass_offset(lace, PF_PASSES, d.W, d.H, r.ch, depth);
     r.filt_off = soff;
     r.out_off = ooff;
     soff += pd_align(r.filt_bytes, 16);
     ooff += (uint64_t)d.H * d.W * r.oc;
     stream_bytes = std::max(stream_bytes, d.stream_off + d.stream_len);
-    lds = std::max(lds, (int)pd_align((uint64_t)d.W * r.ch, 16));
+    lds = std::max(lds, (int)pd_align((uint64_t)r.row_bytes - 1, 16));
+    if (fmt) {
+      PfImage& f = fm[b];
+      f.depth = depth; f.ctype = d.color_type; f.interlace = lace; f.pal_off = 0;
+      if (d.color_type == 3) {                             // padded with zeros: an index past the entries is black
+        f.pal_off = (uint32_t)poff;
+        std::memcpy(t + poff, formats[b].palette, (size_t)formats[b].palette_entries * 3);
+        poff += 768;
+      }
+    }
   }
   if (nchunks) std::memcpy(t + h.off_chunks, chunks, (size_t)nchunks * sizeof(attwarp_pngdec_chunk));
   h.scratch_bytes = soff;
   h.out_bytes = ooff;
   h.stream_bytes = stream_bytes;
-  h.lds_bytes = lds;
+  h.lds_bytes = lds + (fmt ? PF_PALETTE_LDS : 0);
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
+}
+
+extern "C" int attwarp_pngdec_plan(const attwarp_pngdec_image* images, int B, const attwarp_pngdec_chunk* chunks, int nchunks,
+                                   int check_crc, void* table, size_t table_bytes) {
+  return pngdec_plan(images, nullptr, B, chunks, nchunks, check_crc, table, table_bytes);
+}
+
+extern "C" int attwarp_pngdec_plan_formats(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                                           const attwarp_pngdec_chunk* chunks, int nchunks, int check_crc, void* table, size_t table_bytes) {
+  ATTWARP_REQUIRE(formats, "pngdec_plan_formats: null format array");
+  return pngdec_plan(images, formats, B, chunks, nchunks, check_crc, table, table_bytes);
 }
 
 extern "C" int attwarp_pngdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
@@ -430,7 +583,8 @@ extern "C" int attwarp_pngdec_decode(const void* table_host, const void* table_d
   attwarp_pngdec_header h;
   std::memcpy(&h, table_host, sizeof h);
   ATTWARP_REQUIRE(h.magic == PD_MAGIC && h.B > 0 && h.B <= PD_MAX_B && h.nchunks >= 0 && h.nchunks <= PD_MAX_CHUNKS &&
-                      h.lds_bytes >= 16 && h.lds_bytes <= ATTWARP_PNGDEC_MAX_ROW_BYTES,
+                      (h.formats == 0 || h.formats == 1) && h.lds_bytes >= 16 + h.formats * PF_PALETTE_LDS &&
+                      h.lds_bytes <= ATTWARP_PNGDEC_MAX_ROW_BYTES + h.formats * PF_PALETTE_LDS,
                   "pngdec_decode: not a table of attwarp_pngdec_plan");
   ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "pngdec_decode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
   ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
@@ -455,6 +609,12 @@ extern "C" int attwarp_pngdec_decode(const void* table_host, const void* table_d
   if (const int rc = check_launch("pngdec_inflate_kernel (write)")) return rc;
   hipLaunchKernelGGL(pngdec_adler_kernel, dim3(h.B), dim3(PD_NT), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("pngdec_adler_kernel")) return rc;
-  hipLaunchKernelGGL(pngdec_unfilter_kernel, dim3(h.B), dim3(WAVE), (size_t)h.lds_bytes, st, td, sc, out, status);
-  return check_launch("pngdec_unfilter_kernel");
+  if (!h.formats) {
+    hipLaunchKernelGGL(pngdec_unfilter_kernel, dim3(h.B), dim3(WAVE), (size_t)h.lds_bytes, st, td, sc, out, status);
+    return check_launch("pngdec_unfilter_kernel");
+  }
+  hipLaunchKernelGGL(pngdec_unfilter_formats_kernel, dim3(h.B, PF_PASSES), dim3(WAVE), (size_t)h.lds_bytes, st, td, sc, out);
+  if (const int rc = check_launch("pngdec_unfilter_formats_kernel")) return rc;
+  hipLaunchKernelGGL(pngdec_status_formats_kernel, dim3((h.B + WAVE - 1) / WAVE), dim3(WAVE), 0, st, td, sc, status);
+  return check_launch("pngdec_status_formats_kernel");
 }

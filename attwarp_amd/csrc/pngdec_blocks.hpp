@@ -370,8 +370,5 @@ __host__ __device__ inline uint32_t pd_be32(const uint8_t* p) {
 // filtered byte f, a = left, b = up, c = upper left (all reconstructed) -> the reconstructed byte
 __host__ __device__ inline uint32_t pd_recon(int ft, uint32_t f, int a, int b, int c) { return (f - png_filter(ft, 0, a, b, c)) & 255u; }
 __host__ __device__ inline uint32_t pd_luma(uint32_t r, uint32_t g, uint32_t b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }
-__host__ __device__ inline int pd_out_channels(int ch, int mode) {
-  return mode == ATTWARP_PNGDEC_L ? 1 : mode == ATTWARP_PNGDEC_RGB ? 3 : (ch <= 2 ? 1 : 3);
-}
 
 }  // namespace attwarp

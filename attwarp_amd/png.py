@@ -1,6 +1,7 @@
 """PNG files of a whole ragged batch, encoded and decoded on the GPU.  Decoding (csrc/pngdec.hip) is the
 reading half: what the reference does per file with ``Image.open(...).convert(...)`` (evaluate_accuracy.py:157-158,
-MN/dataloader.py:171-382); only compressed bytes cross to the device.  8-bit grey, grey + alpha, RGB, RGBA, non-interlaced.
+MN/dataloader.py:171-382); only compressed bytes cross to the device.  8-bit grey, grey + alpha, RGB, RGBA, non-interlaced;
+with ``all_formats=True`` every format of the specification: palette files, 1 / 2 / 4 / 16 bits, Adam7.
 
 Encoding: PNG files of a whole ragged batch, encoded on the GPU (csrc/png.hip): what the reference's drivers
 write per sample with ``cv2.imwrite`` (main_batched.py:243-303, new_method.py:405-506).  Only compressed bytes cross to
@@ -161,12 +162,35 @@ _SIGNATURE = b"\x89PNG\r\n\x1a\n"
 _CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
 _PNGDEC_IMAGE_DTYPE = np.dtype(_lib.PngDecImage)
 _PNGDEC_CHUNK_DTYPE = np.dtype(_lib.PngDecChunk)
+_PNGDEC_FORMAT_DTYPE = np.dtype(_lib.PngDecFormat)
+_FORMAT_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}       # all_formats: the palette's index is one channel
+_FORMAT_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
+_ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))
 
 
-def parse_png(data, index: int = 0):
+def filtered_bytes(W: int, H: int, channels: int, depth: int, interlace: int) -> int:
+    """Bytes behind inflate: rows of 1 + ceil(w * channels * depth / 8), summed over the seven Adam7 passes of an
+    interlaced file (w = ceil((W - x0) / dx), h = ceil((H - y0) / dy); an empty pass has none)."""
+    total = 0
+    for x0, y0, dx, dy in (_ADAM7 if interlace else ((0, 0, 1, 1),)):
+        w, h = max(0, -(-(W - x0) // dx)), max(0, -(-(H - y0) // dy))
+        if w and h:
+            total += h * (1 + (w * channels * depth + 7) // 8)
+    return total
+
+
+def parse_png(data, index: int = 0, all_formats: bool = False):
     """The host's whole part of decoding one file: the chunk walk.  bytes-like -> ``(W, H, colour type, [(offset, length,
     stated CRC-32) of every IDAT payload])``.  Signature, IHDR first (its CRC and IEND's are checked here: tens of bytes),
-    consecutive IDATs, IEND; ancillary chunks are skipped.  No compressed byte is looked at.  ValueError names the field."""
+    consecutive IDATs, IEND; ancillary chunks are skipped.  No compressed byte is looked at.  ValueError names the field.
+
+    ``all_formats=True`` accepts every depth / colour-type pair of the specification (grey 1 / 2 / 4 / 8 / 16, palette
+    1 / 2 / 4 / 8, RGB, grey + alpha and RGBA 8 / 16) with interlace method 0 or 1, and returns ``(W, H, colour type, spans,
+    bit depth, interlace, palette bytes)``; the palette bytes are empty unless the colour type is 3.  It refuses, by these
+    words: *bit depth* (a pair outside the list), *interlace* (a method above 1), *PLTE* (a palette file without a PLTE
+    before its first IDAT, with one whose length is 0, no multiple of 3 or above 768, with a second one, or with a wrong PLTE
+    CRC -- Pillow is more lenient there, this walk follows the specification), *size limit* (a full-width row above
+    PNGDEC_MAX_ROW_BYTES, filtered bytes over all passes or a stream of 2 GiB or more).  tRNS is skipped."""
     mv = memoryview(data).cast("B")
     n = len(mv)
 
@@ -176,6 +200,7 @@ def parse_png(data, index: int = 0):
     if n < 8 or bytes(mv[:8]) != _SIGNATURE:
         raise bad("bad signature")
     pos, ihdr, spans, idat_done, iend = 8, None, [], False, False
+    plte = None                                               # (all_formats, colour type 3: the PLTE payload)
     while pos < n:
         if pos + 12 > n:
             raise bad("truncated chunk")
@@ -206,12 +231,41 @@ def parse_png(data, index: int = 0):
             idat_done = bool(spans)
             if not (kind[0] & 32) and kind != b"PLTE":        # (a suggested palette is legal in colour files)
                 raise bad(f"unknown critical chunk {kind!r}")
+            if all_formats and kind == b"PLTE" and ihdr[3] == 3:
+                if plte is not None:
+                    raise bad("a second PLTE")
+                if spans:
+                    raise bad("PLTE behind the first IDAT")
+                if ln == 0 or ln % 3 or ln > 768:
+                    raise bad(f"PLTE of {ln} bytes (3 to 768, a multiple of 3)")
+                if zlib.crc32(mv[pos + 4:pos + 8 + ln]) != crc:
+                    raise bad("PLTE CRC")
+                plte = bytes(mv[pos + 8:pos + 8 + ln])
         pos += 12 + ln
     if ihdr is None:
         raise bad("IHDR missing")
     if not iend:
         raise bad("IEND missing")
     W, H, depth, ctype, comp, filt, lace = ihdr
+    if all_formats:
+        if ctype not in _FORMAT_DEPTHS:
+            raise bad(f"colour type {ctype} (0, 2, 3, 4 or 6)")
+        if depth not in _FORMAT_DEPTHS[ctype]:
+            raise bad(f"bit depth {depth} with colour type {ctype} ({_FORMAT_DEPTHS[ctype]} only)")
+        if comp != 0 or filt != 0:
+            raise bad("unknown compression / filter method")
+        if lace > 1:
+            raise bad(f"interlace method {lace} (0 or 1)")
+        if W == 0 or H == 0:
+            raise bad(f"size {W} x {H}")
+        if ctype == 3 and plte is None:
+            raise bad("PLTE missing before the first IDAT of a palette file")
+        ch = _FORMAT_CHANNELS[ctype]
+        if (1 + (W * ch * depth + 7) // 8 > PNGDEC_MAX_ROW_BYTES or filtered_bytes(W, H, ch, depth, lace) >= 1 << 31
+                or sum(s[1] for s in spans) >= 1 << 31):
+            raise bad(f"size limit: {W} x {H} x {ch} at {depth} bits (rows of at most {PNGDEC_MAX_ROW_BYTES} bytes, images and "
+                      "streams below 2 GiB)")
+        return W, H, ctype, spans, depth, lace, plte or b""
     if depth != 8:
         raise bad(f"bit depth {depth} (8 only)")
     if ctype not in _CHANNELS:
@@ -234,17 +288,25 @@ class PngFiles(FileBatch):
     them in ONE transfer; the plan depends only on what IHDR and the chunk lengths say.  ``mode``: "RGB" (what
     ``Image.open(f).convert("RGB")`` gives), "L" (``.convert("L")``) or "keep" (the file's channels without alpha);
     ``order="bgr"`` swaps a 3-channel result.  ``out``: a uint8 device buffer of at least :attr:`out_bytes` bytes.
-    Unsupported files raise ValueError before any launch.  :meth:`run` is seven launches."""
+    Unsupported files raise ValueError before any launch.  :meth:`run` is seven launches.
+
+    ``all_formats=True`` also takes palette, 1- / 2- / 4- / 16-bit and Adam7 files (:func:`parse_png`), with Pillow's pixels:
+    samples below 8 bits MSB first, grey ones scaled by 255 / 85 / 17; 16-bit grey SATURATES (``min(v, 255)``, as Pillow's
+    ``I;16`` does), every other 16-bit sample gives its high byte; a palette index gives its PLTE entry ("L": the entry's
+    luma), one past the entries black; tRNS and alpha are dropped.  "keep" is the file's channels without alpha at 8 bits, a
+    palette file its palette's three; "bgr" swaps palette colours too.  A call whose files are all 8-bit and non-interlaced
+    plans the same table and launches as without the keyword; otherwise every file of the call goes through the formats
+    kernel and :meth:`run` is nine launches."""
     _entry = "attwarp_pngdec_decode"
 
     def __init__(self, files, mode: str = "RGB", order: str = "rgb", check_crc: bool = True, out: Optional[torch.Tensor] = None,
-                 device=None):
+                 device=None, all_formats: bool = False):
         files = [file_bytes(f) for f in files]
         if not files:
             raise ValueError("PngFiles: empty batch")
         if mode not in _lib.PNGDEC_MODE_IDS or order not in _ORDERS:
             raise ValueError(f"PngFiles: mode must be one of {sorted(_lib.PNGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
-        parsed = [parse_png(f, i) for i, f in enumerate(files)]
+        parsed = [parse_png(f, i, True) if all_formats else parse_png(f, i) + (8, 0, b"") for i, f in enumerate(files)]
         B = len(files)
         nchunks = sum(len(p[3]) for p in parsed)
         rec = np.zeros(B, dtype=_PNGDEC_IMAGE_DTYPE)
@@ -253,7 +315,7 @@ class PngFiles(FileBatch):
         offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         spans_of = []                     # per file: (source bytes, [(offset in the file, offset in the packed buffer, length)])
         c = 0
-        for b, (f, (W, H, ctype, spans)) in enumerate(zip(files, parsed)):
+        for b, (f, (W, H, ctype, spans, *_)) in enumerate(zip(files, parsed)):
             at = int(offs[b])
             moves = []
             for off, ln, crc in spans:
@@ -267,11 +329,21 @@ class PngFiles(FileBatch):
         rec["mode"] = _lib.PNGDEC_MODE_IDS[mode]; rec["order"] = _ORDERS[order]
         dev = indexed_device(device, out)
         rp, cp = ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(chunks.ctypes.data)
-        self.table_host, self.header = planned_table(
-            ("attwarp_pngdec_table_bytes", rp, B, nchunks), ("attwarp_pngdec_plan", rp, B, cp, nchunks, int(bool(check_crc)), TABLE),
-            _lib.PngDecHeader, ValueError, "PngFiles: ", wrap_plan=True)
+        if all_formats:
+            fmt = np.zeros(B, dtype=_PNGDEC_FORMAT_DTYPE)
+            fmt["depth"] = [p[4] for p in parsed]; fmt["interlace"] = [p[5] for p in parsed]
+            fmt["palette_entries"] = [len(p[6]) // 3 for p in parsed]
+            for b, p in enumerate(parsed):
+                fmt["palette"][b, :len(p[6])] = np.frombuffer(p[6], np.uint8)
+            fp = ctypes.c_void_p(fmt.ctypes.data)
+            size = ("attwarp_pngdec_table_bytes_formats", rp, fp, B, cp, nchunks)
+            plan = ("attwarp_pngdec_plan_formats", rp, fp, B, cp, nchunks, int(bool(check_crc)), TABLE)
+        else:
+            size = ("attwarp_pngdec_table_bytes", rp, B, nchunks)
+            plan = ("attwarp_pngdec_plan", rp, B, cp, nchunks, int(bool(check_crc)), TABLE)
+        self.table_host, self.header = planned_table(size, plan, _lib.PngDecHeader, ValueError, "PngFiles: ", wrap_plan=True)
         self.B, self._dev, self.mode, self.order = B, dev, mode, order
-        self.shapes = [(p[1], p[0], 1 if mode == "L" else 3 if mode == "RGB" else (1 if _CHANNELS[p[2]] <= 2 else 3)) for p in parsed]
+        self.shapes = [(p[1], p[0], 1 if mode == "L" else 3 if mode == "RGB" else (1 if p[2] in (0, 4) else 3)) for p in parsed]
         self.compressed_bytes = int(offs[-1])
 
         def fill(body):                   # every IDAT payload, gathered straight into the pinned slot
@@ -296,14 +368,16 @@ class PngFiles(FileBatch):
         return [pos[b, :int(nunits[b])].tolist() for b in range(B)]
 
 
-def decode_png(files, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+def decode_png(files, mode: str = "RGB", order: str = "rgb", device=None, all_formats: bool = False) -> List[torch.Tensor]:
     """PNG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
-    first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all."""
-    views, status = PngFiles(files, mode, order, device=device).run()
+    first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all.
+    ``all_formats=True`` also takes palette, 1- / 2- / 4- / 16-bit and interlaced files (:class:`PngFiles`); without it they
+    raise ValueError."""
+    views, status = PngFiles(files, mode, order, device=device, all_formats=all_formats).run()
     raise_first_broken(status, STATUS_NAMES, "png")
     return views
 
 
-def read_png(paths, mode: str = "RGB", order: str = "rgb", device=None) -> List[torch.Tensor]:
+def read_png(paths, mode: str = "RGB", order: str = "rgb", device=None, all_formats: bool = False) -> List[torch.Tensor]:
     """:func:`decode_png` of the files at ``paths``."""
-    return decode_png([os.fspath(p) for p in paths], mode, order, device)
+    return decode_png([os.fspath(p) for p in paths], mode, order, device, all_formats)

@@ -888,7 +888,7 @@ typedef struct attwarp_pngdec_image {
   uint64_t stream_off;                             /* the image's zlib stream in the packed buffer */
   uint64_t stream_len;
   int32_t H, W;
-  int32_t color_type;                              /* 0, 2, 4, 6 */
+  int32_t color_type;                              /* 0, 2, 4, 6 (attwarp_pngdec_plan_formats: 3 too) */
   int32_t mode;                                    /* ATTWARP_PNGDEC_RGB / L / KEEP */
   int32_t order;                                   /* ATTWARP_RGB / ATTWARP_BGR */
   int32_t reserved;
@@ -901,7 +901,7 @@ typedef struct attwarp_pngdec_chunk {              /* one IDAT chunk: its payloa
 typedef struct attwarp_pngdec_header {             /* first bytes of a table written by attwarp_pngdec_plan */
   uint32_t magic;
   int32_t B, nchunks, check_crc;
-  int32_t lds_bytes, reserved;
+  int32_t lds_bytes, formats;                      /* formats: 1 in a table of attwarp_pngdec_plan_formats that needs the formats kernel */
   uint64_t table_bytes, scratch_bytes, out_bytes, stream_bytes;
   uint64_t off_images, off_chunks;
   uint32_t crc_pow8[32];
@@ -912,6 +912,36 @@ ATTWARP_API int attwarp_pngdec_plan(const attwarp_pngdec_image* images, int B, c
                        int check_crc, void* table, size_t table_bytes);
 ATTWARP_API int attwarp_pngdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
+
+/* ---- every format of the PNG specification: attwarp_pngdec_format[B] stands parallel to the image array
+ * and adds what IHDR and PLTE say besides.  Accepted: grey at 1 / 2 / 4 / 8 / 16 bits, palette (color_type 3) at 1 / 2 / 4 / 8,
+ * RGB, grey + alpha and RGBA at 8 / 16, each with interlace 0 or 1 (Adam7).  The two planners are host-only and depend on
+ * IHDR, PLTE and the chunk lengths alone; the table goes to attwarp_pngdec_decode like any other.  When every image is 8-bit,
+ * non-interlaced and no palette file, table and launches are attwarp_pngdec_plan's, byte for byte; otherwise the header's
+ * `formats` is 1, EVERY image of the call is unfiltered by pngdec_unfilter_formats_kernel (one wave per image and pass) and a
+ * closing launch states the statuses: nine launches, still none that depends on anything read back.
+ * Pixels are Pillow's Image.open(f).convert(mode), bit for bit: samples below 8 bits are MSB first and grey ones scaled by
+ * 255 / 85 / 17; 16-bit GREY (colour type 0) SATURATES, min(v, 255), as Pillow's I;16 does (256 -> 255); every other 16-bit
+ * sample gives its high byte (grey + alpha included); a palette index is looked up in PLTE, one at or past palette_entries
+ * is (0, 0, 0), and L is the luma of the entry; tRNS and alpha are dropped.  ATTWARP_PNGDEC_KEEP: the file's channels
+ * without alpha at 8 bits by these rules, a palette file its palette's three; ATTWARP_BGR swaps any 3-channel result.
+ * A filtered row is 1 + ceil(w * channels * depth / 8) bytes, the filters' unit max(1, channels * depth / 8) bytes; the
+ * filtered size is the sum over the passes (w = ceil((W - x0) / dx), h = ceil((H - y0) / dy), an empty pass has no bytes),
+ * and that is what E_OVERFLOW / E_UNDERFLOW compare with.  A filter byte above 4 in ANY pass is E_FILTER.
+ * Limits (ATTWARP_E_UNSUPPORTED): 1 + ceil(W * channels * depth / 8) <= ATTWARP_PNGDEC_MAX_ROW_BYTES; the filtered size
+ * below 2^31.  ATTWARP_E_ARG: a depth / colour-type pair outside the list, interlace above 1, a palette file without
+ * 1 .. 256 entries. */
+typedef struct attwarp_pngdec_format {
+  int32_t depth;                                   /* IHDR's bit depth */
+  int32_t interlace;                               /* 0, or 1: Adam7 */
+  int32_t palette_entries;                         /* PLTE's length / 3 (colour type 3: 1 .. 256; otherwise ignored) */
+  int32_t reserved;
+  uint8_t palette[768];                            /* R, G, B per entry */
+} attwarp_pngdec_format;
+ATTWARP_API size_t attwarp_pngdec_table_bytes_formats(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                       const attwarp_pngdec_chunk* chunks, int nchunks);
+ATTWARP_API int attwarp_pngdec_plan_formats(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                       const attwarp_pngdec_chunk* chunks, int nchunks, int check_crc, void* table, size_t table_bytes);
 
 /* ---- baseline JPEG files of a whole batch DECODED on the device (jpegdec.hip).  SOF0 / SOF1 (sequential
  * Huffman, 8 bits), one component (grey) or three (YCbCr, luma 1x1, 2x1 or 2x2 and chroma 1x1: 4:4:4, 4:2:2, 4:2:0), one
