@@ -177,6 +177,10 @@ SIGNATURES = {
     "attwarp_jpegdec_scans_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "attwarp_jpegdec_plan_scans": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int]),
     "attwarp_jpegdec_decode_scans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # every layout of a sequential file: four components, any sampling, RGB-coded (jpegdec.hip, jpegfmt_blocks.hpp)
+    "attwarp_jpegdec_layouts_table_bytes": (c_size_t, [c_void_p, c_int]),
+    "attwarp_jpegdec_plan_layouts": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int]),
+    "attwarp_jpegdec_decode_layouts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),
@@ -202,6 +206,8 @@ JPEGDEC_MODE_IDS = {"RGB": 0, "L": 1, "keep": 2}
 JPEGDEC_MAX_UNITS, JPEGDEC_MAX_BLOCKS = 65536, 1 << 24
 JPEGDEC_MAX_SCANS = 64
 JPEGDEC_RECORD_BYTES = 2152                              # one image record of a planned table (JdImage of jpegdec_blocks.hpp)
+JPEGDEC_COLOR_IDS = {"grey": 0, "ycc": 1, "rgb": 2, "cmyk": 3, "ycck": 4}   # ATTWARP_JPEGDEC_COLOR_*: the colour rule of a layout image
+JPEGDEC_MAX_SLOTS = 10                                   # blocks per MCU (T.81 B.2.3)
 JPEGDEC_STATUS_NAMES = ("OK", "E_TRUNCATED", "E_HUFFMAN", "E_COEFF", "E_RESTART", "E_NO_EOI")
 (JPEGDEC_OK, JPEGDEC_E_TRUNCATED, JPEGDEC_E_HUFFMAN, JPEGDEC_E_COEFF, JPEGDEC_E_RESTART, JPEGDEC_E_NO_EOI) = range(6)
 # attwarp_panel_grid: limits, flags and source kinds (ATTWARP_PANEL_* of include/attwarp.h)
@@ -274,6 +280,15 @@ class JpegDecImage(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("order", ctypes.c_int32), ("qt", ctypes.c_uint16 * 64 * 3),
                 ("dc_counts", ctypes.c_uint8 * 16 * 3), ("ac_counts", ctypes.c_uint8 * 16 * 3),
                 ("dc_symbols", ctypes.c_uint8 * 256 * 3), ("ac_symbols", ctypes.c_uint8 * 256 * 3)]
+
+
+class JpegDecLayoutImage(ctypes.Structure):
+    """attwarp_jpegdec_layout_image: one file of an attwarp_jpegdec_plan_layouts call, up to four components."""
+    _fields_ = [("stream_off", ctypes.c_uint64), ("stream_len", ctypes.c_uint64), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("ncomp", ctypes.c_int32), ("h", ctypes.c_int32 * 4), ("v", ctypes.c_int32 * 4), ("color", ctypes.c_int32),
+                ("restart_interval", ctypes.c_int32), ("mode", ctypes.c_int32), ("order", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("qt", ctypes.c_uint16 * 64 * 4), ("dc_counts", ctypes.c_uint8 * 16 * 4), ("ac_counts", ctypes.c_uint8 * 16 * 4),
+                ("dc_symbols", ctypes.c_uint8 * 256 * 4), ("ac_symbols", ctypes.c_uint8 * 256 * 4)]
 
 
 class JpegDecScan(ctypes.Structure):

@@ -17,6 +17,8 @@
 //                           mode and order, the store; the first thread of every image writes its status.
 // Every loop is bounded by a header-derived count (units, MCUs per unit, blocks per MCU), by 64 coefficients or 16 bits,
 // by the stream's length, or by the plan's cap on rounds.
+// Files of every other layout (attwarp_jpegdec_plan_layouts / attwarp_jpegdec_decode_layouts, DESIGN.md 3.19: four components,
+// any sampling, RGB-coded) take the same five launches over records of their own: the jpegfmt_* kernels at the file's end.
 // Progressive files (attwarp_jpegdec_plan_scans / attwarp_jpegdec_decode_scans) keep the last two launches
 // and put in front of them
 //   jpegprog_clear_kernel   the coefficient memory of every image zeroed (the scans only refine it), the states opened;
@@ -28,12 +30,13 @@
 #include <cstring>
 #include <vector>
 
+#include "jpegfmt_blocks.hpp"
 #include "jpegprog_blocks.hpp"
 
 namespace attwarp {
 
 #define JD_G __attribute__((address_space(1)))
-constexpr uint32_t JD_MAGIC = 0x4745504au;
+constexpr uint32_t JD_MAGIC = 0x4745504au, JD_MAGIC_LAYOUTS = 0x4745504cu;   // (the second: attwarp_jpegdec_plan_layouts)
 constexpr int JD_NT = 256;
 constexpr int JD_MAX_B = 1 << 20, JD_MAX_TOTAL_UNITS = 1 << 30;
 constexpr int JD_RING = 2048, JD_CHUNK = WAVE * 4;        // bytes of the entropy kernel's ring / loaded per step
@@ -68,24 +71,25 @@ __host__ __device__ inline uint64_t jd_starts_off(int B) { return jd_align((uint
 __host__ __device__ inline uint64_t jd_ends_off(int B, int units) { return jd_starts_off(B) + (uint64_t)units * 4u; }
 __host__ __device__ inline uint64_t jd_data_base(int B, int units) { return jd_align(jd_ends_off(B, units) + (uint64_t)units * 4u, 256); }
 
-struct JdView {
+template <class Image>
+struct JdViewOf {                      // a planned table and its scratch buffer: JdImage records, or JfImage of the layout family
   const attwarp_jpegdec_header* hdr;
-  const JdImage* images;
+  const Image* images;
   const JdSub* subs;
   JdSubInfo* infos;
   JdState* states;
   uint32_t *starts, *ends;
-  __device__ __forceinline__ JdView(const uint8_t* table, uint8_t* scratch) {
+  __device__ __forceinline__ JdViewOf(const uint8_t* table, uint8_t* scratch) {
     hdr = reinterpret_cast<const attwarp_jpegdec_header*>(table);
-    images = reinterpret_cast<const JdImage*>(table + hdr->off_images);
-    subs = reinterpret_cast<const JdSub*>(table + hdr->off_images + (uint64_t)hdr->B * sizeof(JdImage));
+    images = reinterpret_cast<const Image*>(table + hdr->off_images);
+    subs = reinterpret_cast<const JdSub*>(table + hdr->off_images + (uint64_t)hdr->B * sizeof(Image));
     infos = reinterpret_cast<JdSubInfo*>(scratch + subs[0].info_off);
     states = reinterpret_cast<JdState*>(scratch);
     starts = reinterpret_cast<uint32_t*>(scratch + jd_starts_off(hdr->B));
     ends = reinterpret_cast<uint32_t*>(scratch + jd_ends_off(hdr->B, hdr->total_units));
   }
   // the image whose range of units / tiles holds t: the last one whose first is <= t (the firsts ascend strictly)
-  __device__ __forceinline__ int find(int32_t JdImage::*first, int t) const {
+  __device__ __forceinline__ int find(int32_t Image::*first, int t) const {
     int lo = 0, hi = hdr->B - 1;
     for (int it = 0; it < 32 && lo < hi; ++it) {
       const int mid = (lo + hi + 1) >> 1;
@@ -95,6 +99,8 @@ struct JdView {
     return lo;
   }
 };
+using JdView = JdViewOf<JdImage>;
+using JfView = JdViewOf<JfImage>;
 
 __device__ __forceinline__ uint32_t jd_excl_sum(uint32_t v, uint32_t* tmp, uint32_t& total) {
   const int t = threadIdx.x;
@@ -158,12 +164,12 @@ __device__ __forceinline__ void jd_scan_units(const JD_G uint8_t* s, uint32_t n,
   __syncthreads();
 }
 
-__global__ __launch_bounds__(JD_NT) void jpegdec_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
-                                                             uint8_t* __restrict__ scratch) {
-  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const JdView v(table, scratch);
-  const JdImage* im = v.images + b;
+// The restart scan of image b of a view: its units' limits, its state and its (empty) sub-stream result.
+template <class Image>
+__device__ __forceinline__ void jd_scan_image(const JdViewOf<Image>& v, const uint8_t* stream, int b, uint32_t* s_tmp, uint32_t& s_term,
+                                              uint32_t& s_bad) {
+  const int tid = threadIdx.x;
+  const Image* im = v.images + b;
   const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off;
   const uint32_t n = im->stream_len, nunits = (uint32_t)im->nunits;
   uint32_t* ends = v.ends + im->unit0;
@@ -183,6 +189,13 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_scan_kernel(const uint8_t* __re
     info.nseg = v.subs[b].nseg; info.rounds = 0; info.accepted = 0; info.pad = 0;
     v.infos[b] = info;
   }
+}
+
+__global__ __launch_bounds__(JD_NT) void jpegdec_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                             uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
+  const JdView v(table, scratch);
+  jd_scan_image(v, stream, (int)blockIdx.x, s_tmp, s_term, s_bad);
 }
 
 // grid: one workgroup per image planned for sub-streams (at least one workgroup, which then has nothing to do).
@@ -382,21 +395,9 @@ __global__ __launch_bounds__(WAVE) void jpegdec_entropy_kernel(const uint8_t* __
   if (err && lane == 0) atomicMin(&state->fail, k << 8 | err);
 }
 
-// One thread per 8x8 block: all 64 values stay in registers through both passes, no lane talks to another, and the eight
-// stores of neighbouring blocks of a block row are contiguous.
-__global__ __launch_bounds__(JD_NT) void jpegdec_idct_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
-  __shared__ uint16_t s_qt[3][64];
-  const JdView v(table, scratch);
-  const int b = v.find(&JdImage::idct_tile0, (int)blockIdx.x);
-  const JdImage* im = v.images + b;
-  if (threadIdx.x < 192) s_qt[threadIdx.x >> 6][threadIdx.x & 63] = im->qt[threadIdx.x >> 6][threadIdx.x & 63];
-  __syncthreads();
-  const uint32_t bi = (uint32_t)((int)blockIdx.x - im->idct_tile0) * JD_IDCT_TILE + threadIdx.x;
-  if (bi >= im->nblocks) return;
-  const int c = (im->ncomp == 3 && bi >= im->block0[1]) ? (bi >= im->block0[2] ? 2 : 1) : 0;
-  const uint32_t local = bi - im->block0[c];
-  const uint32_t bw = (uint32_t)im->bw[c], by = local / bw, bx = local - by * bw;
-  const uint4* src = reinterpret_cast<const uint4*>(scratch + im->coef_off + (size_t)bi * 128u);
+// One block by one thread: src its 64 int16 coefficients, qt the component's table (LDS), dst its top-left pixel in a plane
+// of `pitch` bytes per row.  All 64 values stay in registers through both passes.
+__device__ __forceinline__ void jd_idct_block(const uint4* src, const uint16_t* qt, uint8_t* dst, size_t pitch) {
   uint32_t x[64];
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_idct_kernel(const uint8_t* __re
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int32_t cf = (int16_t)(d[e >> 1] >> (16 * (e & 1)));
-      x[r * 8 + e] = (uint32_t)cf * (uint32_t)s_qt[c][r * 8 + e];
+      x[r * 8 + e] = (uint32_t)cf * (uint32_t)qt[r * 8 + e];
     }
   }
 #pragma unroll
@@ -418,8 +419,6 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_idct_kernel(const uint8_t* __re
 #pragma unroll
     for (int r = 0; r < 8; ++r) x[r * 8 + col] = (uint32_t)o[r];
   }
-  const size_t pitch = (size_t)bw * 8u;
-  uint8_t* dst = scratch + im->plane_off + (size_t)im->block0[c] * 64u + (size_t)by * 8u * pitch + (size_t)bx * 8u;
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     int32_t o[8];
@@ -429,6 +428,23 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_idct_kernel(const uint8_t* __re
     px.y = jd_clamp8(o[4] + 128) | jd_clamp8(o[5] + 128) << 8 | jd_clamp8(o[6] + 128) << 16 | jd_clamp8(o[7] + 128) << 24;
     *reinterpret_cast<uint2*>(dst + (size_t)r * pitch) = px;
   }
+}
+
+// One thread per 8x8 block: no lane talks to another, and the eight stores of neighbouring blocks of a block row are contiguous.
+__global__ __launch_bounds__(JD_NT) void jpegdec_idct_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint16_t s_qt[3][64];
+  const JdView v(table, scratch);
+  const int b = v.find(&JdImage::idct_tile0, (int)blockIdx.x);
+  const JdImage* im = v.images + b;
+  if (threadIdx.x < 192) s_qt[threadIdx.x >> 6][threadIdx.x & 63] = im->qt[threadIdx.x >> 6][threadIdx.x & 63];
+  __syncthreads();
+  const uint32_t bi = (uint32_t)((int)blockIdx.x - im->idct_tile0) * JD_IDCT_TILE + threadIdx.x;
+  if (bi >= im->nblocks) return;
+  const int c = (im->ncomp == 3 && bi >= im->block0[1]) ? (bi >= im->block0[2] ? 2 : 1) : 0;
+  const uint32_t local = bi - im->block0[c];
+  const uint32_t bw = (uint32_t)im->bw[c], by = local / bw, bx = local - by * bw;
+  jd_idct_block(reinterpret_cast<const uint4*>(scratch + im->coef_off + (size_t)bi * 128u), s_qt[c],
+                scratch + im->plane_off + (size_t)im->block0[c] * 64u + (size_t)by * 8u * ((size_t)bw * 8u) + (size_t)bx * 8u, (size_t)bw * 8u);
 }
 
 __global__ __launch_bounds__(JD_NT) void jpegdec_color_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
@@ -812,9 +828,10 @@ extern "C" uint64_t attwarp_jpegdec_info_offset(const void* table_host) {
   if (!table_host) return 0;
   attwarp_jpegdec_header h;
   std::memcpy(&h, table_host, sizeof h);
-  if (h.magic != JD_MAGIC || h.B <= 0 || h.B > JD_MAX_B) return 0;
+  if ((h.magic != JD_MAGIC && h.magic != JD_MAGIC_LAYOUTS) || h.B <= 0 || h.B > JD_MAX_B) return 0;
   JdSub s;
-  std::memcpy(&s, static_cast<const uint8_t*>(table_host) + h.off_images + (uint64_t)h.B * sizeof(JdImage), sizeof s);
+  const size_t record = h.magic == JD_MAGIC ? sizeof(JdImage) : sizeof(JfImage);
+  std::memcpy(&s, static_cast<const uint8_t*>(table_host) + h.off_images + (uint64_t)h.B * record, sizeof s);
   return s.info_off;
 }
 
@@ -1032,4 +1049,429 @@ extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* 
     if (const int rc = check_launch("jpegprog_entropy_kernel")) return rc;
   }
   return jd_launch_idct_color(h, td, sc, out, status, st);
+}
+
+// ---- every layout of a sequential file (attwarp_jpegdec_plan_layouts / attwarp_jpegdec_decode_layouts): the five
+// launches of the baseline family over JfImage records: up to four components of any sampling, a block-slot map of the MCU,
+// four DC predictors, four quantisation tables, the up-sampler libjpeg picks per component and four colour rules ----------------
+namespace attwarp {
+
+constexpr uint32_t JF_MAGIC = JD_MAGIC_LAYOUTS;
+
+__global__ __launch_bounds__(JD_NT) void jpegfmt_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                             uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
+  const JfView v(table, scratch);
+  jd_scan_image(v, stream, (int)blockIdx.x, s_tmp, s_term, s_bad);
+}
+
+// The code tables of an image's components in LDS, by all lanes of the workgroup; ends behind a barrier.
+__device__ __forceinline__ void jf_build_tables(JdHuff* s_dc, JdHuff* s_ac, const JfImage* im, int ncomp, int tid, int nt) {
+  for (int c = 0; c < ncomp; ++c) {
+    if (tid == 0) { jd_huff_ranges(s_dc[c], im->dc_counts[c]); jd_huff_ranges(s_ac[c], im->ac_counts[c]); }
+    jd_huff_clear(s_dc[c], im->dc_symbols[c], jd_nsym(im->dc_counts[c]), tid, nt);
+    jd_huff_clear(s_ac[c], im->ac_symbols[c], jd_nsym(im->ac_counts[c]), tid, nt);
+  }
+  __syncthreads();
+  for (int c = 0; c < ncomp; ++c) {
+    jd_huff_fill(s_dc[c], im->dc_counts[c], tid, nt);
+    jd_huff_fill(s_ac[c], im->ac_counts[c], tid, nt);
+  }
+  __syncthreads();
+}
+
+// grid: one workgroup per image planned for sub-streams (at least one).  jpegdec_substream_kernel over the general MCU: the
+// slot of a JdSync runs to the period of the image's MCU (up to 10 blocks; JfLayout), a segment carries the DC sums of its
+// owned blocks by their place and four predictors.
+__global__ __launch_bounds__(JD_NT) void jpegfmt_substream_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                                  uint8_t* scratch) {
+  __shared__ JdHuff s_dc[JF_MAX_COMP], s_ac[JF_MAX_COMP];
+  __shared__ int16_t s_blk[JD_NT][JD_SUB_BLK];
+  __shared__ uint32_t s_tmp[JD_NT];
+  __shared__ uint8_t s_zz[64];
+  const int tid = threadIdx.x;
+  const JfView v(table, scratch);
+  if ((int)blockIdx.x >= v.hdr->reserved) return;
+  const int b = v.subs[blockIdx.x].image;
+  if (b < 0 || b >= v.hdr->B) return;
+  const JfImage* im = v.images + b;
+  const JdSub sub = v.subs[b];
+  if (v.states[b].st_scan != 0 || sub.nseg == 0) return;      // (uniform) the info record already says "not accepted"
+  const uint32_t n = im->stream_len, nseg = sub.nseg, S = sub.segment_bytes;
+  uint32_t uend = v.ends[im->unit0];
+  if (uend > n) uend = n;
+  const int ncomp = min(max(im->ncomp, 1), JF_MAX_COMP);
+  if (tid < 64) s_zz[tid] = JD_ZIGZAG[tid];
+  jf_build_tables(s_dc, s_ac, im, ncomp, tid, JD_NT);
+  const uint8_t* data = stream + im->stream_off;
+  const uint32_t lo = (uint32_t)(reinterpret_cast<uintptr_t>(data) & 3u);
+  const uint8_t* p = data - lo;
+  JfSegState* seg = reinterpret_cast<JfSegState*>(scratch + sub.seg_off);
+  JfSegment* res = reinterpret_cast<JfSegment*>(scratch + sub.seg_off + (uint64_t)nseg * sizeof(JfSegState));
+  const uint32_t nblk = (uint32_t)min(max(im->nslot, 1), JF_MAX_SLOTS);
+  const uint32_t expected = (uint32_t)im->mcux * (uint32_t)im->mcuy * nblk;
+  const JfLayout lay{*im};
+  for (uint32_t s = tid; s < nseg; s += JD_NT) {               // (segment s belongs to lane s % JD_NT in every loop below)
+    seg[s].entry = jd_segment_guess(data, s, S, uend);
+    seg[s].dirty = 1u;
+  }
+  uint32_t rounds = 0;
+  bool converged = false;
+  while (rounds < sub.max_rounds) {                          // (uniform)
+    ++rounds;
+    for (uint32_t s = tid; s < nseg; s += JD_NT)
+      if (seg[s].dirty) {
+        JfSegment r;
+        r.pad = 0;
+        jd_decode_segment_of(lay, p, lo, seg[s].entry, jd_segment_end(s, S, uend), uend, s_dc, s_ac, nblk, r);
+        res[s] = r;
+      }
+    __syncthreads();                                         // every exit of this round is written
+    int changed = 0;
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      uint32_t d = 0;
+      if (s > 0) {
+        const JdSync e = res[s - 1].exit;
+        if (!jd_sync_equal(e, seg[s].entry)) { seg[s].entry = e; d = 1u; changed = 1; }
+      }
+      seg[s].dirty = d;
+    }
+    if (!__syncthreads_or(changed)) { converged = true; break; }
+  }
+  // exclusive sums over the segments, lane t over its chunk in order: first the owned blocks, which give every segment the
+  // blocks in front of it and with them the component of each of its owned blocks; then the DC differences per component
+  const uint32_t chunk = (nseg + JD_NT - 1) / JD_NT;
+  const uint32_t s0 = min((uint32_t)tid * chunk, nseg), s1 = min(s0 + chunk, nseg);
+  uint32_t own = 0, total;
+  for (uint32_t s = s0; s < s1; ++s) own += res[s].owned;
+  const uint32_t own0 = jd_excl_sum(own, s_tmp, total);
+  uint32_t sum[JF_MAX_COMP] = {0, 0, 0, 0}, before = own0;
+  for (uint32_t s = s0; s < s1; ++s) {
+    const JfSegment r = res[s];
+    for (uint32_t i = 0; i < nblk; ++i) sum[lay.comp((before + i) % nblk)] += r.dc[i];
+    before += r.owned;
+  }
+  for (int e = 0; e < JF_MAX_COMP; ++e) sum[e] = jd_excl_sum(sum[e], s_tmp, total);
+  uint32_t flags = 0;
+  before = own0;
+  for (uint32_t s = s0; s < s1; ++s) {
+    const JfSegment r = res[s];
+    seg[s].before = before;
+    for (int c = 0; c < JF_MAX_COMP; ++c) seg[s].pred[c] = sum[c];
+    flags |= jd_segment_check(seg[s].entry, r, before, expected, nblk, lay.period(nblk));
+    for (uint32_t i = 0; i < nblk; ++i) sum[lay.comp((before + i) % nblk)] += r.dc[i];
+    before += r.owned;
+  }
+  const int bad = __syncthreads_or((int)(flags & 1u));
+  const int found = __syncthreads_or((int)(flags & 2u));       // (and every `before` and predictor is written)
+  bool accepted = converged && found && !bad;
+  if (accepted) {                                            // (uniform)
+    int16_t* coef = reinterpret_cast<int16_t*>(scratch + im->coef_off);
+    uint32_t werr = 0;
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      const JfSegState e = seg[s];
+      werr |= jd_write_segment_of(lay, p, lo, e.entry, uend, s_dc, s_ac, nblk, e.before, e.pred, res[s].owned, expected, s_blk[tid], s_zz, coef);
+    }
+    if (__syncthreads_or((int)werr)) accepted = false;       // (never, after the checks: the sequential decode then redoes it)
+  }
+  if (tid == 0) {
+    JdSubInfo info;
+    info.nseg = nseg; info.rounds = rounds; info.accepted = accepted ? 1u : 0u; info.pad = 0;
+    v.infos[b] = info;
+  }
+}
+
+// grid: one wave per planned unit of the call: jpegdec_entropy_kernel over the general MCU.
+__global__ __launch_bounds__(WAVE) void jpegfmt_entropy_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                               uint8_t* __restrict__ scratch) {
+  __shared__ JdHuff s_dc[JF_MAX_COMP], s_ac[JF_MAX_COMP];
+  __shared__ uint32_t s_ring[JD_RING / 4];
+  __shared__ int16_t s_blk[64];
+  __shared__ int32_t s_pred[JF_MAX_COMP];
+  __shared__ uint8_t s_zz[64], s_slot_c[16];
+  __shared__ uint32_t s_pos, s_err;
+  const int lane = threadIdx.x, u = blockIdx.x;
+  const JfView v(table, scratch);
+  const int b = v.find(&JfImage::unit0, u);
+  const JfImage* im = v.images + b;
+  JdState* state = v.states + b;
+  if (state->st_scan != 0) return;                           // (uniform) the units' limits were never written
+  if (v.infos[b].accepted != 0) return;                      // (uniform) the sub-stream kernel decoded this image's only unit
+  const uint32_t k = (uint32_t)(u - im->unit0), n = im->stream_len;
+  const int ncomp = min(max(im->ncomp, 1), JF_MAX_COMP);
+  uint32_t start = v.starts[u], end = v.ends[u];
+  if (end > n) end = n;
+  if (start > end) start = end;
+  s_zz[lane] = JD_ZIGZAG[lane];
+  if (lane < 16) s_slot_c[lane] = lane < 12 ? (im->slot_c[lane] & 3u) : 0u;
+  if (lane == 0) { s_pos = start; s_err = 0; }
+  if (lane < JF_MAX_COMP) s_pred[lane] = 0;
+  jf_build_tables(s_dc, s_ac, im, ncomp, lane, WAVE);
+  const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off;
+  JD_G int16_t* coef = (JD_G int16_t*)(scratch + im->coef_off);
+  const int nslot = min(max(im->nslot, 1), JF_MAX_SLOTS);
+  const uint32_t mcux = (uint32_t)im->mcux, nblocks = im->nblocks;
+  const uint32_t nmcu = mcux * (uint32_t)im->mcuy, ri = (uint32_t)im->ri;
+  const uint32_t m0 = k * ri, m1 = m0 + ri < nmcu ? m0 + ri : nmcu;
+  JdBits br;
+  br.init(reinterpret_cast<const uint8_t*>(s_ring), JD_RING - 1, start, end);
+  uint32_t loaded = start & ~3u, err = 0;
+  uint32_t my = m0 / mcux, mx = m0 - my * mcux;
+  for (uint32_t m = m0; m < m1 && !err; ++m) {
+    for (int jb = 0; jb < nslot; ++jb) {
+      __syncthreads();                                       // s_pos of the block before
+      jd_ring_fill(s_ring, s, loaded, s_pos & ~3u, end, lane);   // (the ring's bound is per block: jpegdec_entropy_kernel)
+      s_blk[lane] = 0;
+      __syncthreads();
+      if (lane == 0) {
+        br.end = loaded < end ? loaded : end;
+        const int c = s_slot_c[jb];
+        int32_t p = s_pred[c];
+        const uint32_t st = jd_decode_block(br, s_dc[c], s_ac[c], p, s_blk, s_zz);
+        s_pred[c] = p;
+        s_pos = br.pos;
+        if (st) s_err = st;
+      }
+      __syncthreads();
+      err = s_err;
+      if (err) break;                                        // (uniform)
+      const uint32_t bi = jf_slot_block(*im, (uint32_t)jb, mx, my);
+      if (bi < nblocks) coef[(size_t)bi * 64u + lane] = s_blk[lane];
+    }
+    if (++mx == mcux) { mx = 0; ++my; }
+  }
+  if (err && lane == 0) atomicMin(&state->fail, k << 8 | err);
+}
+
+// One thread per 8x8 block of up to four planes, four quantisation tables in LDS.
+__global__ __launch_bounds__(JD_NT) void jpegfmt_idct_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint16_t s_qt[JF_MAX_COMP][64];
+  const JfView v(table, scratch);
+  const int b = v.find(&JfImage::idct_tile0, (int)blockIdx.x);
+  const JfImage* im = v.images + b;
+  s_qt[threadIdx.x >> 6][threadIdx.x & 63] = im->qt[threadIdx.x >> 6][threadIdx.x & 63];
+  __syncthreads();
+  const uint32_t bi = (uint32_t)((int)blockIdx.x - im->idct_tile0) * JD_IDCT_TILE + threadIdx.x;
+  if (bi >= im->nblocks) return;
+  int c = 0;
+  for (int e = 1; e < JF_MAX_COMP; ++e)
+    if (e < im->ncomp && bi >= im->comp[e].block0) c = e;
+  const JfComp& k = im->comp[c];
+  const uint32_t local = bi - k.block0, bw = (uint32_t)k.bw, by = local / bw, bx = local - by * bw;
+  jd_idct_block(reinterpret_cast<const uint4*>(scratch + im->coef_off + (size_t)bi * 128u), s_qt[c],
+                scratch + im->plane_off + (size_t)k.block0 * 64u + (size_t)by * 8u * ((size_t)bw * 8u) + (size_t)bx * 8u, (size_t)bw * 8u);
+}
+
+// One thread per output pixel (eight pixels, a workgroup apart): every component up-sampled by its own rule (uniform per
+// image), the colour rule, Pillow's conversion, the store; the first thread of every image writes its status.
+__global__ __launch_bounds__(JD_NT) void jpegfmt_color_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
+                                                              const JdState* __restrict__ states, uint8_t* __restrict__ out,
+                                                              int32_t* __restrict__ status) {
+  __shared__ JfComp s_comp[JF_MAX_COMP];
+  const attwarp_jpegdec_header* hdr = reinterpret_cast<const attwarp_jpegdec_header*>(table);
+  const JfImage* images = reinterpret_cast<const JfImage*>(table + hdr->off_images);
+  int lo = 0, hi = hdr->B - 1;
+  for (int it = 0; it < 32 && lo < hi; ++it) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (images[mid].color_tile0 <= (int)blockIdx.x) lo = mid;
+    else hi = mid - 1;
+  }
+  const int b = lo;
+  const JfImage* im = images + b;
+  const int tile = (int)blockIdx.x - im->color_tile0;
+  if (tile == 0 && threadIdx.x == 0) {
+    const JdState st = states[b];
+    status[b] = (int32_t)(st.st_scan ? st.st_scan : st.fail != 0xffffffffu ? (st.fail & 255u) : st.eoi ? 0u : (uint32_t)ATTWARP_JPEGDEC_E_NO_EOI);
+  }
+  if (threadIdx.x < JF_MAX_COMP) s_comp[threadIdx.x] = im->comp[threadIdx.x];
+  __syncthreads();
+  const int W = im->W, oc = min(max(im->oc, 1), 4), ncomp = min(max(im->ncomp, 1), JF_MAX_COMP);
+  const int color = im->color, conv = im->conv;
+  const bool swap = im->swap != 0;
+  const uint32_t npx = (uint32_t)W * (uint32_t)im->H;
+  const uint8_t* planes = scratch + im->plane_off;
+  JD_G uint8_t* o = (JD_G uint8_t*)out + im->out_off;
+  for (int j = 0; j < JD_CPX; ++j) {
+    const uint32_t px = (uint32_t)tile * JD_COLOR_TILE + (uint32_t)j * JD_NT + threadIdx.x;
+    if (px >= npx) break;
+    const int y = (int)(px / (uint32_t)W), x = (int)(px - (uint32_t)y * (uint32_t)W);
+    int32_t smp[JF_MAX_COMP] = {0, 0, 0, 0};
+    for (int c = 0; c < ncomp; ++c) smp[c] = jf_sample(planes + (size_t)s_comp[c].block0 * 64u, s_comp[c].bw * 8, s_comp[c], x, y);
+    uint8_t q[4] = {0, 0, 0, 0};
+    jf_pixel(color, conv, swap, smp, q);
+    JD_G uint8_t* d = o + (size_t)px * oc;
+    for (int e = 0; e < oc; ++e) d[e] = q[e];
+  }
+}
+
+}  // namespace attwarp
+
+static size_t jpegfmt_bytes(int B) {
+  return (size_t)(jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JfImage) + (uint64_t)B * sizeof(JdSub));
+}
+
+extern "C" size_t attwarp_jpegdec_layouts_table_bytes(const attwarp_jpegdec_layout_image* images, int B) {
+  if (!images || B <= 0 || B > JD_MAX_B) {
+    fail(ATTWARP_E_ARG, "jpegdec_layouts_table_bytes: B=%d outside the limits", B);
+    return 0;
+  }
+  return jpegfmt_bytes(B);
+}
+
+// Everything the kernels index by, checked for image b -> its record's geometry in r (nothing else of r is written).
+static int jpegfmt_geom(const attwarp_jpegdec_layout_image& d, int b, JfImage& r) {
+  ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1 && d.H <= 65535 && d.W <= 65535, "jpegdec: image %d: size %d x %d outside 1..65535", b, d.H, d.W);
+  ATTWARP_REQUIRE(d.ncomp == 1 || d.ncomp == 3 || d.ncomp == 4, "jpegdec: image %d: %d components (1, 3 or 4)", b, d.ncomp);
+  ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d: restart interval %d", b, d.restart_interval);
+  ATTWARP_REQUIRE(d.mode >= ATTWARP_JPEGDEC_RGB && d.mode <= ATTWARP_JPEGDEC_KEEP, "jpegdec: image %d: unknown mode %d", b, d.mode);
+  ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegdec: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
+  for (int c = 0; c < d.ncomp; ++c) {
+    ATTWARP_REQUIRE(d.h[c] >= 1 && d.h[c] <= 4 && d.v[c] >= 1 && d.v[c] <= 4, "jpegdec: image %d: component %d: sampling factors %d x %d outside 1..4",
+                    b, c, d.h[c], d.v[c]);
+    for (int k = 0; k < 64; ++k) ATTWARP_REQUIRE(d.qt[c][k] <= 255, "jpegdec: image %d: a quantisation value above 255", b);
+    for (int t = 0; t < 2; ++t) {
+      char what[48];
+      const char* fault = t ? jd_huffman_fault(d.ac_counts[c], d.ac_symbols[c], false, what) : jd_huffman_fault(d.dc_counts[c], d.dc_symbols[c], true, what);
+      ATTWARP_REQUIRE(!fault, "jpegdec: image %d: %s", b, fault);
+    }
+  }
+  const uint64_t blocks = jf_blocks(d.W, d.H, d.ncomp, d.h, d.v);
+  const int rc = jf_layout(r, d.W, d.H, d.ncomp, d.h, d.v, d.color);
+  ATTWARP_REQUIRE(rc != JF_E_SLOTS, "jpegdec: image %d: more than %d blocks per MCU", b, JF_MAX_SLOTS);
+  ATTWARP_REQUIRE(rc != JF_E_FRACTION, "jpegdec: image %d: a component's sampling factors do not divide the frame's largest (fractional up-sampling)", b);
+  ATTWARP_REQUIRE(rc != JF_E_COLOR, "jpegdec: image %d: colour rule %d with %d components", b, d.color, d.ncomp);
+  ATTWARP_REQUIRE(rc == JF_OK, "jpegdec: image %d: bad layout", b);
+  const int64_t nmcu = (int64_t)r.mcux * r.mcuy;
+  const int64_t units = d.restart_interval ? (nmcu + d.restart_interval - 1) / d.restart_interval : 1;
+  if (units > ATTWARP_JPEGDEC_MAX_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld restart intervals (> %d)", b, (long long)units, ATTWARP_JPEGDEC_MAX_UNITS);
+  if (blocks >= ATTWARP_JPEGDEC_MAX_BLOCKS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %llu blocks (>= %d)", b, (unsigned long long)blocks, ATTWARP_JPEGDEC_MAX_BLOCKS);
+  if (d.stream_len >= ((uint64_t)1 << 31) || d.stream_off >= ((uint64_t)1 << 62))
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: entropy data of 2 GiB or more", b);
+  r.ri = d.restart_interval ? d.restart_interval : (int32_t)nmcu;
+  r.nunits = (int32_t)units;
+  return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegdec_plan_layouts(const attwarp_jpegdec_layout_image* images, int B, void* table, size_t table_bytes,
+                                            int segment_bytes, int max_rounds) {
+  ATTWARP_REQUIRE(images, "jpegdec: null image array");
+  const bool substreams = segment_bytes != 0 || max_rounds != 0;
+  if (substreams) {
+    ATTWARP_REQUIRE(segment_bytes >= 32 && segment_bytes <= 512 && (segment_bytes & (segment_bytes - 1)) == 0,
+                    "jpegdec: segment_bytes=%d must be a power of two in 32..512", segment_bytes);
+    ATTWARP_REQUIRE(max_rounds >= 1 && max_rounds <= JD_SUB_MAX_ROUNDS, "jpegdec: max_rounds=%d outside 1..%d", max_rounds, JD_SUB_MAX_ROUNDS);
+  }
+  ATTWARP_REQUIRE(B > 0, "jpegdec: non-positive batch size");
+  if (B > JD_MAX_B) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: B=%d > 2^20", B);
+  ATTWARP_REQUIRE(table, "jpegdec_plan_layouts: null table");
+  const size_t need = jpegfmt_bytes(B);
+  ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan_layouts: table of %zu bytes, %zu needed", table_bytes, need);
+  int64_t units = 0, itiles = 0, ctiles = 0;
+  {
+    std::vector<JfImage> probe(1);
+    for (int b = 0; b < B; ++b) {                            // everything is checked before anything is written
+      if (const int rc = jpegfmt_geom(images[b], b, probe[0])) return rc;
+      units += probe[0].nunits;
+      itiles += (probe[0].nblocks + JD_IDCT_TILE - 1) / JD_IDCT_TILE;
+      ctiles += ((int64_t)images[b].H * images[b].W + JD_COLOR_TILE - 1) / JD_COLOR_TILE;
+    }
+  }
+  if (units > JD_MAX_TOTAL_UNITS || itiles > JD_MAX_TOTAL_UNITS || ctiles > JD_MAX_TOTAL_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units, %lld + %lld workgroups in one call (> 2^30)", (long long)units, (long long)itiles, (long long)ctiles);
+  uint8_t* t = static_cast<uint8_t*>(table);
+  std::memset(t, 0, need);
+  attwarp_jpegdec_header h;
+  std::memset(&h, 0, sizeof h);
+  h.magic = JF_MAGIC;
+  h.B = B;
+  h.total_units = (int32_t)units;
+  h.idct_tiles = (int32_t)itiles;
+  h.color_tiles = (int32_t)ctiles;
+  h.table_bytes = need;
+  h.off_images = jd_align(sizeof(attwarp_jpegdec_header), 16);
+  JfImage* im = reinterpret_cast<JfImage*>(t + h.off_images);
+  JdSub* sub = reinterpret_cast<JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JfImage));
+  int32_t nsub = 0;
+  uint64_t soff = jd_data_base(B, (int)units), ooff = 0, stream_bytes = 0;
+  int32_t u0 = 0, it0 = 0, ct0 = 0;
+  for (int b = 0; b < B; ++b) {
+    const attwarp_jpegdec_layout_image& d = images[b];
+    JfImage& r = im[b];
+    jpegfmt_geom(d, b, r);
+    r.stream_off = d.stream_off;
+    r.stream_len = (uint32_t)d.stream_len;
+    r.oc = d.mode == ATTWARP_JPEGDEC_L ? 1 : d.mode == ATTWARP_JPEGDEC_RGB ? 3 : d.ncomp;
+    r.conv = d.mode == ATTWARP_JPEGDEC_L ? JF_CONV_L : d.mode == ATTWARP_JPEGDEC_RGB ? JF_CONV_RGB : JF_CONV_KEEP;
+    r.swap = d.ncomp != 1 && r.oc == 3 && d.order == ATTWARP_BGR;
+    r.unit0 = u0; r.idct_tile0 = it0; r.color_tile0 = ct0;
+    for (int c = 0; c < d.ncomp; ++c) {
+      std::memcpy(r.qt[c], d.qt[c], sizeof r.qt[c]);
+      std::memcpy(r.dc_counts[c], d.dc_counts[c], 16);
+      std::memcpy(r.ac_counts[c], d.ac_counts[c], 16);
+      std::memcpy(r.dc_symbols[c], d.dc_symbols[c], 256);
+      std::memcpy(r.ac_symbols[c], d.ac_symbols[c], 256);
+    }
+    r.period = jf_period(r);
+    r.coef_off = soff;
+    soff += jd_align((uint64_t)r.nblocks * 128u, 256);
+    r.plane_off = soff;
+    soff += jd_align((uint64_t)r.nblocks * 64u, 256);
+    r.out_off = ooff;
+    ooff += (uint64_t)d.H * d.W * r.oc;
+    u0 += r.nunits;
+    it0 += (int32_t)((r.nblocks + JD_IDCT_TILE - 1) / JD_IDCT_TILE);
+    ct0 += (int32_t)(((int64_t)d.H * d.W + JD_COLOR_TILE - 1) / JD_COLOR_TILE);
+    stream_bytes = std::max(stream_bytes, d.stream_off + d.stream_len);
+    const uint64_t nseg = substreams ? (d.stream_len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes : 0;
+    sub[b].segment_bytes = (uint32_t)segment_bytes;
+    sub[b].max_rounds = (uint32_t)max_rounds;
+    if (substreams && r.nunits == 1 && d.stream_len >= 2u * (uint64_t)segment_bytes && nseg <= (uint64_t)JD_SUB_MAX_SEGS) {
+      sub[b].nseg = (uint32_t)nseg;
+      sub[nsub++].image = b;
+    }
+  }
+  const uint64_t info_off = soff;
+  soff += jd_align((uint64_t)B * sizeof(JdSubInfo), 256);
+  for (int b = 0; b < B; ++b) {
+    sub[b].info_off = info_off;
+    sub[b].seg_off = soff;
+    soff += jd_align((uint64_t)sub[b].nseg * (sizeof(JfSegState) + sizeof(JfSegment)), 256);
+  }
+  h.reserved = nsub;
+  h.scratch_bytes = soff;
+  h.out_bytes = ooff;
+  h.stream_bytes = stream_bytes;
+  std::memcpy(t, &h, sizeof h);
+  return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegdec_decode_layouts(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                              uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  const char* who = "jpegdec_decode_layouts";
+  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "%s: null pointer", who);
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, table_host, sizeof h);
+  ATTWARP_REQUIRE(h.magic == JF_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS &&
+                      h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS && h.total_units >= h.B &&
+                      h.total_units <= JD_MAX_TOTAL_UNITS && h.reserved >= 0 && h.reserved <= h.B,
+                  "%s: not a table of attwarp_jpegdec_plan_layouts", who);
+  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "%s: out of %zu bytes, %llu needed", who, out_bytes, (unsigned long long)h.out_bytes);
+  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
+                      reinterpret_cast<uintptr_t>(status) % 4 == 0,
+                  "%s: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned", who);
+  hipStream_t st = as_stream(stream);
+  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  hipLaunchKernelGGL(jpegfmt_scan_kernel, dim3(h.B), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch("jpegfmt_scan_kernel")) return rc;
+  hipLaunchKernelGGL(jpegfmt_substream_kernel, dim3(std::max(h.reserved, 1)), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch("jpegfmt_substream_kernel")) return rc;
+  hipLaunchKernelGGL(jpegfmt_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch("jpegfmt_entropy_kernel")) return rc;
+  hipLaunchKernelGGL(jpegfmt_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegfmt_idct_kernel")) return rc;
+  hipLaunchKernelGGL(jpegfmt_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
+  return check_launch("jpegfmt_color_kernel");
 }

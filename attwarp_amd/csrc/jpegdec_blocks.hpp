@@ -285,14 +285,34 @@ JD_FN void jd_sync_open(JdBits& br, const uint8_t* p, uint32_t lo, const JdSync&
 // invalid code or a run past 63 marks the decode, skips one bit and starts a new block in the next slot, so a decoder that
 // began in the wrong place goes on until it falls in step; a code or value that needs bits behind the unit's end marks it
 // and ends at the unit's end.  Every turn of the loop consumes at least one bit.
-JD_FN void jd_decode_segment(const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t seg_end, uint32_t uend, const JdHuff* dc,
-                             const JdHuff* ac, uint32_t nb0, uint32_t nblk, JdSegment& r) {
+// (The walk is written once over a LAYOUT: comp(slot) the component of a block slot of the MCU, block(m, slot) the index of
+// that slot's block of MCU m among the image's blocks, nblocks their number, NC the components it may name; period(nblk)
+// the slots a decoder's state tells apart and dc_slot(c, i, nblk) where a segment sums the DC difference of its i-th owned
+// block, of component c, NDC such sums.  JdLayout is the one of the records above: every slot is told apart and the sums
+// are per component; jpegfmt_blocks.hpp has the general one.)
+struct JdLayout {
+  static constexpr int NC = 3, NDC = 3;
+  JD_FN uint32_t period(uint32_t nblk) const { return nblk; }
+  JD_FN uint32_t dc_slot(uint32_t c, uint32_t, uint32_t) const { return c; }
+  const JdImage* im;                   // (nullptr where only comp() is asked)
+  uint32_t nb0;                        // luma blocks of an MCU
+  JD_FN uint32_t comp(uint32_t slot) const { return slot < nb0 ? 0u : slot - nb0 + 1u; }
+  JD_FN uint32_t block(uint32_t m, uint32_t slot) const {
+    const uint32_t c = comp(slot), hs = (uint32_t)im->hs;
+    return jd_block_index(*im, (int)c, m, c == 0 ? (int)(slot / hs) : 0, c == 0 ? (int)(slot % hs) : 0);
+  }
+  JD_FN uint32_t nblocks() const { return im->nblocks; }
+};
+template <class Layout, class Segment>
+JD_FN void jd_decode_segment_of(const Layout& lay, const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t seg_end, uint32_t uend,
+                                const JdHuff* dc, const JdHuff* ac, uint32_t nblk, Segment& r) {
   JdBits br;
   jd_sync_open(br, p, lo, entry, uend);
+  const uint32_t nslot = lay.period(nblk);
   uint32_t slot = (entry.bsk >> 8) & 255u, k = entry.bsk & 63u;
-  if (slot >= nblk) slot = 0;
+  if (slot >= nslot) slot = 0;
   r.owned = 0; r.nend = 0; r.eclean = JD_NO_ERROR;
-  r.dc[0] = 0; r.dc[1] = 0; r.dc[2] = 0;
+  for (int c = 0; c < Layout::NDC; ++c) r.dc[c] = 0;
   const uint32_t from = entry.byte < seg_end ? entry.byte : seg_end;
   const uint32_t limit = (seg_end - from) * 8u + 8u;
   uint32_t byte = 0, bit = 0;
@@ -303,7 +323,7 @@ JD_FN void jd_decode_segment(const uint8_t* p, uint32_t lo, const JdSync& entry,
       jd_sync_position(br, lo, byte, bit);
       if (byte >= lo + seg_end) break;
     }
-    const uint32_t c = slot < nb0 ? 0u : slot - nb0 + 1u;
+    const uint32_t c = lay.comp(slot);
     uint32_t st, s = 0, v = 0;
     bool endblk = false;
     if (k == 0) {
@@ -311,8 +331,8 @@ JD_FN void jd_decode_segment(const uint8_t* p, uint32_t lo, const JdSync& entry,
       s &= 15u;
       if (!st && !br.bits(s, v)) st = ATTWARP_JPEGDEC_E_TRUNCATED;
       if (!st) {
+        r.dc[lay.dc_slot(c, r.owned, nblk)] += (uint32_t)jd_extend(v, s);
         ++r.owned;
-        r.dc[c] += (uint32_t)jd_extend(v, s);
         k = 1;
       }
     } else {
@@ -336,11 +356,11 @@ JD_FN void jd_decode_segment(const uint8_t* p, uint32_t lo, const JdSync& entry,
       br.refill();
       if (st == (uint32_t)ATTWARP_JPEGDEC_E_TRUNCATED || br.cnt == 0) { at_end = true; break; }
       br.skip(1);
-      slot = slot + 1u == nblk ? 0u : slot + 1u;
+      slot = slot + 1u == nslot ? 0u : slot + 1u;
       k = 0;
     } else if (endblk) {
       ++r.nend;
-      slot = slot + 1u == nblk ? 0u : slot + 1u;
+      slot = slot + 1u == nslot ? 0u : slot + 1u;
       k = 0;
     }
   }
@@ -349,16 +369,23 @@ JD_FN void jd_decode_segment(const uint8_t* p, uint32_t lo, const JdSync& entry,
   r.exit.byte = byte - lo;
   r.exit.bsk = bit << 16 | slot << 8 | k;
 }
+JD_FN void jd_decode_segment(const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t seg_end, uint32_t uend, const JdHuff* dc,
+                             const JdHuff* ac, uint32_t nb0, uint32_t nblk, JdSegment& r) {
+  jd_decode_segment_of(JdLayout{nullptr, nb0}, p, lo, entry, seg_end, uend, dc, ac, nblk, r);
+}
 
 // What the converged states must satisfy, segment by segment: `before` blocks start in front of the segment.  Bit 0: the
 // segment contradicts a sequential decode of `expected` blocks (an error in front of the end of block expected - 1, or an
-// entry slot that does not follow from the count); bit 1: block expected - 1 ends in this segment, cleanly.
-JD_FN uint32_t jd_segment_check(const JdSync& entry, const JdSegment& r, uint32_t before, uint32_t expected, uint32_t nblk) {
+// entry slot that does not follow from the count); bit 1: block expected - 1 ends in this segment, cleanly.  period: the
+// slots the states tell apart (0: all nblk of them).
+template <class Segment>                // (JdSegment, or JfSegment of jpegfmt_blocks.hpp: the counts alone are read)
+JD_FN uint32_t jd_segment_check(const JdSync& entry, const Segment& r, uint32_t before, uint32_t expected, uint32_t nblk,
+                                uint32_t period = 0) {
   const uint32_t inprog = (entry.bsk & 63u) != 0u;
   if (before < inprog) return 1u;
   const uint32_t done = before - inprog;                     // blocks that ended in front of the segment
   if (done >= expected) return 0u;                           // behind the last block: whatever follows it is tolerated
-  if (((entry.bsk >> 8) & 255u) != done % nblk) return 1u;
+  if (((entry.bsk >> 8) & 255u) != done % (period ? period : nblk)) return 1u;
   const uint32_t last = expected - 1u - done;
   if (last < r.nend) return r.eclean > last ? 2u : 1u;
   return r.eclean == JD_NO_ERROR ? 0u : 1u;
@@ -368,16 +395,17 @@ JD_FN uint32_t jd_segment_check(const JdSync& entry, const JdSegment& r, uint32_
 // is decoded in full (reading past the segment's end until it ends) and stored whole at its true index.  pred: the
 // predictors at the segment's start (the sums of all DC differences in front of it), before: the owned blocks in front of
 // it; blocks with ordinal >= expected are dropped.  blk: 64 int16 of the caller's (dword aligned).  -> status
-JD_FN uint32_t jd_write_segment(const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t uend, const JdHuff* dc, const JdHuff* ac,
-                                const JdImage& im, uint32_t nb0, uint32_t nblk, uint32_t before, const uint32_t* pred0, uint32_t owned,
-                                uint32_t expected, int16_t* blk, const uint8_t* zz, int16_t* coef) {
+template <class Layout>
+JD_FN uint32_t jd_write_segment_of(const Layout& lay, const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t uend, const JdHuff* dc,
+                                   const JdHuff* ac, uint32_t nblk, uint32_t before, const uint32_t* pred0, uint32_t owned,
+                                   uint32_t expected, int16_t* blk, const uint8_t* zz, int16_t* coef) {
   if (before >= expected || owned == 0) return 0;
   JdBits br;
   jd_sync_open(br, p, lo, entry, uend);
   uint32_t slot = (entry.bsk >> 8) & 255u, k = entry.bsk & 63u;
   if (slot >= nblk) slot = 0;
   if (k != 0) {
-    const uint32_t c = slot < nb0 ? 0u : slot - nb0 + 1u;
+    const uint32_t c = lay.comp(slot);
     for (int it = 0; it < 63 && k < 64u; ++it) {
       uint32_t rs, v;
       if (const uint32_t st = jd_symbol(br, ac[c], rs)) return st;
@@ -394,18 +422,23 @@ JD_FN uint32_t jd_write_segment(const uint8_t* p, uint32_t lo, const JdSync& ent
     }
     slot = slot + 1u == nblk ? 0u : slot + 1u;
   }
-  int32_t pred[3] = {(int32_t)pred0[0], (int32_t)pred0[1], (int32_t)pred0[2]};
+  int32_t pred[Layout::NC];
+  for (int c = 0; c < Layout::NC; ++c) pred[c] = (int32_t)pred0[c];
   const uint32_t n = owned < expected - before ? owned : expected - before;
-  const uint32_t hs = (uint32_t)im.hs;
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t o = before + i, m = o / nblk, j = o - m * nblk;
-    const uint32_t c = j < nb0 ? 0u : j - nb0 + 1u;
+    const uint32_t c = lay.comp(j);
     __builtin_memset(blk, 0, 128);
     if (const uint32_t st = jd_decode_block(br, dc[c], ac[c], pred[c], blk, zz)) return st;
-    const uint32_t bi = jd_block_index(im, (int)c, m, c == 0 ? (int)(j / hs) : 0, c == 0 ? (int)(j % hs) : 0);
-    if (bi < im.nblocks) __builtin_memcpy(coef + (size_t)bi * 64u, blk, 128);
+    const uint32_t bi = lay.block(m, j);
+    if (bi < lay.nblocks()) __builtin_memcpy(coef + (size_t)bi * 64u, blk, 128);
   }
   return 0;
+}
+JD_FN uint32_t jd_write_segment(const uint8_t* p, uint32_t lo, const JdSync& entry, uint32_t uend, const JdHuff* dc, const JdHuff* ac,
+                                const JdImage& im, uint32_t nb0, uint32_t nblk, uint32_t before, const uint32_t* pred0, uint32_t owned,
+                                uint32_t expected, int16_t* blk, const uint8_t* zz, int16_t* coef) {
+  return jd_write_segment_of(JdLayout{&im, nb0}, p, lo, entry, uend, dc, ac, nblk, before, pred0, owned, expected, blk, zz, coef);
 }
 
 // ---- the integer IDCT of jidctint.c (CONST_BITS 13, PASS1_BITS 2), 32-bit wrap-around arithmetic ---------------------------------

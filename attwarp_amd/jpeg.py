@@ -4,6 +4,9 @@ MN/dataloader.py:216,368).  Only compressed bytes cross to the device; the pixel
 SOF0 / SOF1, 8 bits, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, any restart interval.
 With ``progressive=True`` (off by default) also SOF2: the host walks every scan of the file, the device runs one entropy
 launch per dependency level of the scans; baseline and progressive files may share a list.
+With ``all_layouts=True`` (off by default) a sequential file may also have four components (Adobe CMYK / YCCK), be RGB-coded,
+or sample every component by factors of its own (4:4:0, 4:1:1, 4:1:0, a factor of 3, luma coarser than chroma ...): such files
+go through a second family of records and kernels, alone or in a list with the others.
 """
 from __future__ import annotations
 
@@ -105,8 +108,9 @@ def _next_segment(mv, n: int, pos: int, behind_scan: bool, progressive: bool, ba
     return m, bytes(mv[pos + 2:pos + L]), pos + L
 
 
-def _read_sof(seg, bad) -> tuple:
-    """An SOF0 / SOF1 / SOF2 payload -> ``(W, H, [(id, h, v, quantisation table id) per component])``."""
+def _read_sof(seg, bad, all_layouts: bool = False) -> tuple:
+    """An SOF0 / SOF1 / SOF2 payload -> ``(W, H, [(id, h, v, quantisation table id) per component])``.  ``all_layouts``: four
+    components pass too (two, and five or more, never do: Pillow refuses them as well)."""
     if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
         raise bad("bad frame header")
     prec, H, W, nf = struct.unpack(">BHHB", seg[:6])
@@ -114,8 +118,8 @@ def _read_sof(seg, bad) -> tuple:
         raise bad(f"precision {prec} (8 only)")
     if H == 0 or W == 0:
         raise bad(f"size {W} x {H}")
-    if nf not in (1, 3):
-        raise bad(f"{nf} components (1 or 3)")
+    if nf not in ((1, 3, 4) if all_layouts else (1, 3)):
+        raise bad(f"{nf} components ({'1, 3 or 4' if all_layouts else '1 or 3'})")
     return W, H, [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(nf)]
 
 
@@ -170,6 +174,34 @@ def _frame_layout(comps, jfif: bool, adobe, bad) -> tuple:
     return samp[0]
 
 
+def _any_layout(comps, jfif: bool, adobe, bad) -> tuple:
+    """What ``all_layouts`` makes of a frame's components -> ``(hs, vs, None)`` for a file the baseline records hold (grey, or
+    YCbCr 4:4:4 / 4:2:2 / 4:2:0), else ``(hmax, vmax, dict(samp=[(h, v) per component], color=...))``.  The colour rule is
+    libjpeg's (default_decompress_parms): three components are YCbCr if a JFIF marker was seen, else what the Adobe transform
+    says (0: RGB), else RGB only for the component ids ``R``, ``G``, ``B``; four components are CMYK unless an Adobe marker
+    names a transform other than 0 (YCCK).  Factors outside 1..4, more than 10 blocks per MCU (T.81 B.2.3) and factors that
+    do not divide the frame's largest (libjpeg has no fractional up-sampling) are refused."""
+    nf = len(comps)
+    if nf == 1:
+        return 1, 1, None                                   # (not interleaved: its factors do not count)
+    samp = [(c[1], c[2]) for c in comps]
+    if any(not 1 <= f <= 4 for hv in samp for f in hv):
+        raise bad(f"sampling factors {samp} outside 1..4")
+    if sum(h * v for h, v in samp) > _lib.JPEGDEC_MAX_SLOTS:
+        raise bad(f"sampling layout {samp}: {sum(h * v for h, v in samp)} blocks per MCU (at most {_lib.JPEGDEC_MAX_SLOTS})")
+    hmax, vmax = max(h for h, _ in samp), max(v for _, v in samp)
+    if any(hmax % h or vmax % v for h, v in samp):
+        raise bad(f"sampling layout {samp}: a component's factors do not divide the largest (fractional up-sampling)")
+    if nf == 3:
+        rgb = not jfif and (adobe == 0 if adobe is not None else bytes(c[0] for c in comps) == b"RGB")
+        color = "rgb" if rgb else "ycc"
+        if color == "ycc" and samp[1] == samp[2] == (1, 1) and samp[0] in ((1, 1), (2, 1), (2, 2)):
+            return samp[0] + (None,)
+    else:
+        color = "cmyk" if adobe in (None, 0) else "ycck"
+    return hmax, vmax, dict(samp=samp, color=color)
+
+
 def _read_sos(seg, most, bad) -> tuple:
     """An SOS payload -> ``([component id], [(DC table id, AC table id)], (Ss, Se, Ah, Al))``.  ``most``: the components a
     scan may hold, at least one (None: the caller checks which it holds)."""
@@ -186,16 +218,17 @@ def _size_limit(units: int, blocks: int, data_bytes: int, all_scans: bool, bad):
                   f"{blocks} blocks (below {JPEGDEC_MAX_BLOCKS})")
 
 
-def _baseline(frame, sos, layout, tables, ri: int, data_off: int, n: int, bad) -> dict:
+def _baseline(frame, sos, layout, tables, ri: int, data_off: int, n: int, bad, all_layouts: bool = False) -> dict:
     """The result of a sequential file from its one scan: the scan must hold all components with (Ss, Se, Ah, Al) =
-    (0, 63, 0, 0); nothing behind its header is looked at."""
+    (0, 63, 0, 0); nothing behind its header is looked at.  ``all_layouts``: see :func:`_any_layout`; a file of another
+    layout also gets ``layout=True``, ``samp`` and ``color``, and its ``hs``, ``vs`` are the frame's largest factors."""
     (W, H, comps), (ids, tabs, band), (qts, dcs, acs) = frame, sos, tables
     nf = len(comps)
     if ids != [c[0] for c in comps]:
         raise bad("the scan does not hold all components in frame order (more than one scan)")
     if band != (0, 63, 0, 0):
         raise bad("spectral selection / successive approximation")
-    hs, vs = _frame_layout(comps, *layout, bad)
+    hs, vs, other = _any_layout(comps, *layout, bad) if all_layouts else _frame_layout(comps, *layout, bad) + (None,)
     qt, dc, ac = [], [], []
     for c, (td, ta) in zip(comps, tabs):
         if c[3] not in qts or td not in dcs or ta not in acs:
@@ -203,8 +236,9 @@ def _baseline(frame, sos, layout, tables, ri: int, data_off: int, n: int, bad) -
         qt.append(qts[c[3]]); dc.append(dcs[td]); ac.append(acs[ta])
     mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
     units = -(-mcus // ri) if ri else 1
-    _size_limit(units, mcus * (hs * vs + nf - 1), n - data_off, False, bad)
-    return dict(W=W, H=H, ncomp=nf, hs=hs, vs=vs, ri=ri, qt=qt, dc=dc, ac=ac, data_off=data_off, units=units)
+    _size_limit(units, mcus * (sum(h * v for h, v in other["samp"]) if other else hs * vs + nf - 1), n - data_off, False, bad)
+    p = dict(W=W, H=H, ncomp=nf, hs=hs, vs=vs, ri=ri, qt=qt, dc=dc, ac=ac, data_off=data_off, units=units)
+    return dict(p, layout=True, **other) if other else p
 
 
 def _progressive_scan(comps, sos, sent, latched: dict, tables, bad) -> dict:
@@ -242,7 +276,7 @@ def _progressive_scan(comps, sos, sent, latched: dict, tables, bad) -> dict:
     return dict(comps=ci, ss=ss, se=se, ah=ah, al=al, tables=used)
 
 
-def parse_jpeg(data, index: int = 0, progressive: bool = False) -> dict:
+def parse_jpeg(data, index: int = 0, progressive: bool = False, all_layouts: bool = False) -> dict:
     """The host's whole part of decoding one file: the walk over the marker segments up to the SOS header.  bytes-like ->
     ``dict(W, H, ncomp, hs, vs, ri, qt, dc, ac, data_off)``: luma sampling factors, the restart interval (0: none), per
     component the quantisation table (64 values, natural order) and the (counts, symbols) of its DC and AC Huffman tables,
@@ -258,7 +292,14 @@ def parse_jpeg(data, index: int = 0, progressive: bool = False) -> dict:
     not continue the precision sent, a first pass over a coefficient already sent, an AC scan before the component's
     DC, more than :data:`JPEGDEC_MAX_SCANS` scans, and an incomplete file (some coefficient never reached ``Al = 0`` at EOI
     or at the file's end).  A file that ends INSIDE a scan is not refused: the device gives it a status.  One walk for both
-    kinds: a sequential file's first SOS ends it (:func:`_baseline`); an SOF2 file's scans go through the same SOS reader."""
+    kinds: a sequential file's first SOS ends it (:func:`_baseline`); an SOF2 file's scans go through the same SOS reader.
+
+    ``all_layouts=True`` also accepts, in a sequential file, four components, RGB coding and any sampling factors libjpeg
+    decodes (:func:`_any_layout`); the result then has ``layout=True``, ``samp`` ([(h, v)] per component), ``color`` ("ycc",
+    "rgb", "cmyk", "ycck") and the frame's largest factors as ``hs``, ``vs``.  The colour rule is then libjpeg's throughout: a
+    JFIF file stays YCbCr whatever an Adobe marker says.  A file the baseline records hold parses exactly as without the
+    keyword.  Still refused: a progressive file of such a layout, more than one scan, 16-bit quantisation tables, 12-bit,
+    arithmetic, lossless and hierarchical files."""
     mv = memoryview(data).cast("B")
     n = len(mv)
 
@@ -283,7 +324,7 @@ def parse_jpeg(data, index: int = 0, progressive: bool = False) -> dict:
         if m in (0xC0, 0xC1, 0xC2):
             if frame is not None:
                 raise bad("a second frame (hierarchical)")
-            sof, frame = m & 3, _read_sof(seg, bad)
+            sof, frame = m & 3, _read_sof(seg, bad, all_layouts)
         elif m == 0xC4:
             _read_dht(seg, dcs, acs, bad)
         elif m == 0xDB:
@@ -303,10 +344,13 @@ def parse_jpeg(data, index: int = 0, progressive: bool = False) -> dict:
             if frame is None:
                 raise bad("SOS before the frame header")
             if sof != 2:
-                return _baseline(frame, _read_sos(seg, None, bad), (jfif, adobe), (qts, dcs, acs), ri, pos, n, bad)
+                return _baseline(frame, _read_sos(seg, None, bad), (jfif, adobe), (qts, dcs, acs), ri, pos, n, bad, all_layouts)
             W, H, comps = frame
             if not scans:
-                hs, vs = _frame_layout(comps, jfif, adobe, bad)
+                hs, vs, other = _any_layout(comps, jfif, adobe, bad) if all_layouts else _frame_layout(comps, jfif, adobe, bad) + (None,)
+                if other:
+                    raise bad(f"progressive file of {len(comps)} components, {other['color']}-coded, sampling {other['samp']}: "
+                              "all_layouts covers sequential files only")
                 sent = [[None] * 64 for _ in comps]          # per coefficient: the Al it was last sent with
                 markers, data_off = _marker_positions(mv), pos
             if len(scans) >= JPEGDEC_MAX_SCANS:
@@ -340,14 +384,14 @@ def _substream_plan(substreams, segment_bytes, max_rounds):
 
 
 def _put_tables(counts, symbols, tables):
-    """(counts, symbols) pairs into the rows of a record's counts [3,16] and symbols [3,256]."""
+    """(counts, symbols) pairs into the rows of a record's counts [3 or 4, 16] and symbols [3 or 4, 256]."""
     for t, (c, s) in enumerate(tables):
         counts[t] = np.frombuffer(bytes(c), dtype=np.uint8)
         symbols[t, :len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
 
 
 def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segment_bytes: Optional[int] = None,
-         max_rounds: Optional[int] = None, progressive: bool = False, levels: bool = True, _parsed=None):
+         max_rounds: Optional[int] = None, progressive: bool = False, levels: bool = True, all_layouts: bool = False, _parsed=None):
     """Host only (no device is touched): files -> ``(parsed, table, header)``: :func:`parse_jpeg` of every file and the table
     ``attwarp_jpegdec_plan_ex`` writes for them, which depends on the headers and the files' lengths alone.  ``substreams``:
     "auto" / True cut every marker-less file of at least two segments into ``segment_bytes`` (a power of two in 32..512,
@@ -358,22 +402,35 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
     ``progressive=True`` also plans a list of progressive files (all of the list: :class:`JpegFiles` splits a mixed one)
     through ``attwarp_jpegdec_plan_scans``: every scan of every file, one entropy launch per dependency level
     (``parsed[i]["levels"]``).  ``levels=False`` plans one launch per scan position in file order instead; pixels, statuses
-    and coefficients do not depend on it (for tests).  Progressive files take no sub-streams."""
+    and coefficients do not depend on it (for tests).  Progressive files take no sub-streams.
+
+    ``all_layouts=True`` also plans a list of files of the other layouts (``parsed[i]["layout"]``; again all of the list)
+    through ``attwarp_jpegdec_plan_layouts``, sub-streams included.  A list without such a file gets the table it gets
+    without the keyword, byte for byte."""
     if mode not in _lib.JPEGDEC_MODE_IDS or order not in _ORDERS:
         raise ValueError(f"jpeg: mode must be one of {sorted(_lib.JPEGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
     sb, mr = _substream_plan(substreams, segment_bytes, max_rounds)
     files = [file_bytes(f) for f in files]
-    parsed = _parsed if _parsed is not None else [parse_jpeg(f, i, progressive) for i, f in enumerate(files)]
+    parsed = _parsed if _parsed is not None else [parse_jpeg(f, i, progressive, all_layouts) for i, f in enumerate(files)]
     B = len(parsed)
     prog = [bool(p.get("progressive")) for p in parsed]
-    if any(prog) and not all(prog):
+    other = [bool(p.get("layout")) for p in parsed]
+    if any(prog) and not all(prog) and not any(other):
         raise ValueError("jpeg: plan() takes baseline files or progressive files; JpegFiles splits a list that holds both")
-    rec = np.zeros(B, dtype=_IMAGE_DTYPE)
+    if any(other) and not all(other):
+        raise ValueError("jpeg: plan() takes baseline files, progressive files or files of the other layouts; JpegFiles splits a "
+                         "list that holds several kinds")
+    rec = np.zeros(B, dtype=np.dtype(_lib.JpegDecLayoutImage) if any(other) else _IMAGE_DTYPE)
     lens = [len(memoryview(f).cast("B")) - p["data_off"] for f, p in zip(files, parsed)]
     rec["stream_off"] = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
     rec["stream_len"] = lens
-    for key, name in (("H", "H"), ("W", "W"), ("ncomp", "ncomp"), ("hs", "hs"), ("vs", "vs"), ("restart_interval", "ri")):
+    for key, name in (("H", "H"), ("W", "W"), ("ncomp", "ncomp"), ("restart_interval", "ri")) + ((("hs", "hs"), ("vs", "vs")) if not any(other) else ()):
         rec[key] = [p[name] for p in parsed]
+    if any(other):
+        rec["color"] = [_lib.JPEGDEC_COLOR_IDS[p["color"]] for p in parsed]
+        for b, p in enumerate(parsed):
+            rec["h"][b, :p["ncomp"]] = [h for h, _ in p["samp"]]
+            rec["v"][b, :p["ncomp"]] = [v for _, v in p["samp"]]
     rec["mode"] = _lib.JPEGDEC_MODE_IDS[mode]; rec["order"] = _ORDERS[order]
     for b, p in enumerate(parsed):                          # (a progressive file's Huffman tables belong to its scans: none here)
         rec["qt"][b, :p["ncomp"]] = p["qt"]
@@ -381,6 +438,8 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
         _put_tables(rec["ac_counts"][b], rec["ac_symbols"][b], p["ac"])
     rp = ctypes.c_void_p(rec.ctypes.data)
     size, planner = ("attwarp_jpegdec_table_bytes", rp, B), ("attwarp_jpegdec_plan_ex", rp, B, TABLE, sb, mr)
+    if any(other):
+        size, planner = ("attwarp_jpegdec_layouts_table_bytes", rp, B), ("attwarp_jpegdec_plan_layouts", rp, B, TABLE, sb, mr)
     if any(prog):
         scans = [(b, s) for b, p in enumerate(parsed) for s in p["scans"]]
         srec = np.zeros(len(scans), dtype=np.dtype(_lib.JpegDecScan))
@@ -425,23 +484,29 @@ class JpegFiles(FileBatch):
     kind is one plan and one output buffer.  A mixed list is two plans, one per kind (:attr:`parts`: ``[(indices, JpegFiles
     of that kind)]``), each with its own transfer and output buffer (``out`` must then be None); :meth:`views` and the
     status come back in input order, and the baseline files take exactly the path of a ``progressive=False`` call on them
-    alone.  ``levels``: see :func:`plan`."""
+    alone.  ``levels``: see :func:`plan`.
+
+    ``all_layouts=True`` also takes sequential files of four components (CMYK, YCCK), RGB-coded files and every sampling
+    layout libjpeg decodes (DESIGN.md 3.19).  They are a third kind with a plan of its own, so a list may hold all three;
+    "keep" gives such a file its own channels (four: Pillow's ``CMYK`` bytes).  A list without such a file takes exactly the
+    path it takes without the keyword."""
 
     def __init__(self, files, mode: str = "RGB", order: str = "rgb", out: Optional[torch.Tensor] = None, device=None,
                  substreams="auto", segment_bytes: Optional[int] = None, max_rounds: Optional[int] = None,
-                 progressive: bool = False, levels: bool = True):
+                 progressive: bool = False, levels: bool = True, all_layouts: bool = False):
         files = [file_bytes(f) for f in files]
         if not files:
             raise ValueError("JpegFiles: empty batch")
         self.parts, self.B, self.mode, self.order = None, len(files), mode, order
-        pre = [parse_jpeg(f, i, True) for i, f in enumerate(files)] if progressive else None
-        which = [bool(p.get("progressive")) for p in pre or []]
-        self.progressive = any(which) and all(which)
-        if any(which) and not all(which):
+        pre = [parse_jpeg(f, i, progressive, all_layouts) for i, f in enumerate(files)] if progressive or all_layouts else None
+        which = [1 if p.get("progressive") else 2 if p.get("layout") else 0 for p in pre or []]     # baseline, progressive, other layout
+        self.progressive, self.all_layouts = bool(which) and set(which) == {1}, bool(which) and set(which) == {2}
+        if len(set(which)) > 1:
             if out is not None:
-                raise ValueError("JpegFiles: a list of baseline and progressive files decodes into two buffers; out must be None")
-            self.parts = [(idx, JpegFiles([files[i] for i in idx], mode, order, None, device, substreams, segment_bytes, max_rounds, kind, levels))
-                          for kind, idx in split_indices(which, (False, True))]
+                raise ValueError("JpegFiles: a list of baseline and progressive files decodes into two buffers; out must be None"
+                                 if 2 not in which else "JpegFiles: a list of several kinds of files decodes into one buffer per kind; out must be None")
+            self.parts = [(idx, JpegFiles([files[i] for i in idx], mode, order, None, device, substreams, segment_bytes, max_rounds, kind == 1, levels, all_layouts))
+                          for kind, idx in split_indices(which, (0, 1, 2))]
             first = self.parts[0][1]
             self._dev, self.segment_bytes, self.max_rounds = first._dev, first.segment_bytes, first.max_rounds
             self.parsed, self.shapes = (scattered(self.B, ((idx, getattr(part, name)) for idx, part in self.parts)) for name in ("parsed", "shapes"))
@@ -450,8 +515,9 @@ class JpegFiles(FileBatch):
                 self.status = torch.empty(self.B, device=self._dev, dtype=torch.int32)
                 self._index = [torch.tensor(idx, device=self._dev, dtype=torch.int64) for idx, _ in self.parts]
             return
-        self._entry = "attwarp_jpegdec_decode_scans" if self.progressive else "attwarp_jpegdec_decode"
-        self.parsed, self.table_host, self.header = plan(files, mode, order, substreams, segment_bytes, max_rounds, progressive, levels, pre)
+        self._entry = ("attwarp_jpegdec_decode_scans" if self.progressive else "attwarp_jpegdec_decode_layouts" if self.all_layouts
+                       else "attwarp_jpegdec_decode")
+        self.parsed, self.table_host, self.header = plan(files, mode, order, substreams, segment_bytes, max_rounds, progressive, levels, all_layouts, pre)
         self.segment_bytes, self.max_rounds = _substream_plan(substreams, segment_bytes, max_rounds)      # (0, 0): off
         self._info_off = int(_lib.load().attwarp_jpegdec_info_offset(self.table_host.ctypes.data))
         self._dev = indexed_device(device, out)
@@ -484,7 +550,10 @@ class JpegFiles(FileBatch):
 
     @_per_part
     def coefficients(self) -> List[torch.Tensor]:
-        """After a :meth:`run`: per image the int16 [blocks, 64] coefficients as they lie in scratch (views).  For tests."""
+        """After a :meth:`run`: per image the int16 [blocks, 64] coefficients as they lie in scratch (views).  For tests; not
+        for files of the other layouts."""
+        if self.all_layouts:
+            raise ValueError("JpegFiles.coefficients: not offered for files of the other layouts")
         ims = np.frombuffer(self.table_host, dtype=np.uint8)
         out = []
         for b, p in enumerate(self.parsed):
@@ -527,16 +596,19 @@ class JpegFiles(FileBatch):
         return self.views(), self.status
 
 
-def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False) -> List[torch.Tensor]:
+def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False,
+                all_layouts: bool = False) -> List[torch.Tensor]:
     """JPEG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
     first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all.
     ``substreams``: see :func:`plan`.  ``progressive=True`` also decodes progressive files, alone or among baseline files
-    (:class:`JpegFiles`); without it such a file raises ValueError."""
-    views, status = JpegFiles(files, mode, order, device=device, substreams=substreams, progressive=progressive).run()
+    (:class:`JpegFiles`); without it such a file raises ValueError.  ``all_layouts=True`` also decodes CMYK / YCCK files,
+    RGB-coded files and every sampling layout libjpeg decodes; without it such a file raises ValueError."""
+    views, status = JpegFiles(files, mode, order, device=device, substreams=substreams, progressive=progressive, all_layouts=all_layouts).run()
     raise_first_broken(status, STATUS_NAMES, "jpeg")
     return views
 
 
-def read_jpeg(paths, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False) -> List[torch.Tensor]:
+def read_jpeg(paths, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False,
+              all_layouts: bool = False) -> List[torch.Tensor]:
     """:func:`decode_jpeg` of the files at ``paths``."""
-    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device, substreams, progressive)
+    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device, substreams, progressive, all_layouts)

@@ -1062,6 +1062,53 @@ ATTWARP_API int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, 
 ATTWARP_API int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
 
+/* ---- every LAYOUT of a sequential file (jpegdec.hip, jpegfmt_blocks.hpp): a second family beside
+ * attwarp_jpegdec_plan / attwarp_jpegdec_decode, with records of its own, for what those refuse.  SOF0 / SOF1, 8 bits, one
+ * interleaved scan, any restart interval, and
+ *   components: 1, 3 or 4;
+ *   sampling:   per component factors h, v of 1..4 that divide the frame's largest (libjpeg has no fractional up-sampling),
+ *               with sum of h v <= 10 (T.81 B.2.3); a one-component image is not interleaved and its factors do not count;
+ *   colour:     the caller's decision (libjpeg's rule over the Adobe transform, JFIF and the component ids):
+ *               ATTWARP_JPEGDEC_COLOR_GREY (1 component), _YCC or _RGB (3), _CMYK or _YCCK (4).
+ * Everything else is the contract of attwarp_jpegdec_plan_ex / attwarp_jpegdec_decode: the same packed stream, scratch
+ * layout, units, sub-streams (segment_bytes = max_rounds = 0: none), statuses and their precedence, limits, and five
+ * capturable launches.  A sub-stream state carries the block slot modulo the PERIOD of the MCU's sequence of Huffman tables
+ * (components that share their tables, as all four of libjpeg's CMYK files do, make slots no decoder can tell apart), a
+ * segment sums the DC differences of its blocks by their place in it, and every block's slot, component and predictor
+ * follow from the count of blocks in front of its segment: up to 10 slots, four predictors, the same acceptance rule.
+ * Each component is up-sampled as
+ * jdsample.c would: same size copied; 2 x 1 and 2 x 2 by the triangle filters when its true width ceil(W h / hmax) exceeds 2,
+ * else replicated; 1 x 2 by the vertical triangle filter; every other integral ratio replicated.  Then the colour rule,
+ * then Pillow's conversion: mode RGB / L give Image.open(f).convert(mode) bit for bit, for four components through
+ * Pillow's CMYK bytes (every stored sample of a CMYK file inverted; a YCCK file's YCbCr -> RGB taken as C, M, Y and K
+ * inverted), R = (255 - K) - muldiv255(C, 255 - K) with muldiv255(a, b) = ((t >> 8) + t) >> 8, t = a b + 128, then the luma
+ * of that RGB.  KEEP gives the file's channels: 1, 3 (RGB) or 4 (Pillow's CMYK bytes).  ATTWARP_BGR swaps a 3-channel
+ * output only.  The planner refuses (ATTWARP_E_ARG) factors, components and colour rules outside the above and Huffman
+ * tables that are over-subscribed, longer than 256 symbols or hold a DC category above 15. */
+enum { ATTWARP_JPEGDEC_COLOR_GREY = 0, ATTWARP_JPEGDEC_COLOR_YCC = 1, ATTWARP_JPEGDEC_COLOR_RGB = 2, ATTWARP_JPEGDEC_COLOR_CMYK = 3,
+       ATTWARP_JPEGDEC_COLOR_YCCK = 4 };
+typedef struct attwarp_jpegdec_layout_image {
+  uint64_t stream_off;                             /* the image's entropy data in the packed buffer */
+  uint64_t stream_len;
+  int32_t H, W;
+  int32_t ncomp;                                   /* 1, 3 or 4 */
+  int32_t h[4], v[4];                              /* sampling factors per component */
+  int32_t color;                                   /* ATTWARP_JPEGDEC_COLOR_* */
+  int32_t restart_interval;                        /* MCUs, 0: none */
+  int32_t mode;                                    /* ATTWARP_JPEGDEC_RGB / L / KEEP */
+  int32_t order;                                   /* ATTWARP_RGB / ATTWARP_BGR */
+  int32_t reserved;
+  uint16_t qt[4][64];                              /* per component, natural order, 0..255 */
+  uint8_t dc_counts[4][16], ac_counts[4][16];
+  uint8_t dc_symbols[4][256], ac_symbols[4][256];
+} attwarp_jpegdec_layout_image;
+/* The table starts with an attwarp_jpegdec_header (of this family: attwarp_jpegdec_decode refuses it and the reverse). */
+ATTWARP_API size_t attwarp_jpegdec_layouts_table_bytes(const attwarp_jpegdec_layout_image* images, int B);
+ATTWARP_API int attwarp_jpegdec_plan_layouts(const attwarp_jpegdec_layout_image* images, int B, void* table, size_t table_bytes,
+                       int segment_bytes, int max_rounds);
+ATTWARP_API int attwarp_jpegdec_decode_layouts(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                       uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
