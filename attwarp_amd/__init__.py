@@ -22,7 +22,8 @@ model/marginalnet_full_dataset/trainer.py   attwarp_amd.panels           (make_g
 =========================================  =====================================================
 
 plus ``attwarp_amd.pipeline`` (batched device-resident launcher), ``attwarp_amd.png`` (the drivers' PNG files, whole
-ragged batches encoded and decoded on the GPU), ``attwarp_amd.jpeg`` (their baseline JPEG sources decoded on the GPU) and ``attwarp_amd.dist`` (one process per GPU, image shards, one RCCL broadcast of
+ragged batches encoded and decoded on the GPU), ``attwarp_amd.jpeg`` (their baseline JPEG sources decoded, and their JPEG files written byte for byte as Pillow writes
+them, on the GPU) and ``attwarp_amd.dist`` (one process per GPU, image shards, one RCCL broadcast of
 MarginalNet weights).
 
 Compute happens in hand-written HIP kernels (``attwarp_amd/csrc``) reached through a C ABI

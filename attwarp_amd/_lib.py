@@ -181,6 +181,11 @@ SIGNATURES = {
     "attwarp_jpegdec_layouts_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_jpegdec_plan_layouts": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int]),
     "attwarp_jpegdec_decode_layouts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # JPEG files of a ragged batch written on the device (jpegenc.hip)
+    "attwarp_jpegenc_bound": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "attwarp_jpegenc_table_bytes": (c_size_t, [c_void_p, c_int]),
+    "attwarp_jpegenc_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "attwarp_jpegenc_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),
@@ -210,6 +215,9 @@ JPEGDEC_COLOR_IDS = {"grey": 0, "ycc": 1, "rgb": 2, "cmyk": 3, "ycck": 4}   # AT
 JPEGDEC_MAX_SLOTS = 10                                   # blocks per MCU (T.81 B.2.3)
 JPEGDEC_STATUS_NAMES = ("OK", "E_TRUNCATED", "E_HUFFMAN", "E_COEFF", "E_RESTART", "E_NO_EOI")
 (JPEGDEC_OK, JPEGDEC_E_TRUNCATED, JPEGDEC_E_HUFFMAN, JPEGDEC_E_COEFF, JPEGDEC_E_RESTART, JPEGDEC_E_NO_EOI) = range(6)
+# attwarp_jpegenc_*: Pillow's subsampling numbers and the limits (ATTWARP_JPEGENC_* of include/attwarp.h)
+JPEGENC_SUBSAMPLING_IDS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+JPEGENC_UNIT_MCUS, JPEGENC_MAX_DIM = 16, 65500
 # attwarp_panel_grid: limits, flags and source kinds (ATTWARP_PANEL_* of include/attwarp.h)
 PANEL_MAX_SRC, PANEL_MAX_HEAT, PANEL_FOR_PNG = 8, 4096, 1
 PANEL_F32, PANEL_U8, PANEL_HEAT = 0, 1, 2
@@ -310,6 +318,20 @@ class PanelSource(ctypes.Structure):
     """attwarp_panel_source: one row source of an attwarp_panel_grid call, device pointer in a host array."""
     _fields_ = [("data", c_void_p), ("batch_stride", c_int64), ("kind", ctypes.c_int32), ("C", ctypes.c_int32),
                 ("N", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("clamp", ctypes.c_int32)]
+
+
+class JpegEncImage(ctypes.Structure):
+    """attwarp_jpegenc_image: one image of an attwarp_jpegenc_plan call, device pointer in a host array."""
+    _fields_ = [("src", c_void_p)] + [(n, ctypes.c_int32) for n in ("H", "W", "C", "pitch", "order", "quality", "subsampling",
+                                                                   "restart_rows")]
+
+
+class JpegEncHeader(ctypes.Structure):
+    """attwarp_jpegenc_header: the first bytes of a table written by attwarp_jpegenc_plan."""
+    _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("nunits", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("table_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
+                ("off_images", ctypes.c_uint64), ("off_units", ctypes.c_uint64), ("off_huffman", ctypes.c_uint64),
+                ("off_image_out", ctypes.c_uint64)]
 
 
 class PngHeader(ctypes.Structure):

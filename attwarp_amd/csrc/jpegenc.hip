@@ -1,0 +1,586 @@
+// JPEG files of a whole ragged batch of uint8 images, written on the device (include/attwarp.h): the bytes of
+// Pillow's Image.save(f, "JPEG", quality, subsampling, restart_marker_rows).  Seven launches, none with a host-dependent argument:
+//   jpegenc_transform_kernel  one workgroup per UNIT (at most 16 MCUs of one restart interval, planned on the host), one thread
+//                             per block: colour, edge replication, down-sampling, islow DCT, quantisation -> zigzag int16
+//                             coefficients in the scratch buffer (a dummy block: the DC of the block it repeats, no AC);
+//   jpegenc_entropy_kernel    one workgroup per unit, one wave per block, one lane per coefficient: a ballot gives the non-zero
+//                             mask, a bit scan the zero run, a wave prefix sum the place of every lane's bits, which are ORed
+//                             into zeroed LDS words -> the unit's bit string and its length;
+//   jpegenc_scan_bits_kernel  one workgroup per image: prefix sums of the units' bit lengths;
+//   jpegenc_gather_kernel     one workgroup per unit: the bytes of its interval's stream that START in the unit, shifted out of
+//                             the unit's (and, for the last one, its successors') bit strings, 1-bits behind the interval's end
+//                             -> the unstuffed stream; counts the FF bytes among them;
+//   jpegenc_scan_bytes_kernel one workgroup per image: prefix sums of bytes + FF bytes + markers, the file's length;
+//   jpegenc_scan_files_kernel one workgroup: prefix sums of the files' lengths -> offsets[B + 1];
+//   jpegenc_write_kernel      one workgroup per unit: stuffed bytes to their place, RSTn behind an interval, the header before
+//                             the first unit, EOI behind the last.
+// A file with restart markers takes the same route: an interval is a stretch at whose start the bit offset returns to zero.
+// Every loop is bounded by a constant or by a size the planner checked; tests/jpegenc_ref.py restates the byte stream.
+#include <algorithm>
+#include <cstring>
+
+#include "jpegenc_blocks.hpp"
+
+namespace attwarp {
+
+#define JE_G __attribute__((address_space(1)))
+constexpr uint32_t JE_MAGIC = 0x474a5041u;
+constexpr int JE_MAX_UNITS = 1 << 24;
+
+struct JeImageOut {
+  uint64_t bits;                       // (scan A) bits of all units of the image
+  uint64_t file_bytes;                 // (scan B)
+};
+
+// exclusive prefix sum over the JE_NT threads (tmp: JE_NT values)
+template <typename T>
+__device__ __forceinline__ T je_excl_sum(T v, T* tmp, T& total) {
+  const int t = threadIdx.x;
+  tmp[t] = v;
+  __syncthreads();
+  for (int o = 1; o < JE_NT; o <<= 1) {
+    const T a = t >= o ? tmp[t - o] : (T)0;
+    __syncthreads();
+    tmp[t] += a;
+    __syncthreads();
+  }
+  const T incl = tmp[t];
+  total = tmp[JE_NT - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__device__ __forceinline__ uint32_t je_wave_incl_sum(uint32_t v) {
+  const int lane = threadIdx.x & (WAVE - 1);
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const uint32_t a = __shfl_up(v, o, WAVE);
+    if (lane >= o) v += a;
+  }
+  return v;
+}
+
+__device__ __forceinline__ JeSrc je_source(const JeImageDev* im) {
+  JeSrc s;
+  s.p = im->src;
+  s.pitch = im->pitch;
+  s.H = im->H; s.W = im->W; s.C = im->C; s.hmax = im->hmax; s.vmax = im->vmax;
+  s.swap = im->swap != 0;
+  return s;
+}
+
+// ---- 1. pixels -> quantised coefficients ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(JE_TNT) void jpegenc_transform_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[blockIdx.x];
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  const int bpm = im->bpm, i = threadIdx.x;
+  if (i >= u.nmcu * bpm) return;
+  const int mcu = u.mcu0 + i / bpm, s = i - (i / bpm) * bpm;
+  const int my = mcu / im->mcus_x, mx = mcu - my * im->mcus_x;
+  const int wb = (im->W + 7) >> 3, hb = (im->H + 7) >> 3;
+  JeSlot sl = je_slot(s, im->hmax, im->vmax, im->C, mx, my, wb, hb);
+  const bool dummy = sl.src >= 0;
+  if (dummy) sl = je_slot(sl.src, im->hmax, im->vmax, im->C, mx, my, wb, hb);
+  const int col = sl.comp ? mx : mx * im->hmax + sl.bx, row = sl.comp ? my : my * im->vmax + sl.by;
+  int d[64];
+  je_source(im).block(sl.comp, col, row, d);
+  je_fdct(d);
+  const int t = sl.comp ? 1 : 0;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(scratch + im->coef_off) + ((size_t)mcu * bpm + s) * 32;
+#pragma unroll
+  for (int k = 0; k < 64; k += 2) {
+    const int n0 = je_zigzag(k), n1 = je_zigzag(k + 1);
+    int a = je_quantize(d[n0], im->divisor[t][n0], im->recip[t][n0]);
+    int b = je_quantize(d[n1], im->divisor[t][n1], im->recip[t][n1]);
+    if (dummy) { a = k ? 0 : a; b = 0; }
+    dst[k >> 1] = ((uint32_t)a & 0xffffu) | ((uint32_t)b << 16);
+  }
+}
+
+// ---- 2. coefficients -> one bit string per unit ----------------------------------------------------------------------------------
+// What lane k of a wave contributes to its block: nf0 codes of sixteen zeros, then `len` bits of `code` (the symbol's code and
+// the value's low bits; lane 0: the DC difference; lane 63 when its coefficient is zero: the end-of-block code).
+struct JeLane {
+  uint32_t nf0, code, len;
+};
+__device__ __forceinline__ JeLane je_lane_code(int lane, int v, const uint32_t* dc, const uint32_t* ac) {
+  JeLane o = {0u, 0u, 0u};
+  const unsigned long long mask = __ballot(lane > 0 && v != 0);
+  if (lane == 0 || v != 0) {
+    const uint32_t mag = (uint32_t)(v < 0 ? -v : v);
+    const uint32_t n = 32u - (uint32_t)__clz(mag);          // (mag = 0: 32 - 32)
+    const uint32_t low = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1u);
+    uint32_t h;
+    if (lane == 0) h = dc[n];
+    else {
+      const unsigned long long below = mask & ((1ull << lane) - 1ull);
+      const int prev = below ? 63 - __clzll((long long)below) : 0;
+      const uint32_t run = (uint32_t)(lane - 1 - prev);
+      o.nf0 = run >> 4;
+      h = ac[(run & 15u) << 4 | n];
+    }
+    o.code = (h & 0xffffu) << n | low;
+    o.len = (h >> 16) + n;
+  } else if (lane == 63) {
+    o.code = ac[0] & 0xffffu;
+    o.len = ac[0] >> 16;
+  }
+  return o;
+}
+// nbits <= 27 of `value` at bit `pos` of the big-endian words w
+__device__ __forceinline__ void je_put(uint32_t* w, uint32_t pos, uint32_t value, uint32_t nbits) {
+  const uint64_t x = (uint64_t)value << (64u - nbits - (pos & 31u));
+  atomicOr(&w[pos >> 5], (uint32_t)(x >> 32));
+  if ((uint32_t)x) atomicOr(&w[(pos >> 5) + 1], (uint32_t)x);
+}
+
+__global__ __launch_bounds__(JE_NT) void jpegenc_entropy_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_bits[JE_UNIT_WORDS];
+  __shared__ uint32_t s_huff[4 * 256];
+  __shared__ uint32_t s_blen[2 * WAVE], s_bstart[2 * WAVE];
+  __shared__ uint32_t s_total;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[blockIdx.x];
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  const uint32_t* huff = reinterpret_cast<const uint32_t*>(table + hdr->off_huffman);
+  const int bpm = im->bpm, nblk = u.nmcu * bpm, ny = im->C == 3 ? im->hmax * im->vmax : 1;
+  const int nwords = min(JE_UNIT_WORDS, (nblk * im->block_bits + 31) / 32 + 2);
+  for (int i = tid; i < nwords; i += JE_NT) s_bits[i] = 0;
+  for (int i = tid; i < 4 * 256; i += JE_NT) s_huff[i] = huff[i];
+  if (tid < 2 * WAVE) s_blen[tid] = 0;
+  __syncthreads();
+  const int16_t* coef = reinterpret_cast<const int16_t*>(scratch + im->coef_off);
+  const int64_t blk0 = (int64_t)u.mcu0 * bpm;
+  // the coefficient of this lane in block i of the unit; lane 0: the difference to the component's previous block
+  auto lane_code = [&](int i) {
+    const int m = i / bpm, s = i - m * bpm;
+    const int64_t blk = blk0 + i;
+    int v = coef[blk * 64 + lane];
+    const int comp = s < ny ? 0 : s - ny + 1, first = comp ? s : 0, last = comp ? s : ny - 1;
+    if (lane == 0) {
+      int pred = 0;
+      if (s > first) pred = coef[(blk - 1) * 64];
+      else if ((u.mcu0 + m) % im->interval != 0) pred = coef[(blk - s - bpm + last) * 64];
+      v -= pred;
+    }
+    const int t = comp ? 2 : 0;
+    return je_lane_code(lane, v, s_huff + 256 * t, s_huff + 256 * (t + 1));
+  };
+  const uint32_t f0[2] = {s_huff[256 + 0xf0], s_huff[768 + 0xf0]};
+  for (int i = wave; i < nblk; i += JE_NT / WAVE) {
+    const JeLane c = lane_code(i);
+    const int t = (i % bpm) < ny ? 0 : 1;
+    uint32_t n = c.nf0 * (f0[t] >> 16) + c.len;
+    n = je_wave_incl_sum(n);
+    if (lane == WAVE - 1) s_blen[i] = n;
+  }
+  __syncthreads();
+  if (wave == 0) {                                          // 2 x 64 >= JE_UNIT_BLOCKS block lengths -> block starts
+    const uint32_t a = s_blen[2 * lane], b = s_blen[2 * lane + 1];
+    const uint32_t incl = je_wave_incl_sum(a + b);
+    s_bstart[2 * lane] = incl - a - b;
+    s_bstart[2 * lane + 1] = incl - b;
+    if (lane == WAVE - 1) s_total = incl;
+  }
+  __syncthreads();
+  for (int i = wave; i < nblk; i += JE_NT / WAVE) {
+    const JeLane c = lane_code(i);
+    const int t = (i % bpm) < ny ? 0 : 1;
+    const uint32_t fl = f0[t] >> 16, n = c.nf0 * fl + c.len;
+    uint32_t pos = s_bstart[i] + je_wave_incl_sum(n) - n;
+    for (uint32_t k = 0; k < c.nf0; ++k, pos += fl) je_put(s_bits, pos, f0[t] & 0xffffu, fl);     // (nf0 <= 3)
+    if (c.len) je_put(s_bits, pos, c.code, c.len);
+  }
+  __syncthreads();
+  // The bits above were ORed into s_bits without a check: the LDS writes rely on the planner's bound, which holds for every
+  // block (coefficients stay below 1024).  The clamp guards the copy to the unit's slot in global memory only.
+  const uint32_t total = min(s_total, (uint32_t)(nblk * im->block_bits));
+  uint32_t* dst = reinterpret_cast<uint32_t*>(scratch + u.slot_off);
+  for (uint32_t i = tid; i < (total + 31u) / 32u; i += JE_NT) dst[i] = __builtin_bswap32(s_bits[i]);
+  if (tid == 0) reinterpret_cast<JeUnitOut*>(scratch)[blockIdx.x].bits = total;
+}
+
+// ---- 3. bits of the image's earlier units -----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(JE_NT) void jpegenc_scan_bits_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ unsigned long long s_tmp[JE_NT];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + b;
+  JeUnitOut* uo = reinterpret_cast<JeUnitOut*>(scratch) + im->unit0;
+  unsigned long long carry = 0;
+  for (int base = 0; base < im->nunits; base += JE_NT) {
+    const int s = base + tid;
+    const unsigned long long v = s < im->nunits ? uo[s].bits : 0ull;
+    unsigned long long tot;
+    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
+    if (s < im->nunits) uo[s].pre = pre;
+    carry += tot;
+  }
+  if (tid == 0) reinterpret_cast<JeImageOut*>(scratch + hdr->off_image_out)[b].bits = carry;
+}
+
+// Where the unit's bytes lie in its interval's stream: bits [off, off + bits) of `ibits`; it owns bytes [j0, j1), the bytes
+// whose first bit is its own (the last unit: up to the interval's padded end).  The interval's stream starts at `upos0` of the
+// image's unstuffed buffer: floor(bits before it / 8) + its index leaves room for every earlier interval's padding.
+struct JePlace {
+  uint64_t off, end, ibits, upos0;
+  uint32_t j0, j1;
+  int unit_end;                        // index (in the image) behind the interval's last unit
+};
+__device__ __forceinline__ JePlace je_place(const JeUnit& u, const JeImageDev* im, const JeUnitOut* uo, const JeImageOut* io) {
+  JePlace p;
+  const int f = u.interval * im->upi;
+  p.unit_end = min(f + im->upi, im->nunits);
+  const uint64_t base = uo[f].pre;
+  p.off = uo[u.index].pre - base;
+  p.end = p.off + uo[u.index].bits;
+  p.ibits = (p.unit_end < im->nunits ? uo[p.unit_end].pre : io[u.image].bits) - base;
+  p.upos0 = base / 8u + (uint64_t)u.interval;
+  p.j0 = (uint32_t)((p.off + 7u) / 8u);
+  p.j1 = (uint32_t)(((u.last ? p.ibits : p.end) + 7u) / 8u);
+  return p;
+}
+
+// ---- 4. the unstuffed stream: shifted gather, FF count ------------------------------------------------------------------------------
+__global__ __launch_bounds__(JE_NT) void jpegenc_gather_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_ff;
+  const int tid = threadIdx.x;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JeUnit* units = reinterpret_cast<const JeUnit*>(table + hdr->off_units);
+  const JeUnit u = units[blockIdx.x];
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  JeUnitOut* uo = reinterpret_cast<JeUnitOut*>(scratch) + im->unit0;
+  const JePlace p = je_place(u, im, uo, reinterpret_cast<const JeImageOut*>(scratch + hdr->off_image_out));
+  if (tid == 0) s_ff = 0;
+  __syncthreads();
+  const JE_G uint8_t* slot = (const JE_G uint8_t*)scratch + u.slot_off;
+  JE_G uint8_t* ust = (JE_G uint8_t*)scratch + im->ustream_off + p.upos0;
+  // whole bytes of this unit's own bits: 8 j + 8 <= end
+  const uint32_t full = (uint32_t)(p.end / 8u), nfull = full > p.j0 ? full - p.j0 : 0u;
+  uint32_t ff = 0;
+  for (uint32_t k = tid; k < nfull; k += JE_NT) {
+    const uint32_t j = p.j0 + k, q = (uint32_t)(8ull * j - p.off);
+    const uint32_t two = (uint32_t)slot[q >> 3] << 8 | slot[(q >> 3) + 1];
+    const uint32_t byte = (two >> (8u - (q & 7u))) & 255u;
+    ust[j] = (uint8_t)byte;
+    ff += byte == 255u;
+  }
+  // the byte that straddles the unit's end (at most one): bit by bit out of this and the following units, 1-bits behind the interval
+  if (tid == 0 && p.j1 > p.j0 + nfull) {
+    const uint32_t j = p.j1 - 1u;
+    int v = u.index;
+    uint64_t voff = p.off, vend = p.end;
+    uint32_t byte = 0;
+    for (int t = 0; t < 8; ++t) {
+      const uint64_t pos = 8ull * j + (uint64_t)t;
+      while (pos >= vend && v + 1 < p.unit_end) {           // (a unit holds at least one block's four bits)
+        ++v;
+        voff = vend;
+        vend = voff + uo[v].bits;
+      }
+      uint32_t bit = 1;
+      if (pos < p.ibits) {
+        const uint32_t q = (uint32_t)(pos - voff);
+        const JE_G uint8_t* sv = (const JE_G uint8_t*)scratch + units[im->unit0 + v].slot_off;
+        bit = (sv[q >> 3] >> (7u - (q & 7u))) & 1u;
+      }
+      byte = byte << 1 | bit;
+    }
+    ust[j] = (uint8_t)byte;
+    ff += byte == 255u;
+  }
+  for (int o = WAVE / 2; o > 0; o >>= 1) ff += __shfl_xor(ff, o, WAVE);
+  if ((tid & (WAVE - 1)) == 0 && ff) atomicAdd(&s_ff, ff);
+  __syncthreads();
+  if (tid == 0) {
+    JeUnitOut& o = uo[u.index];
+    o.nbytes = p.j1 - p.j0;
+    o.nff = s_ff;
+    o.upos = (uint32_t)(p.upos0 + p.j0);
+  }
+}
+
+// ---- 5. where every unit's stuffed bytes go; the file's length ----------------------------------------------------------------------
+__global__ __launch_bounds__(JE_NT) void jpegenc_scan_bytes_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ unsigned long long s_tmp[JE_NT];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + b;
+  JeUnitOut* uo = reinterpret_cast<JeUnitOut*>(scratch) + im->unit0;
+  unsigned long long carry = 0;
+  for (int base = 0; base < im->nunits; base += JE_NT) {
+    const int s = base + tid;
+    const unsigned long long v = s < im->nunits ? (unsigned long long)uo[s].nbytes + uo[s].nff : 0ull;
+    unsigned long long tot;
+    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
+    if (s < im->nunits) uo[s].fpos = pre + 2ull * (unsigned long long)(s / im->upi);       // an RSTn behind every earlier interval
+    carry += tot;
+  }
+  if (tid == 0)
+    reinterpret_cast<JeImageOut*>(scratch + hdr->off_image_out)[b].file_bytes =
+        (unsigned long long)im->header_len + carry + 2ull * (unsigned long long)(im->nint - 1) + 2ull;
+}
+
+// ---- 6. where every file starts: offsets[B + 1] ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(JE_NT) void jpegenc_scan_files_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
+                                                                   int64_t* __restrict__ offsets) {
+  __shared__ unsigned long long s_tmp[JE_NT];
+  const int tid = threadIdx.x;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JeImageOut* io = reinterpret_cast<const JeImageOut*>(scratch + hdr->off_image_out);
+  unsigned long long carry = 0;
+  for (int base = 0; base < hdr->B; base += JE_NT) {
+    const int b = base + tid;
+    const unsigned long long v = b < hdr->B ? io[b].file_bytes : 0ull;
+    unsigned long long tot;
+    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
+    if (b < hdr->B) offsets[b] = (int64_t)pre;
+    carry += tot;
+  }
+  if (tid == 0) offsets[hdr->B] = (int64_t)carry;
+}
+
+// ---- 7. the files -----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(JE_NT) void jpegenc_write_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
+                                                              uint8_t* __restrict__ out, const int64_t* __restrict__ offsets) {
+  __shared__ uint32_t s_tmp[JE_NT];
+  const int tid = threadIdx.x;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[blockIdx.x];
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  const JeUnitOut o = reinterpret_cast<const JeUnitOut*>(scratch)[blockIdx.x];
+  const int64_t off = offsets[u.image];                      // (jpegenc_scan_files_kernel)
+  JE_G uint8_t* file = (JE_G uint8_t*)out + off;
+  JE_G uint8_t* dst = file + im->header_len + o.fpos;
+  const JE_G uint8_t* ust = (const JE_G uint8_t*)scratch + im->ustream_off + o.upos;
+  const uint32_t n = o.nbytes, per = (n + JE_NT - 1) / JE_NT;
+  const uint32_t lo = min(n, (uint32_t)tid * per), hi = min(n, lo + per);
+  uint32_t ff = 0;
+  for (uint32_t i = lo; i < hi; ++i) ff += ust[i] == 255u;
+  uint32_t tot;
+  uint32_t at = lo + je_excl_sum(ff, s_tmp, tot);
+  for (uint32_t i = lo; i < hi; ++i) {
+    const uint8_t byte = ust[i];
+    dst[at++] = byte;
+    if (byte == 255u) dst[at++] = 0;
+  }
+  if (u.index == 0)
+    for (int i = tid; i < im->header_len; i += JE_NT) file[i] = im->header[i];
+  if (tid == 0 && u.last) {
+    JE_G uint8_t* m = dst + n + o.nff;
+    m[0] = 0xff;
+    m[1] = u.index == im->nunits - 1 ? 0xd9 : (uint8_t)(0xd0 + (u.interval & 7));
+  }
+}
+
+// ---- host: limits, header, bound, plan -----------------------------------------------------------------------------------------------------
+static uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+struct JeGeometry {
+  int hmax, vmax, bpm, mcus_x, interval, nint, upi, nunits;
+  int64_t nmcu;
+};
+// false: outside the limits (what: the reason)
+static bool je_geometry(int H, int W, int C, int quality, int subsampling, int restart_rows, JeGeometry& g, const char*& what) {
+  what = nullptr;
+  if (H < 1 || W < 1) what = "non-positive size";
+  else if (C != 1 && C != 3) what = "channels (1 or 3)";
+  else if (quality < 1 || quality > 100) what = "quality (1 .. 100)";
+  else if (C == 3 && (subsampling < ATTWARP_JPEGENC_444 || subsampling > ATTWARP_JPEGENC_420)) what = "unknown subsampling";
+  else if (restart_rows < 0) what = "negative restart_rows";
+  if (what) return false;
+  if (H > JE_MAX_DIM || W > JE_MAX_DIM) { what = "size above 65500"; return false; }
+  g.hmax = (C == 3 && subsampling != ATTWARP_JPEGENC_444) ? 2 : 1;
+  g.vmax = (C == 3 && subsampling == ATTWARP_JPEGENC_420) ? 2 : 1;
+  g.bpm = C == 3 ? g.hmax * g.vmax + 2 : 1;
+  g.mcus_x = (W + 8 * g.hmax - 1) / (8 * g.hmax);
+  g.nmcu = (int64_t)g.mcus_x * ((H + 8 * g.vmax - 1) / (8 * g.vmax));
+  const int64_t interval = restart_rows ? (int64_t)restart_rows * g.mcus_x : g.nmcu;
+  if (restart_rows && interval > 65535) { what = "restart interval above 65535"; return false; }
+  g.interval = (int)interval;
+  g.nint = (int)((g.nmcu + interval - 1) / interval);
+  g.upi = (int)((interval + JE_UNIT_MCUS - 1) / JE_UNIT_MCUS);
+  const int64_t last = g.nmcu - (int64_t)(g.nint - 1) * interval;
+  g.nunits = (int)((int64_t)(g.nint - 1) * g.upi + (last + JE_UNIT_MCUS - 1) / JE_UNIT_MCUS);
+  return true;
+}
+static int je_header_len(int C, int restart_rows) { return 2 + 18 + (C == 3 ? 2 : 1) * 69 + (10 + 3 * C) + (C == 3 ? 432 : 216) + (restart_rows ? 6 : 0) + (8 + 2 * C); }
+static uint64_t je_bound64(int C, int quality, int restart_rows, const JeGeometry& g) {
+  const uint64_t bits = (uint64_t)g.nmcu * g.bpm * (uint64_t)je_block_bound_bits(quality, C);
+  return (uint64_t)je_header_len(C, restart_rows) + 2u * ((bits + 7u) / 8u + (uint64_t)g.nint) + 2u * (uint64_t)g.nint + 2u;
+}
+
+static int je_write_header(uint8_t* h, const attwarp_jpegenc_image& d, const JeGeometry& g) {
+  int n = 0;
+  auto put = [&](std::initializer_list<int> b) { for (int v : b) h[n++] = (uint8_t)v; };
+  put({0xff, 0xd8, 0xff, 0xe0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00});
+  const int nc = d.C;
+  for (int t = 0; t < (nc == 3 ? 2 : 1); ++t) {
+    put({0xff, 0xdb, 0x00, 0x43, t});
+    for (int k = 0; k < 64; ++k) h[n++] = (uint8_t)je_quant_value(d.quality, t, je_zigzag(k));
+  }
+  put({0xff, 0xc0, 0x00, 8 + 3 * nc, 0x08, d.H >> 8, d.H & 255, d.W >> 8, d.W & 255, nc});
+  for (int c = 0; c < nc; ++c) put({c + 1, c == 0 ? (g.hmax << 4 | g.vmax) : 0x11, c ? 1 : 0});
+  for (int t = 0; t < (nc == 3 ? 4 : 2); ++t) {
+    const int nv = je_nvals(t);
+    put({0xff, 0xc4, (19 + nv) >> 8, (19 + nv) & 255, (t & 1) << 4 | t >> 1});
+    for (int k = 0; k < 16; ++k) h[n++] = JE_BITS[t][k];
+    for (int k = 0; k < nv; ++k) h[n++] = je_vals(t)[k];
+  }
+  if (d.restart_rows) put({0xff, 0xdd, 0x00, 0x04, g.interval >> 8, g.interval & 255});
+  put({0xff, 0xda, 0x00, 6 + 2 * nc, nc});
+  for (int c = 0; c < nc; ++c) put({c + 1, c ? 0x11 : 0x00});
+  put({0x00, 0x3f, 0x00});
+  return n;
+}
+
+}  // namespace attwarp
+
+using namespace attwarp;
+
+extern "C" size_t attwarp_jpegenc_bound(int H, int W, int C, int quality, int subsampling, int restart_rows) {
+  JeGeometry g;
+  const char* what;
+  if (!je_geometry(H, W, C, quality, subsampling, restart_rows, g, what)) return 0;
+  const uint64_t b = je_bound64(C, quality, restart_rows, g);
+  return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
+}
+
+static int jpegenc_count(const attwarp_jpegenc_image* images, int B, int64_t& nunits) {
+  ATTWARP_REQUIRE(images, "jpegenc: null image array");
+  ATTWARP_REQUIRE(B > 0, "jpegenc: non-positive batch size");
+  if (B > (1 << 20)) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: B=%d > 2^20", B);
+  nunits = 0;
+  for (int b = 0; b < B; ++b) {
+    const attwarp_jpegenc_image& d = images[b];
+    ATTWARP_REQUIRE(d.src, "jpegenc: image %d: null pointer", b);
+    ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegenc: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
+    JeGeometry g;
+    const char* what;
+    if (!je_geometry(d.H, d.W, d.C, d.quality, d.subsampling, d.restart_rows, g, what))
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d (%d x %d x %d, quality %d, subsampling %d, restart_rows %d): %s", b, d.H, d.W, d.C,
+                  d.quality, d.subsampling, d.restart_rows, what);
+    ATTWARP_REQUIRE((int64_t)d.pitch >= (int64_t)d.W * d.C, "jpegenc: image %d: pitch %d below the row's %lld bytes", b, d.pitch, (long long)d.W * d.C);
+    if (je_bound64(d.C, d.quality, d.restart_rows, g) >= ((uint64_t)1 << 31))
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: the bound of %d x %d x %d is 2 GiB or more", b, d.H, d.W, d.C);
+    nunits += g.nunits;
+  }
+  if (nunits > JE_MAX_UNITS) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld units in one call (> %d)", (long long)nunits, JE_MAX_UNITS);
+  return ATTWARP_OK;
+}
+
+static uint64_t jpegenc_table_layout(int B, int64_t nunits, uint64_t& off_images, uint64_t& off_units, uint64_t& off_huffman) {
+  off_huffman = align_up(sizeof(attwarp_jpegenc_header), 16);
+  off_images = off_huffman + 4 * 256 * sizeof(uint32_t);
+  off_units = off_images + align_up((uint64_t)B * sizeof(JeImageDev), 16);
+  return off_units + (uint64_t)nunits * sizeof(JeUnit);
+}
+
+extern "C" size_t attwarp_jpegenc_table_bytes(const attwarp_jpegenc_image* images, int B) {
+  int64_t nunits;
+  if (jpegenc_count(images, B, nunits) != ATTWARP_OK) return 0;
+  uint64_t a, b, c;
+  return (size_t)jpegenc_table_layout(B, nunits, a, b, c);
+}
+
+extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, void* table, size_t table_bytes) {
+  int64_t nunits;
+  if (const int rc = jpegenc_count(images, B, nunits)) return rc;
+  ATTWARP_REQUIRE(table, "jpegenc_plan: null table");
+  attwarp_jpegenc_header h;
+  std::memset(&h, 0, sizeof h);
+  const size_t need = (size_t)jpegenc_table_layout(B, nunits, h.off_images, h.off_units, h.off_huffman);
+  ATTWARP_REQUIRE(table_bytes >= need, "jpegenc_plan: table of %zu bytes, %zu needed", table_bytes, need);
+  uint8_t* t = static_cast<uint8_t*>(table);
+  std::memset(t, 0, need);
+  h.magic = JE_MAGIC;
+  h.B = B;
+  h.nunits = (int32_t)nunits;
+  h.table_bytes = need;
+  for (int k = 0; k < 4; ++k) {
+    uint32_t code[256];
+    je_build_huffman(k, code);
+    std::memcpy(t + h.off_huffman + (size_t)k * 1024, code, sizeof code);
+  }
+  JeImageDev* im = reinterpret_cast<JeImageDev*>(t + h.off_images);
+  JeUnit* un = reinterpret_cast<JeUnit*>(t + h.off_units);
+  h.off_image_out = align_up((uint64_t)nunits * sizeof(JeUnitOut), 256);
+  uint64_t soff = h.off_image_out + align_up((uint64_t)B * sizeof(JeImageOut), 256), out_bytes = 0;
+  int32_t s = 0;
+  for (int b = 0; b < B; ++b) {
+    const attwarp_jpegenc_image& d = images[b];
+    JeGeometry g;
+    const char* what;
+    je_geometry(d.H, d.W, d.C, d.quality, d.subsampling, d.restart_rows, g, what);
+    JeImageDev& r = im[b];
+    r.src = d.src; r.H = d.H; r.W = d.W; r.C = d.C; r.pitch = d.pitch;
+    r.swap = d.C == 3 && d.order == ATTWARP_BGR;
+    r.hmax = g.hmax; r.vmax = g.vmax; r.bpm = g.bpm;
+    r.mcus_x = g.mcus_x; r.nmcu = (int32_t)g.nmcu;
+    r.interval = g.interval; r.nint = g.nint; r.upi = g.upi;
+    r.unit0 = s; r.nunits = g.nunits;
+    r.block_bits = je_block_bound_bits(d.quality, d.C);
+    for (int tb = 0; tb < 2; ++tb)
+      for (int k = 0; k < 64; ++k) {
+        r.divisor[tb][k] = (uint16_t)(je_quant_value(d.quality, tb, k) << 3);
+        r.recip[tb][k] = je_recip(r.divisor[tb][k]);
+      }
+    r.header_len = je_write_header(r.header, d, g);
+    const uint64_t nblocks = (uint64_t)g.nmcu * g.bpm;
+    r.coef_off = soff;
+    soff += align_up(nblocks * 128, 256);
+    r.ustream_off = soff;
+    soff += align_up((nblocks * r.block_bits + 7) / 8 + (uint64_t)g.nint + 8, 256);
+    for (int i = 0; i < g.nint; ++i) {
+      const int m0 = i * g.interval, m1 = (int)std::min<int64_t>(g.nmcu, (int64_t)m0 + g.interval);
+      for (int m = m0; m < m1; m += JE_UNIT_MCUS, ++s) {
+        JeUnit& q = un[s];
+        q.image = b;
+        q.mcu0 = m;
+        q.nmcu = std::min(JE_UNIT_MCUS, m1 - m);
+        q.interval = i;
+        q.last = m + JE_UNIT_MCUS >= m1;
+        q.index = s - r.unit0;
+        q.slot_off = soff;
+        soff += align_up(((uint64_t)q.nmcu * g.bpm * r.block_bits + 7) / 8 + 8, 16);
+      }
+    }
+    out_bytes += je_bound64(d.C, d.quality, d.restart_rows, g);
+  }
+  h.scratch_bytes = soff;
+  h.out_bytes = out_bytes;
+  std::memcpy(t, &h, sizeof h);
+  return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegenc_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
+                                      int64_t* offsets, void* stream) {
+  ATTWARP_REQUIRE(table_host && table_dev && scratch && out && offsets, "jpegenc_encode: null pointer");
+  attwarp_jpegenc_header h;
+  std::memcpy(&h, table_host, sizeof h);
+  ATTWARP_REQUIRE(h.magic == JE_MAGIC && h.B > 0 && h.nunits >= h.B && h.nunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan");
+  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegenc_encode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
+  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
+                      reinterpret_cast<uintptr_t>(offsets) % 8 == 0,
+                  "jpegenc_encode: table_dev / offsets must be 8-byte, scratch 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  hipLaunchKernelGGL(jpegenc_transform_kernel, dim3(h.nunits), dim3(JE_TNT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegenc_transform_kernel")) return rc;
+  hipLaunchKernelGGL(jpegenc_entropy_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegenc_entropy_kernel")) return rc;
+  hipLaunchKernelGGL(jpegenc_scan_bits_kernel, dim3(h.B), dim3(JE_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegenc_scan_bits_kernel")) return rc;
+  hipLaunchKernelGGL(jpegenc_gather_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegenc_gather_kernel")) return rc;
+  hipLaunchKernelGGL(jpegenc_scan_bytes_kernel, dim3(h.B), dim3(JE_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegenc_scan_bytes_kernel")) return rc;
+  hipLaunchKernelGGL(jpegenc_scan_files_kernel, dim3(1), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), offsets);
+  if (const int rc = check_launch("jpegenc_scan_files_kernel")) return rc;
+  hipLaunchKernelGGL(jpegenc_write_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), out,
+                     static_cast<const int64_t*>(offsets));
+  return check_launch("jpegenc_write_kernel");
+}

@@ -8,6 +8,7 @@ kernels are stateless.
 """
 from __future__ import annotations
 
+import os
 import sys
 from typing import Optional, Tuple
 
@@ -189,7 +190,9 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
     ``encoder`` (not in the reference): "pillow" (default) downloads every image and writes it with Pillow, as before;
     "hip" keeps the image, the overlay and the warped image on the GPU, encodes the requested files in ONE
     ``png.PngBatch`` (BGR sources swapped while filtering: RGB files, the same decoded pixels) and writes them after the
-    warp -- so an error anywhere leaves no file behind, where the "pillow" route has written the earlier ones."""
+    warp -- so an error anywhere leaves no file behind, where the "pillow" route has written the earlier ones.  Paths that
+    end in ``.jpg`` / ``.jpeg`` (any letter case) go through one ``jpeg.JpegBatch`` with Pillow's defaults instead, as the
+    "pillow" route picks the format from the extension: both encoders then write the same bytes."""
     try:
         from PIL import Image
         if encoder not in ("pillow", "hip"):
@@ -228,8 +231,9 @@ def save_warped_image(image_path, att_map, original_image_save_path, masked_over
 
 def _save_warped_hip(image, att_map, original_image_save_path, masked_overlay_save_path, output_path, width, height,
                      transform, exp_scale, exp_divisor, apply_inverse, attention_alpha, mode):
-    """save_warped_image's body for ``encoder="hip"``: the same steps in the same order on GPU tensors, one PNG batch."""
-    from . import png
+    """save_warped_image's body for ``encoder="hip"``: the same steps in the same order on GPU tensors, one PNG batch and,
+    for the ``.jpg`` / ``.jpeg`` paths, one JPEG batch."""
+    from . import jpeg, png
     if image.dtype != np.uint8:
         raise TypeError(f"encoder='hip' writes 8-bit files: uint8 image expected, got {image.dtype}")
     dev = _lib.default_device()
@@ -246,7 +250,16 @@ def _save_warped_hip(image, att_map, original_image_save_path, masked_overlay_sa
     name = set_transform_function(transform, exp_scale, exp_divisor, apply_inverse)
     paths.append(output_path); orders.append("bgr")
     tensors.append(_warp_on_device(src, att_map, width, height, name, exp_scale, exp_divisor, apply_inverse, mode))
-    png.write_png(paths, tensors, order=orders)
+    is_jpeg = [os.fspath(p).lower().endswith((".jpg", ".jpeg")) for p in paths]
+    files = [None] * len(paths)
+    for kind, encode in ((False, png.encode_png), (True, jpeg.encode_jpeg)):           # every file is encoded before one is written
+        idx = [i for i, j in enumerate(is_jpeg) if j == kind]
+        if idx:
+            for i, f in zip(idx, encode([tensors[i] for i in idx], order=[orders[i] for i in idx])):
+                files[i] = f
+    for p, f in zip(paths, files):
+        with open(p, "wb") as fh:
+            fh.write(f)
     return True
 
 

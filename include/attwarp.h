@@ -1109,6 +1109,45 @@ ATTWARP_API int attwarp_jpegdec_plan_layouts(const attwarp_jpegdec_layout_image*
 ATTWARP_API int attwarp_jpegdec_decode_layouts(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
 
+/* ---- JPEG files of a whole batch of differently sized uint8 images, encoded on the device (jpegenc.hip):
+ * the bytes of Pillow's Image.save(f, "JPEG", quality, subsampling, restart_marker_rows), whole file: baseline sequential,
+ * JFIF APP0, one DQT per table, SOF0, the four Annex K Huffman tables, DRI when restarts are on, one interleaved scan.
+ * C = 1 is one grey component; C = 3 is YCbCr (libjpeg's 16-bit fixed point) with 4:4:4, 4:2:2 or 4:2:0 chroma.  Edges: the
+ * input is replicated to the right and down to a multiple of the vertical factor, the DOWN-SAMPLED rows below that.  The DCT
+ * is jfdctint's, quantisation rounds half away from zero, quality scales the Annex K tables as jpeg_set_quality does.
+ * Seven launches, none with a host-dependent argument (capturable): transform (one thread per block), entropy (one workgroup
+ * per unit of at most ATTWARP_JPEGENC_UNIT_MCUS MCUs, one wave per block), a scan of the units' bit lengths per image, a
+ * shifted gather into the unstuffed stream that counts the FF bytes, a second scan, a scan of the files' lengths into offsets,
+ * and the pass that writes stuffed bytes, RSTn, header and EOI.  Steps 1 - 4 are those of attwarp_png_*.
+ * header.out_bytes is the sum of attwarp_jpegenc_bound over the batch.
+ * Limits (ATTWARP_E_UNSUPPORTED from the planner): H, W <= ATTWARP_JPEGENC_MAX_DIM, a restart interval (restart_rows x MCUs
+ * per row) <= 65535, a file bound below 2^31, B <= 2^20, at most 2^24 units per call. */
+#define ATTWARP_JPEGENC_UNIT_MCUS 16
+#define ATTWARP_JPEGENC_MAX_DIM 65500
+enum { ATTWARP_JPEGENC_444 = 0, ATTWARP_JPEGENC_422 = 1, ATTWARP_JPEGENC_420 = 2 };   /* Pillow's subsampling numbers */
+typedef struct attwarp_jpegenc_image {
+  const uint8_t* src;                              /* device: H rows of W * C bytes, pitch bytes apart, any byte address */
+  int32_t H, W, C;
+  int32_t pitch;
+  int32_t order;                                   /* ATTWARP_RGB / ATTWARP_BGR (ignored for C = 1) */
+  int32_t quality;                                 /* 1 .. 100 */
+  int32_t subsampling;                             /* ATTWARP_JPEGENC_* (ignored for C = 1) */
+  int32_t restart_rows;                            /* MCU rows per restart interval, 0: no restart markers */
+} attwarp_jpegenc_image;
+typedef struct attwarp_jpegenc_header {            /* first bytes of a table written by attwarp_jpegenc_plan */
+  uint32_t magic;
+  int32_t B, nunits, reserved;
+  uint64_t table_bytes, scratch_bytes, out_bytes;
+  uint64_t off_images, off_units, off_huffman;     /* in the table */
+  uint64_t off_image_out;                          /* in the scratch buffer: per image the file's bytes */
+} attwarp_jpegenc_header;
+/* 0: outside the limits */
+ATTWARP_API size_t attwarp_jpegenc_bound(int H, int W, int C, int quality, int subsampling, int restart_rows);
+ATTWARP_API size_t attwarp_jpegenc_table_bytes(const attwarp_jpegenc_image* images, int B);
+ATTWARP_API int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, void* table, size_t table_bytes);
+ATTWARP_API int attwarp_jpegenc_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
+                       int64_t* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
