@@ -181,6 +181,10 @@ SIGNATURES = {
     "attwarp_jpegdec_layouts_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_jpegdec_plan_layouts": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int]),
     "attwarp_jpegdec_decode_layouts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # scans of every layout: progressive files of the layout family's frames, sequential files of several scans (jpegscan_blocks.hpp)
+    "attwarp_jpegdec_layout_scans_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "attwarp_jpegdec_plan_layout_scans": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int]),
+    "attwarp_jpegdec_decode_layout_scans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # JPEG files of a ragged batch written on the device (jpegenc.hip)
     "attwarp_jpegenc_bound": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "attwarp_jpegenc_table_bytes": (c_size_t, [c_void_p, c_int]),
@@ -211,6 +215,7 @@ JPEGDEC_MODE_IDS = {"RGB": 0, "L": 1, "keep": 2}
 JPEGDEC_MAX_UNITS, JPEGDEC_MAX_BLOCKS = 65536, 1 << 24
 JPEGDEC_MAX_SCANS = 64
 JPEGDEC_RECORD_BYTES = 2152                              # one image record of a planned table (JdImage of jpegdec_blocks.hpp)
+JPEGDEC_LAYOUT_RECORD_BYTES = 3000                       # one image record of the layout families' tables (JfImage of jpegfmt_blocks.hpp)
 JPEGDEC_COLOR_IDS = {"grey": 0, "ycc": 1, "rgb": 2, "cmyk": 3, "ycck": 4}   # ATTWARP_JPEGDEC_COLOR_*: the colour rule of a layout image
 JPEGDEC_MAX_SLOTS = 10                                   # blocks per MCU (T.81 B.2.3)
 JPEGDEC_STATUS_NAMES = ("OK", "E_TRUNCATED", "E_HUFFMAN", "E_COEFF", "E_RESTART", "E_NO_EOI")
@@ -304,6 +309,15 @@ class JpegDecScan(ctypes.Structure):
     _fields_ = [("image", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("comp", ctypes.c_int32 * 3), ("ss", ctypes.c_int32),
                 ("se", ctypes.c_int32), ("ah", ctypes.c_int32), ("al", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
                 ("stream_off", ctypes.c_uint64), ("counts", ctypes.c_uint8 * 16 * 3), ("symbols", ctypes.c_uint8 * 256 * 3)]
+
+
+class JpegDecLayoutScan(ctypes.Structure):
+    """attwarp_jpegdec_layout_scan: one scan of a file of an attwarp_jpegdec_plan_layout_scans call."""
+    _fields_ = [("image", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("comp", ctypes.c_int32 * 4), ("ss", ctypes.c_int32),
+                ("se", ctypes.c_int32), ("ah", ctypes.c_int32), ("al", ctypes.c_int32), ("sequential", ctypes.c_int32),
+                ("restart_interval", ctypes.c_int32), ("stream_off", ctypes.c_uint64),
+                ("dc_counts", ctypes.c_uint8 * 16 * 4), ("ac_counts", ctypes.c_uint8 * 16 * 4),
+                ("dc_symbols", ctypes.c_uint8 * 256 * 4), ("ac_symbols", ctypes.c_uint8 * 256 * 4)]
 
 
 class JpegDecHeader(ctypes.Structure):

@@ -25,6 +25,10 @@
 //   jpegprog_scan_kernel    one workgroup per SCAN: the restart-marker rule above (jd_scan_units) for the scan's own data;
 //   jpegprog_entropy_kernel one launch per dependency level of the scans, one wave per (scan, unit): the four block routines
 //                           of jpegprog_blocks.hpp; a wave stores only the int16s of its band Ss..Se (the band rule).
+// Progressive files of every other layout and sequential files of several scans (attwarp_jpegdec_plan_layout_scans /
+// attwarp_jpegdec_decode_layout_scans) are the cross term: JfImage frames, JsScan records (jpegscan_blocks.hpp),
+// jpegscan_clear_kernel, jpegscan_marks_kernel, one jpegscan_entropy_kernel launch per level over the general MCU with a
+// fifth, sequential kind of block, then jpegfmt_idct_kernel and jpegfmt_color_kernel unchanged.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -32,11 +36,13 @@
 
 #include "jpegfmt_blocks.hpp"
 #include "jpegprog_blocks.hpp"
+#include "jpegscan_blocks.hpp"
 
 namespace attwarp {
 
 #define JD_G __attribute__((address_space(1)))
 constexpr uint32_t JD_MAGIC = 0x4745504au, JD_MAGIC_LAYOUTS = 0x4745504cu;   // (the second: attwarp_jpegdec_plan_layouts)
+constexpr uint32_t JD_MAGIC_LAYOUT_SCANS = 0x4745504du;                      // (attwarp_jpegdec_plan_layout_scans)
 constexpr int JD_NT = 256;
 constexpr int JD_MAX_B = 1 << 20, JD_MAX_TOTAL_UNITS = 1 << 30;
 constexpr int JD_RING = 2048, JD_CHUNK = WAVE * 4;        // bytes of the entropy kernel's ring / loaded per step
@@ -511,12 +517,12 @@ __host__ __device__ inline uint64_t jp_header_off(int B) {
   return jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JdImage) + (uint64_t)B * sizeof(JdSub);
 }
 
-// The coefficient memory of every image zeroed (the scans only refine it) and the per-image states opened.
-__global__ __launch_bounds__(JD_NT) void jpegprog_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
-  const JdView v(table, scratch);
-  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
-  uint4* d = reinterpret_cast<uint4*>(scratch + ph->clear_off);
-  const uint64_t n = ph->clear_bytes / 16u;
+// The coefficient memory of every image zeroed (the scans only refine it) and the per-image states opened: the clear launch of
+// both scan families (JdImage records with a JpHeader, JfImage records with a JsHeader).
+template <class Image>
+__device__ __forceinline__ void jp_clear_body(const JdViewOf<Image>& v, uint8_t* scratch, uint64_t clear_off, uint64_t clear_bytes) {
+  uint4* d = reinterpret_cast<uint4*>(scratch + clear_off);
+  const uint64_t n = clear_bytes / 16u;
   for (uint64_t i = (uint64_t)blockIdx.x * JD_NT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * JD_NT) d[i] = make_uint4(0, 0, 0, 0);
   for (int b = (int)(blockIdx.x * JD_NT + threadIdx.x); b < v.hdr->B; b += (int)(gridDim.x * JD_NT)) {
     JdState st;
@@ -528,20 +534,24 @@ __global__ __launch_bounds__(JD_NT) void jpegprog_clear_kernel(const uint8_t* __
   }
 }
 
-// grid: one workgroup per SCAN; the rule of jpegdec_scan_kernel for the scan's own data and units.
-__global__ __launch_bounds__(JD_NT) void jpegprog_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
-                                                              uint8_t* __restrict__ scratch) {
-  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
+__global__ __launch_bounds__(JD_NT) void jpegprog_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   const JdView v(table, scratch);
   const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
-  const JpScan* sc = reinterpret_cast<const JpScan*>(table + ph->off_scans) + blockIdx.x;
+  jp_clear_body(v, scratch, ph->clear_off, ph->clear_bytes);
+}
+
+// The restart-marker rule of jpegdec_scan_kernel for one SCAN's own data and units, by one workgroup: the restart launch of
+// both scan families (sc: a JpScan or a JsScan; starts: uint32 starts[total_units], ends[total_units] of the call).
+template <class Image, class Scan>
+__device__ __forceinline__ void jp_marks_body(const JdViewOf<Image>& v, const Scan* sc, const uint8_t* stream, uint32_t* all_starts,
+                                              int32_t total_units, uint32_t* s_tmp, uint32_t& s_term, uint32_t& s_bad) {
   if (sc->image >= (uint32_t)v.hdr->B) return;
-  const JdImage* im = v.images + sc->image;
+  const Image* im = v.images + sc->image;
   const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len;
   const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off + off;
   const uint32_t n = im->stream_len - off, nunits = sc->nunits;
-  uint32_t* starts = reinterpret_cast<uint32_t*>(scratch + ph->starts_off) + sc->unit0;
-  uint32_t* ends = starts + ph->total_units;
+  uint32_t* starts = all_starts + sc->unit0;
+  uint32_t* ends = starts + total_units;
   uint32_t running, term;
   jd_scan_units(s, n, nunits, starts, ends, s_tmp, s_term, s_bad, running, term);
   if (threadIdx.x == 0) {
@@ -555,6 +565,16 @@ __global__ __launch_bounds__(JD_NT) void jpegprog_scan_kernel(const uint8_t* __r
       st->eoi = q > term && q < n && s[q] == 0xd9u;
     }
   }
+}
+
+// grid: one workgroup per SCAN.
+__global__ __launch_bounds__(JD_NT) void jpegprog_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                              uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
+  const JdView v(table, scratch);
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  jp_marks_body(v, reinterpret_cast<const JpScan*>(table + ph->off_scans) + blockIdx.x, stream,
+                reinterpret_cast<uint32_t*>(scratch + ph->starts_off), ph->total_units, s_tmp, s_term, s_bad);
 }
 
 // grid: one wave per (scan, unit) of the launch's level.  The band rule: a wave may LOAD a block's whole row for its
@@ -828,7 +848,7 @@ extern "C" uint64_t attwarp_jpegdec_info_offset(const void* table_host) {
   if (!table_host) return 0;
   attwarp_jpegdec_header h;
   std::memcpy(&h, table_host, sizeof h);
-  if ((h.magic != JD_MAGIC && h.magic != JD_MAGIC_LAYOUTS) || h.B <= 0 || h.B > JD_MAX_B) return 0;
+  if ((h.magic != JD_MAGIC && h.magic != JD_MAGIC_LAYOUTS && h.magic != JD_MAGIC_LAYOUT_SCANS) || h.B <= 0 || h.B > JD_MAX_B) return 0;
   JdSub s;
   const size_t record = h.magic == JD_MAGIC ? sizeof(JdImage) : sizeof(JfImage);
   std::memcpy(&s, static_cast<const uint8_t*>(table_host) + h.off_images + (uint64_t)h.B * record, sizeof s);
@@ -1470,6 +1490,356 @@ extern "C" int attwarp_jpegdec_decode_layouts(const void* table_host, const void
   if (const int rc = check_launch("jpegfmt_substream_kernel")) return rc;
   hipLaunchKernelGGL(jpegfmt_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegfmt_entropy_kernel")) return rc;
+  hipLaunchKernelGGL(jpegfmt_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegfmt_idct_kernel")) return rc;
+  hipLaunchKernelGGL(jpegfmt_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
+  return check_launch("jpegfmt_color_kernel");
+}
+
+// ---- scans of every layout (attwarp_jpegdec_plan_layout_scans / attwarp_jpegdec_decode_layout_scans): a table of
+// attwarp_jpegdec_plan_layouts for B one-unit images (all the IDCT and colour kernels read; its magic replaced, so that
+// attwarp_jpegdec_decode_layouts refuses it) with a JsHeader and the JsScan records behind it, sorted by (level, image, position) ---
+namespace attwarp {
+
+constexpr uint32_t JS_MAGIC = JD_MAGIC_LAYOUT_SCANS, JS_MAGIC_SCANS = 0x4745504eu;   // of the table's first header / of the JsHeader
+struct JsHeader {
+  uint32_t magic;
+  int32_t nscans, nlevels, total_units;
+  uint64_t off_scans;                  // JsScan[nscans] in the table
+  uint64_t starts_off;                 // uint32 starts[total_units], ends[total_units] in the scratch buffer
+  uint64_t clear_off, clear_bytes;     // every image's coefficients and planes in the scratch buffer, multiples of 16
+  int32_t level_scan0[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // the first record of each level
+  int32_t level_waves[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // waves of each level's launch
+  int32_t level_tables[ATTWARP_JPEGDEC_MAX_SCANS + 1];  // code tables the scans of each level hold in LDS at most (1 .. 8)
+};
+static_assert(sizeof(JsHeader) % 8 == 0, "record layout");
+__host__ __device__ inline uint64_t js_header_off(int B) {
+  return jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JfImage) + (uint64_t)B * sizeof(JdSub);
+}
+
+__global__ __launch_bounds__(JD_NT) void jpegscan_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  const JfView v(table, scratch);
+  const JsHeader* sh = reinterpret_cast<const JsHeader*>(table + js_header_off(v.hdr->B));
+  jp_clear_body(v, scratch, sh->clear_off, sh->clear_bytes);
+}
+
+// grid: one workgroup per SCAN.
+__global__ __launch_bounds__(JD_NT) void jpegscan_marks_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                               uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
+  const JfView v(table, scratch);
+  const JsHeader* sh = reinterpret_cast<const JsHeader*>(table + js_header_off(v.hdr->B));
+  jp_marks_body(v, reinterpret_cast<const JsScan*>(table + sh->off_scans) + blockIdx.x, stream,
+                reinterpret_cast<uint32_t*>(scratch + sh->starts_off), sh->total_units, s_tmp, s_term, s_bad);
+}
+
+// grid: one wave per (scan, unit) of the launch's level: jpegprog_entropy_kernel over the general MCU (up to ten slots, four
+// predictors) with a fifth kind of block, the sequential one, whose scan names a DC and an AC table per component (eight
+// tables in LDS at most).  The band rule holds: only zigzag positions Ss..Se are stored (DC: position 0), which is the whole
+// row for a sequential scan, and such a scan never shares a block with another scan of its level: every component of a
+// sequential file is sent once.  The code tables live in dynamic LDS, ntab of them (the most a scan of this level names:
+// 1 for AC scans, up to 4 for a DC first pass, up to 8 for a sequential scan), so that a level of AC scans keeps 8 waves
+// per SIMD; a scan that names more than the launch holds is not decoded (the planner never writes such a level).
+__global__ __launch_bounds__(WAVE) void jpegscan_entropy_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                                uint8_t* scratch, int level, int ntab) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ uint32_t s_ring[JD_RING / 4];
+  __shared__ int16_t s_blk[64];
+  __shared__ int32_t s_pred[JF_MAX_COMP];
+  __shared__ uint8_t s_zz[64], s_slot_t[16];
+  __shared__ uint32_t s_pos, s_err, s_run;
+  const int lane = threadIdx.x, w = blockIdx.x;
+  const JfView v(table, scratch);
+  const JsHeader* sh = reinterpret_cast<const JsHeader*>(table + js_header_off(v.hdr->B));
+  const JsScan* scans = reinterpret_cast<const JsScan*>(table + sh->off_scans);
+  if (level < 0 || level >= ATTWARP_JPEGDEC_MAX_SCANS) return;
+  int lo = sh->level_scan0[level], hi = sh->level_scan0[level + 1] - 1;
+  if (hi < lo || lo < 0 || hi >= sh->nscans) return;
+  for (int it = 0; it < 32 && lo < hi; ++it) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (scans[mid].wave0 <= (uint32_t)w) lo = mid;
+    else hi = mid - 1;
+  }
+  const JsScan* sc = scans + lo;
+  if (sc->image >= (uint32_t)v.hdr->B) return;
+  const JfImage* im = v.images + sc->image;
+  JdState* state = v.states + sc->image;
+  if (state->st_scan != 0) return;                           // (uniform) some scan's limits were never written
+  const uint32_t k = (uint32_t)w - sc->wave0;
+  if (k >= sc->nunits) return;
+  const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len, n = im->stream_len - off;
+  const uint32_t* pstarts = reinterpret_cast<const uint32_t*>(scratch + sh->starts_off) + sc->unit0;
+  uint32_t start = pstarts[k], end = pstarts[sh->total_units + k];
+  if (end > n) end = n;
+  if (start > end) start = end;
+  const uint32_t kind = sc->kind <= JS_SEQUENTIAL ? sc->kind : JS_SEQUENTIAL;
+  const uint32_t ss = sc->ss < 63u ? sc->ss : 63u, se = sc->se < 63u ? sc->se : 63u, al = sc->al < 15u ? sc->al : 15u;
+  const int nc = (int)(sc->ncomp >= 1u && sc->ncomp <= (uint32_t)JF_MAX_COMP ? sc->ncomp : 1u);
+  const int ndc = kind == JS_SEQUENTIAL || kind == JP_DC_FIRST ? nc : 0;                  // (uniform: the scan's)
+  const int nac = kind == JS_SEQUENTIAL ? nc : kind >= JP_AC_FIRST ? 1 : 0;
+  if (ndc + nac > ntab) return;                              // (uniform)
+  JdHuff* s_dc = reinterpret_cast<JdHuff*>(s_dyn);
+  JdHuff* s_ac = s_dc + ndc;
+  for (int c = 0; c < ndc; ++c) {
+    if (lane == 0) jd_huff_ranges(s_dc[c], sc->dc_counts[c]);
+    jd_huff_clear(s_dc[c], sc->dc_symbols[c], jd_nsym(sc->dc_counts[c]), lane, WAVE);
+  }
+  for (int c = 0; c < nac; ++c) {
+    if (lane == 0) jd_huff_ranges(s_ac[c], sc->ac_counts[c]);
+    jd_huff_clear(s_ac[c], sc->ac_symbols[c], jd_nsym(sc->ac_counts[c]), lane, WAVE);
+  }
+  s_zz[lane] = JD_ZIGZAG[lane];
+  if (lane < 16) s_slot_t[lane] = lane < 12 && (int)(sc->slot_t[lane] & 3u) < nc ? (sc->slot_t[lane] & 3u) : 0u;   // (below the tables built)
+  if (lane == 0) { s_pos = start; s_err = 0; s_run = 0; }
+  if (lane < JF_MAX_COMP) s_pred[lane] = 0;
+  __syncthreads();
+  for (int c = 0; c < ndc; ++c) jd_huff_fill(s_dc[c], sc->dc_counts[c], lane, WAVE);
+  for (int c = 0; c < nac; ++c) jd_huff_fill(s_ac[c], sc->ac_counts[c], lane, WAVE);
+  const JD_G uint8_t* s = (const JD_G uint8_t*)stream + im->stream_off + off;
+  JD_G int16_t* coef = (JD_G int16_t*)(scratch + im->coef_off);
+  const uint32_t nslot = js_nslot(*sc), nblocks = im->nblocks;
+  const uint32_t nmcu = sc->nmcu, ri = sc->ri;
+  const uint32_t m0 = k * ri, m1 = m0 + ri < nmcu ? m0 + ri : nmcu;
+  const uint32_t iend = m1 * nslot;
+  const bool dc = kind <= JP_DC_REFINE, seq = kind == JS_SEQUENTIAL;
+  JdBits br;
+  br.init(reinterpret_cast<const uint8_t*>(s_ring), JD_RING - 1, start, end);
+  uint32_t loaded = start & ~3u, err = 0, eobrun = 0;
+  for (uint32_t i = m0 * nslot; i < iend;) {
+    const uint32_t m = i / nslot, j = i - m * nslot;
+    const uint32_t bi = js_block_index(*im, *sc, m, j);
+    __syncthreads();                                         // s_pos of the block before; the tables the first time
+    jd_ring_fill(s_ring, s, loaded, s_pos & ~3u, end, lane);  // (the ring's bound is per block: jpegdec_entropy_kernel's holds for all five kinds)
+    int16_t have = 0;
+    if (bi < nblocks && (kind == JP_AC_REFINE || (kind == JP_DC_REFINE && lane == 0))) have = coef[(size_t)bi * 64u + lane];
+    s_blk[lane] = have;
+    __syncthreads();
+    if (lane == 0) {
+      br.end = loaded < end ? loaded : end;
+      const uint32_t st = js_decode_block(br, kind, s_dc, s_ac, s_slot_t[j & 15u], s_pred, ss, se, al, eobrun, s_blk, s_zz);
+      s_pos = br.pos;
+      s_run = eobrun;
+      if (st) s_err = st;
+    }
+    __syncthreads();
+    err = s_err;
+    if (err) break;                                          // (uniform)
+    if (bi < nblocks) {
+      if (seq) coef[(size_t)bi * 64u + lane] = s_blk[lane];
+      else if (dc ? lane == 0 : ((uint32_t)lane >= ss && (uint32_t)lane <= se)) {
+        const uint32_t at = s_zz[lane] & 63u;
+        coef[(size_t)bi * 64u + at] = s_blk[at];
+      }
+    }
+    eobrun = s_run;
+    uint32_t adv = 1;
+    if (kind == JP_AC_FIRST && eobrun > 0) {                 // the blocks of the run are skipped without touching memory
+      const uint32_t skip = eobrun < iend - i - 1u ? eobrun : iend - i - 1u;
+      adv += skip;
+      eobrun -= skip;                                        // (what is left at the unit's end is dropped with the unit)
+    }
+    i += adv;
+  }
+  if (err && lane == 0) atomicMin(&state->fail, sc->index << 24 | k << 8 | err);
+}
+
+}  // namespace attwarp
+
+static size_t jpegscan_bytes(int B, int nscans) { return (size_t)(js_header_off(B) + sizeof(JsHeader) + (uint64_t)nscans * sizeof(JsScan)); }
+
+extern "C" size_t attwarp_jpegdec_layout_scans_table_bytes(const attwarp_jpegdec_layout_image* images, int B, int nscans) {
+  if (!images || B <= 0 || B > JD_MAX_B || nscans < B || (int64_t)nscans > (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS) {
+    fail(ATTWARP_E_ARG, "jpegdec_layout_scans_table_bytes: B=%d, %d scans outside the limits", B, nscans);
+    return 0;
+  }
+  return jpegscan_bytes(B, nscans);
+}
+
+extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_image* images, int B, const attwarp_jpegdec_layout_scan* scans,
+                                                 int nscans, void* table, size_t table_bytes, int by_level) {
+  ATTWARP_REQUIRE(images && scans && table, "jpegdec_plan_layout_scans: null pointer");
+  ATTWARP_REQUIRE(B > 0 && B <= JD_MAX_B && nscans >= B && (int64_t)nscans <= (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS,
+                  "jpegdec_plan_layout_scans: B=%d, %d scans outside the limits", B, nscans);
+  const size_t need = jpegscan_bytes(B, nscans);
+  ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan_layout_scans: table of %zu bytes, %zu needed", table_bytes, need);
+  for (int b = 0; b < B; ++b)
+    ATTWARP_REQUIRE(images[b].restart_interval == 0, "jpegdec_plan_layout_scans: image %d: the restart interval belongs to the scans", b);
+  // everything is checked before anything is written: the scans come image by image, in file order
+  std::vector<JsScan> rec((size_t)nscans);
+  std::vector<int> count(B, 0);
+  std::vector<int64_t> per(B, 0);
+  std::vector<JfImage> frame(1);
+  int64_t total_units = 0;
+  int nlevels = 0, prev = -1;
+  for (int i = 0, first = 0; i < nscans; ++i) {
+    const attwarp_jpegdec_layout_scan& d = scans[i];
+    ATTWARP_REQUIRE(d.image >= 0 && d.image < B && d.image >= prev, "jpegdec_plan_layout_scans: scan %d: image %d out of order", i, d.image);
+    const attwarp_jpegdec_layout_image& img = images[d.image];
+    if (d.image != prev) {
+      first = i; prev = d.image;
+      if (const int rc = jpegfmt_geom(img, d.image, frame[0])) return rc;
+    }
+    const JfImage& f = frame[0];
+    const int index = i - first;
+    if (index >= ATTWARP_JPEGDEC_MAX_SCANS)
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: more than %d scans", d.image, ATTWARP_JPEGDEC_MAX_SCANS);
+    ++count[d.image];
+    ATTWARP_REQUIRE(d.ncomp >= 1 && d.ncomp <= img.ncomp && d.ncomp <= JF_MAX_COMP, "jpegdec: image %d scan %d: %d components", d.image, index, d.ncomp);
+    for (int c = 0; c < d.ncomp; ++c)
+      ATTWARP_REQUIRE(d.comp[c] >= 0 && d.comp[c] < img.ncomp && (c == 0 || d.comp[c] > d.comp[c - 1]),
+                      "jpegdec: image %d scan %d: components not in frame order", d.image, index);
+    if (d.sequential)
+      ATTWARP_REQUIRE(d.ss == 0 && d.se == 63 && d.ah == 0 && d.al == 0, "jpegdec: image %d scan %d: a sequential scan with Ss=%d Se=%d Ah=%d Al=%d",
+                      d.image, index, d.ss, d.se, d.ah, d.al);
+    else
+      ATTWARP_REQUIRE(d.ss >= 0 && d.ss <= d.se && d.se <= 63 && (d.ss != 0 || d.se == 0) && (d.ss == 0 || d.ncomp == 1) && d.al >= 0 &&
+                          d.al <= 13 && d.ah >= 0 && d.ah <= 14 && (d.ah == 0 || d.al == d.ah - 1),
+                      "jpegdec: image %d scan %d: bad progression Ss=%d Se=%d Ah=%d Al=%d in a scan of %d component(s)", d.image, index, d.ss,
+                      d.se, d.ah, d.al, d.ncomp);
+    ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d scan %d: restart interval %d", d.image, index,
+                    d.restart_interval);
+    ATTWARP_REQUIRE(d.stream_off <= img.stream_len, "jpegdec: image %d scan %d: data outside the image's", d.image, index);
+    JsScan& r = rec[(size_t)i];
+    std::memset(&r, 0, sizeof r);
+    r.image = (uint32_t)d.image; r.index = (uint32_t)index; r.off = (uint32_t)d.stream_off;
+    r.kind = d.sequential ? JS_SEQUENTIAL : (uint32_t)((d.ss ? 2 : 0) + (d.ah ? 1 : 0));
+    r.ss = (uint32_t)d.ss; r.se = (uint32_t)d.se; r.al = (uint32_t)d.al;
+    r.ncomp = (uint32_t)d.ncomp;
+    const int ndc = r.kind == JS_SEQUENTIAL || r.kind == JP_DC_FIRST ? d.ncomp : 0;
+    const int nac = r.kind == JS_SEQUENTIAL ? d.ncomp : r.kind >= JP_AC_FIRST ? 1 : 0;
+    for (int t = 0; t < ndc + nac; ++t) {
+      const bool isdc = t < ndc;
+      const int e = isdc ? t : t - ndc;
+      char what[48];
+      const char* fault = isdc ? jd_huffman_fault(d.dc_counts[e], d.dc_symbols[e], true, what) : jd_huffman_fault(d.ac_counts[e], d.ac_symbols[e], false, what);
+      ATTWARP_REQUIRE(!fault, "jpegdec: image %d scan %d: %s", d.image, index, fault);
+      std::memcpy(isdc ? r.dc_counts[e] : r.ac_counts[e], isdc ? d.dc_counts[e] : d.ac_counts[e], 16);
+      std::memcpy(isdc ? r.dc_symbols[e] : r.ac_symbols[e], isdc ? d.dc_symbols[e] : d.ac_symbols[e], 256);
+    }
+    if (d.ncomp == 1) {                                        // not interleaved: the blocks that cover the component's true size
+      const JfComp& k = f.comp[d.comp[0]];
+      r.nslot = 1;
+      r.mcux = (uint32_t)((k.dw + 7) / 8);
+      r.nmcu = r.mcux * (uint32_t)((k.dh + 7) / 8);
+      r.slot_c[0] = (uint8_t)d.comp[0];
+    } else {                                                   // the frame's MCUs, also for a subset of its components
+      r.mcux = (uint32_t)f.mcux;
+      r.nmcu = (uint32_t)f.mcux * (uint32_t)f.mcuy;
+      for (int t = 0; t < d.ncomp; ++t) {
+        const JfComp& k = f.comp[d.comp[t]];
+        for (int y = 0; y < k.v; ++y)
+          for (int x = 0; x < k.h; ++x) {
+            ATTWARP_REQUIRE(r.nslot < (uint32_t)JF_MAX_SLOTS, "jpegdec: image %d scan %d: more than %d blocks per MCU", d.image, index, JF_MAX_SLOTS);
+            r.slot_c[r.nslot] = (uint8_t)d.comp[t]; r.slot_y[r.nslot] = (uint8_t)y; r.slot_x[r.nslot] = (uint8_t)x; r.slot_t[r.nslot] = (uint8_t)t;
+            ++r.nslot;
+          }
+      }
+    }
+    r.ri = d.restart_interval ? (uint32_t)d.restart_interval : r.nmcu;
+    r.nunits = (r.nmcu + r.ri - 1) / r.ri;
+    // the level: behind every earlier scan of the image that shares a component and overlaps the band
+    uint32_t level = by_level ? 0u : (uint32_t)index;
+    if (by_level)
+      for (int j = first; j < i; ++j) {
+        const attwarp_jpegdec_layout_scan& e = scans[j];
+        bool share = false;
+        for (int a = 0; a < d.ncomp; ++a)
+          for (int bb = 0; bb < e.ncomp; ++bb) share = share || d.comp[a] == e.comp[bb];
+        if (share && e.ss <= d.se && d.ss <= e.se) level = std::max(level, rec[(size_t)j].level + 1u);
+      }
+    r.level = level;
+    nlevels = std::max(nlevels, (int)level + 1);
+    total_units += r.nunits;
+    per[d.image] += r.nunits;
+  }
+  for (int b = 0; b < B; ++b) {
+    ATTWARP_REQUIRE(count[b] >= 1, "jpegdec_plan_layout_scans: image %d has no scan", b);
+    if (per[b] > ATTWARP_JPEGDEC_MAX_UNITS)
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld units over its scans (> %d)", b, (long long)per[b], ATTWARP_JPEGDEC_MAX_UNITS);
+  }
+  if (total_units > JD_MAX_TOTAL_UNITS) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units in one call (> 2^30)", (long long)total_units);
+  if (const int rc = attwarp_jpegdec_plan_layouts(images, B, table, table_bytes, 0, 0)) return rc;
+  uint8_t* t = static_cast<uint8_t*>(table);
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, t, sizeof h);
+  JsHeader sh;
+  std::memset(&sh, 0, sizeof sh);
+  sh.magic = JS_MAGIC_SCANS;
+  sh.nscans = nscans; sh.nlevels = nlevels; sh.total_units = (int32_t)total_units;
+  sh.off_scans = js_header_off(B) + sizeof(JsHeader);
+  const JdSub* sub = reinterpret_cast<const JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JfImage));
+  sh.clear_off = jd_data_base(B, h.total_units);
+  sh.clear_bytes = sub[0].info_off - sh.clear_off;             // (both are multiples of 256)
+  sh.starts_off = jd_align(h.scratch_bytes, 256);
+  h.scratch_bytes = sh.starts_off + jd_align((uint64_t)total_units * 8u, 256);
+  h.table_bytes = need;
+  h.magic = JS_MAGIC;
+  JsScan* out = reinterpret_cast<JsScan*>(t + sh.off_scans);
+  uint32_t unit0 = 0;
+  for (int i = 0; i < nscans; ++i) {
+    rec[(size_t)i].unit0 = unit0;
+    unit0 += rec[(size_t)i].nunits;
+    rec[(size_t)i].last = i + 1 == nscans || scans[i + 1].image != scans[i].image;
+  }
+  int at = 0;
+  for (int l = 0; l < nlevels; ++l) {                          // records sorted by (level, image, position): a stable pass per level
+    sh.level_scan0[l] = at;
+    uint32_t wave = 0;
+    for (int i = 0; i < nscans; ++i)
+      if ((int)rec[(size_t)i].level == l) {
+        rec[(size_t)i].wave0 = wave;
+        wave += rec[(size_t)i].nunits;
+        std::memcpy(out + at++, &rec[(size_t)i], sizeof(JsScan));
+      }
+    sh.level_waves[l] = (int32_t)wave;
+    sh.level_tables[l] = 1;
+    for (int i = 0; i < nscans; ++i)
+      if ((int)rec[(size_t)i].level == l) {
+        const JsScan& r = rec[(size_t)i];
+        const int n = r.kind == JS_SEQUENTIAL ? 2 * (int)r.ncomp : r.kind == JP_DC_FIRST ? (int)r.ncomp : r.kind == JP_DC_REFINE ? 0 : 1;
+        sh.level_tables[l] = std::max(sh.level_tables[l], n);
+      }
+  }
+  sh.level_scan0[nlevels] = at;
+  std::memcpy(t + js_header_off(B), &sh, sizeof sh);
+  std::memcpy(t, &h, sizeof h);
+  return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegdec_decode_layout_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                                   uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  const char* who = "jpegdec_decode_layout_scans";
+  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "%s: null pointer", who);
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, table_host, sizeof h);
+  bool ok = h.magic == JS_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS &&
+            h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS && h.total_units == h.B && h.reserved == 0 &&
+            h.table_bytes >= js_header_off(h.B) + sizeof(JsHeader);
+  JsHeader sh;
+  if (ok) {
+    std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + js_header_off(h.B), sizeof sh);
+    ok = sh.magic == JS_MAGIC_SCANS && sh.nscans >= h.B && sh.nlevels >= 1 && sh.nlevels <= ATTWARP_JPEGDEC_MAX_SCANS &&
+         sh.total_units >= sh.nscans && sh.total_units <= JD_MAX_TOTAL_UNITS;
+    for (int l = 0; ok && l < sh.nlevels; ++l) ok = sh.level_waves[l] >= 1 && sh.level_tables[l] >= 1 && sh.level_tables[l] <= 2 * JF_MAX_COMP;
+  }
+  ATTWARP_REQUIRE(ok, "%s: not a table of attwarp_jpegdec_plan_layout_scans", who);
+  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "%s: out of %zu bytes, %llu needed", who, out_bytes, (unsigned long long)h.out_bytes);
+  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
+                      reinterpret_cast<uintptr_t>(status) % 4 == 0,
+                  "%s: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned", who);
+  hipStream_t st = as_stream(stream);
+  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  const uint64_t clear_groups = std::min<uint64_t>(std::max<uint64_t>((sh.clear_bytes / 16u + JD_NT - 1) / JD_NT, (uint64_t)(h.B + JD_NT - 1) / JD_NT), 4096);
+  hipLaunchKernelGGL(jpegscan_clear_kernel, dim3((unsigned)clear_groups), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegscan_clear_kernel")) return rc;
+  hipLaunchKernelGGL(jpegscan_marks_kernel, dim3(sh.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch("jpegscan_marks_kernel")) return rc;
+  for (int l = 0; l < sh.nlevels; ++l) {
+    hipLaunchKernelGGL(jpegscan_entropy_kernel, dim3(sh.level_waves[l]), dim3(WAVE), (size_t)sh.level_tables[l] * sizeof(JdHuff), st, td,
+                       stream_bytes, sc, l, sh.level_tables[l]);
+    if (const int rc = check_launch("jpegscan_entropy_kernel")) return rc;
+  }
   hipLaunchKernelGGL(jpegfmt_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
   if (const int rc = check_launch("jpegfmt_idct_kernel")) return rc;
   hipLaunchKernelGGL(jpegfmt_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);

@@ -46,7 +46,7 @@ struct JfImage {                       // the per-image record of a table of att
   uint8_t dc_counts[JF_MAX_COMP][16], ac_counts[JF_MAX_COMP][16];
   uint8_t dc_symbols[JF_MAX_COMP][256], ac_symbols[JF_MAX_COMP][256];
 };
-static_assert(sizeof(JfImage) % 8 == 0, "record layout");
+static_assert(sizeof(JfImage) == 3000, "record layout (JPEGDEC_LAYOUT_RECORD_BYTES of _lib.py)");
 
 struct JfSegState {                    // per segment (scratch): JdSegState with four predictors
   JdSync entry;

@@ -7,6 +7,9 @@ launch per dependency level of the scans; baseline and progress
 With ``all_layouts=True`` (off by default) a sequential file may also have four components (Adobe CMYK / YCCK), be RGB-coded,
 or sample every component by factors of its own (4:4:0, 4:1:1, 4:1:0, a factor of 3, luma coarser than chroma ...): such files
 go through a second family of records and kernels, alone or in a list with the others.
+With ``all_scans=True`` (off by default; implies both) also the two cross terms they refuse: progressive files of those layouts
+and sequential files whose components come in several scans, through a fourth family of scan records over the layout
+family's image records.  It is the one switch for a folder somebody else made.
 
 Encoding (csrc/jpegenc.hip): what the reference writes with ``img.save(f"{image_id}.jpg")`` (main.py:163-167)
 and ``cv2.imwrite(output_path, warped)`` for a ``.jpg`` path (new_method.py:491): baseline JPEG files of a whole ragged
@@ -64,6 +67,18 @@ def scan_geometry(p: dict, comps) -> tuple:
         return -(-cw // 8), -(-cw // 8) * -(-ch // 8)
     mcux = -(-p["W"] // (8 * hs))
     return mcux, mcux * -(-p["H"] // (8 * vs))
+
+
+def layout_scan_geometry(W: int, H: int, samp, comps) -> tuple:
+    """:func:`scan_geometry` for a frame of any layout (``samp``: [(h, v)] per component): a scan of several components
+    walks the FRAME's MCUs, also when it holds a subset of the components."""
+    hmax, vmax = max(h for h, _ in samp), max(v for _, v in samp)
+    if len(comps) == 1:
+        h, v = samp[comps[0]]
+        cw, ch = -(-W * h // hmax), -(-H * v // vmax)
+        return -(-cw // 8), -(-cw // 8) * -(-ch // 8)
+    mcux = -(-W // (8 * hmax))
+    return mcux, mcux * -(-H // (8 * vmax))
 
 
 def scan_levels(scans) -> List[int]:
@@ -282,7 +297,34 @@ def _progressive_scan(comps, sos, sent, latched: dict, tables, bad) -> dict:
     return dict(comps=ci, ss=ss, se=se, ah=ah, al=al, tables=used)
 
 
-def parse_jpeg(data, index: int = 0, progressive: bool = False, all_layouts: bool = False) -> dict:
+def _sequential_scan(comps, sos, sent, latched: dict, tables, bad) -> dict:
+    """One scan of a sequential file of several scans (``all_scans``): band (0, 63, 0, 0), 1 .. 4 components in frame order,
+    each component of the file sent exactly once -> ``dict(comps, ss, se, ah, al, tables)`` with ``tables`` the DC table of
+    every component of the scan, then the AC table of every component.  ``sent``, ``latched``: as :func:`_progressive_scan`."""
+    (ids, tabs, band), (qts, dcs, acs) = sos, tables
+    frame_ids = [c[0] for c in comps]
+    if not 1 <= len(ids) <= len(comps):
+        raise bad("bad scan header")
+    if any(i not in frame_ids for i in ids):
+        raise bad("the scan names a component the frame does not have")
+    ci = [frame_ids.index(i) for i in ids]
+    if any(b <= a for a, b in zip(ci, ci[1:])):
+        raise bad("the scan's components are not in frame order")
+    if band != (0, 63, 0, 0):
+        raise bad("spectral selection / successive approximation in a sequential file")
+    dc, ac = [], []
+    for c, (td, ta) in zip(ci, tabs):
+        if sent[c][0] is not None:
+            raise bad(f"a second scan of component {c} of a sequential file, which was already sent")
+        sent[c][:] = [0] * 64
+        if comps[c][3] not in qts or td not in dcs or ta not in acs:
+            raise bad("the scan names a table never defined")
+        latched[c] = qts[comps[c][3]]
+        dc.append(dcs[td]); ac.append(acs[ta])
+    return dict(comps=ci, ss=0, se=63, ah=0, al=0, tables=dc + ac, sequential=True)
+
+
+def parse_jpeg(data, index: int = 0, progressive: bool = False, all_layouts: bool = False, all_scans: bool = False) -> dict:
     """The host's whole part of decoding one file: the walk over the marker segments up to the SOS header.  bytes-like ->
     ``dict(W, H, ncomp, hs, vs, ri, qt, dc, ac, data_off)``: luma sampling factors, the restart interval (0: none), per
     component the quantisation table (64 values, natural order) and the (counts, symbols) of its DC and AC Huffman tables,
@@ -305,7 +347,21 @@ def parse_jpeg(data, index: int = 0, progressive: bool = False, all_layouts: boo
     "rgb", "cmyk", "ycck") and the frame's largest factors as ``hs``, ``vs``.  The colour rule is then libjpeg's throughout: a
     JFIF file stays YCbCr whatever an Adobe marker says.  A file the baseline records hold parses exactly as without the
     keyword.  Still refused: a progressive file of such a layout, more than one scan, 16-bit quantisation tables, 12-bit,
-    arithmetic, lossless and hierarchical files."""
+    arithmetic, lossless and hierarchical files.
+
+    ``all_scans=True`` implies both keywords and also accepts the two cross terms they refuse: an SOF2 frame
+    of any layout :func:`_any_layout` accepts (at most 10 blocks per MCU: the slot map of an image record has ten entries),
+    under the progression checks above over up to four components; and an SOF0 / SOF1 file of several scans, each with band
+    (0, 63, 0, 0) and 1 .. 4 components in frame order, in any order of scans (a plain 4:2:0 file in three scans too).  The
+    walk goes over the whole file, and the result has ``scanned=True``, ``sequential`` (the frame is SOF0 / SOF1), ``samp``,
+    ``color``, the largest factors as ``hs``, ``vs``, ``ri=0``, empty ``dc`` / ``ac``, and ``scans`` and ``levels`` as
+    above; a sequential scan has ``sequential=True`` and names in ``tables`` the DC table of each of its components, then
+    the AC table of each.  ValueError for a second scan of a component of a sequential file (*already sent*) and for a
+    component never sent at EOI (*incomplete*); a file that ends inside a scan gets a status from the device.  A file one of
+    the three other kinds holds parses exactly as with ``progressive=True, all_layouts=True``.  Still refused: 16-bit
+    quantisation tables, 12-bit, arithmetic, lossless and hierarchical files, more than :data:`JPEGDEC_MAX_SCANS` scans, more
+    than :data:`JPEGDEC_MAX_UNITS` units over all scans."""
+    progressive, all_layouts = progressive or all_scans, all_layouts or all_scans
     mv = memoryview(data).cast("B")
     n = len(mv)
 
@@ -349,32 +405,44 @@ def parse_jpeg(data, index: int = 0, progressive: bool = False, all_layouts: boo
         elif m == 0xDA:
             if frame is None:
                 raise bad("SOS before the frame header")
-            if sof != 2:
-                return _baseline(frame, _read_sos(seg, None, bad), (jfif, adobe), (qts, dcs, acs), ri, pos, n, bad, all_layouts)
             W, H, comps = frame
+            if sof != 2:
+                sos = _read_sos(seg, None, bad)
+                # (all_scans: a first scan that does not hold all components in frame order starts a file of several scans)
+                if not (all_scans and (scans or sos[0] != [c[0] for c in comps])):
+                    return _baseline(frame, sos, (jfif, adobe), (qts, dcs, acs), ri, pos, n, bad, all_layouts)
             if not scans:
                 hs, vs, other = _any_layout(comps, jfif, adobe, bad) if all_layouts else _frame_layout(comps, jfif, adobe, bad) + (None,)
-                if other:
+                if other and not all_scans:
                     raise bad(f"progressive file of {len(comps)} components, {other['color']}-coded, sampling {other['samp']}: "
                               "all_layouts covers sequential files only")
+                if sof != 2 and other is None:               # a plain layout in several scans: the general records hold it too
+                    other = dict(samp=[(hs, vs)] + [(1, 1)] * (len(comps) - 1), color="ycc" if len(comps) == 3 else "grey")
                 sent = [[None] * 64 for _ in comps]          # per coefficient: the Al it was last sent with
                 markers, data_off = _marker_positions(mv), pos
             if len(scans) >= JPEGDEC_MAX_SCANS:
                 raise bad(f"more than {JPEGDEC_MAX_SCANS} scans")
-            scan = _progressive_scan(comps, _read_sos(seg, len(comps), bad), sent, latched, (qts, dcs, acs), bad)
-            nmcu = scan_geometry(dict(W=W, H=H, hs=hs, vs=vs), scan["comps"])[1]
+            if sof != 2:
+                scan = _sequential_scan(comps, sos, sent, latched, (qts, dcs, acs), bad)
+            else:
+                scan = _progressive_scan(comps, _read_sos(seg, len(comps), bad), sent, latched, (qts, dcs, acs), bad)
+            nmcu = (layout_scan_geometry(W, H, other["samp"], scan["comps"]) if other else
+                    scan_geometry(dict(W=W, H=H, hs=hs, vs=vs), scan["comps"]))[1]
             k = int(np.searchsorted(markers, pos))
             end = int(markers[k]) if k < markers.size else n
             scans.append(dict(scan, ri=ri, off=pos, end=end, units=-(-nmcu // ri) if ri else 1))
             cut = end + 1 >= n                              # nothing, or a lone FF, behind the data: the file ends inside the scan
             pos = end
     if not cut and any(a != 0 for row in sent for a in row):
-        raise bad("incomplete progressive file: some coefficient was never sent or never reached Al = 0")
+        raise bad("incomplete progressive file: some coefficient was never sent or never reached Al = 0" if sof == 2 else
+                  "incomplete sequential file: a component was never sent")
     nf, units = len(comps), sum(s["units"] for s in scans)
-    _size_limit(units, -(-W // (8 * hs)) * -(-H // (8 * vs)) * (hs * vs + nf - 1), n - data_off, True, bad)
+    slots = sum(h * v for h, v in other["samp"]) if other else hs * vs + nf - 1
+    _size_limit(units, -(-W // (8 * hs)) * -(-H // (8 * vs)) * slots, n - data_off, True, bad)
     qt = [latched.get(c, qts.get(comps[c][3], [0] * 64)) for c in range(nf)]
-    return dict(W=W, H=H, ncomp=nf, hs=hs, vs=vs, ri=0, qt=qt, dc=[], ac=[], data_off=data_off, units=units, progressive=True,
-                scans=scans, levels=scan_levels(scans))
+    p = dict(W=W, H=H, ncomp=nf, hs=hs, vs=vs, ri=0, qt=qt, dc=[], ac=[], data_off=data_off, units=units, scans=scans,
+             levels=scan_levels(scans))
+    return dict(p, scanned=True, sequential=sof != 2, **other) if other else dict(p, progressive=True)
 
 
 def _substream_plan(substreams, segment_bytes, max_rounds):
@@ -397,7 +465,8 @@ def _put_tables(counts, symbols, tables):
 
 
 def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segment_bytes: Optional[int] = None,
-         max_rounds: Optional[int] = None, progressive: bool = False, levels: bool = True, all_layouts: bool = False, _parsed=None):
+         max_rounds: Optional[int] = None, progressive: bool = False, levels: bool = True, all_layouts: bool = False, _parsed=None,
+         all_scans: bool = False):
     """Host only (no device is touched): files -> ``(parsed, table, header)``: :func:`parse_jpeg` of every file and the table
     ``attwarp_jpegdec_plan_ex`` writes for them, which depends on the headers and the files' lengths alone.  ``substreams``:
     "auto" / True cut every marker-less file of at least two segments into ``segment_bytes`` (a power of two in 32..512,
@@ -412,15 +481,23 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
 
     ``all_layouts=True`` also plans a list of files of the other layouts (``parsed[i]["layout"]``; again all of the list)
     through ``attwarp_jpegdec_plan_layouts``, sub-streams included.  A list without such a file gets the table it gets
-    without the keyword, byte for byte."""
+    without the keyword, byte for byte.
+
+    ``all_scans=True`` (implies both) also plans a list of progressive files of the other layouts and sequential files of
+    several scans (``parsed[i]["scanned"]``; again all of the list) through ``attwarp_jpegdec_plan_layout_scans``: every scan
+    of every file over the layout family's image records, one entropy launch per dependency level; ``levels`` as above.  A
+    list without such a file gets the table it gets with ``progressive=True, all_layouts=True``, byte for byte."""
     if mode not in _lib.JPEGDEC_MODE_IDS or order not in _ORDERS:
         raise ValueError(f"jpeg: mode must be one of {sorted(_lib.JPEGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
     sb, mr = _substream_plan(substreams, segment_bytes, max_rounds)
     files = [file_bytes(f) for f in files]
-    parsed = _parsed if _parsed is not None else [parse_jpeg(f, i, progressive, all_layouts) for i, f in enumerate(files)]
+    parsed = _parsed if _parsed is not None else [parse_jpeg(f, i, progressive, all_layouts, all_scans) for i, f in enumerate(files)]
     B = len(parsed)
     prog = [bool(p.get("progressive")) for p in parsed]
-    other = [bool(p.get("layout")) for p in parsed]
+    scanned = [bool(p.get("scanned")) for p in parsed]
+    if any(scanned) and not all(scanned):
+        raise ValueError("jpeg: plan() takes files of one kind; JpegFiles splits a list that holds several kinds")
+    other = [bool(p.get("layout") or p.get("scanned")) for p in parsed]
     if any(prog) and not all(prog) and not any(other):
         raise ValueError("jpeg: plan() takes baseline files or progressive files; JpegFiles splits a list that holds both")
     if any(other) and not all(other):
@@ -446,6 +523,25 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
     size, planner = ("attwarp_jpegdec_table_bytes", rp, B), ("attwarp_jpegdec_plan_ex", rp, B, TABLE, sb, mr)
     if any(other):
         size, planner = ("attwarp_jpegdec_layouts_table_bytes", rp, B), ("attwarp_jpegdec_plan_layouts", rp, B, TABLE, sb, mr)
+    if any(scanned):
+        scans = [(b, s) for b, p in enumerate(parsed) for s in p["scans"]]
+        srec = np.zeros(len(scans), dtype=np.dtype(_lib.JpegDecLayoutScan))
+        srec["image"] = [b for b, _ in scans]
+        srec["ncomp"] = [len(s["comps"]) for _, s in scans]
+        srec["comp"] = [(s["comps"] + [0, 0, 0])[:4] for _, s in scans]
+        for key, name in (("ss", "ss"), ("se", "se"), ("ah", "ah"), ("al", "al"), ("restart_interval", "ri")):
+            srec[key] = [s[name] for _, s in scans]
+        srec["sequential"] = [1 if s.get("sequential") else 0 for _, s in scans]
+        srec["stream_off"] = [s["off"] - parsed[b]["data_off"] for b, s in scans]
+        for i, (_, s) in enumerate(scans):
+            nc = len(s["comps"])                            # a sequential scan: its DC tables, then its AC tables
+            dc = s["tables"][:nc] if s.get("sequential") else s["tables"] if s["ss"] == 0 else []
+            ac = s["tables"][nc:] if s.get("sequential") else s["tables"] if s["ss"] > 0 else []
+            _put_tables(srec["dc_counts"][i], srec["dc_symbols"][i], dc)
+            _put_tables(srec["ac_counts"][i], srec["ac_symbols"][i], ac)
+        size = ("attwarp_jpegdec_layout_scans_table_bytes", rp, B, len(scans))
+        planner = ("attwarp_jpegdec_plan_layout_scans", rp, B, srec.ctypes.data, len(scans), TABLE, 1 if levels else 0)
+        sb = 0                                              # files planned scan by scan take no sub-streams
     if any(prog):
         scans = [(b, s) for b, p in enumerate(parsed) for s in p["scans"]]
         srec = np.zeros(len(scans), dtype=np.dtype(_lib.JpegDecScan))
@@ -495,24 +591,33 @@ class JpegFiles(FileBatch):
     ``all_layouts=True`` also takes sequential files of four components (CMYK, YCCK), RGB-coded files and every sampling
     layout libjpeg decodes (DESIGN.md 3.19).  They are a third kind with a plan of its own, so a list may hold all three;
     "keep" gives such a file its own channels (four: Pillow's ``CMYK`` bytes).  A list without such a file takes exactly the
-    path it takes without the keyword."""
+    path it takes without the keyword.
+
+    ``all_scans=True`` is the one switch for a folder somebody else made: it implies both keywords and also takes what both
+    refuse, progressive files of the other layouts and sequential files of several scans.  Those are a
+    fourth kind with a plan of its own; only files the three other kinds refuse take it, the other parts plan and launch
+    exactly as with ``progressive=True, all_layouts=True``, and views and statuses come back in input order."""
 
     def __init__(self, files, mode: str = "RGB", order: str = "rgb", out: Optional[torch.Tensor] = None, device=None,
                  substreams="auto", segment_bytes: Optional[int] = None, max_rounds: Optional[int] = None,
-                 progressive: bool = False, levels: bool = True, all_layouts: bool = False):
+                 progressive: bool = False, levels: bool = True, all_layouts: bool = False, all_scans: bool = False):
         files = [file_bytes(f) for f in files]
         if not files:
             raise ValueError("JpegFiles: empty batch")
         self.parts, self.B, self.mode, self.order = None, len(files), mode, order
-        pre = [parse_jpeg(f, i, progressive, all_layouts) for i, f in enumerate(files)] if progressive or all_layouts else None
-        which = [1 if p.get("progressive") else 2 if p.get("layout") else 0 for p in pre or []]     # baseline, progressive, other layout
+        progressive, all_layouts = progressive or all_scans, all_layouts or all_scans
+        pre = [parse_jpeg(f, i, progressive, all_layouts, all_scans) for i, f in enumerate(files)] if progressive or all_layouts else None
+        # baseline, progressive, other layout, scans of any layout
+        which = [1 if p.get("progressive") else 2 if p.get("layout") else 3 if p.get("scanned") else 0 for p in pre or []]
         self.progressive, self.all_layouts = bool(which) and set(which) == {1}, bool(which) and set(which) == {2}
+        self.all_scans = bool(which) and set(which) == {3}
         if len(set(which)) > 1:
             if out is not None:
                 raise ValueError("JpegFiles: a list of baseline and progressive files decodes into two buffers; out must be None"
                                  if 2 not in which else "JpegFiles: a list of several kinds of files decodes into one buffer per kind; out must be None")
-            self.parts = [(idx, JpegFiles([files[i] for i in idx], mode, order, None, device, substreams, segment_bytes, max_rounds, kind == 1, levels, all_layouts))
-                          for kind, idx in split_indices(which, (0, 1, 2))]
+            self.parts = [(idx, JpegFiles([files[i] for i in idx], mode, order, None, device, substreams, segment_bytes, max_rounds, kind == 1, levels,
+                                          all_layouts, kind == 3))
+                          for kind, idx in split_indices(which, (0, 1, 2, 3))]
             first = self.parts[0][1]
             self._dev, self.segment_bytes, self.max_rounds = first._dev, first.segment_bytes, first.max_rounds
             self.parsed, self.shapes = (scattered(self.B, ((idx, getattr(part, name)) for idx, part in self.parts)) for name in ("parsed", "shapes"))
@@ -522,8 +627,9 @@ class JpegFiles(FileBatch):
                 self._index = [torch.tensor(idx, device=self._dev, dtype=torch.int64) for idx, _ in self.parts]
             return
         self._entry = ("attwarp_jpegdec_decode_scans" if self.progressive else "attwarp_jpegdec_decode_layouts" if self.all_layouts
-                       else "attwarp_jpegdec_decode")
-        self.parsed, self.table_host, self.header = plan(files, mode, order, substreams, segment_bytes, max_rounds, progressive, levels, all_layouts, pre)
+                       else "attwarp_jpegdec_decode_layout_scans" if self.all_scans else "attwarp_jpegdec_decode")
+        self.parsed, self.table_host, self.header = plan(files, mode, order, substreams, segment_bytes, max_rounds, progressive, levels, all_layouts, pre,
+                                                         all_scans)
         self.segment_bytes, self.max_rounds = _substream_plan(substreams, segment_bytes, max_rounds)      # (0, 0): off
         self._info_off = int(_lib.load().attwarp_jpegdec_info_offset(self.table_host.ctypes.data))
         self._dev = indexed_device(device, out)
@@ -552,16 +658,29 @@ class JpegFiles(FileBatch):
     def levels(self) -> List[int]:
         """Dependency levels of each image's scans, from the headers alone (0 for a baseline file): the entropy launches of a
         progressive plan number the largest of them."""
-        return [1 + max(p["levels"]) if p.get("progressive") else 0 for p in self.parsed]
+        return [1 + max(p["levels"]) if p.get("progressive") or p.get("scanned") else 0 for p in self.parsed]
 
     @_per_part
     def coefficients(self) -> List[torch.Tensor]:
-        """After a :meth:`run`: per image the int16 [blocks, 64] coefficients as they lie in scratch (views).  For tests; not
-        for files of the other layouts."""
+        """After a :meth:`run`: per image the int16 [blocks, 64] coefficients as they lie in scratch (views); for a file planned
+        scan by scan over the layout records (``all_scans``) a list of one int16 [block rows, blocks per row, 64] view per
+        component, the padded planes.  For tests; not for one-scan files of the other layouts."""
         if self.all_layouts:
             raise ValueError("JpegFiles.coefficients: not offered for files of the other layouts")
         ims = np.frombuffer(self.table_host, dtype=np.uint8)
         out = []
+        if self.all_scans:
+            for b, p in enumerate(self.parsed):
+                at = int(self.header.off_images) + b * _lib.JPEGDEC_LAYOUT_RECORD_BYTES
+                off = int(ims[at + 8:at + 16].view(np.uint64)[0])
+                mcux, mcuy = -(-p["W"] // (8 * p["hs"])), -(-p["H"] // (8 * p["vs"]))
+                planes = []
+                for h, v in p["samp"]:
+                    nb = mcux * h * mcuy * v
+                    planes.append(self.scratch[off:off + nb * 128].view(torch.int16).view(mcuy * v, mcux * h, 64))
+                    off += nb * 128
+                out.append(planes)
+            return out
         for b, p in enumerate(self.parsed):
             at = int(self.header.off_images) + b * _lib.JPEGDEC_RECORD_BYTES
             coef_off = int(ims[at + 8:at + 16].view(np.uint64)[0])
@@ -603,21 +722,24 @@ class JpegFiles(FileBatch):
 
 
 def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False,
-                all_layouts: bool = False) -> List[torch.Tensor]:
+                all_layouts: bool = False, all_scans: bool = False) -> List[torch.Tensor]:
     """JPEG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
     first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all.
     ``substreams``: see :func:`plan`.  ``progressive=True`` also decodes progressive files, alone or among baseline files
     (:class:`JpegFiles`); without it such a file raises ValueError.  ``all_layouts=True`` also decodes CMYK / YCCK files,
-    RGB-coded files and every sampling layout libjpeg decodes; without it such a file raises ValueError."""
-    views, status = JpegFiles(files, mode, order, device=device, substreams=substreams, progressive=progressive, all_layouts=all_layouts).run()
+    RGB-coded files and every sampling layout libjpeg decodes; without it such a file raises ValueError.  ``all_scans=True``
+    implies both and also decodes progressive files of those layouts and sequential files of several scans: the one switch
+    for a folder somebody else made."""
+    views, status = JpegFiles(files, mode, order, device=device, substreams=substreams, progressive=progressive, all_layouts=all_layouts,
+                              all_scans=all_scans).run()
     raise_first_broken(status, STATUS_NAMES, "jpeg")
     return views
 
 
 def read_jpeg(paths, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False,
-              all_layouts: bool = False) -> List[torch.Tensor]:
+              all_layouts: bool = False, all_scans: bool = False) -> List[torch.Tensor]:
     """:func:`decode_jpeg` of the files at ``paths``."""
-    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device, substreams, progressive, all_layouts)
+    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device, substreams, progressive, all_layouts, all_scans)
 
 
 # ---- encoding ---------------------------------------------------------------------------------------------------------------

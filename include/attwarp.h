@@ -1109,6 +1109,46 @@ ATTWARP_API int attwarp_jpegdec_plan_layouts(const attwarp_jpegdec_layout_image*
 ATTWARP_API int attwarp_jpegdec_decode_layouts(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
 
+/* ---- SCANS of every layout (jpegdec.hip, jpegscan_blocks.hpp): a fourth family, the cross term of the two
+ * above, for what both refuse: a PROGRESSIVE file (SOF2) of any layout attwarp_jpegdec_plan_layouts takes (1, 3 or 4 components,
+ * factors 1..4 that divide the largest, sum of h v <= 10: the slot map of an image record has ten entries, colour by the
+ * caller), and a SEQUENTIAL file (SOF0 / SOF1) whose components come in several scans.  The images are
+ * attwarp_jpegdec_layout_image records with the tables and restart_interval left zero; the scans are passed image by image,
+ * in file order, as for attwarp_jpegdec_plan_scans, with
+ *   comp[]:      the scan's components, indices in frame order, ascending, any subset of the frame's;
+ *   sequential:  1: band 0..63 with Ah = Al = 0, DC and AC of every block in one pass (a scan of a sequential file);
+ *                0: a progressive scan under the rules of attwarp_jpegdec_plan_scans;
+ *   tables:      dc_*[t], ac_*[t] for the t-th component of a sequential scan; dc_*[t] of a DC first pass; ac_*[0] of an AC
+ *                scan; none of a DC refinement.
+ * Geometry: a scan of several components walks the FRAME's MCUs, ceil(W / 8 hmax) x ceil(H / 8 vmax), also when it holds a
+ * subset of the components, and visits its components' h x v blocks of each; a scan of one component walks the
+ * ceil(cw / 8) x ceil(ch / 8) blocks that cover the component's true size (cw = ceil(W h / hmax)) in raster order, at the
+ * pitch of the component's padded plane.  Restart intervals count those.  Levels, by_level, units, launches (one clear, one
+ * restart scan per SCAN, one entropy launch per level, then the IDCT and colour launches of attwarp_jpegdec_decode_layouts,
+ * unchanged), statuses and their precedence are those of attwarp_jpegdec_plan_scans / attwarp_jpegdec_decode_scans; all scans
+ * of a sequential file are level 0, since each of its components is sent once.  The table is a table of
+ * attwarp_jpegdec_plan_layouts for B one-unit images under a magic of its own (each decode entry point refuses the tables of
+ * the other families before any launch), then a header and the scan records.  The planner checks what the kernels'
+ * bounds rest on: the band and Al rules, an AC or refinement scan of one component, component indices ascending and below
+ * the frame's, every table named, ATTWARP_JPEGDEC_MAX_SCANS scans and ATTWARP_JPEGDEC_MAX_UNITS units per image over all
+ * its scans.  Whether the scans form a complete, consistent file (every coefficient reaching Al = 0; every component of a
+ * sequential file sent exactly once) is the caller's to check. */
+typedef struct attwarp_jpegdec_layout_scan {
+  int32_t image;                                   /* index into the images of the call; ascending over the array */
+  int32_t ncomp, comp[4];                          /* components of the scan, indices in frame order */
+  int32_t ss, se, ah, al;
+  int32_t sequential;                              /* 1: band 0..63, DC and AC in one pass */
+  int32_t restart_interval;                        /* MCUs of this scan, 0: none */
+  uint64_t stream_off;                             /* its entropy data, relative to the image's stream_off */
+  uint8_t dc_counts[4][16], ac_counts[4][16];      /* DHT of the tables it names */
+  uint8_t dc_symbols[4][256], ac_symbols[4][256];
+} attwarp_jpegdec_layout_scan;
+ATTWARP_API size_t attwarp_jpegdec_layout_scans_table_bytes(const attwarp_jpegdec_layout_image* images, int B, int nscans);
+ATTWARP_API int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_image* images, int B, const attwarp_jpegdec_layout_scan* scans,
+                       int nscans, void* table, size_t table_bytes, int by_level);
+ATTWARP_API int attwarp_jpegdec_decode_layout_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes,
+                       void* scratch, uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
+
 /* ---- JPEG files of a whole batch of differently sized uint8 images, encoded on the device (jpegenc.hip):
  * the bytes of Pillow's Image.save(f, "JPEG", quality, subsampling, restart_marker_rows), whole file: baseline sequential,
  * JFIF APP0, one DQT per table, SOF0, the four Annex K Huffman tables, DRI when restarts are on, one interleaved scan.
