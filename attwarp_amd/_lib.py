@@ -167,6 +167,8 @@ SIGNATURES = {
     "attwarp_pngdec_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "attwarp_pngdec_table_bytes_formats": (c_size_t, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
     "attwarp_pngdec_plan_formats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t]),
+    "attwarp_pngdec_table_bytes_wave": (c_size_t, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    "attwarp_pngdec_plan_wave": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
     # baseline JPEG files decoded on the device (jpegdec.hip)
     "attwarp_jpegdec_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_jpegdec_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),

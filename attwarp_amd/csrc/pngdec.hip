@@ -14,11 +14,15 @@
 //                           lane away; reconstructs, converts and writes the pixels, then the image's status.
 // A table of attwarp_pngdec_plan_formats with the format flag (palette, 1 / 2 / 4 / 16 bits, Adam7: DESIGN.md 3.18) takes, in
 // place of the last launch, pngdec_unfilter_formats_kernel (one wave per image and PASS) and pngdec_status_formats_kernel.
+// A table of attwarp_pngdec_plan_wave takes one launch more, between the chain and the write pass:
+//   pngdec_wave_kernel      one wave per image of the serial route: all 64 lanes inflate the one stream (pngdec_wave_blocks.hpp);
+//                           an image it accepts is skipped by the write pass's serial slot, any other decodes there as ever.
 // Every loop is bounded by a constant, by a size the planner checked, or by the stream's bits (pngdec_blocks.hpp).
 #include <algorithm>
 #include <cstring>
 
 #include "pngfmt_blocks.hpp"
+#include "pngdec_wave_blocks.hpp"
 
 namespace attwarp {
 
@@ -36,6 +40,15 @@ __host__ __device__ inline uint64_t pd_filt_base(int B) { return pd_align(pd_kep
 __host__ __device__ inline uint64_t pf_formats_off(const attwarp_pngdec_header& h) {
   return pd_align(h.off_chunks + (uint64_t)h.nchunks * sizeof(attwarp_pngdec_chunk), 16);
 }
+
+// a table of attwarp_pngdec_plan_wave: header.reserved2 = 1 | segment_bytes << 8 | max_rounds << 20, and the per-image wave
+// records are the last B * sizeof(PwRecord) bytes of the scratch buffer
+__host__ __device__ inline uint32_t pw_segment_bytes(uint32_t r2) { return (r2 >> 8) & 0xfffu; }
+__host__ __device__ inline uint32_t pw_max_rounds(uint32_t r2) { return (r2 >> 20) & 0xfffu; }
+__host__ __device__ inline bool pw_valid(uint32_t sb, uint32_t mr) {
+  return (sb == 16 || sb == 32 || sb == 64 || sb == 128 || sb == 256) && mr >= 1 && mr <= (uint32_t)PW_WAVE;
+}
+__host__ __device__ inline uint64_t pw_records_off(const attwarp_pngdec_header& h) { return h.scratch_bytes - (uint64_t)h.B * sizeof(PwRecord); }
 
 struct PdView {
   const attwarp_pngdec_header* hdr;
@@ -182,6 +195,7 @@ __global__ __launch_bounds__(WAVE) void pngdec_inflate_kernel(const uint8_t* __r
     out = filt + U->out_off;
   } else {                                                 // the serial route
     if (st->route != 1) return;
+    if (v.hdr->reserved2 && reinterpret_cast<const PwRecord*>(scratch + pw_records_off(*v.hdr))[b].accepted) return;   // (the wave route wrote it)
     start = 2;
     cap = im.filt_bytes;
     out = filt;
@@ -215,6 +229,47 @@ __global__ __launch_bounds__(WAVE) void pngdec_chain_kernel(const uint8_t* __res
   st->route = route;
   st->adler_pos = adler_pos;
   st->chain_len = route == 0 ? chain_len : 0u;
+}
+
+// Grid B, one wave each: the wave route for every image that the chain left to the serial route.  Writes the image's wave
+// record; on acceptance the filtered bytes and adler_pos too, and st_inflate stays OK as pd_serial_status would leave it.
+__global__ __launch_bounds__(WAVE) void pngdec_wave_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                           uint8_t* __restrict__ scratch) {
+  __shared__ PwShared S;
+  static_assert(WAVE == PW_WAVE, "one wave per image");
+  const int b = blockIdx.x;
+  const PdView v(table, scratch);
+  PdState* st = v.states + b;
+  PwRecord* rec = reinterpret_cast<PwRecord*>(scratch + pw_records_off(*v.hdr)) + b;
+  const uint32_t sb = pw_segment_bytes(v.hdr->reserved2), mr = pw_max_rounds(v.hdr->reserved2);
+  if (st->route != 1 || st->nunits == 0 || st->st_crc != 0 || !pw_valid(sb, mr)) {   // (uniform; a file with a wrong CRC is not worth a wave)
+    if (threadIdx.x == 0) *rec = PwRecord{0, 0, 0, 0};
+    return;
+  }
+  const PdImage im = v.images[b];
+  uint8_t* filt = scratch + im.filt_off;
+  pw_image(S, stream + im.stream_off, im.stream_len, filt, im.filt_bytes, sb, mr, rec, &st->adler_pos);
+  if (!rec->accepted) return;                              // (uniform: written in front of pw_image's last barrier)
+  // a filter byte above 4 is the unfilter kernels' to state: such an image, too, takes the lane route as without the wave
+  bool badf = false;
+  if (v.hdr->formats) {
+    const PfImage fm = reinterpret_cast<const PfImage*>(table + pf_formats_off(*v.hdr))[b];
+    for (int p = 0; p < PF_PASSES; ++p) {
+      const PfPass g = pf_pass(fm.interlace, p, im.W, im.H);
+      if (g.w <= 0 || g.h <= 0) continue;
+      const uint64_t rb = (uint64_t)pf_row_bytes(g.w, im.ch, fm.depth), off = (uint64_t)pf_pass_offset(fm.interlace, p, im.W, im.H, im.ch, fm.depth);
+      for (int r = threadIdx.x; r < g.h; r += WAVE) {
+        const uint64_t q = off + (uint64_t)r * rb;
+        badf |= q < im.filt_bytes && filt[q] > 4;
+      }
+    }
+  } else {
+    for (int r = threadIdx.x; r < im.H; r += WAVE) {
+      const uint64_t q = (uint64_t)r * (uint64_t)im.row_bytes;
+      badf |= q < im.filt_bytes && filt[q] > 4;
+    }
+  }
+  if (__ballot(badf) != 0ull && threadIdx.x == 0) rec->accepted = 0;
 }
 
 __global__ __launch_bounds__(PD_NT) void pngdec_adler_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
@@ -501,8 +556,9 @@ extern "C" size_t attwarp_pngdec_table_bytes_formats(const attwarp_pngdec_image*
   return pngdec_bytes(images, formats, B, nchunks);
 }
 
+// wave != 0: the table of attwarp_pngdec_plan_wave (segment_bytes, max_rounds checked by the caller)
 static int pngdec_plan(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B, const attwarp_pngdec_chunk* chunks,
-                       int nchunks, int check_crc, void* table, size_t table_bytes) {
+                       int nchunks, int check_crc, void* table, size_t table_bytes, uint32_t wave = 0) {
   if (const int rc = pngdec_check(images, formats, B, chunks, nchunks)) return rc;
   ATTWARP_REQUIRE(table, "pngdec_plan: null table");
   const bool fmt = pngdec_needs_formats(images, formats, B);
@@ -558,7 +614,8 @@ static int pngdec_plan(const attwarp_pngdec_image* images, const attwarp_pngdec_
     }
   }
   if (nchunks) std::memcpy(t + h.off_chunks, chunks, (size_t)nchunks * sizeof(attwarp_pngdec_chunk));
-  h.scratch_bytes = soff;
+  h.scratch_bytes = soff + (wave ? (uint64_t)B * sizeof(PwRecord) : 0);   // (soff is a multiple of 16)
+  h.reserved2 = wave;
   h.out_bytes = ooff;
   h.stream_bytes = stream_bytes;
   h.lds_bytes = lds + (fmt ? PF_PALETTE_LDS : 0);
@@ -577,6 +634,21 @@ extern "C" int attwarp_pngdec_plan_formats(const attwarp_pngdec_image* images, c
   return pngdec_plan(images, formats, B, chunks, nchunks, check_crc, table, table_bytes);
 }
 
+extern "C" size_t attwarp_pngdec_table_bytes_wave(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                                                  const attwarp_pngdec_chunk* chunks, int nchunks) {
+  (void)chunks;
+  return pngdec_bytes_args(images, B, nchunks) ? pngdec_bytes(images, formats, B, nchunks) : 0;
+}
+
+extern "C" int attwarp_pngdec_plan_wave(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                                        const attwarp_pngdec_chunk* chunks, int nchunks, int check_crc, int segment_bytes, int max_rounds,
+                                        void* table, size_t table_bytes) {
+  ATTWARP_REQUIRE(segment_bytes > 0 && max_rounds > 0 && pw_valid((uint32_t)segment_bytes, (uint32_t)max_rounds),
+                  "pngdec_plan_wave: segment_bytes=%d (16, 32, 64, 128 or 256), max_rounds=%d (1 .. 64)", segment_bytes, max_rounds);
+  return pngdec_plan(images, formats, B, chunks, nchunks, check_crc, table, table_bytes,
+                     1u | (uint32_t)segment_bytes << 8 | (uint32_t)max_rounds << 20);
+}
+
 extern "C" int attwarp_pngdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                                      uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
   ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "pngdec_decode: null pointer");
@@ -584,7 +656,9 @@ extern "C" int attwarp_pngdec_decode(const void* table_host, const void* table_d
   std::memcpy(&h, table_host, sizeof h);
   ATTWARP_REQUIRE(h.magic == PD_MAGIC && h.B > 0 && h.B <= PD_MAX_B && h.nchunks >= 0 && h.nchunks <= PD_MAX_CHUNKS &&
                       (h.formats == 0 || h.formats == 1) && h.lds_bytes >= 16 + h.formats * PF_PALETTE_LDS &&
-                      h.lds_bytes <= ATTWARP_PNGDEC_MAX_ROW_BYTES + h.formats * PF_PALETTE_LDS,
+                      h.lds_bytes <= ATTWARP_PNGDEC_MAX_ROW_BYTES + h.formats * PF_PALETTE_LDS &&
+                      (h.reserved2 == 0 || ((h.reserved2 & 0xffu) == 1u && pw_valid(pw_segment_bytes(h.reserved2), pw_max_rounds(h.reserved2)) &&
+                                            h.scratch_bytes >= (uint64_t)h.B * sizeof(PwRecord))),
                   "pngdec_decode: not a table of attwarp_pngdec_plan");
   ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "pngdec_decode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
   ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
@@ -605,6 +679,10 @@ extern "C" int attwarp_pngdec_decode(const void* table_host, const void* table_d
   if (const int rc = check_launch("pngdec_inflate_kernel (count)")) return rc;
   hipLaunchKernelGGL(pngdec_chain_kernel, dim3((h.B + WAVE - 1) / WAVE), dim3(WAVE), 0, st, td, sc, force_serial);
   if (const int rc = check_launch("pngdec_chain_kernel")) return rc;
+  if (h.reserved2) {
+    hipLaunchKernelGGL(pngdec_wave_kernel, dim3(h.B), dim3(WAVE), 0, st, td, stream_bytes, sc);
+    if (const int rc = check_launch("pngdec_wave_kernel")) return rc;
+  }
   hipLaunchKernelGGL(pngdec_inflate_kernel, ugrid, dim3(WAVE), 0, st, td, stream_bytes, sc, 1);
   if (const int rc = check_launch("pngdec_inflate_kernel (write)")) return rc;
   hipLaunchKernelGGL(pngdec_adler_kernel, dim3(h.B), dim3(PD_NT), 0, st, td, stream_bytes, sc);

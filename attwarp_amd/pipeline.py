@@ -1412,14 +1412,16 @@ def upload_images(images, device=None):
     return packed_views(uploaded(host, dev), [a.shape for a in arrs])
 
 
-def upload_png_files(files_or_paths, device=None, all_formats=False):
+def upload_png_files(files_or_paths, device=None, all_formats=False, inflate="lane"):
     """:func:`upload_images` for a batch still in its PNG files (bytes-like or paths; the warped, overlay and attention-map
     files the drivers wrote, or anyone's 8-bit non-interlaced PNG): the COMPRESSED bytes go up in one transfer and are decoded
     on the GPU (attwarp_amd.png.decode_png) -> list of uint8 [H_i,W_i,3] RGB GPU tensors, views into one packed buffer, as
     ``Image.open(f).convert("RGB")`` gives them.  OSError for a broken file, ValueError for an unsupported one.
     ``all_formats=True`` also takes palette, 1- / 2- / 4- / 16-bit and Adam7-interlaced files (png.PngFiles: document scans and
-    web graphics; 16-bit grey saturates as Pillow's does); without it they raise ValueError."""
-    return png.decode_png(files_or_paths, "RGB", "rgb", device, all_formats)
+    web graphics; 16-bit grey saturates as Pillow's does); without it they raise ValueError.
+    ``inflate="wave"`` inflates every one-stream file (anything another encoder wrote) with a whole wave instead of one lane
+    (png.PngFiles); the pixels do not depend on it."""
+    return png.decode_png(files_or_paths, "RGB", "rgb", device, all_formats, inflate)
 
 
 def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressive=False, all_layouts=False, all_scans=False):
@@ -1437,11 +1439,11 @@ def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressiv
 
 
 def upload_image_files(files_or_paths, device=None, substreams="auto", progressive=False, all_formats=False, all_layouts=False,
-                       all_scans=False):
+                       all_scans=False, inflate="lane"):
     """A batch of image files of either kind (bytes-like or paths), each sent by its signature to the PNG or the JPEG decoder
     (:func:`upload_png_files`, :func:`upload_jpeg_files`): one transfer and one decode per kind -> the uint8 [H_i,W_i,3] RGB
     GPU tensors in input order.  ValueError for a file that is neither.  ``progressive``, ``all_layouts``, ``all_scans``: see
-    :func:`upload_jpeg_files`; ``all_formats``: see :func:`upload_png_files`."""
+    :func:`upload_jpeg_files`; ``all_formats``, ``inflate``: see :func:`upload_png_files`."""
     files = [file_bytes(f) for f in files_or_paths]
     kinds = []
     for i, f in enumerate(files):
@@ -1452,7 +1454,7 @@ def upload_image_files(files_or_paths, device=None, substreams="auto", progressi
             kinds.append("jpeg")
         else:
             raise ValueError(f"upload_image_files: file {i} is neither a PNG nor a JPEG file")
-    decode = {"png": lambda f, d: upload_png_files(f, d, all_formats), "jpeg": lambda f, d: upload_jpeg_files(f, d, substreams, progressive, all_layouts, all_scans)}
+    decode = {"png": lambda f, d: upload_png_files(f, d, all_formats, inflate), "jpeg": lambda f, d: upload_jpeg_files(f, d, substreams, progressive, all_layouts, all_scans)}
     return per_kind(files, kinds, ("png", "jpeg"), lambda kind, group: decode[kind](group, device))
 
 

@@ -158,6 +158,8 @@ def write_png(paths, images, filter="sub", order="rgb") -> None:
 PNGDEC_MAX_UNITS = _lib.PNGDEC_MAX_UNITS                # decoding units (sync points) kept per image
 PNGDEC_MAX_ROW_BYTES = _lib.PNGDEC_MAX_ROW_BYTES        # 1 + W * channels at most
 STATUS_NAMES = _lib.PNGDEC_STATUS_NAMES
+WAVE_SEGMENT_BYTES = 64                                 # inflate="wave": stream bytes per lane (DESIGN.md 3.22 has the rounds table)
+WAVE_MAX_ROUNDS = 64                                    # rounds per window of 64 segments: 64 always suffice
 _SIGNATURE = b"\x89PNG\r\n\x1a\n"
 _CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
 _PNGDEC_IMAGE_DTYPE = np.dtype(_lib.PngDecImage)
@@ -296,14 +298,29 @@ class PngFiles(FileBatch):
     luma), one past the entries black; tRNS and alpha are dropped.  "keep" is the file's channels without alpha at 8 bits, a
     palette file its palette's three; "bgr" swaps palette colours too.  A call whose files are all 8-bit and non-interlaced
     plans the same table and launches as without the keyword; otherwise every file of the call goes through the formats
-    kernel and :meth:`run` is nine launches."""
+    kernel and :meth:`run` is nine launches.
+
+    ``inflate="wave"`` (the default is "lane") adds one launch: every image of the serial route -- no sync
+    point, a dependent unit or more than 256 units, so every one-stream file of another encoder -- is inflated by one whole
+    wave, 64 segments of ``segment_bytes`` (16, 32, 64, 128 or 256, default :data:`WAVE_SEGMENT_BYTES`) stream bytes at a
+    time in at most ``max_rounds`` (1 .. 64, the default: no well-formed stream needs more) rounds per window.  An image that
+    does not check out there is decoded by the serial route as ever, so pixels and statuses do not depend on the keyword;
+    :meth:`wave_info` says what happened.  It composes with every other keyword."""
     _entry = "attwarp_pngdec_decode"
 
     def __init__(self, files, mode: str = "RGB", order: str = "rgb", check_crc: bool = True, out: Optional[torch.Tensor] = None,
-                 device=None, all_formats: bool = False):
+                 device=None, all_formats: bool = False, inflate: str = "lane", segment_bytes: Optional[int] = None,
+                 max_rounds: Optional[int] = None):
         files = [file_bytes(f) for f in files]
         if not files:
             raise ValueError("PngFiles: empty batch")
+        if inflate not in ("lane", "wave"):
+            raise ValueError(f"PngFiles: inflate={inflate!r} must be 'lane' or 'wave'")
+        sb = WAVE_SEGMENT_BYTES if segment_bytes is None else int(segment_bytes)
+        mr = WAVE_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+        if sb not in (16, 32, 64, 128, 256) or not 1 <= mr <= 64:
+            raise ValueError(f"PngFiles: segment_bytes={sb} must be 16, 32, 64, 128 or 256, max_rounds={mr} in 1..64")
+        self.inflate, self.segment_bytes, self.max_rounds = inflate, sb, mr
         if mode not in _lib.PNGDEC_MODE_IDS or order not in _ORDERS:
             raise ValueError(f"PngFiles: mode must be one of {sorted(_lib.PNGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
         parsed = [parse_png(f, i, True) if all_formats else parse_png(f, i) + (8, 0, b"") for i, f in enumerate(files)]
@@ -329,6 +346,7 @@ class PngFiles(FileBatch):
         rec["mode"] = _lib.PNGDEC_MODE_IDS[mode]; rec["order"] = _ORDERS[order]
         dev = indexed_device(device, out)
         rp, cp = ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(chunks.ctypes.data)
+        fp = None
         if all_formats:
             fmt = np.zeros(B, dtype=_PNGDEC_FORMAT_DTYPE)
             fmt["depth"] = [p[4] for p in parsed]; fmt["interlace"] = [p[5] for p in parsed]
@@ -341,6 +359,9 @@ class PngFiles(FileBatch):
         else:
             size = ("attwarp_pngdec_table_bytes", rp, B, nchunks)
             plan = ("attwarp_pngdec_plan", rp, B, cp, nchunks, int(bool(check_crc)), TABLE)
+        if inflate == "wave":             # (formats: the array or NULL; the table is the other planners' plus the mark)
+            size = ("attwarp_pngdec_table_bytes_wave", rp, fp, B, cp, nchunks)
+            plan = ("attwarp_pngdec_plan_wave", rp, fp, B, cp, nchunks, int(bool(check_crc)), sb, mr, TABLE)
         self.table_host, self.header = planned_table(size, plan, _lib.PngDecHeader, ValueError, "PngFiles: ", wrap_plan=True)
         self.B, self._dev, self.mode, self.order = B, dev, mode, order
         self.shapes = [(p[1], p[0], 1 if mode == "L" else 3 if mode == "RGB" else (1 if p[2] in (0, 4) else 3)) for p in parsed]
@@ -367,17 +388,31 @@ class PngFiles(FileBatch):
         pos = self.scratch[off:off + B * U * 4].cpu().numpy().view(np.uint32).reshape(B, U)
         return [pos[b, :int(nunits[b])].tolist() for b in range(B)]
 
+    def wave_info(self, resolution: bool = False):
+        """After a :meth:`run` with ``inflate="wave"`` (synchronises): per image ``(windows, rounds, accepted)`` as the
+        device left them -- windows of 64 segments decoded, rounds over all of them, 1 if the wave route's bytes stand (0: the
+        image took another route, or fell back to the serial one).  ``resolution=True`` adds the match-resolution rounds as
+        a fourth number.  For measurements and tests."""
+        if self.inflate != "wave":
+            raise ValueError("PngFiles.wave_info: planned with inflate='lane'")
+        n = int(self.header.scratch_bytes)
+        rec = self.scratch[n - self.B * 16:n].cpu().numpy().view(np.uint32).reshape(self.B, 4)
+        return [tuple(int(x) for x in (r if resolution else r[:3])) for r in rec]
 
-def decode_png(files, mode: str = "RGB", order: str = "rgb", device=None, all_formats: bool = False) -> List[torch.Tensor]:
+
+def decode_png(files, mode: str = "RGB", order: str = "rgb", device=None, all_formats: bool = False,
+               inflate: str = "lane") -> List[torch.Tensor]:
     """PNG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
     first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all.
     ``all_formats=True`` also takes palette, 1- / 2- / 4- / 16-bit and interlaced files (:class:`PngFiles`); without it they
-    raise ValueError."""
-    views, status = PngFiles(files, mode, order, device=device, all_formats=all_formats).run()
+    raise ValueError.  ``inflate="wave"`` inflates every one-stream file with a whole wave (:class:`PngFiles`); the result does
+    not depend on it."""
+    views, status = PngFiles(files, mode, order, device=device, all_formats=all_formats, inflate=inflate).run()
     raise_first_broken(status, STATUS_NAMES, "png")
     return views
 
 
-def read_png(paths, mode: str = "RGB", order: str = "rgb", device=None, all_formats: bool = False) -> List[torch.Tensor]:
-    """:func:`decode_png` of the files at ``paths``."""
-    return decode_png([os.fspath(p) for p in paths], mode, order, device, all_formats)
+def read_png(paths, mode: str = "RGB", order: str = "rgb", device=None, all_formats: bool = False,
+             inflate: str = "lane") -> List[torch.Tensor]:
+    """:func:`decode_png` of the files at ``paths`` (``inflate``: see there)."""
+    return decode_png([os.fspath(p) for p in paths], mode, order, device, all_formats, inflate)

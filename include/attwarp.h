@@ -943,6 +943,21 @@ ATTWARP_API size_t attwarp_pngdec_table_bytes_formats(const attwarp_pngdec_image
 ATTWARP_API int attwarp_pngdec_plan_formats(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
                        const attwarp_pngdec_chunk* chunks, int nchunks, int check_crc, void* table, size_t table_bytes);
 
+/* ---- the wave route: the same table as attwarp_pngdec_plan (formats == NULL) or attwarp_pngdec_plan_formats,
+ * with header.reserved2 = 1 | segment_bytes << 8 | max_rounds << 20 and B records of four uint32 (windows, rounds, accepted,
+ * resolution rounds) added at the END of the scratch buffer.  attwarp_pngdec_decode then launches pngdec_wave_kernel between
+ * the chain and the write pass: one wave per image of the serial route (no sync point, a dependent unit, more than
+ * ATTWARP_PNGDEC_MAX_UNITS units) inflates the one stream with all 64 lanes, segments of segment_bytes (16, 32, 64, 128 or
+ * 256) stream bytes per lane, at most max_rounds (1 .. 64) rounds per window of 64 segments.  An image that does not check
+ * out (rounds, an error on the true chain, a match before the first byte, the size, the Adler-32's place) is decoded by the
+ * serial route from the stream's start as without this planner, so pixels, filtered bytes and statuses are the same; the
+ * wave route never sets a status.  Streams of 2^28 bytes or more stay on the serial route. */
+ATTWARP_API size_t attwarp_pngdec_table_bytes_wave(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                       const attwarp_pngdec_chunk* chunks, int nchunks);
+ATTWARP_API int attwarp_pngdec_plan_wave(const attwarp_pngdec_image* images, const attwarp_pngdec_format* formats, int B,
+                       const attwarp_pngdec_chunk* chunks, int nchunks, int check_crc, int segment_bytes, int max_rounds,
+                       void* table, size_t table_bytes);
+
 /* ---- baseline JPEG files of a whole batch DECODED on the device (jpegdec.hip).  SOF0 / SOF1 (sequential
  * Huffman, 8 bits), one component (grey) or three (YCbCr, luma 1x1, 2x1 or 2x2 and chroma 1x1: 4:4:4, 4:2:2, 4:2:0), one
  * interleaved scan.  The HOST walks the marker segments only and packs, per file, everything behind the SOS header into
