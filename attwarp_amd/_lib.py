@@ -179,6 +179,10 @@ SIGNATURES = {
     "attwarp_jpegdec_scans_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "attwarp_jpegdec_plan_scans": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int]),
     "attwarp_jpegdec_decode_scans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # the same with marker-less scans cut into segments (segment_bytes, max_rounds, per scan the bytes of its entropy data)
+    "attwarp_jpegdec_scans_table_bytes_ex": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "attwarp_jpegdec_plan_scans_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "attwarp_jpegdec_scan_info_offset": (ctypes.c_uint64, [c_void_p]),
     # every layout of a sequential file: four components, any sampling, RGB-coded (jpegdec.hip, jpegfmt_blocks.hpp)
     "attwarp_jpegdec_layouts_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_jpegdec_plan_layouts": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int]),

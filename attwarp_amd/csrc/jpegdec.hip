@@ -25,6 +25,9 @@
 //   jpegprog_scan_kernel    one workgroup per SCAN: the restart-marker rule above (jd_scan_units) for the scan's own data;
 //   jpegprog_entropy_kernel one launch per dependency level of the scans, one wave per (scan, unit): the four block routines
 //                           of jpegprog_blocks.hpp; a wave stores only the int16s of its band Ss..Se (the band rule).
+// A table of attwarp_jpegdec_plan_scans_ex with sub-streams puts, in front of a level's entropy launch,
+//   jpegprog_substream_kernel one workgroup per marker-less scan of the level that is cut into segments: the four routes of
+//                           jpegprog_sync_blocks.hpp; a scan it accepts is flagged and skipped by the entropy launch.
 // Progressive files of every other layout and sequential files of several scans (attwarp_jpegdec_plan_layout_scans /
 // attwarp_jpegdec_decode_layout_scans) are the cross term: JfImage frames, JsScan records (jpegscan_blocks.hpp),
 // jpegscan_clear_kernel, jpegscan_marks_kernel, one jpegscan_entropy_kernel launch per level over the general MCU with a
@@ -36,6 +39,7 @@
 
 #include "jpegfmt_blocks.hpp"
 #include "jpegprog_blocks.hpp"
+#include "jpegprog_sync_blocks.hpp"
 #include "jpegscan_blocks.hpp"
 
 namespace attwarp {
@@ -534,10 +538,34 @@ __device__ __forceinline__ void jp_clear_body(const JdViewOf<Image>& v, uint8_t*
   }
 }
 
+// The sub-stream records of a table planned with them (behind the scan records) and the per-scan results in scratch.
+struct JpSyncView {
+  const JpSyncHeader* sh;
+  const JpSync* sy;
+  JpSyncInfo* infos;
+};
+__device__ __forceinline__ bool jp_sync_view(const JdView& v, const JpHeader* ph, const uint8_t* table, uint8_t* scratch, JpSyncView& y) {
+  const uint64_t at = ph->off_scans + (uint64_t)ph->nscans * sizeof(JpScan);
+  if (v.hdr->table_bytes < at + sizeof(JpSyncHeader) + (uint64_t)ph->nscans * sizeof(JpSync)) return false;   // planned without them
+  y.sh = reinterpret_cast<const JpSyncHeader*>(table + at);
+  y.sy = reinterpret_cast<const JpSync*>(table + at + sizeof(JpSyncHeader));
+  y.infos = reinterpret_cast<JpSyncInfo*>(scratch + y.sh->info_off);
+  return y.sh->magic == JP_SYNC_MAGIC;
+}
+
 __global__ __launch_bounds__(JD_NT) void jpegprog_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   const JdView v(table, scratch);
   const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
   jp_clear_body(v, scratch, ph->clear_off, ph->clear_bytes);
+  JpSyncView y;
+  if (!jp_sync_view(v, ph, table, scratch, y)) return;
+  const JpScan* scans = reinterpret_cast<const JpScan*>(table + ph->off_scans);
+  for (int i = (int)(blockIdx.x * JD_NT + threadIdx.x); i < ph->nscans; i += (int)(gridDim.x * JD_NT)) {
+    JpSyncInfo info;
+    info.route = y.sy[i].nseg ? 1u + scans[i].kind : 0u; info.nseg = y.sy[i].nseg; info.rounds = 0; info.accepted = 0;
+    info.ticks[0] = info.ticks[1] = info.ticks[2] = 0; info.pad = 0;
+    if (y.sy[i].slot < (uint32_t)ph->nscans) y.infos[y.sy[i].slot] = info;
+  }
 }
 
 // The restart-marker rule of jpegdec_scan_kernel for one SCAN's own data and units, by one workgroup: the restart launch of
@@ -604,6 +632,9 @@ __global__ __launch_bounds__(WAVE) void jpegprog_entropy_kernel(const uint8_t* _
   const JdImage* im = v.images + sc->image;
   JdState* state = v.states + sc->image;
   if (state->st_scan != 0) return;                           // (uniform) some scan's limits were never written
+  JpSyncView y;
+  if (jp_sync_view(v, ph, table, scratch, y) && y.sy[lo].slot < (uint32_t)ph->nscans && y.infos[y.sy[lo].slot].accepted != 0)
+    return;                                                  // (uniform) the sub-stream kernel decoded this scan's only unit
   const uint32_t k = (uint32_t)w - sc->wave0;
   if (k >= sc->nunits) return;
   const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len, n = im->stream_len - off;
@@ -673,6 +704,202 @@ __global__ __launch_bounds__(WAVE) void jpegprog_entropy_kernel(const uint8_t* _
     i += adv;
   }
   if (err && lane == 0) atomicMin(&state->fail, sc->index << 24 | k << 8 | err);
+}
+
+// jd_excl_sum over block counts that saturate at JP_SYNC_CAP (saturating addition of such counts is associative)
+__device__ __forceinline__ uint32_t jp_excl_sum_sat(uint32_t v, uint32_t* tmp) {
+  const int t = threadIdx.x;
+  tmp[t] = v;
+  __syncthreads();
+  for (int o = 1; o < JD_NT; o <<= 1) {
+    const uint32_t a = t >= o ? tmp[t - o] : 0u;
+    __syncthreads();
+    tmp[t] = jp_sat_add(tmp[t], a);
+    __syncthreads();
+  }
+  const uint32_t before = t > 0 ? tmp[t - 1] : 0u;
+  __syncthreads();
+  return before;
+}
+
+// grid: one workgroup per cut scan of the launch's level.  Segment s goes to lane s % JD_NT in every loop
+// over segments, so a lane reads back its own entry and dirty flag; sums over the segments go by chunks of neighbours.
+__global__ __launch_bounds__(JD_NT) void jpegprog_substream_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                                   uint8_t* scratch, int level) {
+  __shared__ JdHuff s_h[3];
+  __shared__ uint32_t s_tmp[JD_NT];
+  __shared__ uint8_t s_zz[64];
+  __shared__ uint32_t s_ok;
+  const int tid = threadIdx.x;
+  const JdView v(table, scratch);
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  const JpScan* scans = reinterpret_cast<const JpScan*>(table + ph->off_scans);
+  JpSyncView y;
+  if (!jp_sync_view(v, ph, table, scratch, y) || level < 0 || level >= ph->nlevels) return;
+  const uint32_t w = y.sh->level_cut0[level] + blockIdx.x;
+  if (w >= y.sh->level_cut0[level + 1] || w >= (uint32_t)ph->nscans) return;
+  const uint32_t si = y.sy[w].cut;
+  if (si >= (uint32_t)ph->nscans) return;
+  const JpScan* sc = scans + si;
+  const JpSync sub = y.sy[si];
+  if (sc->image >= (uint32_t)v.hdr->B || sub.nseg < 2u || sub.nseg > JP_SYNC_MAX_SEGS || sc->nunits != 1u || sub.slot >= (uint32_t)ph->nscans) return;
+  const JdImage* im = v.images + sc->image;
+  if (v.states[sc->image].st_scan != 0) return;               // (uniform) the info record already says "not accepted"
+  const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len, n = im->stream_len - off;
+  const uint32_t* pstarts = reinterpret_cast<const uint32_t*>(scratch + ph->starts_off) + sc->unit0;
+  uint32_t uend = pstarts[ph->total_units];
+  if (uend > n) uend = n;
+  const uint32_t nseg = sub.nseg, S = sub.segment_bytes;
+  if ((uint64_t)nseg * S < uend) return;                      // (uniform) never: the plan's length is the marker walk's
+  const uint32_t kind = sc->kind, se = sc->se < 63u ? sc->se : 63u, ss = sc->ss < se ? sc->ss : se;
+  const int ntab = kind == JP_DC_FIRST ? 3 : kind == JP_DC_REFINE ? 0 : 1;
+  for (int c = 0; c < ntab; ++c) {
+    if (tid == 0) jd_huff_ranges(s_h[c], sc->counts[c]);
+    jd_huff_clear(s_h[c], sc->symbols[c], jd_nsym(sc->counts[c]), tid, JD_NT);
+  }
+  if (tid < 64) s_zz[tid] = JD_ZIGZAG[tid];
+  if (tid == 0) s_ok = 0;
+  __syncthreads();
+  for (int c = 0; c < ntab; ++c) jd_huff_fill(s_h[c], sc->counts[c], tid, JD_NT);
+  __syncthreads();
+  // the stream is read in place: p is the dword in front of the scan's first byte, lo that byte's offset in it
+  const uint8_t* data = stream + im->stream_off + off;
+  const uint32_t lo = (uint32_t)(reinterpret_cast<uintptr_t>(data) & 3u);
+  const uint8_t* p = data - lo;
+  JpSeg* seg = reinterpret_cast<JpSeg*>(scratch + sub.seg_off);
+  int16_t* coef = reinterpret_cast<int16_t*>(scratch + im->coef_off);
+  const uint32_t nslot = sc->nslot >= 1u && sc->nslot <= 6u ? sc->nslot : 1u;
+  const uint64_t nblk = (uint64_t)sc->nmcu * nslot;
+  const uint32_t expected = nblk < JP_SYNC_CAP ? (uint32_t)nblk : JP_SYNC_CAP - 1u;        // (the planner: fewer than 2^24 blocks)
+  const uint32_t chunk = (nseg + JD_NT - 1) / JD_NT;
+  const uint32_t s0 = min((uint32_t)tid * chunk, nseg), s1 = min(s0 + chunk, nseg);
+  uint32_t rounds = 0, total;
+  bool accepted = false;
+  const uint64_t t0 = wall_clock64();                        // (lane 0's stamps go into the scan's record: 100 MHz)
+  uint64_t t1 = t0, t2 = t0;
+  if (kind == JP_DC_FIRST || kind == JP_AC_FIRST) {
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      JdSync e = jd_segment_guess(data, s, S, uend);
+      if (kind == JP_AC_FIRST) e.bsk = ss;
+      seg[s].entry = e;
+      seg[s].dirty = 1u;
+    }
+    bool converged = false;
+    while (rounds < sub.max_rounds) {                        // (uniform)
+      ++rounds;
+      for (uint32_t s = tid; s < nseg; s += JD_NT)
+        if (seg[s].dirty) {
+          JpSeg r;
+          jp_first_segment(*sc, p, lo, seg[s].entry, jd_segment_end(s, S, uend), uend, s_h, r);
+          seg[s].exit = r.exit;
+          seg[s].nbeg = r.nbeg; seg[s].nend = r.nend; seg[s].eclean = r.eclean;
+          seg[s].dc[0] = r.dc[0]; seg[s].dc[1] = r.dc[1]; seg[s].dc[2] = r.dc[2];
+        }
+      __syncthreads();                                       // every exit of this round is written
+      int changed = 0;
+      for (uint32_t s = tid; s < nseg; s += JD_NT) {
+        uint32_t d = 0;
+        if (s > 0) {
+          const JdSync e = seg[s - 1].exit;
+          if (!jd_sync_equal(e, seg[s].entry)) { seg[s].entry = e; d = 1u; changed = 1; }
+        }
+        seg[s].dirty = d;
+      }
+      if (!__syncthreads_or(changed)) { converged = true; break; }
+    }
+    t1 = wall_clock64();
+    // exclusive sums of (blocks ended, DC differences) over the segments
+    uint32_t sum[4] = {0, 0, 0, 0};
+    for (uint32_t s = s0; s < s1; ++s) {
+      sum[0] = jp_sat_add(sum[0], seg[s].nend);
+      sum[1] += seg[s].dc[0]; sum[2] += seg[s].dc[1]; sum[3] += seg[s].dc[2];
+    }
+    sum[0] = jp_excl_sum_sat(sum[0], s_tmp);
+    for (int e = 1; e < 4; ++e) sum[e] = jd_excl_sum(sum[e], s_tmp, total);
+    uint32_t flags = 0;
+    for (uint32_t s = s0; s < s1; ++s) {
+      const JpSeg r = seg[s];
+      seg[s].before = sum[0];
+      seg[s].pred[0] = sum[1]; seg[s].pred[1] = sum[2]; seg[s].pred[2] = sum[3];
+      flags |= jp_first_check(*sc, r.entry, r, sum[0], expected);
+      sum[0] = jp_sat_add(sum[0], r.nend);
+      sum[1] += r.dc[0]; sum[2] += r.dc[1]; sum[3] += r.dc[2];
+    }
+    const int bad = __syncthreads_or((int)(flags & 1u));
+    const int found = __syncthreads_or((int)(flags & 2u));     // (and every `before` and predictor is written)
+    accepted = converged && found && !bad;
+    t2 = wall_clock64();
+    if (accepted)                                            // (uniform)
+      for (uint32_t s = tid; s < nseg; s += JD_NT) {
+        const JpSeg e = seg[s];
+        jp_first_write(*sc, *im, p, lo, e.entry, jd_segment_end(s, S, uend), uend, s_h, e.before, e.pred, expected, s_zz, coef);
+      }
+  } else {
+    // the data bytes of every segment and of everything in front of it
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      const uint64_t b = (uint64_t)s * S;
+      seg[s].nbeg = jp_data_bytes(data, b < uend ? (uint32_t)b : uend, jd_segment_end(s, S, uend));
+    }
+    __syncthreads();
+    uint32_t bytes = 0;
+    for (uint32_t s = s0; s < s1; ++s) bytes += seg[s].nbeg;
+    bytes = jd_excl_sum(bytes, s_tmp, total);
+    for (uint32_t s = s0; s < s1; ++s) {
+      seg[s].pred[1] = bytes;
+      bytes += seg[s].nbeg;
+    }
+    __syncthreads();
+    if (kind == JP_DC_REFINE) {
+      t1 = t2 = wall_clock64();
+      accepted = (uint64_t)total * 8u >= expected;
+      if (accepted)
+        for (uint32_t s = tid; s < nseg; s += JD_NT) {
+          const uint64_t b = (uint64_t)s * S;
+          jp_dc_refine_write(*sc, *im, data, b < uend ? (uint32_t)b : uend, jd_segment_end(s, S, uend), seg[s].pred[1], expected, coef);
+        }
+    } else {
+      // phase 1: the history masks of the scan's blocks and the bits set in front of each
+      uint64_t* masks = reinterpret_cast<uint64_t*>(scratch + sub.mask_off);
+      uint32_t* P = reinterpret_cast<uint32_t*>(masks + sc->nmcu);
+      const uint32_t bchunk = (expected + JD_NT - 1) / JD_NT;
+      const uint32_t b0 = min((uint32_t)tid * bchunk, expected), b1 = min(b0 + bchunk, expected);
+      uint32_t bits = 0;
+      for (uint32_t b = b0; b < b1; ++b) {
+        const uint32_t bi = jp_ac_block_index(*im, *sc, b);
+        const uint64_t m = bi < im->nblocks ? jp_refine_mask(coef + (size_t)bi * 64u, ss, se, s_zz) : 0u;
+        masks[b] = m;
+        bits += jp_popc64(m);
+      }
+      bits = jd_excl_sum(bits, s_tmp, total);
+      for (uint32_t b = b0; b < b1; ++b) {
+        P[b] = bits;
+        bits += jp_popc64(masks[b]);
+      }
+      if (tid == 0) P[expected] = total;
+      __syncthreads();
+      t1 = wall_clock64();
+      // phase 2: the exact skim by one lane
+      if (tid == 0) s_ok = jp_refine_skim(*sc, p, lo, uend, s_h[0], masks, P, expected, seg, nseg) ? 1u : 0u;
+      __syncthreads();
+      accepted = s_ok != 0;
+      t2 = wall_clock64();
+      // phase 3: every segment from its true entry up to the next one's
+      if (accepted)                                          // (uniform)
+        for (uint32_t s = tid; s < nseg; s += JD_NT) {
+          const uint32_t n1 = s + 1u < nseg ? seg[s + 1u].before : expected, k1 = s + 1u < nseg ? seg[s + 1u].entry.bsk & 63u : ss;
+          const JpSeg e = seg[s];
+          jp_refine_write(*sc, *im, p, lo, jd_segment_guess(data, s, S, uend).byte, uend, s_h[0], e, n1, k1, masks, expected, s_zz, coef);
+        }
+    }
+  }
+  __syncthreads();                                           // every lane's write is done
+  if (tid == 0) {
+    const uint64_t t3 = wall_clock64();
+    JpSyncInfo info;
+    info.route = 1u + kind; info.nseg = nseg; info.rounds = rounds; info.accepted = accepted ? 1u : 0u;
+    info.ticks[0] = (uint32_t)(t1 - t0); info.ticks[1] = (uint32_t)(t2 - t1); info.ticks[2] = (uint32_t)(t3 - t2); info.pad = 0;
+    y.infos[sub.slot] = info;
+  }
 }
 
 }  // namespace attwarp
@@ -915,12 +1142,32 @@ extern "C" size_t attwarp_jpegdec_scans_table_bytes(const attwarp_jpegdec_image*
   return jpegprog_bytes(B, nscans);
 }
 
-extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
-                                          void* table, size_t table_bytes, int by_level) {
+static size_t jpegprog_sync_bytes(int nscans) { return sizeof(JpSyncHeader) + (size_t)nscans * sizeof(JpSync); }
+
+extern "C" size_t attwarp_jpegdec_scans_table_bytes_ex(const attwarp_jpegdec_image* images, int B, int nscans, int segment_bytes,
+                                                       int max_rounds) {
+  const size_t base = attwarp_jpegdec_scans_table_bytes(images, B, nscans);
+  return base && (segment_bytes != 0 || max_rounds != 0) ? base + jpegprog_sync_bytes(nscans) : base;
+}
+
+// Both planners: segment_bytes = max_rounds = 0 plans no sub-streams and writes the table of attwarp_jpegdec_plan_scans.
+static int jp_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans, void* table,
+                         size_t table_bytes, int by_level, int segment_bytes, int max_rounds, const uint64_t* data_bytes) {
   ATTWARP_REQUIRE(images && scans && table, "jpegdec_plan_scans: null pointer");
   ATTWARP_REQUIRE(B > 0 && B <= JD_MAX_B && nscans >= B && (int64_t)nscans <= (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS,
                   "jpegdec_plan_scans: B=%d, %d scans outside the limits", B, nscans);
-  const size_t need = jpegprog_bytes(B, nscans);
+  const bool substreams = segment_bytes != 0 || max_rounds != 0;
+  if (substreams) {
+    ATTWARP_REQUIRE(segment_bytes >= 32 && segment_bytes <= 512 && (segment_bytes & (segment_bytes - 1)) == 0,
+                    "jpegdec: segment_bytes=%d must be a power of two in 32..512", segment_bytes);
+    ATTWARP_REQUIRE(max_rounds >= 1 && max_rounds <= JD_SUB_MAX_ROUNDS, "jpegdec: max_rounds=%d outside 1..%d", max_rounds, JD_SUB_MAX_ROUNDS);
+    ATTWARP_REQUIRE(data_bytes, "jpegdec_plan_scans_ex: null data_bytes");
+    for (int i = 0; i < nscans; ++i)
+      ATTWARP_REQUIRE(scans[i].image >= 0 && scans[i].image < B && scans[i].stream_off <= images[scans[i].image].stream_len &&
+                          data_bytes[i] <= images[scans[i].image].stream_len - scans[i].stream_off,
+                      "jpegdec_plan_scans_ex: scan %d: data outside the image's", i);
+  }
+  const size_t need = jpegprog_bytes(B, nscans) + (substreams ? jpegprog_sync_bytes(nscans) : 0);
   ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan_scans: table of %zu bytes, %zu needed", table_bytes, need);
   for (int b = 0; b < B; ++b)
     ATTWARP_REQUIRE(images[b].restart_interval == 0, "jpegdec_plan_scans: image %d: the restart interval belongs to the scans", b);
@@ -1031,6 +1278,7 @@ extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, i
     rec[(size_t)i].last = i + 1 == nscans || scans[i + 1].image != scans[i].image;
   }
   int at = 0;
+  std::vector<int> order((size_t)nscans);                     // record -> the scan's position in the caller's array
   for (int l = 0; l < nlevels; ++l) {
     ph.level_scan0[l] = at;
     uint32_t wave = 0;
@@ -1038,14 +1286,83 @@ extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, i
       if ((int)rec[(size_t)i].level == l) {
         rec[(size_t)i].wave0 = wave;
         wave += rec[(size_t)i].nunits;
+        order[(size_t)at] = i;
         std::memcpy(out + at++, &rec[(size_t)i], sizeof(JpScan));
       }
     ph.level_waves[l] = (int32_t)wave;
   }
   ph.level_scan0[nlevels] = at;
+  if (substreams) {
+    // behind everything there was: the per-scan results, then per cut scan its segments and, for an AC refinement, the
+    // history masks (8 bytes per block of the scan) and their prefix sums (4 bytes per block, one more)
+    JpSyncHeader sh;
+    std::memset(&sh, 0, sizeof sh);
+    sh.magic = JP_SYNC_MAGIC;
+    uint64_t soff = jd_align(h.scratch_bytes, 256);
+    sh.info_off = soff;
+    soff += jd_align((uint64_t)nscans * sizeof(JpSyncInfo), 256);
+    std::vector<JpSync> sy((size_t)nscans);
+    uint32_t ncut = 0;
+    int level = 0;
+    for (int q = 0; q < nscans; ++q) {
+      const JpScan& r = rec[(size_t)order[(size_t)q]];
+      const uint64_t len = data_bytes[order[(size_t)q]];
+      for (; level < (int)r.level; ++level) sh.level_cut0[level + 1] = ncut;
+      JpSync& y = sy[(size_t)q];
+      std::memset(&y, 0, sizeof y);
+      y.segment_bytes = (uint32_t)segment_bytes;
+      y.max_rounds = (uint32_t)max_rounds;
+      y.slot = (uint32_t)order[(size_t)q];
+      const uint64_t nseg = (len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes;
+      // a marker-less scan (one unit) whose data is at least two segments long
+      const int kinds = tune(TUNE_JPEGPROG_SYNC_KINDS);        // (the tuning flavour's per-kind timing; -1 in the product)
+      if (r.nunits == 1 && len >= 2u * (uint64_t)segment_bytes && nseg <= JP_SYNC_MAX_SEGS && (kinds < 0 || ((kinds >> r.kind) & 1))) {
+        y.nseg = (uint32_t)nseg;
+        y.seg_off = soff;
+        soff += jd_align(nseg * sizeof(JpSeg), 256);
+        if (r.kind == JP_AC_REFINE) {
+          y.mask_off = soff;
+          soff += jd_align((uint64_t)r.nmcu * 12u + 4u, 256);
+        }
+        sy[ncut++].cut = (uint32_t)q;
+      }
+    }
+    for (; level < nlevels + 1 && level <= ATTWARP_JPEGDEC_MAX_SCANS; ++level) sh.level_cut0[level + 1] = ncut;
+    sh.ncut = ncut;
+    h.scratch_bytes = soff;
+    uint8_t* trailer = t + ph.off_scans + (uint64_t)nscans * sizeof(JpScan);
+    std::memcpy(trailer, &sh, sizeof sh);
+    std::memcpy(trailer + sizeof sh, sy.data(), (size_t)nscans * sizeof(JpSync));
+  }
   std::memcpy(t + jp_header_off(B), &ph, sizeof ph);
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
+                                          void* table, size_t table_bytes, int by_level) {
+  return jp_plan_scans(images, B, scans, nscans, table, table_bytes, by_level, 0, 0, nullptr);
+}
+
+extern "C" int attwarp_jpegdec_plan_scans_ex(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
+                                             void* table, size_t table_bytes, int by_level, int segment_bytes, int max_rounds,
+                                             const uint64_t* data_bytes) {
+  return jp_plan_scans(images, B, scans, nscans, table, table_bytes, by_level, segment_bytes, max_rounds, data_bytes);
+}
+
+extern "C" uint64_t attwarp_jpegdec_scan_info_offset(const void* table_host) {
+  if (!table_host) return 0;
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, table_host, sizeof h);
+  if (h.magic != JD_MAGIC || h.B <= 0 || h.B > JD_MAX_B || h.table_bytes < jp_header_off(h.B) + sizeof(JpHeader)) return 0;
+  JpHeader ph;
+  std::memcpy(&ph, static_cast<const uint8_t*>(table_host) + jp_header_off(h.B), sizeof ph);
+  if (ph.magic != JP_MAGIC || ph.nscans < 1) return 0;
+  const uint64_t at = ph.off_scans + (uint64_t)ph.nscans * sizeof(JpScan);
+  if (h.table_bytes < at + jpegprog_sync_bytes(ph.nscans)) return 0;
+  JpSyncHeader sh;
+  std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + at, sizeof sh);
+  return sh.magic == JP_SYNC_MAGIC ? sh.info_off : 0;
 }
 
 extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
@@ -1063,8 +1380,21 @@ extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* 
   if (const int rc = check_launch("jpegprog_clear_kernel")) return rc;
   hipLaunchKernelGGL(jpegprog_scan_kernel, dim3(ph.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegprog_scan_kernel")) return rc;
+  JpSyncHeader sh;
+  std::memset(&sh, 0, sizeof sh);
+  const uint64_t sync_at = ph.off_scans + (uint64_t)ph.nscans * sizeof(JpScan);
+  if (h.table_bytes >= sync_at + jpegprog_sync_bytes(ph.nscans)) {       // planned with sub-streams
+    std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + sync_at, sizeof sh);
+    bool ok = sh.magic == JP_SYNC_MAGIC && sh.ncut <= (uint32_t)ph.nscans && sh.level_cut0[0] == 0;
+    for (int l = 0; ok && l < ph.nlevels; ++l) ok = sh.level_cut0[l] <= sh.level_cut0[l + 1] && sh.level_cut0[l + 1] <= sh.ncut;
+    ATTWARP_REQUIRE(ok, "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans_ex");
+  }
   for (int l = 0; l < ph.nlevels; ++l) {
     ATTWARP_REQUIRE(ph.level_waves[l] >= 1, "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
+    if (const uint32_t ncut = sh.level_cut0[l + 1] - sh.level_cut0[l]) {  // the level holds a cut scan
+      hipLaunchKernelGGL(jpegprog_substream_kernel, dim3(ncut), dim3(JD_NT), 0, st, td, stream_bytes, sc, l);
+      if (const int rc = check_launch("jpegprog_substream_kernel")) return rc;
+    }
     hipLaunchKernelGGL(jpegprog_entropy_kernel, dim3(ph.level_waves[l]), dim3(WAVE), 0, st, td, stream_bytes, sc, l);
     if (const int rc = check_launch("jpegprog_entropy_kernel")) return rc;
   }

@@ -457,6 +457,23 @@ def _substream_plan(substreams, segment_bytes, max_rounds):
     return sb, mr
 
 
+SCAN_KINDS = ("dc_first", "dc_refine", "ac_first", "ac_refine")
+# The kinds of scan that scan_substreams="auto" cuts: those whose route made JpegFiles.run faster on the marker-less rows of
+# tools/jpegprogsync_bench.py, measured by leaving the kind out of all four.  True cuts every kind.
+AUTO_SCAN_KINDS = ("ac_first", "ac_refine", "dc_refine")
+
+
+def scan_kind(scan: dict) -> str:
+    """The kind of a progressive scan of :func:`parse_jpeg`: one of :data:`SCAN_KINDS`."""
+    return SCAN_KINDS[(2 if scan["ss"] else 0) + (1 if scan["ah"] else 0)]
+
+
+def scan_segments(nbytes: int, units: int, segment_bytes: int) -> int:
+    """Segments ``attwarp_jpegdec_plan_scans_ex`` plans for a scan of ``nbytes`` of entropy data and ``units`` units (0: one lane)."""
+    nseg = -(-nbytes // segment_bytes) if segment_bytes else 0
+    return nseg if segment_bytes and units == 1 and nbytes >= 2 * segment_bytes and nseg <= MAX_SEGMENTS else 0
+
+
 def _put_tables(counts, symbols, tables):
     """(counts, symbols) pairs into the rows of a record's counts [3 or 4, 16] and symbols [3 or 4, 256]."""
     for t, (c, s) in enumerate(tables):
@@ -466,7 +483,7 @@ def _put_tables(counts, symbols, tables):
 
 def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segment_bytes: Optional[int] = None,
          max_rounds: Optional[int] = None, progressive: bool = False, levels: bool = True, all_layouts: bool = False, _parsed=None,
-         all_scans: bool = False):
+         all_scans: bool = False, scan_substreams=False):
     """Host only (no device is touched): files -> ``(parsed, table, header)``: :func:`parse_jpeg` of every file and the table
     ``attwarp_jpegdec_plan_ex`` writes for them, which depends on the headers and the files' lengths alone.  ``substreams``:
     "auto" / True cut every marker-less file of at least two segments into ``segment_bytes`` (a power of two in 32..512,
@@ -486,7 +503,18 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
     ``all_scans=True`` (implies both) also plans a list of progressive files of the other layouts and sequential files of
     several scans (``parsed[i]["scanned"]``; again all of the list) through ``attwarp_jpegdec_plan_layout_scans``: every scan
     of every file over the layout family's image records, one entropy launch per dependency level; ``levels`` as above.  A
-    list without such a file gets the table it gets with ``progressive=True, all_layouts=True``, byte for byte."""
+    list without such a file gets the table it gets with ``progressive=True, all_layouts=True``, byte for byte.
+
+    ``scan_substreams``: "auto" / True (opt-in, default False; "auto" cuts the scan kinds of :data:`AUTO_SCAN_KINDS`, the ones
+    measured to pay, True all four) plan a list of plain progressive files through
+    ``attwarp_jpegdec_plan_scans_ex``: every scan that is ONE unit (no restart markers) and at least two segments of
+    ``segment_bytes`` long (at most 16384 of them) is cut into such segments, its length known from the marker walk, and
+    decoded by one lane per segment in front of its level's entropy launch; ``max_rounds`` caps the rounds
+    of the first passes.  ``parsed[i]["scan_segments"]`` holds the segments planned per scan (0: one lane).  Pixels and
+    statuses do not depend on it; False gives the table of ``attwarp_jpegdec_plan_scans``, byte for byte.  Files planned
+    through the layout records (``all_scans``' own kind) are never cut."""
+    if not (scan_substreams is True or scan_substreams is False or (isinstance(scan_substreams, str) and scan_substreams == "auto")):
+        raise ValueError("jpeg: scan_substreams must be 'auto', True or False")
     if mode not in _lib.JPEGDEC_MODE_IDS or order not in _ORDERS:
         raise ValueError(f"jpeg: mode must be one of {sorted(_lib.JPEGDEC_MODE_IDS)}, order one of {sorted(_ORDERS)}")
     sb, mr = _substream_plan(substreams, segment_bytes, max_rounds)
@@ -555,7 +583,19 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
             _put_tables(srec["counts"][i], srec["symbols"][i], s["tables"])
         size = ("attwarp_jpegdec_scans_table_bytes", rp, B, len(scans))
         planner = ("attwarp_jpegdec_plan_scans", rp, B, srec.ctypes.data, len(scans), TABLE, 1 if levels else 0)
-        sb = 0                                              # progressive files take no sub-streams
+        sb = 0                                              # progressive files take no sub-streams of the whole file
+        ssb = 0
+        cuts = [False] * len(scans)
+        if scan_substreams is not False:                    # their marker-less scans do, each on its own
+            ssb, smr = _substream_plan(True, segment_bytes, max_rounds)
+            # "auto": only the kinds that pay (AUTO_SCAN_KINDS); a scan of another kind is planned with no data, so it is not cut
+            cuts = [scan_substreams is True or scan_kind(s) in AUTO_SCAN_KINDS for _, s in scans]
+            slen = np.array([s["end"] - s["off"] if c else 0 for (_, s), c in zip(scans, cuts)], dtype=np.uint64)
+            size = ("attwarp_jpegdec_scans_table_bytes_ex", rp, B, len(scans), ssb, smr)
+            planner = ("attwarp_jpegdec_plan_scans_ex", rp, B, srec.ctypes.data, len(scans), TABLE, 1 if levels else 0, ssb, smr, slen.ctypes.data)
+        for p in parsed:
+            p["scan_segments"] = [scan_segments(s["end"] - s["off"], s["units"], ssb) if scan_substreams is True or scan_kind(s) in AUTO_SCAN_KINDS
+                                  else 0 for s in p["scans"]]
     table, header = planned_table(size, planner, _lib.JpegDecHeader, ValueError, "jpeg: ", wrap_plan=True)
     for p, n in zip(parsed, lens):
         nseg = -(-n // sb) if sb else 0
@@ -596,14 +636,21 @@ class JpegFiles(FileBatch):
     ``all_scans=True`` is the one switch for a folder somebody else made: it implies both keywords and also takes what both
     refuse, progressive files of the other layouts and sequential files of several scans.  Those are a
     fourth kind with a plan of its own; only files the three other kinds refuse take it, the other parts plan and launch
-    exactly as with ``progressive=True, all_layouts=True``, and views and statuses come back in input order."""
+    exactly as with ``progressive=True, all_layouts=True``, and views and statuses come back in input order.
+
+    ``scan_substreams="auto"`` / True (opt-in) cuts the marker-less scans of the plain progressive files into segments of
+    ``segment_bytes`` decoded by one lane each (:func:`plan`): one more launch in front of the entropy launch
+    of every level that holds such a scan, constant per plan.  Pixels and statuses do not depend on it;
+    :meth:`scan_substream_info` tells what the device did per scan."""
 
     def __init__(self, files, mode: str = "RGB", order: str = "rgb", out: Optional[torch.Tensor] = None, device=None,
                  substreams="auto", segment_bytes: Optional[int] = None, max_rounds: Optional[int] = None,
-                 progressive: bool = False, levels: bool = True, all_layouts: bool = False, all_scans: bool = False):
+                 progressive: bool = False, levels: bool = True, all_layouts: bool = False, all_scans: bool = False, scan_substreams=False):
         files = [file_bytes(f) for f in files]
         if not files:
             raise ValueError("JpegFiles: empty batch")
+        if not (scan_substreams is True or scan_substreams is False or (isinstance(scan_substreams, str) and scan_substreams == "auto")):
+            raise ValueError("jpeg: scan_substreams must be 'auto', True or False")
         self.parts, self.B, self.mode, self.order = None, len(files), mode, order
         progressive, all_layouts = progressive or all_scans, all_layouts or all_scans
         pre = [parse_jpeg(f, i, progressive, all_layouts, all_scans) for i, f in enumerate(files)] if progressive or all_layouts else None
@@ -616,7 +663,7 @@ class JpegFiles(FileBatch):
                 raise ValueError("JpegFiles: a list of baseline and progressive files decodes into two buffers; out must be None"
                                  if 2 not in which else "JpegFiles: a list of several kinds of files decodes into one buffer per kind; out must be None")
             self.parts = [(idx, JpegFiles([files[i] for i in idx], mode, order, None, device, substreams, segment_bytes, max_rounds, kind == 1, levels,
-                                          all_layouts, kind == 3))
+                                          all_layouts, kind == 3, scan_substreams))
                           for kind, idx in split_indices(which, (0, 1, 2, 3))]
             first = self.parts[0][1]
             self._dev, self.segment_bytes, self.max_rounds = first._dev, first.segment_bytes, first.max_rounds
@@ -629,7 +676,8 @@ class JpegFiles(FileBatch):
         self._entry = ("attwarp_jpegdec_decode_scans" if self.progressive else "attwarp_jpegdec_decode_layouts" if self.all_layouts
                        else "attwarp_jpegdec_decode_layout_scans" if self.all_scans else "attwarp_jpegdec_decode")
         self.parsed, self.table_host, self.header = plan(files, mode, order, substreams, segment_bytes, max_rounds, progressive, levels, all_layouts, pre,
-                                                         all_scans)
+                                                         all_scans, scan_substreams)
+        self._scan_info_off = int(_lib.load().attwarp_jpegdec_scan_info_offset(self.table_host.ctypes.data)) if self.progressive else 0
         self.segment_bytes, self.max_rounds = _substream_plan(substreams, segment_bytes, max_rounds)      # (0, 0): off
         self._info_off = int(_lib.load().attwarp_jpegdec_info_offset(self.table_host.ctypes.data))
         self._dev = indexed_device(device, out)
@@ -702,6 +750,37 @@ class JpegFiles(FileBatch):
         return [(int(r[0]), int(r[1]), int(r[2])) for r in raw]
 
     @_per_part
+    def scan_substream_info(self) -> List[list]:
+        """After a :meth:`run` (synchronises): per image a list, in file order, of ``(route, segments, rounds, accepted)`` per
+        scan as the device left them: route 0 for a scan on one lane, else 1 DC first pass, 2 DC refinement, 3 AC first pass,
+        4 AC refinement; the segments planned; the rounds of a first pass; 1 if the segments decoded the scan, 0 if the
+        one-lane route did.  A plan without ``scan_substreams`` has no such records: all zeros; an image that is not a plain
+        progressive file has no scans here: an empty list.  For measurements and tests."""
+        if not self.progressive:
+            return [[] for _ in self.parsed]
+        return self._scan_records(slice(0, 4))
+
+    def _scan_records(self, fields):
+        n = sum(len(p["scans"]) for p in self.parsed)
+        raw = np.zeros((n, 8), np.uint32)
+        if self._scan_info_off:
+            raw = self.scratch[self._scan_info_off:self._scan_info_off + n * 32].cpu().numpy().view(np.uint32).reshape(n, 8)
+        out, at = [], 0
+        for p in self.parsed:
+            out.append([tuple(int(x) for x in r[fields]) for r in raw[at:at + len(p["scans"])]])
+            at += len(p["scans"])
+        return out
+
+    @_per_part
+    def scan_substream_ticks(self) -> List[list]:
+        """After a :meth:`run` (synchronises): per image and scan, beside :meth:`scan_substream_info`, the 100 MHz ticks its
+        workgroup spent in its three parts: a first pass: rounds, sums and checks, write; a refinement: counts and masks,
+        skim (a DC refinement: none), write.  Zeros for a scan on one lane.  For measurements."""
+        if not self.progressive:
+            return [[] for _ in self.parsed]
+        return self._scan_records(slice(4, 7))
+
+    @_per_part
     def restarts(self) -> List[int]:
         """After a :meth:`run` (synchronises): restart markers the device found in front of each image's data end; units - 1
         in a file that decodes (a progressive file: over all its scans).  For measurements and tests."""
@@ -722,24 +801,27 @@ class JpegFiles(FileBatch):
 
 
 def decode_jpeg(files, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False,
-                all_layouts: bool = False, all_scans: bool = False) -> List[torch.Tensor]:
+                all_layouts: bool = False, all_scans: bool = False, scan_substreams=False,
+                segment_bytes: Optional[int] = None) -> List[torch.Tensor]:
     """JPEG files (bytes-like or paths) -> uint8 [H_i, W_i, C] GPU tensors, views into one packed buffer.  OSError names the
     first file the device rejects (Pillow raises OSError for such files too); ValueError for what is not decoded at all.
     ``substreams``: see :func:`plan`.  ``progressive=True`` also decodes progressive files, alone or among baseline files
     (:class:`JpegFiles`); without it such a file raises ValueError.  ``all_layouts=True`` also decodes CMYK / YCCK files,
     RGB-coded files and every sampling layout libjpeg decodes; without it such a file raises ValueError.  ``all_scans=True``
     implies both and also decodes progressive files of those layouts and sequential files of several scans: the one switch
-    for a folder somebody else made."""
-    views, status = JpegFiles(files, mode, order, device=device, substreams=substreams, progressive=progressive, all_layouts=all_layouts,
-                              all_scans=all_scans).run()
+    for a folder somebody else made.  ``scan_substreams``, ``segment_bytes``: see :func:`plan`; pixels do not depend on them."""
+    views, status = JpegFiles(files, mode, order, device=device, substreams=substreams, segment_bytes=segment_bytes, progressive=progressive,
+                              all_layouts=all_layouts, all_scans=all_scans, scan_substreams=scan_substreams).run()
     raise_first_broken(status, STATUS_NAMES, "jpeg")
     return views
 
 
 def read_jpeg(paths, mode: str = "RGB", order: str = "rgb", device=None, substreams="auto", progressive: bool = False,
-              all_layouts: bool = False, all_scans: bool = False) -> List[torch.Tensor]:
+              all_layouts: bool = False, all_scans: bool = False, scan_substreams=False,
+              segment_bytes: Optional[int] = None) -> List[torch.Tensor]:
     """:func:`decode_jpeg` of the files at ``paths``."""
-    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device, substreams, progressive, all_layouts, all_scans)
+    return decode_jpeg([os.fspath(p) for p in paths], mode, order, device, substreams, progressive, all_layouts, all_scans, scan_substreams,
+                       segment_bytes)
 
 
 # ---- encoding ---------------------------------------------------------------------------------------------------------------

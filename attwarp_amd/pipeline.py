@@ -1424,7 +1424,8 @@ def upload_png_files(files_or_paths, device=None, all_formats=False, inflate="la
     return png.decode_png(files_or_paths, "RGB", "rgb", device, all_formats, inflate)
 
 
-def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressive=False, all_layouts=False, all_scans=False):
+def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressive=False, all_layouts=False, all_scans=False,
+                      scan_substreams=False, segment_bytes=None):
     """:func:`upload_images` for a batch still in its JPEG files (bytes-like or paths; the TextVQA / GQA images the drivers and
     the MarginalNet loader open, or anyone's baseline JPEG): the COMPRESSED bytes go up in one transfer and are decoded on
     the GPU (attwarp_amd.jpeg.decode_jpeg) -> list of uint8 [H_i,W_i,3] RGB GPU tensors, views into one packed buffer, as
@@ -1434,16 +1435,20 @@ def upload_jpeg_files(files_or_paths, device=None, substreams="auto", progressiv
     ``all_layouts=True`` also takes CMYK / YCCK files, RGB-coded files and every sampling layout libjpeg decodes (4:4:0,
     4:1:1 ...; jpeg.JpegFiles); without it they raise ValueError.
     ``all_scans=True`` is the one switch for a folder somebody else made: both keywords, and also progressive files of those
-    layouts (what web optimisers write from CMYK and rotated camera pictures) and sequential files of several scans."""
-    return jpeg.decode_jpeg(files_or_paths, "RGB", "rgb", device, substreams, progressive, all_layouts, all_scans)
+    layouts (what web optimisers write from CMYK and rotated camera pictures) and sequential files of several scans.
+    ``scan_substreams="auto"`` / True (opt-in) cuts the marker-less scans of plain progressive files into ``segment_bytes``
+    decoded by one lane each (jpeg.plan); pixels and statuses do not depend on it."""
+    return jpeg.decode_jpeg(files_or_paths, "RGB", "rgb", device, substreams, progressive, all_layouts, all_scans, scan_substreams,
+                            segment_bytes)
 
 
 def upload_image_files(files_or_paths, device=None, substreams="auto", progressive=False, all_formats=False, all_layouts=False,
-                       all_scans=False, inflate="lane"):
+                       all_scans=False, inflate="lane", scan_substreams=False, segment_bytes=None):
     """A batch of image files of either kind (bytes-like or paths), each sent by its signature to the PNG or the JPEG decoder
     (:func:`upload_png_files`, :func:`upload_jpeg_files`): one transfer and one decode per kind -> the uint8 [H_i,W_i,3] RGB
     GPU tensors in input order.  ValueError for a file that is neither.  ``progressive``, ``all_layouts``, ``all_scans``: see
-    :func:`upload_jpeg_files`; ``all_formats``, ``inflate``: see :func:`upload_png_files`."""
+    :func:`upload_jpeg_files`; ``all_formats``, ``inflate``: see :func:`upload_png_files`; ``scan_substreams``, ``segment_bytes``: see
+    :func:`upload_jpeg_files`."""
     files = [file_bytes(f) for f in files_or_paths]
     kinds = []
     for i, f in enumerate(files):
@@ -1454,7 +1459,7 @@ def upload_image_files(files_or_paths, device=None, substreams="auto", progressi
             kinds.append("jpeg")
         else:
             raise ValueError(f"upload_image_files: file {i} is neither a PNG nor a JPEG file")
-    decode = {"png": lambda f, d: upload_png_files(f, d, all_formats, inflate), "jpeg": lambda f, d: upload_jpeg_files(f, d, substreams, progressive, all_layouts, all_scans)}
+    decode = {"png": lambda f, d: upload_png_files(f, d, all_formats, inflate), "jpeg": lambda f, d: upload_jpeg_files(f, d, substreams, progressive, all_layouts, all_scans, scan_substreams, segment_bytes)}
     return per_kind(files, kinds, ("png", "jpeg"), lambda kind, group: decode[kind](group, device))
 
 

@@ -1076,6 +1076,37 @@ ATTWARP_API int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, 
                        void* table, size_t table_bytes, int by_level);
 ATTWARP_API int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
                        uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
+/* The same with SUB-STREAMS PER SCAN: attwarp_jpegdec_plan_scans plus segment_bytes (a power of two in
+ * 32..512) and max_rounds (1..65536), as attwarp_jpegdec_plan_ex is to attwarp_jpegdec_plan, and data_bytes[nscans]: the
+ * bytes of each scan's entropy data, up to the first FF that neither 00 nor D0..D7 follows (the scan record carries no
+ * length).  (0, 0, NULL) is attwarp_jpegdec_plan_scans and writes the same table, byte for byte.  A scan of ONE unit whose
+ * data is at least two segments long (at most 16384 of them) is cut; attwarp_jpegdec_decode_scans then launches, per level
+ * that holds a cut scan and in front of that level's entropy launch, jpegprog_substream_kernel with one workgroup of 256
+ * lanes per cut scan, segment s on lane s mod 256: constant launches per plan.  Routes: a DC or AC first pass runs the rounds
+ * of attwarp_jpegdec_plan_ex over its own blocks (one DC symbol; the AC symbols of the band, an EOB run ending its blocks at
+ * once) and is accepted under the same rule; a DC refinement counts the segments' data bytes (block n's bit is data bit n)
+ * and is accepted when the bits cover the blocks; an AC refinement is skimmed exactly by one lane over bit masks of the
+ * coefficients with history (no coefficient touched), which notes every segment's true entry, and is accepted unless the
+ * one-lane route would report a status; then all lanes write.  The entropy launch skips an accepted scan and decodes every
+ * other one exactly as without sub-streams; the sub-stream path never sets a status and stores no coefficient before its
+ * scan is accepted, so status[] and the pixels do not depend on the plan.
+ * Table: behind the scan records a header and one 64-byte record per scan; attwarp_jpegdec_scans_table_bytes_ex gives the
+ * size.  Scratch, behind everything the other kernels use: per scan, in the order of scans[], an attwarp_jpegdec_scan_info (32 bytes)
+ * at attwarp_jpegdec_scan_info_offset (0: the table has none), written on every run, first by the clear launch; per cut
+ * scan 64 bytes per segment and, for an AC refinement, 12 bytes per block of the scan (masks and prefix sums). */
+typedef struct attwarp_jpegdec_scan_info {
+  uint32_t route;                                  /* 0: one lane; 1 DC first pass, 2 DC refinement, 3 AC first pass, 4 AC refinement */
+  uint32_t segments, rounds, accepted;
+  uint32_t ticks[3];                               /* FOR MEASUREMENTS ONLY (tools/jpegprogsync_bench.py; four clock reads by one lane per
+                                                      workgroup): 100 MHz ticks of its workgroup's three parts: a first pass: rounds,
+                                                      sums and checks, write; a refinement: counts and masks, skim (DC: none), write */
+  uint32_t pad;
+} attwarp_jpegdec_scan_info;
+ATTWARP_API size_t attwarp_jpegdec_scans_table_bytes_ex(const attwarp_jpegdec_image* images, int B, int nscans, int segment_bytes,
+                       int max_rounds);
+ATTWARP_API int attwarp_jpegdec_plan_scans_ex(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
+                       void* table, size_t table_bytes, int by_level, int segment_bytes, int max_rounds, const uint64_t* data_bytes);
+ATTWARP_API uint64_t attwarp_jpegdec_scan_info_offset(const void* table_host);
 
 /* ---- every LAYOUT of a sequential file (jpegdec.hip, jpegfmt_blocks.hpp): a second family beside
  * attwarp_jpegdec_plan / attwarp_jpegdec_decode, with records of its own, for what those refuse.  SOF0 / SOF1, 8 bits, one
