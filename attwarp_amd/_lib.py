@@ -160,6 +160,8 @@ SIGNATURES = {
     "attwarp_png_bound": (c_size_t, [c_int, c_int, c_int]),
     "attwarp_png_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_png_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
+    "attwarp_png_table_bytes_ex": (c_size_t, [c_void_p, c_int, c_void_p]),
+    "attwarp_png_plan_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
     "attwarp_png_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # PNG files decoded on the device (pngdec.hip)
     "attwarp_pngdec_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
@@ -209,6 +211,7 @@ RGB, BGR = 0, 1
 # attwarp_png_*: filters and limits (ATTWARP_PNG_* of include/attwarp.h)
 PNG_FILTER_IDS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
 PNG_SEG_BYTES, PNG_MAX_ROW_BYTES, PNG_SEG_MAX_ROWS, PNG_FILE_OVERHEAD = 24576, 24576, 1024, 68
+PNG_MATCH_IDS = {"rle": 0, "lz": 1}
 # attwarp_pngdec_*: modes, limits and status codes (ATTWARP_PNGDEC_* of include/attwarp.h)
 PNGDEC_MODE_IDS = {"RGB": 0, "L": 1, "keep": 2}
 PNGDEC_MAX_UNITS, PNGDEC_MAX_ROW_BYTES = 256, 49152

@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "png_blocks.hpp"
+#include "png_lz_blocks.hpp"
 
 namespace attwarp {
 
@@ -152,35 +152,126 @@ struct PngRun {
   }
 };
 
-__global__ __launch_bounds__(PNG_NT) void png_encode_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
-  __shared__ uint32_t s_filt[PNG_FILT_WORDS];
-  __shared__ uint32_t s_out[PNG_OUT_WORDS];
-  __shared__ uint32_t s_hist[PNG_SYMS_PAD], s_freq[PNG_SYMS_PAD], s_lf[PNG_SYMS_PAD], s_nf[PNG_SYMS_PAD], s_code[PNG_SYMS_PAD];
-  __shared__ uint16_t s_parent[2 * PNG_SYMS_PAD];
-  __shared__ uint8_t s_len[PNG_SYMS_PAD];
-  __shared__ uint32_t s_crc[256], s_tmp[PNG_NT], s_pow[32], s_blc[16];
-  __shared__ uint8_t s_rowf[ATTWARP_PNG_SEG_MAX_ROWS];
-  __shared__ uint32_t s_n, s_maxd, s_bits, s_x;
-  __shared__ unsigned long long s_a1, s_a2;
+// The segment a workgroup of an encode launch takes.  A table without LZ images (header.reserved == 0) has no order list:
+// workgroup k takes segment k.  Otherwise the list behind the segments names the RLE segments first, then the LZ ones;
+// `base` is where the launch's part starts.
+__device__ __forceinline__ int png_segment_of(const uint8_t* table, const attwarp_png_header* hdr, int k, int base = 0) {
+  if (hdr->reserved == 0) return k;
+  return reinterpret_cast<const int32_t*>(table + hdr->off_segs + (uint64_t)hdr->nseg * sizeof(PngSeg))[base + k];
+}
 
+// Stage 4 of both encode kernels: code lengths of at most 15 bits for nsym <= PNG_SYMS symbols, at least two of them used:
+// Huffman over (frequency, symbol) order; too deep -> halve the frequencies and rebuild.  Thread t owns symbols t and t + PNG_NT.
+// At most 17 rounds: frequencies are below 2^16, after 16 halvings all are 1 and a tree of 286 equal leaves is 9 deep.  Ends on a
+// barrier.
+struct PngTree {
+  uint32_t *freq, *lf, *nf;
+  uint16_t* parent;
+  uint32_t *n, *maxd;
+};
+__device__ __forceinline__ void png_code_lengths(const uint32_t* hist, int nsym, uint8_t* lens, const PngTree& w) {
   const int tid = threadIdx.x;
-  const attwarp_png_header* hdr = reinterpret_cast<const attwarp_png_header*>(table);
-  const PngSeg sg = reinterpret_cast<const PngSeg*>(table + hdr->off_segs)[blockIdx.x];
-  const PngImageDev* imp = reinterpret_cast<const PngImageDev*>(table + hdr->off_images) + sg.image;
-  const int N = sg.n, RB = imp->row_bytes, WC = RB - 1, ftype = imp->filter;
-  PngSrc src;
-  src.p = (const PNG_G uint8_t*)imp->src;
-  src.pitch = imp->pitch;
-  src.C = imp->C;
-  src.swap = imp->swap != 0;
+  const int sy[2] = {tid, tid + PNG_NT};
+  for (int k = 0; k < 2; ++k)
+    if (sy[k] < nsym) w.freq[sy[k]] = hist[sy[k]];
+  __syncthreads();
+  for (int round = 0; round < 17; ++round) {
+    if (tid == 0) { *w.n = 0; *w.maxd = 0; }
+    __syncthreads();
+    int rank[2] = {-1, -1};
+    for (int k = 0; k < 2; ++k) {
+      const int s = sy[k];
+      const uint32_t f = s < nsym ? w.freq[s] : 0u;
+      if (f) {
+        int r = 0;
+        for (int o = 0; o < nsym; ++o) {
+          const uint32_t fo = w.freq[o];
+          r += (fo != 0u) && (fo < f || (fo == f && o < s));
+        }
+        rank[k] = r;
+        w.lf[r] = f;
+        atomicAdd(w.n, 1u);
+      }
+    }
+    __syncthreads();
+    const int n = (int)*w.n;
+    if (tid == 0) {
+      int li = 0, nj = 0, nn = 0;
+      uint32_t lf = w.lf[0], nf = 0;
+      for (int k = 0; k < n - 1; ++k) {
+        uint32_t fsum = 0;
+        for (int pick = 0; pick < 2; ++pick) {
+          int id;
+          if (li < n && (nj >= nn || lf <= nf)) {
+            id = li; fsum += lf; ++li;
+            lf = li < n ? w.lf[li] : 0u;
+          } else {
+            id = n + nj; fsum += nf; ++nj;
+            nf = nj < nn ? w.nf[nj] : 0u;
+          }
+          w.parent[id] = (uint16_t)(n + k);
+        }
+        w.nf[k] = fsum;
+        if (nj == nn) nf = fsum;
+        nn = k + 1;
+      }
+    }
+    __syncthreads();
+    const int root = 2 * n - 2;
+    for (int k = 0; k < 2; ++k) {
+      if (sy[k] >= nsym) continue;
+      int d = 0;
+      if (rank[k] >= 0) {
+        int id = rank[k];
+        for (int step = 0; step < PNG_SYMS && id != root; ++step) { id = w.parent[id]; ++d; }
+        atomicMax(w.maxd, (uint32_t)d);
+      }
+      lens[sy[k]] = (uint8_t)d;
+    }
+    __syncthreads();
+    if (*w.maxd <= 15u) break;
+    for (int k = 0; k < 2; ++k)
+      if (sy[k] < nsym) { const uint32_t f = w.freq[sy[k]]; w.freq[sy[k]] = f ? (f + 1u) >> 1 : 0u; }
+    __syncthreads();
+  }
+  __syncthreads();
+}
 
-  for (int i = tid; i < PNG_OUT_WORDS; i += PNG_NT) s_out[i] = 0;
-  for (int i = tid; i < PNG_SYMS_PAD; i += PNG_NT) { s_hist[i] = 0; s_len[i] = 0; s_code[i] = 0; }
-  s_crc[tid] = crc_table_entry((uint32_t)tid);
-  if (tid < 32) s_pow[tid] = hdr->crc_pow8[tid];
-  if (tid == 0) { s_bits = 0; s_x = 0; s_a1 = 0; s_a2 = 0; }
+// Canonical codes of nsym <= PNG_SYMS lengths, reversed for the LSB-first writer, packed as code | length << 16.  blc: 16 words.
+__device__ __forceinline__ void png_canonical_codes(const uint8_t* lens, int nsym, uint32_t* codes, uint32_t* blc) {
+  const int tid = threadIdx.x;
+  const int sy[2] = {tid, tid + PNG_NT};
+  if (tid < 16) blc[tid] = 0;
+  __syncthreads();
+  for (int k = 0; k < 2; ++k)
+    if (sy[k] < nsym && lens[sy[k]]) atomicAdd(&blc[lens[sy[k]]], 1u);
+  __syncthreads();
+  uint32_t next[16];
+  {
+    uint32_t code = 0;
+    next[0] = 0;
+    for (int b = 1; b < 16; ++b) { code = (code + (b > 1 ? blc[b - 1] : 0u)) << 1; next[b] = code; }
+  }
+  for (int k = 0; k < 2; ++k) {
+    const int s = sy[k];
+    if (s >= nsym) continue;
+    const uint32_t l = lens[s];
+    uint32_t packed = 0;
+    if (l) {
+      uint32_t c = 0;
+      for (int b = 1; b < 16; ++b) c = (l == (uint32_t)b) ? next[b] : c;
+      for (int o = 0; o < s; ++o) c += lens[o] == l;
+      packed = (__brev(c) >> (32u - l)) | (l << 16);
+    }
+    codes[s] = packed;
+  }
+  __syncthreads();
+}
 
-  // ---- 1. filter the segment's rows into LDS ------------------------------------------------------------------------------
+// Stage 1 of both encode kernels: the segment's rows, filtered, into LDS (one pad dword per chunk of PNG_CH bytes).
+__device__ __forceinline__ void png_filter_segment(const PngSrc& src, const PngSeg& sg, int ftype, int RB, int WC, uint32_t* s_filt,
+                                                   uint8_t* s_rowf) {
+  const int tid = threadIdx.x;
   if (ftype == ATTWARP_PNG_ADAPTIVE) {                     // per row: the filter with the smallest sum of |int8|, one wave per row
     const int lane = tid & (WAVE - 1);
     for (int lr = tid / WAVE; lr < sg.nrows; lr += PNG_NT / WAVE) {
@@ -227,6 +318,71 @@ __global__ __launch_bounds__(PNG_NT) void png_encode_kernel(const uint8_t* __res
     }
   }
   __syncthreads();
+}
+
+// Last stage of both encode kernels: CRC-32 of the segment's deflate bytes (one table CRC per lane over equal slices, shifted to
+// the end, XORed), the bytes to the segment's scratch slot, the segment's record (pad: the route, for PngBatch.routes()).
+__device__ __forceinline__ void png_finish_segment(uint32_t out_len, uint32_t route, int seg, const PngSeg& sg, uint8_t* scratch,
+                                                   const uint32_t* s_out, const uint32_t* s_crc, const uint32_t* s_pow, uint32_t* s_x,
+                                                   const unsigned long long& s_a1, const unsigned long long& s_a2) {
+  const int tid = threadIdx.x;
+  const uint8_t* out8 = reinterpret_cast<const uint8_t*>(s_out);
+  {
+    const uint32_t L = (out_len + PNG_NT - 1) / PNG_NT;
+    const uint32_t b0 = min(out_len, (uint32_t)tid * L), b1 = min(out_len, b0 + L);
+    uint32_t c = 0xffffffffu;
+    for (uint32_t i = b0; i < b1; ++i) c = s_crc[(c ^ out8[i]) & 255u] ^ (c >> 8);
+    c = ~c;
+    if (b0 == b1) c = 0;
+    c = crc_mulmod(c, crc_xpow8(out_len - b1, s_pow));
+    for (int o = WAVE / 2; o > 0; o >>= 1) c ^= __shfl_xor(c, o, WAVE);
+    if ((tid & (WAVE - 1)) == 0) atomicXor(s_x, c);
+  }
+  uint32_t* dst = reinterpret_cast<uint32_t*>(scratch + sg.scratch_off);
+  for (uint32_t i = tid; i < (out_len + 3u) / 4u; i += PNG_NT) dst[i] = s_out[i];
+  __syncthreads();
+  if (tid == 0) {
+    PngSegOut o;
+    o.len = out_len;
+    o.crc = *s_x;
+    o.s1 = (uint32_t)(s_a1 % PNG_ADLER);
+    o.s2 = (uint32_t)(s_a2 % PNG_ADLER);
+    o.pre = 0; o.pad = route;
+    reinterpret_cast<PngSegOut*>(scratch)[seg] = o;
+  }
+}
+
+__global__ __launch_bounds__(PNG_NT) void png_encode_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_filt[PNG_FILT_WORDS];
+  __shared__ uint32_t s_out[PNG_OUT_WORDS];
+  __shared__ uint32_t s_hist[PNG_SYMS_PAD], s_freq[PNG_SYMS_PAD], s_lf[PNG_SYMS_PAD], s_nf[PNG_SYMS_PAD], s_code[PNG_SYMS_PAD];
+  __shared__ uint16_t s_parent[2 * PNG_SYMS_PAD];
+  __shared__ uint8_t s_len[PNG_SYMS_PAD];
+  __shared__ uint32_t s_crc[256], s_tmp[PNG_NT], s_pow[32], s_blc[16];
+  __shared__ uint8_t s_rowf[ATTWARP_PNG_SEG_MAX_ROWS];
+  __shared__ uint32_t s_n, s_maxd, s_bits, s_x;
+  __shared__ unsigned long long s_a1, s_a2;
+
+  const int tid = threadIdx.x;
+  const attwarp_png_header* hdr = reinterpret_cast<const attwarp_png_header*>(table);
+  const int seg = png_segment_of(table, hdr, (int)blockIdx.x);
+  const PngSeg sg = reinterpret_cast<const PngSeg*>(table + hdr->off_segs)[seg];
+  const PngImageDev* imp = reinterpret_cast<const PngImageDev*>(table + hdr->off_images) + sg.image;
+  const int N = sg.n, RB = imp->row_bytes, WC = RB - 1, ftype = imp->filter;
+  PngSrc src;
+  src.p = (const PNG_G uint8_t*)imp->src;
+  src.pitch = imp->pitch;
+  src.C = imp->C;
+  src.swap = imp->swap != 0;
+
+  for (int i = tid; i < PNG_OUT_WORDS; i += PNG_NT) s_out[i] = 0;
+  for (int i = tid; i < PNG_SYMS_PAD; i += PNG_NT) { s_hist[i] = 0; s_len[i] = 0; s_code[i] = 0; }
+  s_crc[tid] = crc_table_entry((uint32_t)tid);
+  if (tid < 32) s_pow[tid] = hdr->crc_pow8[tid];
+  if (tid == 0) { s_bits = 0; s_x = 0; s_a1 = 0; s_a2 = 0; }
+
+  // ---- 1. filter the segment's rows into LDS ------------------------------------------------------------------------------
+  png_filter_segment(src, sg, ftype, RB, WC, s_filt, s_rowf);
 
   // ---- 2. run starts, Adler partial sums -----------------------------------------------------------------------------------
   const int lo = min(N, tid * PNG_CH), hi = min(N, lo + PNG_CH);
@@ -267,72 +423,9 @@ __global__ __launch_bounds__(PNG_NT) void png_encode_kernel(const uint8_t* __res
   if (tid == 0) atomicAdd(&s_hist[256], 1u);               // end of block
   __syncthreads();
 
-  // ---- 4. code lengths of at most 15 bits: Huffman over (frequency, symbol) order; too deep -> halve and rebuild -----------------
-  // Thread t owns symbols t and t + 256.  At most 17 rounds: frequencies are below 2^16, after 16 halvings all are 1 and the
-  // tree of 286 equal leaves is 9 deep.
+  // ---- 4. code lengths of at most 15 bits ----------------------------------------------------------------------------------------
   const int sy[2] = {tid, tid + PNG_NT};
-  for (int k = 0; k < 2; ++k)
-    if (sy[k] < PNG_SYMS_PAD) s_freq[sy[k]] = sy[k] < PNG_SYMS ? s_hist[sy[k]] : 0u;
-  __syncthreads();
-  for (int round = 0; round < 17; ++round) {
-    if (tid == 0) { s_n = 0; s_maxd = 0; }
-    __syncthreads();
-    int rank[2] = {-1, -1};
-    for (int k = 0; k < 2; ++k) {
-      const int s = sy[k];
-      const uint32_t f = s < PNG_SYMS ? s_freq[s] : 0u;
-      if (f) {
-        int r = 0;
-        for (int o = 0; o < PNG_SYMS; ++o) {
-          const uint32_t fo = s_freq[o];
-          r += (fo != 0u) && (fo < f || (fo == f && o < s));
-        }
-        rank[k] = r;
-        s_lf[r] = f;
-        atomicAdd(&s_n, 1u);
-      }
-    }
-    __syncthreads();
-    const int n = (int)s_n;                                // >= 2: end of block and at least one literal
-    if (tid == 0) {                                        // two queues: sorted leaves, internal nodes in creation order
-      int li = 0, nj = 0, nn = 0;
-      uint32_t lf = s_lf[0], nf = 0;
-      for (int k = 0; k < n - 1; ++k) {
-        uint32_t fsum = 0;
-        for (int pick = 0; pick < 2; ++pick) {
-          int id;
-          if (li < n && (nj >= nn || lf <= nf)) {          // (a leaf before an internal node of the same weight)
-            id = li; fsum += lf; ++li;
-            lf = li < n ? s_lf[li] : 0u;
-          } else {
-            id = n + nj; fsum += nf; ++nj;
-            nf = nj < nn ? s_nf[nj] : 0u;
-          }
-          s_parent[id] = (uint16_t)(n + k);
-        }
-        s_nf[k] = fsum;
-        if (nj == nn) nf = fsum;                           // (the node queue was empty: the new node is its head)
-        nn = k + 1;
-      }
-    }
-    __syncthreads();
-    const int root = 2 * n - 2;
-    for (int k = 0; k < 2; ++k) {
-      if (sy[k] >= PNG_SYMS_PAD) continue;
-      int d = 0;
-      if (rank[k] >= 0) {
-        int id = rank[k];
-        for (int step = 0; step < PNG_SYMS && id != root; ++step) { id = s_parent[id]; ++d; }
-        atomicMax(&s_maxd, (uint32_t)d);
-      }
-      s_len[sy[k]] = (uint8_t)d;
-    }
-    __syncthreads();
-    if (s_maxd <= 15u) break;                              // (uniform: every thread reads the same word)
-    for (int k = 0; k < 2; ++k)
-      if (sy[k] < PNG_SYMS) { const uint32_t f = s_freq[sy[k]]; s_freq[sy[k]] = f ? (f + 1u) >> 1 : 0u; }
-    __syncthreads();
-  }
+  png_code_lengths(s_hist, PNG_SYMS, s_len, PngTree{s_freq, s_lf, s_nf, s_parent, &s_n, &s_maxd});
 
   // ---- 5. size of the dynamic block; canonical codes ------------------------------------------------------------------------------
   {
@@ -349,7 +442,6 @@ __global__ __launch_bounds__(PNG_NT) void png_encode_kernel(const uint8_t* __res
       }
     }
     atomicAdd(&s_bits, bits);
-    if (tid < 16) s_blc[tid] = 0;
   }
   __syncthreads();
   const uint32_t dyn_bits = PNG_HEADER_BITS + s_bits;
@@ -369,29 +461,7 @@ __global__ __launch_bounds__(PNG_NT) void png_encode_kernel(const uint8_t* __res
     }
     out_len = (uint32_t)N + 5u;
   } else {
-    for (int k = 0; k < 2; ++k)
-      if (sy[k] < PNG_SYMS && s_len[sy[k]]) atomicAdd(&s_blc[s_len[sy[k]]], 1u);
-    __syncthreads();
-    uint32_t next[16];
-    {
-      uint32_t code = 0;
-      next[0] = 0;
-      for (int b = 1; b < 16; ++b) { code = (code + (b > 1 ? s_blc[b - 1] : 0u)) << 1; next[b] = code; }
-    }
-    for (int k = 0; k < 2; ++k) {
-      const int s = sy[k];
-      if (s >= PNG_SYMS) continue;
-      const uint32_t l = s_len[s];
-      uint32_t packed = 0;
-      if (l) {
-        uint32_t c = 0;
-        for (int b = 1; b < 16; ++b) c = (l == (uint32_t)b) ? next[b] : c;
-        for (int o = 0; o < s; ++o) c += s_len[o] == l;
-        packed = (__brev(c) >> (32u - l)) | (l << 16);     // reversed for the LSB-first writer
-      }
-      s_code[s] = packed;
-    }
-    __syncthreads();
+    png_canonical_codes(s_len, PNG_SYMS, s_code, s_blc);
     // block header: BFINAL 0, BTYPE 10, HLIT 286, HDIST 1, HCLEN 19; a flat 4-bit code-length code for 0 .. 15 (16, 17, 18
     // unused come first in the transmission order); 286 + 1 lengths of 4 bits each, the distance code's being 1
     if (tid == 0) {
@@ -457,30 +527,298 @@ __global__ __launch_bounds__(PNG_NT) void png_encode_kernel(const uint8_t* __res
   }
   __syncthreads();
 
-  // ---- 6. CRC-32 of the segment's bytes (one table CRC per lane over equal slices, shifted to the end, XORed); write out ------
+  // ---- 6. CRC-32 of the segment's bytes; write out -------------------------------------------------------------------------------
+  png_finish_segment(out_len, stored ? PNG_ROUTE_STORED : PNG_ROUTE_RLE, seg, sg, scratch, s_out, s_crc, s_pow, &s_x, s_a1, s_a2);
+}
+
+// ---- the second token route: matches at any distance inside the segment (tests/pnglz_ref.py restates it) ---------
+// The segment's bytes in LDS (the chunk layout above): aligned dword q, byte i, the four bytes at i (i + 4 <= N).
+__device__ __forceinline__ uint32_t png_seg_word(const uint32_t* f, int q) { return f[q + q / PNG_CHW]; }
+__device__ __forceinline__ uint32_t png_seg_byte(const uint32_t* f, int i) { return (png_seg_word(f, i >> 2) >> (8 * (i & 3))) & 255u; }
+__device__ __forceinline__ uint32_t png_seg_ld32(const uint32_t* f, int i) {
+  const int q = i >> 2, sh = 8 * (i & 3);
+  const uint32_t a = png_seg_word(f, q);
+  return sh ? (a >> sh) | (png_seg_word(f, q + 1) << (32 - sh)) : a;
+}
+// common prefix of the bytes at i and at c < i, at most cap <= min(258, N - i): at most 64 dword rounds and 3 bytes
+__device__ __forceinline__ uint32_t png_match_len(const uint32_t* f, int i, int c, uint32_t cap) {
+  uint32_t k = 0;
+  for (; k + 4u <= cap; k += 4u) {
+    const uint32_t x = png_seg_ld32(f, i + (int)k) ^ png_seg_ld32(f, c + (int)k);
+    if (x) return k + ((uint32_t)__builtin_ctz(x) >> 3);
+  }
+  for (; k < cap; ++k)
+    if (png_seg_byte(f, i + (int)k) != png_seg_byte(f, c + (int)k)) break;
+  return k;
+}
+
+// Where position i's token word lives: one pad word per chunk, as the filtered bytes (a wave walking its chunks hits 64 banks).
+__device__ __forceinline__ int png_tok_at(int i) { return i + i / PNG_CH; }
+
+// The LZ tokens that START in [e, hi), e being where the greedy chain enters the chunk (>= hi: none): fl(value) for a
+// literal, fm(length, distance) for a match.  At most hi - e <= PNG_CH rounds.
+template <class FL, class FM>
+__device__ __forceinline__ void png_lz_walk(const uint32_t* tok, const uint32_t* f, int e, int hi, FL&& fl, FM&& fm) {
+  for (int i = e; i < hi;) {
+    const uint32_t t = tok[png_tok_at(i)], dist = png_lz_token_dist(t);
+    if (dist == 0) { fl(png_seg_byte(f, i)); ++i; }
+    else { const uint32_t len = png_lz_token_len(t); fm(len, dist); i += (int)len; }
+  }
+}
+
+// One workgroup per segment of a match = LZ image.  It sizes png_encode_kernel's block, the LZ block and the stored block and
+// writes the shortest (ties: in that order), so a segment where RLE wins carries png_encode_kernel's bytes.
+__global__ __launch_bounds__(PNG_NT) void png_encode_lz_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  // The __shared__ variables below sum to PNG_LZ_STATIC_LDS (png_lz_blocks.hpp), which the launcher's static_assert holds against the
+  // CU's 160 KiB beside the token words: change that constant with them ("LDS Size" of -Rpass-analysis=kernel-resource-usage).
+  extern __shared__ uint32_t s_tok[];                      // PNG_LZ_TOKEN_BYTES: candidate + 1, then the token, of every position
+  __shared__ uint32_t s_filt[PNG_FILT_WORDS];
+  __shared__ uint32_t s_out[PNG_OUT_WORDS];
+  __shared__ uint32_t s_hist[PNG_SYMS_PAD], s_histz[PNG_SYMS_PAD], s_freq[PNG_SYMS_PAD], s_lf[PNG_SYMS_PAD], s_nf[PNG_SYMS_PAD];
+  __shared__ uint32_t s_code[PNG_SYMS_PAD], s_dhist[32], s_dcode[32];
+  __shared__ uint16_t s_parent[2 * PNG_SYMS_PAD];
+  __shared__ uint8_t s_len[PNG_SYMS_PAD], s_lenz[PNG_SYMS_PAD], s_dlen[32];
+  __shared__ uint32_t s_crc[256], s_tmp[PNG_NT], s_entry[PNG_NT], s_pow[32], s_blc[16];
+  __shared__ uint8_t s_rowf[ATTWARP_PNG_SEG_MAX_ROWS];
+  __shared__ uint32_t s_n, s_maxd, s_bits[2], s_x;
+  __shared__ unsigned long long s_a1, s_a2;
+
+  const int tid = threadIdx.x;
+  const attwarp_png_header* hdr = reinterpret_cast<const attwarp_png_header*>(table);
+  const int seg = png_segment_of(table, hdr, (int)blockIdx.x, hdr->nseg - hdr->reserved);
+  const PngSeg sg = reinterpret_cast<const PngSeg*>(table + hdr->off_segs)[seg];
+  const PngImageDev* imp = reinterpret_cast<const PngImageDev*>(table + hdr->off_images) + sg.image;
+  const int N = sg.n, RB = imp->row_bytes, WC = RB - 1, ftype = imp->filter;
+  PngSrc src;
+  src.p = (const PNG_G uint8_t*)imp->src;
+  src.pitch = imp->pitch;
+  src.C = imp->C;
+  src.swap = imp->swap != 0;
+  const PngTree tree = {s_freq, s_lf, s_nf, s_parent, &s_n, &s_maxd};
+
+  for (int i = tid; i < PNG_OUT_WORDS; i += PNG_NT) s_out[i] = 0;
+  for (int i = tid; i < PNG_SYMS_PAD; i += PNG_NT) { s_hist[i] = 0; s_histz[i] = 0; s_len[i] = 0; s_lenz[i] = 0; s_code[i] = 0; }
+  if (tid < 32) { s_dhist[tid] = 0; s_dcode[tid] = 0; s_dlen[tid] = 0; }
+  s_crc[tid] = crc_table_entry((uint32_t)tid);
+  if (tid < 32) s_pow[tid] = hdr->crc_pow8[tid];
+  if (tid == 0) { s_bits[0] = 0; s_bits[1] = 0; s_x = 0; s_a1 = 0; s_a2 = 0; }
+
+  // ---- 1. filter the segment's rows into LDS ------------------------------------------------------------------------------
+  png_filter_segment(src, sg, ftype, RB, WC, s_filt, s_rowf);
+
+  // ---- 2. run starts, Adler partial sums (png_encode_kernel's stage 2) ----------------------------------------------------------
+  const int lo = min(N, tid * PNG_CH), hi = min(N, lo + PNG_CH);
+  const uint32_t* myw = s_filt + tid * (PNG_CHW + 1);
+  uint32_t prevb = 0x100u;
+  if (lo > 0 && lo < N) prevb = png_seg_byte(s_filt, lo - 1);
+  uint32_t first = (uint32_t)N;
   {
-    const uint32_t L = (out_len + PNG_NT - 1) / PNG_NT;
-    const uint32_t b0 = min(out_len, (uint32_t)tid * L), b1 = min(out_len, b0 + L);
-    uint32_t c = 0xffffffffu;
-    for (uint32_t i = b0; i < b1; ++i) c = s_crc[(c ^ out8[i]) & 255u] ^ (c >> 8);
-    c = ~c;
-    if (b0 == b1) c = 0;
-    c = crc_mulmod(c, crc_xpow8(out_len - b1, s_pow));
-    for (int o = WAVE / 2; o > 0; o >>= 1) c ^= __shfl_xor(c, o, WAVE);
-    if ((tid & (WAVE - 1)) == 0) atomicXor(&s_x, c);
+    uint32_t prev = prevb, w = 0;
+    unsigned long long a1 = 0, a2 = 0;
+    for (int i = lo; i < hi; ++i) {
+      const int k = i - lo;
+      if ((k & 3) == 0) w = myw[k >> 2];
+      const uint32_t b = (w >> (8 * (k & 3))) & 255u;
+      if (b != prev && first == (uint32_t)N) first = (uint32_t)i;
+      prev = b;
+      a1 += b;
+      a2 += (unsigned long long)(N - i) * b;
+    }
+    if (lo < hi) { atomicAdd(&s_a1, a1); atomicAdd(&s_a2, a2); }
   }
-  uint32_t* dst = reinterpret_cast<uint32_t*>(scratch + sg.scratch_off);
-  for (uint32_t i = tid; i < (out_len + 3u) / 4u; i += PNG_NT) dst[i] = s_out[i];
+  const int e_next = (int)png_suffix_min_excl(first, s_tmp, (uint32_t)N);
+
+  // ---- 3. candidates: block after block of PNG_LZ_BLOCK positions looks its hash up, then publishes itself.  atomicMax of
+  // positions: the head of a hash is the largest position of the earlier blocks whatever the order of arrival.  The heads live
+  // in the (still unused, zero) output words as position + 1. ----------------------------------------------------------------------
+  {
+    uint32_t* head = s_out;
+    const int nh = N >= 4 ? N - 3 : 0;                     // positions that have a key
+    for (int b0 = 0; b0 < N; b0 += PNG_LZ_BLOCK) {         // (<= PNG_SEG / PNG_LZ_BLOCK rounds, uniform)
+      const int i = b0 + tid;
+      const bool keyed = i < nh;
+      uint32_t h = 0;
+      if (keyed) h = png_lz_hash(png_seg_ld32(s_filt, i));
+      if (i < N) s_tok[png_tok_at(i)] = keyed ? head[h] : 0u;
+      __syncthreads();
+      if (keyed) atomicMax(&head[h], (uint32_t)i + 1u);
+      __syncthreads();
+    }
+    for (int i = tid; i < (1 << PNG_LZ_HASH_BITS); i += PNG_NT) head[i] = 0;
+    s_entry[tid] = (uint32_t)N;
+  }
   __syncthreads();
-  if (tid == 0) {
-    PngSegOut o;
-    o.len = out_len;
-    o.crc = s_x;
-    o.s1 = (uint32_t)(s_a1 % PNG_ADLER);
-    o.s2 = (uint32_t)(s_a2 % PNG_ADLER);
-    o.pre = 0; o.pad = 0;
-    reinterpret_cast<PngSegOut*>(scratch)[blockIdx.x] = o;
+
+  // ---- 4. the token of every position of this thread's chunk, last position first: the distance-1 run from the run ends, the
+  // far match by comparing dwords, and where the chain through the position leaves the chunk -----------------------------------------
+  {
+    int re = e_next;                                       // the first run start behind position i
+    uint32_t b = hi > lo ? png_seg_byte(s_filt, hi - 1) : 0u;
+    for (int i = hi - 1; i >= lo; --i) {
+      const uint32_t pb = i > 0 ? png_seg_byte(s_filt, i - 1) : 0x100u;
+      const uint32_t cap = min(PNG_LZ_MAX_LEN, (uint32_t)(N - i));
+      uint32_t run = 0;
+      if (b == pb) run = min(cap, (uint32_t)(re - i));
+      else re = i;
+      const uint32_t c1 = s_tok[png_tok_at(i)];                        // candidate + 1 <= i
+      uint32_t far = 0;
+      if (c1 && run < cap) far = png_match_len(s_filt, i, (int)c1 - 1, cap);
+      uint32_t len = 1, dist = 0;
+      if (png_lz_takes_far(far, run)) { len = far; dist = (uint32_t)i + 1u - c1; }
+      else if (run >= 3u) { len = run; dist = 1; }
+      const int nx = i + (int)len;                         // <= N
+      const uint32_t ex = nx >= hi ? (uint32_t)(nx - hi) : png_lz_token_exit(s_tok[png_tok_at(nx)]);
+      s_tok[png_tok_at(i)] = png_lz_token(dist, len, ex);
+      b = pb;
+    }
   }
+  __syncthreads();
+  // the greedy chain from position 0, chunk by chunk: where it enters each chunk (N: it jumps over the chunk)
+  if (tid == 0) {
+    int p = 0;
+    for (int k = 0; k < PNG_NT && p < N; ++k) {
+      const int t = p / PNG_CH;
+      s_entry[t] = (uint32_t)p;
+      p = min(N, (t + 1) * PNG_CH) + (int)png_lz_token_exit(s_tok[png_tok_at(p)]);
+    }
+  }
+  __syncthreads();
+  const int entry = (int)s_entry[tid];
+
+  // ---- 5. both histograms, both pairs of codes, the three sizes ------------------------------------------------------------------------
+  png_walk(myw, lo, hi, prevb, e_next, [&](uint32_t v, uint32_t n) {
+    const PngRun run(n);
+    atomicAdd(&s_hist[v], run.lits);
+    if (run.full) atomicAdd(&s_hist[285], run.full);
+    if (run.rem) {
+      uint32_t sym, eb, ev;
+      png_length_symbol(run.rem, sym, eb, ev);
+      atomicAdd(&s_hist[sym], 1u);
+    }
+  });
+  png_lz_walk(s_tok, s_filt, entry, hi, [&](uint32_t v) { atomicAdd(&s_histz[v], 1u); },
+              [&](uint32_t len, uint32_t dist) {
+                uint32_t sym, eb, ev;
+                png_length_symbol(len, sym, eb, ev);
+                atomicAdd(&s_histz[sym], 1u);
+                png_dist_symbol(dist, sym, eb, ev);
+                atomicAdd(&s_dhist[sym], 1u);
+              });
+  if (tid == 0) { atomicAdd(&s_hist[256], 1u); atomicAdd(&s_histz[256], 1u); }
+  __syncthreads();
+  png_code_lengths(s_hist, PNG_SYMS, s_len, tree);
+  png_code_lengths(s_histz, PNG_SYMS, s_lenz, tree);
+  int dused = 0, dfirst = 0;                               // (uniform: every thread reads the same 30 words)
+  for (int s = PNG_DSYMS - 1; s >= 0; --s)
+    if (s_dhist[s]) { ++dused; dfirst = s; }
+  if (dused >= 2) png_code_lengths(s_dhist, PNG_DSYMS, s_dlen, tree);
+  else if (tid < 32) s_dlen[tid] = tid == dfirst;          // no distance or one: a single 1-bit code
+  __syncthreads();
+  {
+    const int sy[2] = {tid, tid + PNG_NT};
+    uint32_t br = 0, bz = 0;
+    for (int k = 0; k < 2; ++k) {
+      const int s = sy[k];
+      if (s >= PNG_SYMS) continue;
+      const uint32_t ex = s > 256 ? png_length_extra((uint32_t)s - 257u) : 0u;
+      br += s_hist[s] * (s_len[s] + ex + (s > 256 ? 1u : 0u));      // (+ the 1-bit distance code)
+      bz += s_histz[s] * (s_lenz[s] + ex);
+    }
+    if (tid < PNG_DSYMS) bz += s_dhist[tid] * (s_dlen[tid] + png_dist_extra((uint32_t)tid));
+    atomicAdd(&s_bits[0], br);
+    atomicAdd(&s_bits[1], bz);
+  }
+  __syncthreads();
+  const uint32_t rle_bytes = (PNG_HEADER_BITS + s_bits[0] + 3u + 7u) / 8u + 4u;
+  const uint32_t lz_bytes = (PNG_LZ_HEADER_BITS + s_bits[1] + 3u + 7u) / 8u + 4u;
+  const uint32_t st_bytes = (uint32_t)N + 5u;
+  const uint32_t route = (rle_bytes <= lz_bytes && rle_bytes <= st_bytes) ? PNG_ROUTE_RLE : lz_bytes <= st_bytes ? PNG_ROUTE_LZ : PNG_ROUTE_STORED;
+
+  // ---- 6. the chosen form into the output words ---------------------------------------------------------------------------------------
+  uint32_t out_len;
+  uint8_t* out8 = reinterpret_cast<uint8_t*>(s_out);
+  if (route == PNG_ROUTE_STORED) {
+    if (tid == 0) {
+      out8[0] = 0;
+      out8[1] = (uint8_t)N; out8[2] = (uint8_t)(N >> 8);
+      out8[3] = (uint8_t)~N; out8[4] = (uint8_t)(~N >> 8);
+    }
+    for (int i = tid; i < N; i += PNG_NT) out8[5 + i] = (uint8_t)png_seg_byte(s_filt, i);
+    out_len = st_bytes;
+  } else {
+    const bool lz = route == PNG_ROUTE_LZ;
+    const uint8_t* lens = lz ? s_lenz : s_len;
+    const int nd = lz ? PNG_DSYMS : 1;
+    const uint32_t header_bits = lz ? PNG_LZ_HEADER_BITS : PNG_HEADER_BITS;
+    if (!lz && tid < 32) s_dlen[tid] = tid == 0;           // the RLE block's one distance code
+    png_canonical_codes(lens, PNG_SYMS, s_code, s_blc);    // (its first barrier covers s_dlen)
+    png_canonical_codes(s_dlen, PNG_DSYMS, s_dcode, s_blc);
+    // block header: BFINAL 0, BTYPE 10, HLIT 286, HDIST nd, HCLEN 19; the flat 4-bit code-length code; 286 + nd lengths
+    if (tid == 0) {
+      PngBits w(s_out, 0);
+      w.put(4u | 29u << 3 | (uint32_t)(nd - 1) << 8 | 15u << 13, 17);
+      w.put(0, 9);
+      for (int k = 0; k < 16; ++k) w.put(4, 3);
+      w.flush();
+    }
+    for (int s = tid; s < PNG_SYMS + nd; s += PNG_NT) {
+      const uint32_t l = s < PNG_SYMS ? lens[s] : s_dlen[s - PNG_SYMS];
+      PngBits w(s_out, 74u + 4u * (uint32_t)s);
+      w.put(((l & 1u) << 3) | ((l & 2u) << 1) | ((l & 4u) >> 1) | ((l & 8u) >> 3), 4);
+      w.flush();
+    }
+    // the tokens of this thread's chunk in stream order, of either route: fl(value), fm(length, distance)
+    auto walk = [&](auto&& fl, auto&& fm) {
+      if (lz) png_lz_walk(s_tok, s_filt, entry, hi, fl, fm);
+      else
+        png_walk(myw, lo, hi, prevb, e_next, [&](uint32_t v, uint32_t n) {
+          const PngRun run(n);
+          fl(v);
+          for (uint32_t k = 0; k < run.full; ++k) fm(258u, 1u);       // (<= PNG_SEG / 258)
+          if (run.rem) fm(run.rem, 1u);
+          else
+            for (uint32_t k = 1; k < run.lits; ++k) fl(v);
+        });
+    };
+    uint32_t mybits = 0;
+    walk([&](uint32_t v) { mybits += s_code[v] >> 16; },
+         [&](uint32_t len, uint32_t dist) {
+           uint32_t sym, eb, ev, dsym, deb, dev;
+           png_length_symbol(len, sym, eb, ev);
+           png_dist_symbol(dist, dsym, deb, dev);
+           mybits += (s_code[sym] >> 16) + eb + (s_dcode[dsym] >> 16) + deb;
+         });
+    uint32_t total;
+    const uint32_t at = png_excl_sum(mybits, s_tmp, total);
+    PngBits w(s_out, header_bits + at);
+    walk([&](uint32_t v) { const uint32_t c = s_code[v]; w.put(c & 0xffffu, c >> 16); },
+         [&](uint32_t len, uint32_t dist) {
+           uint32_t sym, eb, ev, dsym, deb, dev;
+           png_length_symbol(len, sym, eb, ev);
+           png_dist_symbol(dist, dsym, deb, dev);
+           const uint32_t c = s_code[sym], d = s_dcode[dsym];
+           w.put(c & 0xffffu, c >> 16);
+           w.put(ev, eb);
+           w.put(d & 0xffffu, d >> 16);
+           w.put(dev, deb);
+         });
+    w.flush();
+    if (tid == PNG_NT - 1) {                               // end of block, then the empty stored block 000 / pad / 00 00 FF FF
+      PngBits e(s_out, header_bits + total);
+      const uint32_t c = s_code[256];
+      e.put(c & 0xffffu, c >> 16);
+      e.flush();
+      const uint32_t byte = (e.pos() + 3u + 7u) / 8u;
+      PngBits t(s_out, byte * 8u);
+      t.put(0xffff0000u, 32);
+      t.flush();
+    }
+    out_len = lz ? lz_bytes : rle_bytes;
+  }
+  __syncthreads();
+
+  // ---- 7. CRC-32 of the segment's bytes; write out -------------------------------------------------------------------------------
+  png_finish_segment(out_len, route, seg, sg, scratch, s_out, s_crc, s_pow, &s_x, s_a1, s_a2);
 }
 
 // One workgroup per image.
@@ -600,14 +938,16 @@ extern "C" size_t attwarp_png_bound(int H, int W, int C) {
   return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
 }
 
-static int png_count(const attwarp_png_image* images, int B, int64_t& nseg) {
+static int png_count(const attwarp_png_image* images, int B, const int32_t* match, int64_t& nseg, int64_t& nlz) {
   ATTWARP_REQUIRE(images, "png: null image array");
   ATTWARP_REQUIRE(B > 0, "png: non-positive batch size");
   if (B > (1 << 20)) return fail(ATTWARP_E_UNSUPPORTED, "png: B=%d > 2^20", B);
-  nseg = 0;
+  nseg = nlz = 0;
   for (int b = 0; b < B; ++b) {
     const attwarp_png_image& d = images[b];
     ATTWARP_REQUIRE(d.src, "png: image %d: null pointer", b);
+    ATTWARP_REQUIRE(!match || match[b] == ATTWARP_PNG_MATCH_RLE || match[b] == ATTWARP_PNG_MATCH_LZ, "png: image %d: unknown match %d", b,
+                    match ? match[b] : 0);
     ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1, "png: image %d: non-positive size %d x %d", b, d.H, d.W);
     ATTWARP_REQUIRE(d.C == 1 || d.C == 3, "png: image %d: %d channels (1 or 3)", b, d.C);
     ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "png: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
@@ -618,22 +958,26 @@ static int png_count(const attwarp_png_image* images, int B, int64_t& nseg) {
     if (attwarp_png_bound(d.H, d.W, d.C) == 0) return fail(ATTWARP_E_UNSUPPORTED, "png: image %d: %d x %d x %d is 2 GiB or more", b, d.H, d.W, d.C);
     const int rps = png_rows_per_segment(1 + d.W * d.C);
     nseg += (d.H + rps - 1) / rps;
+    if (match && match[b] == ATTWARP_PNG_MATCH_LZ) nlz += (d.H + rps - 1) / rps;
   }
   if (nseg > PNG_MAX_SEGS) return fail(ATTWARP_E_UNSUPPORTED, "png: %lld segments in one call (> %d)", (long long)nseg, PNG_MAX_SEGS);
   return ATTWARP_OK;
 }
 
-extern "C" size_t attwarp_png_table_bytes(const attwarp_png_image* images, int B) {
-  int64_t nseg;
-  if (png_count(images, B, nseg) != ATTWARP_OK) return 0;
-  return (size_t)(align_up(sizeof(attwarp_png_header), 16) + align_up((uint64_t)B * sizeof(PngImageDev), 16) + (uint64_t)nseg * sizeof(PngSeg));
+// A table with LZ segments ends with the order list (png_segment_of): one int32 per segment.
+extern "C" size_t attwarp_png_table_bytes_ex(const attwarp_png_image* images, int B, const int32_t* match) {
+  int64_t nseg, nlz;
+  if (png_count(images, B, match, nseg, nlz) != ATTWARP_OK) return 0;
+  return (size_t)(align_up(sizeof(attwarp_png_header), 16) + align_up((uint64_t)B * sizeof(PngImageDev), 16) + (uint64_t)nseg * sizeof(PngSeg) +
+                  (nlz ? align_up((uint64_t)nseg * sizeof(int32_t), 8) : 0u));
 }
+extern "C" size_t attwarp_png_table_bytes(const attwarp_png_image* images, int B) { return attwarp_png_table_bytes_ex(images, B, nullptr); }
 
-extern "C" int attwarp_png_plan(const attwarp_png_image* images, int B, void* table, size_t table_bytes) {
-  int64_t nseg;
-  if (const int rc = png_count(images, B, nseg)) return rc;
+extern "C" int attwarp_png_plan_ex(const attwarp_png_image* images, int B, const int32_t* match, void* table, size_t table_bytes) {
+  int64_t nseg, nlz;
+  if (const int rc = png_count(images, B, match, nseg, nlz)) return rc;
   ATTWARP_REQUIRE(table, "png_plan: null table");
-  const size_t need = attwarp_png_table_bytes(images, B);
+  const size_t need = attwarp_png_table_bytes_ex(images, B, match);
   ATTWARP_REQUIRE(table_bytes >= need, "png_plan: table of %zu bytes, %zu needed", table_bytes, need);
   uint8_t* t = static_cast<uint8_t*>(table);
   std::memset(t, 0, need);
@@ -642,6 +986,7 @@ extern "C" int attwarp_png_plan(const attwarp_png_image* images, int B, void* ta
   h.magic = PNG_MAGIC;
   h.B = B;
   h.nseg = (int32_t)nseg;
+  h.reserved = (int32_t)nlz;                               // LZ segments: the LZ launch's grid (0: no order list, no LZ launch)
   h.table_bytes = need;
   h.off_images = align_up(sizeof(attwarp_png_header), 16);
   h.off_segs = h.off_images + align_up((uint64_t)B * sizeof(PngImageDev), 16);
@@ -660,6 +1005,7 @@ extern "C" int attwarp_png_plan(const attwarp_png_image* images, int B, void* ta
     r.src = d.src; r.H = d.H; r.W = d.W; r.C = d.C; r.pitch = d.pitch;
     r.swap = d.C == 3 && d.order == ATTWARP_BGR;
     r.filter = d.filter;
+    r.pad[0] = (uint8_t)(match ? match[b] : ATTWARP_PNG_MATCH_RLE);
     r.row_bytes = 1 + d.W * d.C;
     r.rows_per_seg = png_rows_per_segment(r.row_bytes);
     r.seg0 = s;
@@ -683,10 +1029,18 @@ extern "C" int attwarp_png_plan(const attwarp_png_image* images, int B, void* ta
     }
     out_bytes += png_bound64(d.H, d.W, d.C);
   }
+  if (nlz) {                                               // RLE segments first, then LZ, each in segment order
+    int32_t* order = reinterpret_cast<int32_t*>(t + h.off_segs + (uint64_t)nseg * sizeof(PngSeg));
+    int64_t at[2] = {0, nseg - nlz};
+    for (int32_t k = 0; k < (int32_t)nseg; ++k) order[at[im[sg[k].image].pad[0] == ATTWARP_PNG_MATCH_LZ]++] = k;
+  }
   h.scratch_bytes = soff;
   h.out_bytes = out_bytes;
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
+}
+extern "C" int attwarp_png_plan(const attwarp_png_image* images, int B, void* table, size_t table_bytes) {
+  return attwarp_png_plan_ex(images, B, nullptr, table, table_bytes);
 }
 
 extern "C" int attwarp_png_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
@@ -694,7 +1048,8 @@ extern "C" int attwarp_png_encode(const void* table_host, const void* table_dev,
   ATTWARP_REQUIRE(table_host && table_dev && scratch && out && offsets, "png_encode: null pointer");
   attwarp_png_header h;
   std::memcpy(&h, table_host, sizeof h);
-  ATTWARP_REQUIRE(h.magic == PNG_MAGIC && h.B > 0 && h.nseg >= h.B && h.nseg <= PNG_MAX_SEGS, "png_encode: not a table of attwarp_png_plan");
+  ATTWARP_REQUIRE(h.magic == PNG_MAGIC && h.B > 0 && h.nseg >= h.B && h.nseg <= PNG_MAX_SEGS && h.reserved >= 0 && h.reserved <= h.nseg,
+                  "png_encode: not a table of attwarp_png_plan");
   ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "png_encode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
   ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
                       reinterpret_cast<uintptr_t>(offsets) % 8 == 0,
@@ -702,8 +1057,18 @@ extern "C" int attwarp_png_encode(const void* table_host, const void* table_dev,
   hipStream_t st = as_stream(stream);
   const uint8_t* td = static_cast<const uint8_t*>(table_dev);
   uint8_t* sc = static_cast<uint8_t*>(scratch);
-  hipLaunchKernelGGL(png_encode_kernel, dim3(h.nseg), dim3(PNG_NT), 0, st, td, sc);
-  if (const int rc = check_launch("png_encode_kernel")) return rc;
+  const int nlz = h.reserved, nrle = h.nseg - nlz;
+  if (nrle) {
+    hipLaunchKernelGGL(png_encode_kernel, dim3(nrle), dim3(PNG_NT), 0, st, td, sc);
+    if (const int rc = check_launch("png_encode_kernel")) return rc;
+  }
+  if (nlz) {                                               // (the token words need more than the default 64 KB of LDS)
+    // (the grant is for the dynamic part alone: the runtime adds the kernel's static LDS itself and refuses a sum above the CU's)
+    static_assert(PNG_LZ_TOKEN_BYTES + PNG_LZ_STATIC_LDS <= LDS_CU_BYTES, "the LZ kernel's LDS must fit a CU");
+    if (const int rc = grant_dynamic_lds(png_encode_lz_kernel, PNG_LZ_TOKEN_BYTES, "png_encode")) return rc;
+    hipLaunchKernelGGL(png_encode_lz_kernel, dim3(nlz), dim3(PNG_NT), PNG_LZ_TOKEN_BYTES, st, td, sc);
+    if (const int rc = check_launch("png_encode_lz_kernel")) return rc;
+  }
   hipLaunchKernelGGL(png_assemble_kernel, dim3(h.B), dim3(PNG_NT), 0, st, td, sc, out, offsets);
   if (const int rc = check_launch("png_assemble_kernel")) return rc;
   hipLaunchKernelGGL(png_gather_kernel, dim3(h.nseg), dim3(PNG_NT), 0, st, td, static_cast<const uint8_t*>(sc), out, offsets);

@@ -144,11 +144,12 @@ def trainer_debug_grid(img: torch.Tensor, A: torch.Tensor, warps: Sequence[torch
 
 
 def write_trainer_debug(grid_path, sample_paths, img: torch.Tensor, A: torch.Tensor, warps: Sequence[torch.Tensor],
-                        num_vis: int = 4, filter: str = "sub") -> List:
+                        num_vis: int = 4, filter: str = "sub", match="rle") -> List:
     """The files of MN/trainer.py:305-325: the grid (``grid_path``) and, per sample ``i < min(num_vis, B)``, the cells of
     ``warps[0]`` (``Wimg``) and ``warps[1]`` (``Wimg_gt``) -- ``sample_paths[i] = (pred_path, gt_path)``; they hold
     ``(W[i].clamp(0, 1) * 255).byte()``.  One panel launch, then ONE ``PngBatch`` over the grid and its cell views; only
-    compressed bytes are downloaded.  Returns the paths written, the grid's first.  Slice the warps at the call site:
+    compressed bytes are downloaded (``match``: :class:`attwarp_amd.png.PngBatch`, one value or one per file, the grid's
+    first).  Returns the paths written, the grid's first.  Slice the warps at the call site:
     ``warp_from_cdf_torch(img[:n], Fx[:n], Fy[:n])`` (see :func:`trainer_debug_grid`)."""
     from . import png
     warps = list(warps)
@@ -163,7 +164,7 @@ def write_trainer_debug(grid_path, sample_paths, img: torch.Tensor, A: torch.Ten
     for i in range(n):
         images += [cells[2][i], cells[3][i]]
         paths += list(sample_paths[i])
-    files = png.download(*png.PngBatch(images, filter).run())
+    files = png.download(*png.PngBatch(images, filter, match=match).run())
     for p, f in zip(paths, files):
         with open(p, "wb") as fh:
             fh.write(f)

@@ -1761,11 +1761,12 @@ def heatmap_overlay_ragged(rb: RaggedBatch, alpha: float = 0.5, order: str = "rg
     return packed, views
 
 
-def save_png_ragged(rb: RaggedBatch, paths, what: str = "warped", filter: str = "sub", order: str = "rgb"):
+def save_png_ragged(rb: RaggedBatch, paths, what: str = "warped", filter: str = "sub", order: str = "rgb", match="rle"):
     """The file-writing leg of the driver loop (main_batched.py:243-303) for a whole ragged batch: the warped images
     (``what="warped"``: ``rb.out``) or the up-sampled masks (``what="mota"``: :meth:`RaggedBatch.mota_of`, grey files) of
     ``rb`` as PNG files, encoded on the GPU in one :class:`attwarp_amd.png.PngBatch` -- only compressed bytes are copied
-    to the host.  Enqueue it after the launches that produced what it saves; ``order``: channel order of ``rb.images``."""
+    to the host.  Enqueue it after the launches that produced what it saves; ``order``: channel order of ``rb.images``;
+    ``match``: "rle" / "lz", one value or one per image (:class:`attwarp_amd.png.PngBatch`)."""
     paths = list(paths)
     if len(paths) != rb.B:
         raise ValueError(f"save_png_ragged: {len(paths)} paths for a batch of {rb.B}")
@@ -1777,7 +1778,7 @@ def save_png_ragged(rb: RaggedBatch, paths, what: str = "warped", filter: str = 
         images, order = [rb.mota_of(b) for b in range(rb.B)], "rgb"
     else:
         raise ValueError("save_png_ragged: what is 'warped' or 'mota'")
-    png.write_png(paths, images, filter=filter, order=order)
+    png.write_png(paths, images, filter=filter, order=order, match=match)
 
 
 def save_jpeg_ragged(rb: RaggedBatch, paths, what: str = "warped", quality=75, subsampling="4:2:0", restart_rows=0,

@@ -73,17 +73,24 @@ class PngBatch:
     tensors or one [B,H,W,C] tensor, C 1 or 3.  The images are referenced, not copied (any byte address, any row pitch):
     keep them alive; their CONTENT is read at every :meth:`run`, so a captured run re-encodes whatever they hold then.
 
-    ``filter``: "none" / "sub" / "up" / "average" / "paeth" / "adaptive", ``order``: "rgb" / "bgr" -- one value or one per
-    image.  ``out``: a uint8 device buffer of at least :attr:`bound` bytes.  Limits raise ValueError before any launch."""
+    ``filter``: "none" / "sub" / "up" / "average" / "paeth" / "adaptive", ``order``: "rgb" / "bgr", ``match``: "rle" / "lz"
+    -- one value or one per image.  ``out``: a uint8 device buffer of at least :attr:`bound` bytes.  Limits raise ValueError
+    before any launch.
+
+    ``match="lz"`` (the default "rle" is OpenCV's Z_RLE) also looks for repeated content inside each segment
+    and keeps, per segment, the shortest of the two token streams and the stored form: pages of text, up-sampled masks and
+    panels come out much smaller, photographs the same bytes as with "rle", never longer; the encode launch takes longer.
+    tests/pnglz_ref.py restates the bytes; :meth:`routes` says what each segment chose."""
 
     def __init__(self, images, filter: Union[str, Sequence[str]] = "sub", order: Union[str, Sequence[str]] = "rgb",
-                 out: Optional[torch.Tensor] = None):
+                 out: Optional[torch.Tensor] = None, match: Union[str, Sequence[str]] = "rle"):
         images = _views(images)
         if not images:
             raise ValueError("PngBatch: empty batch")
         B = len(images)
         filters = _per_image(filter, _lib.PNG_FILTER_IDS, B, "filter")
         orders = _per_image(order, _ORDERS, B, "order")
+        matches = np.array([_lib.PNG_MATCH_IDS[m] for m in _per_image(match, _lib.PNG_MATCH_IDS, B, "match")], np.int32)
         geo = [_geometry(t) for t in images]
         dev = _lib.require_gpu(*images)
         self.images, self.B, self._dev = images, B, dev
@@ -94,7 +101,8 @@ class PngBatch:
         rec["order"] = [_ORDERS[o] for o in orders]
         rec["filter"] = [_lib.PNG_FILTER_IDS[f] for f in filters]
         rp = ctypes.c_void_p(rec.ctypes.data)
-        self.table_host, self.header = planned_table(("attwarp_png_table_bytes", rp, B), ("attwarp_png_plan", rp, B, TABLE),
+        mp = ctypes.c_void_p(matches.ctypes.data) if matches.any() else None      # (NULL: the plain planners' table)
+        self.table_host, self.header = planned_table(("attwarp_png_table_bytes_ex", rp, B, mp), ("attwarp_png_plan_ex", rp, B, mp, TABLE),
                                                      _lib.PngHeader, ValueError, "PngBatch: ")
         self._pixels = sum(g[0] * g[1] * g[2] for g in geo)
         with torch.cuda.device(dev):
@@ -121,12 +129,20 @@ class PngBatch:
         return self._pixels
 
     def run(self):
-        """Three launches on the current stream -> ``(buffer, offsets)``: file b is ``buffer[offsets[b]:offsets[b+1]]``
+        """Three launches on the current stream (four when the batch mixes ``match="rle"`` and ``"lz"`` images: one encode
+        launch per route) -> ``(buffer, offsets)``: file b is ``buffer[offsets[b]:offsets[b+1]]``
         (uint8 and int64 [B+1], both on the device).  No host-dependent argument: capturable in a graph."""
         with torch.cuda.device(self._dev):
             call("attwarp_png_encode", self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.scratch), ptr(self.buffer),
                  self.buffer.numel(), ptr(self.offsets), stream_ptr(self._dev))
         return self.buffer, self.offsets
+
+    def routes(self) -> List[int]:
+        """After a :meth:`run` (synchronises): what every segment was written as, in file order -- 0 the distance-1 block,
+        1 the ``match="lz"`` block, 2 stored.  From the segment records at the head of the scratch buffer; for measurements
+        and tests."""
+        rec = self.scratch[:self.segments * 24].cpu().numpy().view(np.uint32).reshape(self.segments, 6)
+        return [int(r) for r in rec[:, 5]]
 
 
 def download(buffer: torch.Tensor, offsets: torch.Tensor) -> List[bytes]:
@@ -136,19 +152,19 @@ def download(buffer: torch.Tensor, offsets: torch.Tensor) -> List[bytes]:
     return [data[a:b] for a, b in zip(offs[:-1], offs[1:])]
 
 
-def encode_png(images, filter="sub", order="rgb") -> List[bytes]:
+def encode_png(images, filter="sub", order="rgb", match="rle") -> List[bytes]:
     """uint8 GPU images (list of [H,W,C] / [H,W] of any sizes, or [B,H,W,C]) -> the bytes of one PNG file each.  The outputs
     of ``warp_from_masks_ragged``, ``heatmap_overlay[_ragged]``, ``RaggedBatch.mota_of`` and ``upload_images`` are taken as
-    they are.  Raw pixels never leave the device."""
-    return download(*PngBatch(images, filter, order).run())
+    they are.  Raw pixels never leave the device.  ``match``: :class:`PngBatch`."""
+    return download(*PngBatch(images, filter, order, match=match).run())
 
 
-def write_png(paths, images, filter="sub", order="rgb") -> None:
+def write_png(paths, images, filter="sub", order="rgb", match="rle") -> None:
     """:func:`encode_png`, each file written to its path."""
     paths, images = list(paths), _views(images)
     if len(paths) != len(images):
         raise ValueError(f"write_png: {len(paths)} paths for {len(images)} images")
-    files = encode_png(images, filter, order)
+    files = encode_png(images, filter, order, match)
     for p, f in zip(paths, files):
         with open(p, "wb") as fh:
             fh.write(f)

@@ -777,13 +777,21 @@ ATTWARP_API int attwarp_adamw_step(const attwarp_adamw_tensor* tensors, int n, d
  * Filters: the specification's five, and ADAPTIVE: per row the filter with the smallest sum of |filtered byte as int8|,
  * ties to the lower number.  order = ATTWARP_BGR swaps the channels of a 3-channel source while filtering (the file is RGB).
  * Limits (ATTWARP_E_UNSUPPORTED from the planner): 1 + W * C <= ATTWARP_PNG_MAX_ROW_BYTES, C 1 or 3, a file bound below
- * 2^31, at most 2^24 segments per call; pitch >= W * C is the distance between rows in bytes, any byte address. */
+ * 2^31, at most 2^24 segments per call; pitch >= W * C is the distance between rows in bytes, any byte address.
+ * The _ex planners take match[B] (or NULL: all ATTWARP_PNG_MATCH_RLE, the table of the plain planners byte for byte; any
+ * other value is ATTWARP_E_INVALID).  The segments of an ATTWARP_PNG_MATCH_LZ image are encoded by a
+ * second kernel, launched only when the table has such segments: it also looks for matches of 4 .. 258 bytes at distance
+ * 2 .. 24,572 INSIDE the segment (one hashed candidate per position from the earlier 256-position blocks, greedy parse,
+ * HDIST = 30) and writes per segment the shortest of the distance-1 block above, that block and the stored block -- so
+ * the file is never longer, a segment where distance 1 wins carries the same bytes, and segments stay independent.
+ * header.reserved is the number of such segments; bound, scratch size and the other two launches do not change. */
 #define ATTWARP_PNG_SEG_BYTES 24576
 #define ATTWARP_PNG_MAX_ROW_BYTES 24576
 #define ATTWARP_PNG_SEG_MAX_ROWS 1024
 #define ATTWARP_PNG_FILE_OVERHEAD 68  /* bytes of a file that belong to no segment */
 enum { ATTWARP_PNG_NONE = 0, ATTWARP_PNG_SUB = 1, ATTWARP_PNG_UP = 2, ATTWARP_PNG_AVERAGE = 3, ATTWARP_PNG_PAETH = 4,
        ATTWARP_PNG_ADAPTIVE = 5 };
+enum { ATTWARP_PNG_MATCH_RLE = 0, ATTWARP_PNG_MATCH_LZ = 1 };
 typedef struct attwarp_png_image {
   const uint8_t* src;                              /* device: H rows of W * C bytes, pitch bytes apart */
   int32_t H, W, C;
@@ -793,7 +801,7 @@ typedef struct attwarp_png_image {
 } attwarp_png_image;
 typedef struct attwarp_png_header {                /* first bytes of a table written by attwarp_png_plan */
   uint32_t magic;
-  int32_t B, nseg, reserved;
+  int32_t B, nseg, reserved;                       /* reserved: segments of ATTWARP_PNG_MATCH_LZ images */
   uint64_t table_bytes, scratch_bytes, out_bytes;
   uint64_t off_images, off_segs;
   uint32_t crc_pow8[32];                           /* x^(8 * 2^k) mod the CRC-32 polynomial, reflected */
@@ -802,6 +810,8 @@ typedef struct attwarp_png_header {                /* first bytes of a table wri
 ATTWARP_API size_t attwarp_png_bound(int H, int W, int C);   /* 0: outside the limits */
 ATTWARP_API size_t attwarp_png_table_bytes(const attwarp_png_image* images, int B);
 ATTWARP_API int attwarp_png_plan(const attwarp_png_image* images, int B, void* table, size_t table_bytes);
+ATTWARP_API size_t attwarp_png_table_bytes_ex(const attwarp_png_image* images, int B, const int32_t* match);
+ATTWARP_API int attwarp_png_plan_ex(const attwarp_png_image* images, int B, const int32_t* match, void* table, size_t table_bytes);
 ATTWARP_API int attwarp_png_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
                        int64_t* offsets, void* stream);
 
