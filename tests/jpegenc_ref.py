@@ -8,6 +8,9 @@ factor, DOWN-SAMPLED rows replicated below that (``early=True`` is the wrong ord
 apart), (3) h2v2 / h2v1 down-sampling with the alternating bias, (4) jfdctint's islow DCT, (5) quantisation by q << 3 with
 rounding half away from zero, (6) interleaved MCUs with dummy blocks, (7) Huffman coding with the Annex K tables, byte
 stuffing, restart markers, and the file layout.
+
+``encode`` joins an interval's bits as one string; ``assemble_by_units`` / ``assemble_batch`` (at the end) put the same file
+together unit by unit the way launches 3 .. 7 do, and take one seeded ``defect`` (tests/test_jpegenc_limits_ref_cpu.py).
 """
 import numpy as np
 
@@ -293,7 +296,7 @@ def encode(img, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", ea
     interval = restart_rows * mx
     if interval > 65535:
         raise ValueError(f"restart interval {interval} (at most 65535)")
-    used, unit_bits, ff_ends, stuffed = set(), [], [], 0
+    used, unit_bits, unit_strings, ff_ends, stuffed = set(), [], [], [], 0
     out = bytearray(header(H, W, ncomp, quality, subsampling, interval))
     head = len(out)
     step = interval or len(mcus)
@@ -312,6 +315,7 @@ def encode(img, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", ea
         s = "".join(bits)
         cuts.append(len(s))
         unit_bits += [b - a_ for a_, b in zip(cuts[:-1], cuts[1:])]
+        unit_strings += [s[a_:b] for a_, b in zip(cuts[:-1], cuts[1:])]
         s += "1" * (-len(s) % 8)
         data = int(s, 2).to_bytes(len(s) // 8, "big")
         for c in cuts[1:-1]:                                  # an FF byte that holds bits of two units
@@ -324,5 +328,188 @@ def encode(img, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", ea
     if info is not None:
         info.update(symbols=used, unit_bits=unit_bits, stuffed=stuffed, ff_ends=ff_ends, ff_straddle=raw_ff_straddle,
                     header_bytes=head, mcus=len(mcus), intervals=-(-len(mcus) // step), geometry=(hmax, vmax, mx, my),
-                    blocks=[z for m in mcus for _, _, z in m])
+                    blocks=[z for m in mcus for _, _, z in m], unit_strings=unit_strings, upi=-(-step // UNIT_MCUS))
     return bytes(out)
+
+
+# ---- the assembly: launches 3 .. 7 of jpegenc.hip restated unit by unit ------------------------------------------------------------
+# ``encode`` joins an interval's bits as one string.  The device never has that string: every unit (at most UNIT_MCUS MCUs of
+# one interval) has its own, and five launches put the file together from prefix sums.  The functions below compute the file
+# THAT way, so that a case can be judged on the CPU for whether it would notice an error in the assembly: ``defect`` seeds
+# exactly one.  The defects live in this file only; nothing of the kind is built into or run through the kernels.
+SCAN_CHUNK = 256                      # JE_NT: items one round of the three scan kernels takes
+UST_POISON, OUT_POISON = 0xA5, 0x5A   # what a byte nobody wrote holds here (the device never zeroes either buffer)
+DEFECTS = {
+    "bits_carry_dropped": "(a) jpegenc_scan_bits_kernel: units of the second and later chunks get no carry",
+    "bytes_carry_dropped": "(a) jpegenc_scan_bytes_kernel: units of the second and later chunks get no carry",
+    "files_carry_dropped": "(a) jpegenc_scan_files_kernel: files of the second and later chunks get no carry",
+    "interval_in_chunk": "(b) fpos = pre + 2 * ((s - chunk base) // upi): the earlier intervals counted inside the chunk",
+    "straddle_one_unit": "(c) the straddling byte: this unit's bits, then the NEXT unit's slot for all the rest; 1-bits only "
+                         "where the unit itself is the interval's last (the walk never leaves the one following unit, and "
+                         "what lies behind that unit's string are the zeros of its slot)",
+    "empty_unit_no_marker": "(d) a last unit that owns no byte writes nothing, its RSTn / EOI included",
+    "empty_unit_marker_late": "(d) a last unit that owns no byte places its RSTn / EOI one byte late",
+    "upos0_without_interval": "(e) upos0 = base // 8: an interval starts IN the byte the one before it padded",
+    "rst_not_modulo": "(f) RSTn = D0 + interval, not modulo 8",
+    "row_address_32bit": "(g) the source fetch: y * pitch wrapped to 32 bits (source_rows, not the assembly)",
+}
+
+
+class AssemblyError(Exception):
+    """The (defective) assembly left its buffers: a negative offset, or a store or load outside them."""
+
+
+def _excl_scan(values, drop_carry=False):
+    """Exclusive sums the way the scan kernels take them: chunks of SCAN_CHUNK, a carry between them -> (sums, total)."""
+    pre, carry = [], 0
+    for base in range(0, len(values), SCAN_CHUNK):
+        run = 0
+        for v in values[base:base + SCAN_CHUNK]:
+            pre.append((0 if drop_carry and base else carry) + run)
+            run += v
+        carry += run
+    return pre, carry
+
+
+def _store(buf, at, data):
+    if at < 0 or at + len(data) > len(buf):
+        raise AssemblyError(f"store of {len(data)} bytes at {at} of {len(buf)}")
+    buf[at:at + len(data)] = data
+
+
+def unit_plan(img, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb"):
+    """What launches 1 and 2 and the planner leave for the assembly: the header, one bit string per unit, the units of a full
+    interval, the file's bound; and ``file``, the bytes ``encode`` makes of the same image."""
+    info = {}
+    data = encode(img, quality, subsampling, restart_rows, order, info=info)
+    a = np.asarray(img)
+    ncomp = 3 if a.ndim == 3 and a.shape[2] == 3 else 1
+    return dict(header=data[:info["header_bytes"]], units=info["unit_strings"], upi=info["upi"], file=data, stuffed=info["stuffed"],
+                ff_ends=info["ff_ends"], bound=bound(a.shape[0], a.shape[1], ncomp, quality, subsampling, restart_rows))
+
+
+def _assemble_image(plan, defect, out, file_off, unit_info):
+    """Launches 3, 4, 5 and 7 for one image whose file starts at ``file_off`` of ``out``."""
+    units, upi, header = plan["units"], plan["upi"], plan["header"]
+    n = len(units)
+    nint = -(-n // upi)
+    bits = [len(u) for u in units]
+    pre, total = _excl_scan(bits, defect == "bits_carry_dropped")                       # 3. scan_bits
+    ust = bytearray([UST_POISON]) * ((sum(bits) + 7) // 8 + nint + 8)
+    nbytes, nff, upos = [0] * n, [0] * n, [0] * n
+    for s in range(n):                                                                  # 4. gather: je_place, then the bytes
+        interval = s // upi                                                             # (JeUnit.interval: the host's, not a scan's)
+        f = interval * upi
+        unit_end = min(f + upi, n)
+        last = s == unit_end - 1
+        base = pre[f]
+        off = pre[s] - base
+        end = off + bits[s]
+        ibits = (pre[unit_end] if unit_end < n else total) - base
+        if off < 0 or ibits < 0:
+            raise AssemblyError(f"unit {s}: bit offset {off} of {ibits}")
+        upos0 = base // 8 + (0 if defect == "upos0_without_interval" else interval)
+        j0 = (off + 7) // 8
+        j1 = ((ibits if last else end) + 7) // 8
+        if j1 < j0:
+            raise AssemblyError(f"unit {s}: owns [{j0}, {j1})")
+        full = end // 8
+        nfull = max(full - j0, 0)
+        if nfull:                                                                       # whole bytes of its own bits, by shift
+            q = 8 * j0 - off
+            own = int(units[s][q:q + 8 * nfull], 2).to_bytes(nfull, "big")
+            _store(ust, upos0 + j0, own)
+            nff[s] += own.count(0xff)
+        if j1 > j0 + nfull:                                                             # the one straddling byte, bit by bit
+            j, v, voff, vend, byte = j1 - 1, s, off, end, 0
+            for t in range(8):
+                pos = 8 * j + t
+                if defect == "straddle_one_unit":
+                    if pos >= vend and v == s and s + 1 < unit_end:
+                        v, voff, vend = s + 1, vend, vend + bits[s + 1]
+                    inside = pos < ibits or not last
+                else:
+                    while pos >= vend and v + 1 < unit_end:
+                        v, voff, vend = v + 1, vend, vend + bits[v + 1]
+                    inside = pos < ibits
+                bit = 1
+                if inside:
+                    q = pos - voff
+                    if q < 0:
+                        raise AssemblyError(f"unit {s}: bit {q} of unit {v}")
+                    bit = int(units[v][q]) if q < bits[v] else 0
+                byte = byte << 1 | bit
+            _store(ust, upos0 + j, bytes([byte]))
+            nff[s] += byte == 0xff
+        nbytes[s], upos[s] = j1 - j0, upos0 + j0
+    sums, total_bytes = _excl_scan([a + b for a, b in zip(nbytes, nff)], defect == "bytes_carry_dropped")       # 5. scan_bytes
+    fpos = [p + 2 * ((s % SCAN_CHUNK if defect == "interval_in_chunk" else s) // upi) for s, p in enumerate(sums)]
+    for s in range(n):                                                                  # 7. write
+        dst = file_off + len(header) + fpos[s]
+        if upos[s] + nbytes[s] > len(ust):
+            raise AssemblyError(f"unit {s}: load of {nbytes[s]} bytes at {upos[s]} of {len(ust)}")
+        _store(out, dst, bytes(ust[upos[s]:upos[s] + nbytes[s]]).replace(b"\xff", b"\xff\x00"))
+        if s == 0:
+            _store(out, file_off, header)
+        if s == min((s // upi + 1) * upi, n) - 1:
+            at = dst + nbytes[s] + nff[s]
+            if nbytes[s] == 0 and defect == "empty_unit_no_marker":
+                continue
+            if nbytes[s] == 0 and defect == "empty_unit_marker_late":
+                at += 1
+            k = s // upi
+            _store(out, at, bytes([0xff, 0xd9 if s == n - 1 else (0xd0 + (k if defect == "rst_not_modulo" else k & 7)) & 255]))
+    unit_info.append(dict(owned=nbytes, owning_none=sum(b == 0 for b in nbytes), nff=nff, upos=upos, fpos=fpos))
+    return len(header) + total_bytes + 2 * (nint - 1) + 2
+
+
+def assemble_batch(plans, defect=None, info=None):
+    """The files of a batch of :func:`unit_plan` s, put together the way launches 3 .. 7 do -> (files, offsets[B + 1]).
+    ``defect``: a key of DEFECTS.  ``info``: a list that receives one dict per image: ``owned`` (bytes of the unstuffed stream
+    each unit owns), ``owning_none`` (units that own none), ``nff``, ``upos``, ``fpos``.  AssemblyError where the (defective)
+    arithmetic leaves the buffers."""
+    if defect is not None and defect not in DEFECTS:
+        raise ValueError(f"unknown defect {defect!r}")
+    out = bytearray([OUT_POISON]) * sum(p["bound"] for p in plans)
+    # A file's bytes do not depend on where it lies, so every image is written into a buffer of its own first (at its bound,
+    # as `out` is sized) and moved to its offset once launch 6 has run; files that a defect lays over each other are
+    # moved in the order of the batch.
+    unit_info, lengths, own = [], [], []
+    for p in plans:
+        own.append(bytearray([OUT_POISON]) * p["bound"])
+        lengths.append(_assemble_image(p, defect, own[-1], 0, unit_info))
+    offsets, total = _excl_scan(lengths, defect == "files_carry_dropped")                # 6. scan_files
+    offsets.append(total)
+    for buf, off, n in zip(own, offsets, lengths):
+        _store(out, off, buf[:n])
+    if info is not None:
+        info.extend(unit_info)
+    return [bytes(out[a:a + n]) for a, n in zip(offsets, lengths)], offsets
+
+
+def assemble_by_units(img, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", defect=None, info=None):
+    """:func:`encode`'s file, computed unit by unit the way the device does.  ``info``: a dict that receives ``owned`` and
+    ``owning_none`` (see :func:`assemble_batch`) besides the places of every unit."""
+    got = []
+    files, _ = assemble_batch([unit_plan(img, quality, subsampling, restart_rows, order)], defect, got)
+    if info is not None:
+        info.update(got[0])
+    return files[0]
+
+
+def source_rows(dense, pitch, defect=None, fill=0):
+    """What the transform kernel fetches of an image whose row y starts ``y * pitch`` bytes behind its first pixel:
+    ``dense`` itself; with ``defect="row_address_32bit"`` the product taken as an int32, where a byte that belongs to no
+    row of the view (in front of it, or in the gap between two rows) reads as ``fill``."""
+    a = np.asarray(dense)
+    if defect is None:
+        return a
+    if defect != "row_address_32bit":
+        raise ValueError(f"unknown defect {defect!r}")
+    flat = a.reshape(a.shape[0], -1)
+    H, row = flat.shape
+    start = ((np.arange(H, dtype=np.int64) * pitch + (1 << 31)) & 0xffffffff) - (1 << 31)        # as an int32 product
+    addr = start[:, None] + np.arange(row, dtype=np.int64)[None, :]
+    y, x = addr // pitch, addr % pitch
+    ok = (y >= 0) & (y < H) & (x < row)
+    return np.where(ok, flat[np.clip(y, 0, H - 1), np.minimum(x, row - 1)], fill).astype(np.uint8).reshape(a.shape)
