@@ -436,11 +436,14 @@ extern "C" size_t attwarp_axis_sums_workspace_bytes(int B, int H, int W) {
 
 extern "C" int attwarp_gt_marginals(const float* A, int B, int H, int W, float* px, float* py, void* ws,
                                     void* stream) {
-  ATTWARP_REQUIRE(A && px && py && ws, "gt_marginals: null pointer");
+  ATTWARP_REQUIRE(A && px && py, "gt_marginals: null pointer");
   ATTWARP_REQUIRE(B > 0 && H > 0 && W > 0, "gt_marginals: non-positive size");
   if (B > 65535) return fail(ATTWARP_E_UNSUPPORTED, "gt_marginals: B > 65535");
   PairwisePlan P;
   if (!pw_build(W, P) || H > 16384) return fail(ATTWARP_E_UNSUPPORTED, "gt_marginals: H, W must be <= 16384");
+  // (after the limits: attwarp_axis_sums_workspace_bytes answers 0 for a refused width, and a caller who sized the
+  //  workspace by it is told about the width, not about the pointer)
+  ATTWARP_REQUIRE(ws, "gt_marginals: null workspace");
   double* col = (double*)ws;
   double* ls = col + (size_t)B * W;
   hipStream_t st = as_stream(stream);
@@ -495,7 +498,7 @@ extern "C" int attwarp_axis_maps_from_attention(const void* att, int dtype, int 
                                                 int transform, double exp_scale, double exp_divisor,
                                                 int apply_inverse, float* map_x, float* map_y, void* ws,
                                                 void* stream) {
-  ATTWARP_REQUIRE(att && map_x && map_y && ws, "axis_maps_from_attention: null pointer");
+  ATTWARP_REQUIRE(att && map_x && map_y, "axis_maps_from_attention: null pointer");
   ATTWARP_REQUIRE(B > 0 && h > 0 && w > 0 && new_w > 0 && new_h > 0, "axis_maps_from_attention: non-positive size");
   ATTWARP_REQUIRE(transform >= ATTWARP_T_IDENTITY && transform <= ATTWARP_T_LOG,
                   "axis_maps_from_attention: unknown transform %d", transform);
@@ -504,6 +507,7 @@ extern "C" int attwarp_axis_maps_from_attention(const void* att, int dtype, int 
   PairwisePlan Pw, Ph;
   if (!pw_build(w, Pw) || !pw_build(h, Ph))
     return fail(ATTWARP_E_UNSUPPORTED, "axis_maps_from_attention: max(h,w)=%d > 16384", n);
+  ATTWARP_REQUIRE(ws, "axis_maps_from_attention: null workspace");   // after the limits, as in attwarp_gt_marginals
   double* col = (double*)ws;
   double* ls = col + (size_t)B * w;
   hipStream_t st = as_stream(stream);

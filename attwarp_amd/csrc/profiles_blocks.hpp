@@ -59,7 +59,12 @@ struct XfAttention {  // new_method: max(att,0) -> transform -> + BASE_ATTENTION
 // The recursion only depends on n, so it is flattened once on the host into a list of leaves
 // (offset, length <= 128) and a postfix program over the leaf sums (0 = push next leaf, 1 = add).
 // tests/test_oracle_golden.py::test_numpy_pairwise_restatement pins this against np.sum itself.
-constexpr int PW_MAX_LEAVES = 128;   // rows up to 16384 elements
+// A row of n elements makes ceil(n / 128) leaves when n is a multiple of 128 and up to one more otherwise: the right half
+// of every split keeps the remainder (n - n2 <= n/2 + 7), and where that half ends at 129 .. 135 elements it splits once
+// more.  Of the rows up to PW_MAX_N, those of 15369 .. 16383 elements that are not a multiple of 8 make 129 leaves,
+// the most (tests/test_axis_limits_cpu.py walks every n), so the tables hold more than PW_MAX_N / 128.
+constexpr int PW_MAX_N = 16384;      // longest row
+constexpr int PW_MAX_LEAVES = 136;   // >= 129, the most leaves a row of <= PW_MAX_N elements makes
 struct PairwisePlan {
   int nleaves;
   int nprog;
@@ -70,6 +75,7 @@ struct PairwisePlan {
 
 inline void pw_build_rec(int off, int n, PairwisePlan& P) {
   if (n <= 128) {
+    if (P.nleaves >= PW_MAX_LEAVES) { P.nprog = -1; return; }   // never for n <= PW_MAX_N; pw_build reports it
     P.off[P.nleaves] = off;
     P.len[P.nleaves] = n;
     P.nleaves++;
@@ -79,14 +85,16 @@ inline void pw_build_rec(int off, int n, PairwisePlan& P) {
     n2 -= n2 % 8;
     pw_build_rec(off, n2, P);
     pw_build_rec(off + n2, n - n2, P);
+    if (P.nprog < 0) return;
     P.prog[P.nprog++] = 1;
   }
 }
 inline bool pw_build(int n, PairwisePlan& P) {
   P.nleaves = 0;
   P.nprog = 0;
-  if (n <= 0 || n > 128 * PW_MAX_LEAVES) return false;
+  if (n <= 0 || n > PW_MAX_N) return false;
   pw_build_rec(0, n, P);
+  if (P.nprog < 0) { P.nleaves = 0; P.nprog = 0; return false; }
   return true;
 }
 // deepest stack the postfix program reaches (<= 10 for rows up to 16384 elements)
