@@ -18,7 +18,7 @@
 // Every loop is bounded by a header-derived count (units, MCUs per unit, blocks per MCU), by 64 coefficients or 16 bits,
 // by the stream's length, or by the plan's cap on rounds.
 // Files of every other layout (attwarp_jpegdec_plan_layouts / attwarp_jpegdec_decode_layouts, DESIGN.md 3.19: four components,
-// any sampling, RGB-coded) take the same five launches over records of their own: the jpegfmt_* kernels at the file's end.
+// any sampling, RGB-coded) take the same five launches over records of their own: the jpegfmt_* kernels behind the scan families'.
 // Progressive files (attwarp_jpegdec_plan_scans / attwarp_jpegdec_decode_scans) keep the last two launches
 // and put in front of them
 //   jpegprog_clear_kernel   the coefficient memory of every image zeroed (the scans only refine it), the states opened;
@@ -32,9 +32,15 @@
 // attwarp_jpegdec_decode_layout_scans) are the cross term: JfImage frames, JsScan records (jpegscan_blocks.hpp),
 // jpegscan_clear_kernel, jpegscan_marks_kernel, one jpegscan_entropy_kernel launch per level over the general MCU with a
 // fifth, sequential kind of block, then jpegfmt_idct_kernel and jpegfmt_color_kernel unchanged.
+// All kernels come first, then the host side, written once over the record family: JdFrames / JfFrames (the image records:
+// jd_plan_frames is both frame planners), JpScans / JsScans (the scan records: jp_plan_scans is the three scan planners), and
+// jd_decode_args, jd_decode_frames and jd_launch_idct_color for the four decode entry points.  The kernels themselves stay
+// one per family and launch: they share the block-level code (JdLayout / JfLayout), jd_scan_image, jp_clear_body, jp_marks_body
+// and jd_status, and no more, because any further sharing tried changed their instructions (docs/experiments.md).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "jpegfmt_blocks.hpp"
@@ -457,6 +463,11 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_idct_kernel(const uint8_t* __re
                 scratch + im->plane_off + (size_t)im->block0[c] * 64u + (size_t)by * 8u * ((size_t)bw * 8u) + (size_t)bx * 8u, (size_t)bw * 8u);
 }
 
+// The status word of an image: the restart scan's, else the first failing unit's, else whether EOI follows the data.
+__device__ __forceinline__ int32_t jd_status(const JdState& st) {
+  return (int32_t)(st.st_scan ? st.st_scan : st.fail != 0xffffffffu ? (st.fail & 255u) : st.eoi ? 0u : (uint32_t)ATTWARP_JPEGDEC_E_NO_EOI);
+}
+
 __global__ __launch_bounds__(JD_NT) void jpegdec_color_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
                                                               const JdState* __restrict__ states, uint8_t* __restrict__ out,
                                                               int32_t* __restrict__ status) {
@@ -473,7 +484,7 @@ __global__ __launch_bounds__(JD_NT) void jpegdec_color_kernel(const uint8_t* __r
   const int tile = (int)blockIdx.x - im->color_tile0;
   if (tile == 0 && threadIdx.x == 0) {
     const JdState st = states[b];
-    status[b] = (int32_t)(st.st_scan ? st.st_scan : st.fail != 0xffffffffu ? (st.fail & 255u) : st.eoi ? 0u : (uint32_t)ATTWARP_JPEGDEC_E_NO_EOI);
+    status[b] = jd_status(st);
   }
   const int W = im->W, H = im->H, hs = im->hs, vs = im->vs, oc = im->oc;
   const bool colour = im->ncomp == 3, to_luma = im->to_luma != 0, swap = im->swap != 0;
@@ -516,10 +527,20 @@ struct JpHeader {
   int32_t level_waves[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // waves of each level's launch
 };
 static_assert(sizeof(JpHeader) % 8 == 0, "record layout");
-// (behind a baseline table: header, image records, sub-stream records, always present: attwarp_jpegdec_table_bytes is this sum)
-__host__ __device__ inline uint64_t jp_header_off(int B) {
-  return jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JdImage) + (uint64_t)B * sizeof(JdSub);
+// (behind the first part of a table: header, image records of `record` bytes, sub-stream records, always present; for
+// JdImage records attwarp_jpegdec_table_bytes is this sum)
+__host__ __device__ inline uint64_t jp_header_off(int B, size_t record) {
+  return jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * record + (uint64_t)B * sizeof(JdSub);
 }
+struct JsHeader {                      // of the scans over JfImage records: a JpHeader and
+  JpHeader h;
+  int32_t level_tables[ATTWARP_JPEGDEC_MAX_SCANS + 1];  // code tables the scans of each level hold in LDS at most (1 .. 8)
+};
+static_assert(sizeof(JpHeader) == 568 && sizeof(JsHeader) == 832 && offsetof(JsHeader, level_tables) == sizeof(JpHeader), "record layout");
+static_assert(offsetof(JsHeader, h.magic) == 0 && offsetof(JsHeader, h.nscans) == 4 && offsetof(JsHeader, h.nlevels) == 8 &&
+                  offsetof(JsHeader, h.total_units) == 12 && offsetof(JsHeader, h.off_scans) == 16 && offsetof(JsHeader, h.starts_off) == 24 &&
+                  offsetof(JsHeader, h.clear_off) == 32 && offsetof(JsHeader, h.clear_bytes) == 40 && offsetof(JsHeader, h.level_scan0) == 48 &&
+                  offsetof(JsHeader, h.level_waves) == 48 + 4 * (ATTWARP_JPEGDEC_MAX_SCANS + 1), "record layout");
 
 // The coefficient memory of every image zeroed (the scans only refine it) and the per-image states opened: the clear launch of
 // both scan families (JdImage records with a JpHeader, JfImage records with a JsHeader).
@@ -555,7 +576,7 @@ __device__ __forceinline__ bool jp_sync_view(const JdView& v, const JpHeader* ph
 
 __global__ __launch_bounds__(JD_NT) void jpegprog_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   const JdView v(table, scratch);
-  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JdImage)));
   jp_clear_body(v, scratch, ph->clear_off, ph->clear_bytes);
   JpSyncView y;
   if (!jp_sync_view(v, ph, table, scratch, y)) return;
@@ -600,7 +621,7 @@ __global__ __launch_bounds__(JD_NT) void jpegprog_scan_kernel(const uint8_t* __r
                                                               uint8_t* __restrict__ scratch) {
   __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
   const JdView v(table, scratch);
-  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JdImage)));
   jp_marks_body(v, reinterpret_cast<const JpScan*>(table + ph->off_scans) + blockIdx.x, stream,
                 reinterpret_cast<uint32_t*>(scratch + ph->starts_off), ph->total_units, s_tmp, s_term, s_bad);
 }
@@ -618,7 +639,7 @@ __global__ __launch_bounds__(WAVE) void jpegprog_entropy_kernel(const uint8_t* _
   __shared__ uint32_t s_pos, s_err, s_run;
   const int lane = threadIdx.x, w = blockIdx.x;
   const JdView v(table, scratch);
-  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JdImage)));
   const JpScan* scans = reinterpret_cast<const JpScan*>(table + ph->off_scans);
   int lo = ph->level_scan0[level], hi = ph->level_scan0[level + 1] - 1;
   if (hi < lo) return;
@@ -732,7 +753,7 @@ __global__ __launch_bounds__(JD_NT) void jpegprog_substream_kernel(const uint8_t
   __shared__ uint32_t s_ok;
   const int tid = threadIdx.x;
   const JdView v(table, scratch);
-  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B));
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JdImage)));
   const JpScan* scans = reinterpret_cast<const JpScan*>(table + ph->off_scans);
   JpSyncView y;
   if (!jp_sync_view(v, ph, table, scratch, y) || level < 0 || level >= ph->nlevels) return;
@@ -902,512 +923,9 @@ __global__ __launch_bounds__(JD_NT) void jpegprog_substream_kernel(const uint8_t
   }
 }
 
-}  // namespace attwarp
-
-using namespace attwarp;
-
-struct JdGeom {
-  int mcux, mcuy, nunits;
-  int bw[3], bh[3];
-  uint32_t block0[3], nblocks;
-};
-
-// What is wrong with a Huffman table (counts per length, symbols), in words for the caller's message; nullptr: nothing.
-static const char* jd_huffman_fault(const uint8_t* counts, const uint8_t* symbols, bool dc, char (&what)[48]) {
-  int left = 1, n = 0;
-  for (int l = 0; l < 16 && left >= 0; ++l) { left = 2 * left - counts[l]; n += counts[l]; }
-  if (left < 0) return "an over-subscribed Huffman table";
-  std::snprintf(what, sizeof what, "a Huffman table of %d symbols", n);
-  if (n > 256) return what;
-  for (int k = 0; dc && k < n; ++k)
-    if (symbols[k] > 15) return "a DC category above 15";
-  return nullptr;
-}
-
-static int jpegdec_geom(const attwarp_jpegdec_image& d, int b, JdGeom& g) {
-  ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1 && d.H <= 65535 && d.W <= 65535, "jpegdec: image %d: size %d x %d outside 1..65535", b, d.H, d.W);
-  ATTWARP_REQUIRE(d.ncomp == 1 || d.ncomp == 3, "jpegdec: image %d: %d components (1 or 3)", b, d.ncomp);
-  ATTWARP_REQUIRE((d.hs == 1 && d.vs == 1) || (d.ncomp == 3 && d.hs == 2 && (d.vs == 1 || d.vs == 2)),
-                  "jpegdec: image %d: luma sampling %d x %d (1x1, 2x1, 2x2; grey 1x1)", b, d.hs, d.vs);
-  ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d: restart interval %d", b, d.restart_interval);
-  ATTWARP_REQUIRE(d.mode >= ATTWARP_JPEGDEC_RGB && d.mode <= ATTWARP_JPEGDEC_KEEP, "jpegdec: image %d: unknown mode %d", b, d.mode);
-  ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegdec: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
-  for (int c = 0; c < d.ncomp; ++c) {
-    for (int k = 0; k < 64; ++k) ATTWARP_REQUIRE(d.qt[c][k] <= 255, "jpegdec: image %d: a quantisation value above 255", b);
-    for (int t = 0; t < 2; ++t) {
-      char what[48];
-      const char* fault = t ? jd_huffman_fault(d.ac_counts[c], d.ac_symbols[c], false, what) : jd_huffman_fault(d.dc_counts[c], d.dc_symbols[c], true, what);
-      ATTWARP_REQUIRE(!fault, "jpegdec: image %d: %s", b, fault);
-    }
-  }
-  g.mcux = (d.W + 8 * d.hs - 1) / (8 * d.hs);
-  g.mcuy = (d.H + 8 * d.vs - 1) / (8 * d.vs);
-  const int64_t nmcu = (int64_t)g.mcux * g.mcuy;
-  const int64_t units = d.restart_interval ? (nmcu + d.restart_interval - 1) / d.restart_interval : 1;
-  int64_t blocks = 0;
-  for (int c = 0; c < 3; ++c) {
-    g.bw[c] = c < d.ncomp ? g.mcux * (c == 0 ? d.hs : 1) : 0;
-    g.bh[c] = c < d.ncomp ? g.mcuy * (c == 0 ? d.vs : 1) : 0;
-    g.block0[c] = (uint32_t)blocks;
-    blocks += (int64_t)g.bw[c] * g.bh[c];
-  }
-  if (units > ATTWARP_JPEGDEC_MAX_UNITS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld restart intervals (> %d)", b, (long long)units, ATTWARP_JPEGDEC_MAX_UNITS);
-  if (blocks >= ATTWARP_JPEGDEC_MAX_BLOCKS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld blocks (>= %d)", b, (long long)blocks, ATTWARP_JPEGDEC_MAX_BLOCKS);
-  if (d.stream_len >= ((uint64_t)1 << 31) || d.stream_off >= ((uint64_t)1 << 62))
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: entropy data of 2 GiB or more", b);
-  g.nunits = (int)units;
-  g.nblocks = (uint32_t)blocks;
-  return ATTWARP_OK;
-}
-
-extern "C" size_t attwarp_jpegdec_table_bytes(const attwarp_jpegdec_image* images, int B) {
-  if (!images || B <= 0 || B > JD_MAX_B) {
-    fail(ATTWARP_E_ARG, "jpegdec_table_bytes: B=%d outside the limits", B);
-    return 0;
-  }
-  return (size_t)jp_header_off(B);
-}
-
-extern "C" int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes) {
-  return attwarp_jpegdec_plan_ex(images, B, table, table_bytes, 0, 0);
-}
-
-extern "C" int attwarp_jpegdec_plan_ex(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes, int segment_bytes,
-                                       int max_rounds) {
-  ATTWARP_REQUIRE(images, "jpegdec: null image array");
-  const bool substreams = segment_bytes != 0 || max_rounds != 0;
-  if (substreams) {
-    ATTWARP_REQUIRE(segment_bytes >= 32 && segment_bytes <= 512 && (segment_bytes & (segment_bytes - 1)) == 0,
-                    "jpegdec: segment_bytes=%d must be a power of two in 32..512", segment_bytes);
-    ATTWARP_REQUIRE(max_rounds >= 1 && max_rounds <= JD_SUB_MAX_ROUNDS, "jpegdec: max_rounds=%d outside 1..%d", max_rounds, JD_SUB_MAX_ROUNDS);
-  }
-  ATTWARP_REQUIRE(B > 0, "jpegdec: non-positive batch size");
-  if (B > JD_MAX_B) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: B=%d > 2^20", B);
-  ATTWARP_REQUIRE(table, "jpegdec_plan: null table");
-  const size_t need = (size_t)jp_header_off(B);
-  ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan: table of %zu bytes, %zu needed", table_bytes, need);
-  int64_t units = 0, itiles = 0, ctiles = 0;
-  for (int b = 0; b < B; ++b) {                              // everything is checked before anything is written
-    JdGeom g;
-    if (const int rc = jpegdec_geom(images[b], b, g)) return rc;
-    units += g.nunits;
-    itiles += (g.nblocks + JD_IDCT_TILE - 1) / JD_IDCT_TILE;
-    ctiles += ((int64_t)images[b].H * images[b].W + JD_COLOR_TILE - 1) / JD_COLOR_TILE;
-  }
-  if (units > JD_MAX_TOTAL_UNITS || itiles > JD_MAX_TOTAL_UNITS || ctiles > JD_MAX_TOTAL_UNITS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units, %lld + %lld workgroups in one call (> 2^30)", (long long)units, (long long)itiles, (long long)ctiles);
-  uint8_t* t = static_cast<uint8_t*>(table);
-  std::memset(t, 0, need);
-  attwarp_jpegdec_header h;
-  std::memset(&h, 0, sizeof h);
-  h.magic = JD_MAGIC;
-  h.B = B;
-  h.total_units = (int32_t)units;
-  h.idct_tiles = (int32_t)itiles;
-  h.color_tiles = (int32_t)ctiles;
-  h.table_bytes = need;
-  h.off_images = jd_align(sizeof(attwarp_jpegdec_header), 16);
-  JdImage* im = reinterpret_cast<JdImage*>(t + h.off_images);
-  JdSub* sub = reinterpret_cast<JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JdImage));
-  int32_t nsub = 0;
-  uint64_t soff = jd_data_base(B, (int)units), ooff = 0, stream_bytes = 0;
-  int32_t u0 = 0, it0 = 0, ct0 = 0;
-  for (int b = 0; b < B; ++b) {
-    const attwarp_jpegdec_image& d = images[b];
-    JdGeom g;
-    jpegdec_geom(d, b, g);
-    JdImage& r = im[b];
-    r.stream_off = d.stream_off;
-    r.stream_len = (uint32_t)d.stream_len;
-    r.H = d.H; r.W = d.W; r.ncomp = d.ncomp; r.hs = d.hs; r.vs = d.vs;
-    r.oc = d.mode == ATTWARP_JPEGDEC_L ? 1 : d.mode == ATTWARP_JPEGDEC_RGB ? 3 : d.ncomp;
-    r.to_luma = d.ncomp == 3 && r.oc == 1;
-    r.swap = d.ncomp == 3 && r.oc == 3 && d.order == ATTWARP_BGR;
-    r.mcux = g.mcux; r.mcuy = g.mcuy;
-    r.ri = d.restart_interval ? d.restart_interval : g.mcux * g.mcuy;
-    r.nunits = g.nunits; r.unit0 = u0;
-    r.idct_tile0 = it0; r.color_tile0 = ct0;
-    for (int c = 0; c < 3; ++c) { r.bw[c] = g.bw[c]; r.bh[c] = g.bh[c]; r.block0[c] = g.block0[c]; }
-    r.nblocks = g.nblocks;
-    std::memcpy(r.qt, d.qt, sizeof r.qt);
-    std::memcpy(r.dc_counts, d.dc_counts, sizeof r.dc_counts);
-    std::memcpy(r.ac_counts, d.ac_counts, sizeof r.ac_counts);
-    std::memcpy(r.dc_symbols, d.dc_symbols, sizeof r.dc_symbols);
-    std::memcpy(r.ac_symbols, d.ac_symbols, sizeof r.ac_symbols);
-    r.coef_off = soff;
-    soff += jd_align((uint64_t)g.nblocks * 128u, 256);
-    r.plane_off = soff;
-    soff += jd_align((uint64_t)g.nblocks * 64u, 256);
-    r.out_off = ooff;
-    ooff += (uint64_t)d.H * d.W * r.oc;
-    u0 += g.nunits;
-    it0 += (int32_t)((g.nblocks + JD_IDCT_TILE - 1) / JD_IDCT_TILE);
-    ct0 += (int32_t)(((int64_t)d.H * d.W + JD_COLOR_TILE - 1) / JD_COLOR_TILE);
-    stream_bytes = std::max(stream_bytes, d.stream_off + d.stream_len);
-    // sub-streams: a marker-less image (one unit) whose data is at least two segments long
-    const uint64_t nseg = substreams ? (d.stream_len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes : 0;
-    sub[b].segment_bytes = (uint32_t)segment_bytes;
-    sub[b].max_rounds = (uint32_t)max_rounds;
-    if (substreams && g.nunits == 1 && d.stream_len >= 2u * (uint64_t)segment_bytes && nseg <= (uint64_t)JD_SUB_MAX_SEGS) {
-      sub[b].nseg = (uint32_t)nseg;
-      sub[nsub++].image = b;
-    }
-  }
-  // behind everything there was: the per-image sub-stream results, then the segments of every image planned for them
-  const uint64_t info_off = soff;
-  soff += jd_align((uint64_t)B * sizeof(JdSubInfo), 256);
-  for (int b = 0; b < B; ++b) {
-    sub[b].info_off = info_off;
-    sub[b].seg_off = soff;
-    soff += jd_align((uint64_t)sub[b].nseg * (sizeof(JdSegState) + sizeof(JdSegment)), 256);
-  }
-  h.reserved = nsub;
-  h.scratch_bytes = soff;
-  h.out_bytes = ooff;
-  h.stream_bytes = stream_bytes;
-  std::memcpy(t, &h, sizeof h);
-  return ATTWARP_OK;
-}
-
-extern "C" uint64_t attwarp_jpegdec_info_offset(const void* table_host) {
-  if (!table_host) return 0;
-  attwarp_jpegdec_header h;
-  std::memcpy(&h, table_host, sizeof h);
-  if ((h.magic != JD_MAGIC && h.magic != JD_MAGIC_LAYOUTS && h.magic != JD_MAGIC_LAYOUT_SCANS) || h.B <= 0 || h.B > JD_MAX_B) return 0;
-  JdSub s;
-  const size_t record = h.magic == JD_MAGIC ? sizeof(JdImage) : sizeof(JfImage);
-  std::memcpy(&s, static_cast<const uint8_t*>(table_host) + h.off_images + (uint64_t)h.B * record, sizeof s);
-  return s.info_off;
-}
-
-// What both decode entry points (`who`) check: pointers, the table of `planner` (-> h; `ph`: and its scan header), sizes, alignment.
-static int jd_decode_args(const char* who, const char* planner, const void* table_host, const void* table_dev, const uint8_t* stream_bytes,
-                          const void* scratch, const uint8_t* out, size_t out_bytes, const int32_t* status, attwarp_jpegdec_header& h,
-                          JpHeader* ph) {
-  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "%s: null pointer", who);
-  std::memcpy(&h, table_host, sizeof h);
-  bool ok = h.magic == JD_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS &&
-            h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS;
-  if (!ph) ok = ok && h.total_units >= h.B && h.total_units <= JD_MAX_TOTAL_UNITS && h.reserved >= 0 && h.reserved <= h.B;
-  else ok = ok && h.total_units == h.B && h.reserved == 0 && h.table_bytes >= jp_header_off(h.B) + sizeof(JpHeader);
-  if (ok && ph) {
-    std::memcpy(ph, static_cast<const uint8_t*>(table_host) + jp_header_off(h.B), sizeof *ph);
-    ok = ph->magic == JP_MAGIC && ph->nscans >= h.B && ph->nlevels >= 1 && ph->nlevels <= ATTWARP_JPEGDEC_MAX_SCANS &&
-         ph->total_units >= ph->nscans && ph->total_units <= JD_MAX_TOTAL_UNITS;
-  }
-  ATTWARP_REQUIRE(ok, "%s: not a table of %s", who, planner);
-  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "%s: out of %zu bytes, %llu needed", who, out_bytes, (unsigned long long)h.out_bytes);
-  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
-                      reinterpret_cast<uintptr_t>(status) % 4 == 0,
-                  "%s: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned", who);
-  return ATTWARP_OK;
-}
-
-// The last two launches of both entry points: coefficients -> planes -> pixels and statuses.
-static int jd_launch_idct_color(const attwarp_jpegdec_header& h, const uint8_t* td, uint8_t* sc, uint8_t* out, int32_t* status, hipStream_t st) {
-  hipLaunchKernelGGL(jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegdec_idct_kernel")) return rc;
-  hipLaunchKernelGGL(jpegdec_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
-  return check_launch("jpegdec_color_kernel");
-}
-
-extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
-                                      uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
-  attwarp_jpegdec_header h;
-  if (const int rc = jd_decode_args("jpegdec_decode", "attwarp_jpegdec_plan", table_host, table_dev, stream_bytes, scratch, out, out_bytes,
-                                    status, h, nullptr))
-    return rc;
-  hipStream_t st = as_stream(stream);
-  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
-  uint8_t* sc = static_cast<uint8_t*>(scratch);
-  hipLaunchKernelGGL(jpegdec_scan_kernel, dim3(h.B), dim3(JD_NT), 0, st, td, stream_bytes, sc);
-  if (const int rc = check_launch("jpegdec_scan_kernel")) return rc;
-  hipLaunchKernelGGL(jpegdec_substream_kernel, dim3(std::max(h.reserved, 1)), dim3(JD_NT), 0, st, td, stream_bytes, sc);
-  if (const int rc = check_launch("jpegdec_substream_kernel")) return rc;
-  hipLaunchKernelGGL(jpegdec_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
-  if (const int rc = check_launch("jpegdec_entropy_kernel")) return rc;
-  return jd_launch_idct_color(h, td, sc, out, status, st);
-}
-
-// ---- progressive files: the plan over all scans ---------------------------------------------------------------------------------------
-static size_t jpegprog_bytes(int B, int nscans) { return (size_t)(jp_header_off(B) + sizeof(JpHeader) + (uint64_t)nscans * sizeof(JpScan)); }
-
-extern "C" size_t attwarp_jpegdec_scans_table_bytes(const attwarp_jpegdec_image* images, int B, int nscans) {
-  if (!images || B <= 0 || B > JD_MAX_B || nscans < B || (int64_t)nscans > (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS) {
-    fail(ATTWARP_E_ARG, "jpegdec_scans_table_bytes: B=%d, %d scans outside the limits", B, nscans);
-    return 0;
-  }
-  return jpegprog_bytes(B, nscans);
-}
-
-static size_t jpegprog_sync_bytes(int nscans) { return sizeof(JpSyncHeader) + (size_t)nscans * sizeof(JpSync); }
-
-extern "C" size_t attwarp_jpegdec_scans_table_bytes_ex(const attwarp_jpegdec_image* images, int B, int nscans, int segment_bytes,
-                                                       int max_rounds) {
-  const size_t base = attwarp_jpegdec_scans_table_bytes(images, B, nscans);
-  return base && (segment_bytes != 0 || max_rounds != 0) ? base + jpegprog_sync_bytes(nscans) : base;
-}
-
-// Both planners: segment_bytes = max_rounds = 0 plans no sub-streams and writes the table of attwarp_jpegdec_plan_scans.
-static int jp_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans, void* table,
-                         size_t table_bytes, int by_level, int segment_bytes, int max_rounds, const uint64_t* data_bytes) {
-  ATTWARP_REQUIRE(images && scans && table, "jpegdec_plan_scans: null pointer");
-  ATTWARP_REQUIRE(B > 0 && B <= JD_MAX_B && nscans >= B && (int64_t)nscans <= (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS,
-                  "jpegdec_plan_scans: B=%d, %d scans outside the limits", B, nscans);
-  const bool substreams = segment_bytes != 0 || max_rounds != 0;
-  if (substreams) {
-    ATTWARP_REQUIRE(segment_bytes >= 32 && segment_bytes <= 512 && (segment_bytes & (segment_bytes - 1)) == 0,
-                    "jpegdec: segment_bytes=%d must be a power of two in 32..512", segment_bytes);
-    ATTWARP_REQUIRE(max_rounds >= 1 && max_rounds <= JD_SUB_MAX_ROUNDS, "jpegdec: max_rounds=%d outside 1..%d", max_rounds, JD_SUB_MAX_ROUNDS);
-    ATTWARP_REQUIRE(data_bytes, "jpegdec_plan_scans_ex: null data_bytes");
-    for (int i = 0; i < nscans; ++i)
-      ATTWARP_REQUIRE(scans[i].image >= 0 && scans[i].image < B && scans[i].stream_off <= images[scans[i].image].stream_len &&
-                          data_bytes[i] <= images[scans[i].image].stream_len - scans[i].stream_off,
-                      "jpegdec_plan_scans_ex: scan %d: data outside the image's", i);
-  }
-  const size_t need = jpegprog_bytes(B, nscans) + (substreams ? jpegprog_sync_bytes(nscans) : 0);
-  ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan_scans: table of %zu bytes, %zu needed", table_bytes, need);
-  for (int b = 0; b < B; ++b)
-    ATTWARP_REQUIRE(images[b].restart_interval == 0, "jpegdec_plan_scans: image %d: the restart interval belongs to the scans", b);
-  // everything is checked before anything is written: the scans come image by image, in file order
-  std::vector<JpScan> rec((size_t)nscans);
-  std::vector<int> count(B, 0);
-  int64_t total_units = 0;
-  int nlevels = 0, prev = -1;
-  for (int i = 0, first = 0; i < nscans; ++i) {
-    const attwarp_jpegdec_scan& d = scans[i];
-    ATTWARP_REQUIRE(d.image >= 0 && d.image < B && d.image >= prev, "jpegdec_plan_scans: scan %d: image %d out of order", i, d.image);
-    if (d.image != prev) { first = i; prev = d.image; }
-    const attwarp_jpegdec_image& img = images[d.image];
-    const int index = i - first;
-    if (index >= ATTWARP_JPEGDEC_MAX_SCANS)
-      return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: more than %d scans", d.image, ATTWARP_JPEGDEC_MAX_SCANS);
-    ++count[d.image];
-    ATTWARP_REQUIRE(d.ncomp >= 1 && d.ncomp <= img.ncomp, "jpegdec: image %d scan %d: %d components", d.image, index, d.ncomp);
-    for (int c = 0; c < d.ncomp; ++c)
-      ATTWARP_REQUIRE(d.comp[c] >= 0 && d.comp[c] < img.ncomp && (c == 0 || d.comp[c] > d.comp[c - 1]),
-                      "jpegdec: image %d scan %d: components not in frame order", d.image, index);
-    ATTWARP_REQUIRE(d.ss >= 0 && d.ss <= d.se && d.se <= 63 && (d.ss != 0 || d.se == 0) && (d.ss == 0 || d.ncomp == 1) && d.al >= 0 &&
-                        d.al <= 13 && d.ah >= 0 && d.ah <= 14 && (d.ah == 0 || d.al == d.ah - 1),
-                    "jpegdec: image %d scan %d: bad progression Ss=%d Se=%d Ah=%d Al=%d", d.image, index, d.ss, d.se, d.ah, d.al);
-    ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d scan %d: restart interval %d", d.image, index,
-                    d.restart_interval);
-    ATTWARP_REQUIRE(d.stream_off <= img.stream_len, "jpegdec: image %d scan %d: data outside the image's", d.image, index);
-    JdGeom g;
-    if (const int rc = jpegdec_geom(img, d.image, g)) return rc;
-    JpScan& r = rec[(size_t)i];
-    std::memset(&r, 0, sizeof r);
-    r.image = (uint32_t)d.image; r.index = (uint32_t)index; r.off = (uint32_t)d.stream_off;
-    r.kind = (uint32_t)((d.ss ? 2 : 0) + (d.ah ? 1 : 0));
-    r.ss = (uint32_t)d.ss; r.se = (uint32_t)d.se; r.al = (uint32_t)d.al;
-    const int ntab = d.ss ? 1 : d.ncomp;
-    for (int t = 0; t < ntab; ++t) {
-      char what[48];
-      const char* fault = jd_huffman_fault(d.counts[t], d.symbols[t], !d.ss, what);
-      ATTWARP_REQUIRE(!fault, "jpegdec: image %d scan %d: %s", d.image, index, fault);
-      std::memcpy(r.counts[t], d.counts[t], 16);
-      std::memcpy(r.symbols[t], d.symbols[t], 256);
-    }
-    if (d.ncomp == 1) {                                        // not interleaved: the blocks that cover the component's true size
-      const int c = d.comp[0], h = c == 0 ? img.hs : 1, vv = c == 0 ? img.vs : 1;
-      const int cw = (img.W * h + img.hs - 1) / img.hs, ch = (img.H * vv + img.vs - 1) / img.vs;
-      r.nslot = 1;
-      r.mcux = (uint32_t)((cw + 7) / 8);
-      r.nmcu = r.mcux * (uint32_t)((ch + 7) / 8);
-      r.slot_c[0] = (uint8_t)c;
-    } else {
-      r.mcux = (uint32_t)g.mcux;
-      r.nmcu = (uint32_t)g.mcux * (uint32_t)g.mcuy;
-      for (int t = 0; t < d.ncomp; ++t) {
-        const int c = d.comp[t], h = c == 0 ? img.hs : 1, vv = c == 0 ? img.vs : 1;
-        for (int y = 0; y < vv; ++y)
-          for (int x = 0; x < h; ++x) {
-            r.slot_c[r.nslot] = (uint8_t)c; r.slot_y[r.nslot] = (uint8_t)y; r.slot_x[r.nslot] = (uint8_t)x; r.slot_t[r.nslot] = (uint8_t)t;
-            ++r.nslot;
-          }
-      }
-    }
-    r.ri = d.restart_interval ? (uint32_t)d.restart_interval : r.nmcu;
-    r.nunits = (r.nmcu + r.ri - 1) / r.ri;
-    // the level: behind every earlier scan of the image that shares a component and overlaps the band
-    uint32_t level = by_level ? 0u : (uint32_t)index;
-    if (by_level)
-      for (int j = first; j < i; ++j) {
-        const attwarp_jpegdec_scan& e = scans[j];
-        bool share = false;
-        for (int a = 0; a < d.ncomp; ++a)
-          for (int bb = 0; bb < e.ncomp; ++bb) share = share || d.comp[a] == e.comp[bb];
-        if (share && e.ss <= d.se && d.ss <= e.se) level = std::max(level, rec[(size_t)j].level + 1u);
-      }
-    r.level = level;
-    nlevels = std::max(nlevels, (int)level + 1);
-    total_units += r.nunits;
-  }
-  for (int b = 0; b < B; ++b) ATTWARP_REQUIRE(count[b] >= 1, "jpegdec_plan_scans: image %d has no scan", b);
-  {                                                            // the units of an image, over all its scans
-    std::vector<int64_t> per(B, 0);
-    for (int i = 0; i < nscans; ++i) per[scans[i].image] += rec[(size_t)i].nunits;
-    for (int b = 0; b < B; ++b)
-      if (per[b] > ATTWARP_JPEGDEC_MAX_UNITS)
-        return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld units over its scans (> %d)", b, (long long)per[b], ATTWARP_JPEGDEC_MAX_UNITS);
-  }
-  if (total_units > JD_MAX_TOTAL_UNITS) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units in one call (> 2^30)", (long long)total_units);
-  if (const int rc = attwarp_jpegdec_plan_ex(images, B, table, table_bytes, 0, 0)) return rc;
-  uint8_t* t = static_cast<uint8_t*>(table);
-  attwarp_jpegdec_header h;
-  std::memcpy(&h, t, sizeof h);
-  JpHeader ph;
-  std::memset(&ph, 0, sizeof ph);
-  ph.magic = JP_MAGIC;
-  ph.nscans = nscans; ph.nlevels = nlevels; ph.total_units = (int32_t)total_units;
-  ph.off_scans = jp_header_off(B) + sizeof(JpHeader);
-  const JdSub* sub = reinterpret_cast<const JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JdImage));
-  ph.clear_off = jd_data_base(B, h.total_units);
-  ph.clear_bytes = sub[0].info_off - ph.clear_off;             // (both are multiples of 256)
-  ph.starts_off = jd_align(h.scratch_bytes, 256);
-  h.scratch_bytes = ph.starts_off + jd_align((uint64_t)total_units * 8u, 256);
-  h.table_bytes = need;
-  // records sorted by (level, image, position): a stable pass per level over the input order
-  JpScan* out = reinterpret_cast<JpScan*>(t + ph.off_scans);
-  uint32_t unit0 = 0;
-  for (int i = 0; i < nscans; ++i) {
-    rec[(size_t)i].unit0 = unit0;
-    unit0 += rec[(size_t)i].nunits;
-    rec[(size_t)i].last = i + 1 == nscans || scans[i + 1].image != scans[i].image;
-  }
-  int at = 0;
-  std::vector<int> order((size_t)nscans);                     // record -> the scan's position in the caller's array
-  for (int l = 0; l < nlevels; ++l) {
-    ph.level_scan0[l] = at;
-    uint32_t wave = 0;
-    for (int i = 0; i < nscans; ++i)
-      if ((int)rec[(size_t)i].level == l) {
-        rec[(size_t)i].wave0 = wave;
-        wave += rec[(size_t)i].nunits;
-        order[(size_t)at] = i;
-        std::memcpy(out + at++, &rec[(size_t)i], sizeof(JpScan));
-      }
-    ph.level_waves[l] = (int32_t)wave;
-  }
-  ph.level_scan0[nlevels] = at;
-  if (substreams) {
-    // behind everything there was: the per-scan results, then per cut scan its segments and, for an AC refinement, the
-    // history masks (8 bytes per block of the scan) and their prefix sums (4 bytes per block, one more)
-    JpSyncHeader sh;
-    std::memset(&sh, 0, sizeof sh);
-    sh.magic = JP_SYNC_MAGIC;
-    uint64_t soff = jd_align(h.scratch_bytes, 256);
-    sh.info_off = soff;
-    soff += jd_align((uint64_t)nscans * sizeof(JpSyncInfo), 256);
-    std::vector<JpSync> sy((size_t)nscans);
-    uint32_t ncut = 0;
-    int level = 0;
-    for (int q = 0; q < nscans; ++q) {
-      const JpScan& r = rec[(size_t)order[(size_t)q]];
-      const uint64_t len = data_bytes[order[(size_t)q]];
-      for (; level < (int)r.level; ++level) sh.level_cut0[level + 1] = ncut;
-      JpSync& y = sy[(size_t)q];
-      std::memset(&y, 0, sizeof y);
-      y.segment_bytes = (uint32_t)segment_bytes;
-      y.max_rounds = (uint32_t)max_rounds;
-      y.slot = (uint32_t)order[(size_t)q];
-      const uint64_t nseg = (len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes;
-      // a marker-less scan (one unit) whose data is at least two segments long
-      const int kinds = tune(TUNE_JPEGPROG_SYNC_KINDS);        // (the tuning flavour's per-kind timing; -1 in the product)
-      if (r.nunits == 1 && len >= 2u * (uint64_t)segment_bytes && nseg <= JP_SYNC_MAX_SEGS && (kinds < 0 || ((kinds >> r.kind) & 1))) {
-        y.nseg = (uint32_t)nseg;
-        y.seg_off = soff;
-        soff += jd_align(nseg * sizeof(JpSeg), 256);
-        if (r.kind == JP_AC_REFINE) {
-          y.mask_off = soff;
-          soff += jd_align((uint64_t)r.nmcu * 12u + 4u, 256);
-        }
-        sy[ncut++].cut = (uint32_t)q;
-      }
-    }
-    for (; level < nlevels + 1 && level <= ATTWARP_JPEGDEC_MAX_SCANS; ++level) sh.level_cut0[level + 1] = ncut;
-    sh.ncut = ncut;
-    h.scratch_bytes = soff;
-    uint8_t* trailer = t + ph.off_scans + (uint64_t)nscans * sizeof(JpScan);
-    std::memcpy(trailer, &sh, sizeof sh);
-    std::memcpy(trailer + sizeof sh, sy.data(), (size_t)nscans * sizeof(JpSync));
-  }
-  std::memcpy(t + jp_header_off(B), &ph, sizeof ph);
-  std::memcpy(t, &h, sizeof h);
-  return ATTWARP_OK;
-}
-
-extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
-                                          void* table, size_t table_bytes, int by_level) {
-  return jp_plan_scans(images, B, scans, nscans, table, table_bytes, by_level, 0, 0, nullptr);
-}
-
-extern "C" int attwarp_jpegdec_plan_scans_ex(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
-                                             void* table, size_t table_bytes, int by_level, int segment_bytes, int max_rounds,
-                                             const uint64_t* data_bytes) {
-  return jp_plan_scans(images, B, scans, nscans, table, table_bytes, by_level, segment_bytes, max_rounds, data_bytes);
-}
-
-extern "C" uint64_t attwarp_jpegdec_scan_info_offset(const void* table_host) {
-  if (!table_host) return 0;
-  attwarp_jpegdec_header h;
-  std::memcpy(&h, table_host, sizeof h);
-  if (h.magic != JD_MAGIC || h.B <= 0 || h.B > JD_MAX_B || h.table_bytes < jp_header_off(h.B) + sizeof(JpHeader)) return 0;
-  JpHeader ph;
-  std::memcpy(&ph, static_cast<const uint8_t*>(table_host) + jp_header_off(h.B), sizeof ph);
-  if (ph.magic != JP_MAGIC || ph.nscans < 1) return 0;
-  const uint64_t at = ph.off_scans + (uint64_t)ph.nscans * sizeof(JpScan);
-  if (h.table_bytes < at + jpegprog_sync_bytes(ph.nscans)) return 0;
-  JpSyncHeader sh;
-  std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + at, sizeof sh);
-  return sh.magic == JP_SYNC_MAGIC ? sh.info_off : 0;
-}
-
-extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
-                                            uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
-  attwarp_jpegdec_header h;
-  JpHeader ph;
-  if (const int rc = jd_decode_args("jpegdec_decode_scans", "attwarp_jpegdec_plan_scans", table_host, table_dev, stream_bytes, scratch, out,
-                                    out_bytes, status, h, &ph))
-    return rc;
-  hipStream_t st = as_stream(stream);
-  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
-  uint8_t* sc = static_cast<uint8_t*>(scratch);
-  const uint64_t clear_groups = std::min<uint64_t>(std::max<uint64_t>((ph.clear_bytes / 16u + JD_NT - 1) / JD_NT, (uint64_t)(h.B + JD_NT - 1) / JD_NT), 4096);
-  hipLaunchKernelGGL(jpegprog_clear_kernel, dim3((unsigned)clear_groups), dim3(JD_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegprog_clear_kernel")) return rc;
-  hipLaunchKernelGGL(jpegprog_scan_kernel, dim3(ph.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
-  if (const int rc = check_launch("jpegprog_scan_kernel")) return rc;
-  JpSyncHeader sh;
-  std::memset(&sh, 0, sizeof sh);
-  const uint64_t sync_at = ph.off_scans + (uint64_t)ph.nscans * sizeof(JpScan);
-  if (h.table_bytes >= sync_at + jpegprog_sync_bytes(ph.nscans)) {       // planned with sub-streams
-    std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + sync_at, sizeof sh);
-    bool ok = sh.magic == JP_SYNC_MAGIC && sh.ncut <= (uint32_t)ph.nscans && sh.level_cut0[0] == 0;
-    for (int l = 0; ok && l < ph.nlevels; ++l) ok = sh.level_cut0[l] <= sh.level_cut0[l + 1] && sh.level_cut0[l + 1] <= sh.ncut;
-    ATTWARP_REQUIRE(ok, "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans_ex");
-  }
-  for (int l = 0; l < ph.nlevels; ++l) {
-    ATTWARP_REQUIRE(ph.level_waves[l] >= 1, "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
-    if (const uint32_t ncut = sh.level_cut0[l + 1] - sh.level_cut0[l]) {  // the level holds a cut scan
-      hipLaunchKernelGGL(jpegprog_substream_kernel, dim3(ncut), dim3(JD_NT), 0, st, td, stream_bytes, sc, l);
-      if (const int rc = check_launch("jpegprog_substream_kernel")) return rc;
-    }
-    hipLaunchKernelGGL(jpegprog_entropy_kernel, dim3(ph.level_waves[l]), dim3(WAVE), 0, st, td, stream_bytes, sc, l);
-    if (const int rc = check_launch("jpegprog_entropy_kernel")) return rc;
-  }
-  return jd_launch_idct_color(h, td, sc, out, status, st);
-}
-
 // ---- every layout of a sequential file (attwarp_jpegdec_plan_layouts / attwarp_jpegdec_decode_layouts): the five
 // launches of the baseline family over JfImage records: up to four components of any sampling, a block-slot map of the MCU,
 // four DC predictors, four quantisation tables, the up-sampler libjpeg picks per component and four colour rules ----------------
-namespace attwarp {
-
-constexpr uint32_t JF_MAGIC = JD_MAGIC_LAYOUTS;
-
 __global__ __launch_bounds__(JD_NT) void jpegfmt_scan_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
                                                              uint8_t* __restrict__ scratch) {
   __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
@@ -1631,7 +1149,7 @@ __global__ __launch_bounds__(JD_NT) void jpegfmt_color_kernel(const uint8_t* __r
   const int tile = (int)blockIdx.x - im->color_tile0;
   if (tile == 0 && threadIdx.x == 0) {
     const JdState st = states[b];
-    status[b] = (int32_t)(st.st_scan ? st.st_scan : st.fail != 0xffffffffu ? (st.fail & 255u) : st.eoi ? 0u : (uint32_t)ATTWARP_JPEGDEC_E_NO_EOI);
+    status[b] = jd_status(st);
   }
   if (threadIdx.x < JF_MAX_COMP) s_comp[threadIdx.x] = im->comp[threadIdx.x];
   __syncthreads();
@@ -1654,202 +1172,13 @@ __global__ __launch_bounds__(JD_NT) void jpegfmt_color_kernel(const uint8_t* __r
   }
 }
 
-}  // namespace attwarp
-
-static size_t jpegfmt_bytes(int B) {
-  return (size_t)(jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JfImage) + (uint64_t)B * sizeof(JdSub));
-}
-
-extern "C" size_t attwarp_jpegdec_layouts_table_bytes(const attwarp_jpegdec_layout_image* images, int B) {
-  if (!images || B <= 0 || B > JD_MAX_B) {
-    fail(ATTWARP_E_ARG, "jpegdec_layouts_table_bytes: B=%d outside the limits", B);
-    return 0;
-  }
-  return jpegfmt_bytes(B);
-}
-
-// Everything the kernels index by, checked for image b -> its record's geometry in r (nothing else of r is written).
-static int jpegfmt_geom(const attwarp_jpegdec_layout_image& d, int b, JfImage& r) {
-  ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1 && d.H <= 65535 && d.W <= 65535, "jpegdec: image %d: size %d x %d outside 1..65535", b, d.H, d.W);
-  ATTWARP_REQUIRE(d.ncomp == 1 || d.ncomp == 3 || d.ncomp == 4, "jpegdec: image %d: %d components (1, 3 or 4)", b, d.ncomp);
-  ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d: restart interval %d", b, d.restart_interval);
-  ATTWARP_REQUIRE(d.mode >= ATTWARP_JPEGDEC_RGB && d.mode <= ATTWARP_JPEGDEC_KEEP, "jpegdec: image %d: unknown mode %d", b, d.mode);
-  ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegdec: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
-  for (int c = 0; c < d.ncomp; ++c) {
-    ATTWARP_REQUIRE(d.h[c] >= 1 && d.h[c] <= 4 && d.v[c] >= 1 && d.v[c] <= 4, "jpegdec: image %d: component %d: sampling factors %d x %d outside 1..4",
-                    b, c, d.h[c], d.v[c]);
-    for (int k = 0; k < 64; ++k) ATTWARP_REQUIRE(d.qt[c][k] <= 255, "jpegdec: image %d: a quantisation value above 255", b);
-    for (int t = 0; t < 2; ++t) {
-      char what[48];
-      const char* fault = t ? jd_huffman_fault(d.ac_counts[c], d.ac_symbols[c], false, what) : jd_huffman_fault(d.dc_counts[c], d.dc_symbols[c], true, what);
-      ATTWARP_REQUIRE(!fault, "jpegdec: image %d: %s", b, fault);
-    }
-  }
-  const uint64_t blocks = jf_blocks(d.W, d.H, d.ncomp, d.h, d.v);
-  const int rc = jf_layout(r, d.W, d.H, d.ncomp, d.h, d.v, d.color);
-  ATTWARP_REQUIRE(rc != JF_E_SLOTS, "jpegdec: image %d: more than %d blocks per MCU", b, JF_MAX_SLOTS);
-  ATTWARP_REQUIRE(rc != JF_E_FRACTION, "jpegdec: image %d: a component's sampling factors do not divide the frame's largest (fractional up-sampling)", b);
-  ATTWARP_REQUIRE(rc != JF_E_COLOR, "jpegdec: image %d: colour rule %d with %d components", b, d.color, d.ncomp);
-  ATTWARP_REQUIRE(rc == JF_OK, "jpegdec: image %d: bad layout", b);
-  const int64_t nmcu = (int64_t)r.mcux * r.mcuy;
-  const int64_t units = d.restart_interval ? (nmcu + d.restart_interval - 1) / d.restart_interval : 1;
-  if (units > ATTWARP_JPEGDEC_MAX_UNITS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld restart intervals (> %d)", b, (long long)units, ATTWARP_JPEGDEC_MAX_UNITS);
-  if (blocks >= ATTWARP_JPEGDEC_MAX_BLOCKS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %llu blocks (>= %d)", b, (unsigned long long)blocks, ATTWARP_JPEGDEC_MAX_BLOCKS);
-  if (d.stream_len >= ((uint64_t)1 << 31) || d.stream_off >= ((uint64_t)1 << 62))
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: entropy data of 2 GiB or more", b);
-  r.ri = d.restart_interval ? d.restart_interval : (int32_t)nmcu;
-  r.nunits = (int32_t)units;
-  return ATTWARP_OK;
-}
-
-extern "C" int attwarp_jpegdec_plan_layouts(const attwarp_jpegdec_layout_image* images, int B, void* table, size_t table_bytes,
-                                            int segment_bytes, int max_rounds) {
-  ATTWARP_REQUIRE(images, "jpegdec: null image array");
-  const bool substreams = segment_bytes != 0 || max_rounds != 0;
-  if (substreams) {
-    ATTWARP_REQUIRE(segment_bytes >= 32 && segment_bytes <= 512 && (segment_bytes & (segment_bytes - 1)) == 0,
-                    "jpegdec: segment_bytes=%d must be a power of two in 32..512", segment_bytes);
-    ATTWARP_REQUIRE(max_rounds >= 1 && max_rounds <= JD_SUB_MAX_ROUNDS, "jpegdec: max_rounds=%d outside 1..%d", max_rounds, JD_SUB_MAX_ROUNDS);
-  }
-  ATTWARP_REQUIRE(B > 0, "jpegdec: non-positive batch size");
-  if (B > JD_MAX_B) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: B=%d > 2^20", B);
-  ATTWARP_REQUIRE(table, "jpegdec_plan_layouts: null table");
-  const size_t need = jpegfmt_bytes(B);
-  ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan_layouts: table of %zu bytes, %zu needed", table_bytes, need);
-  int64_t units = 0, itiles = 0, ctiles = 0;
-  {
-    std::vector<JfImage> probe(1);
-    for (int b = 0; b < B; ++b) {                            // everything is checked before anything is written
-      if (const int rc = jpegfmt_geom(images[b], b, probe[0])) return rc;
-      units += probe[0].nunits;
-      itiles += (probe[0].nblocks + JD_IDCT_TILE - 1) / JD_IDCT_TILE;
-      ctiles += ((int64_t)images[b].H * images[b].W + JD_COLOR_TILE - 1) / JD_COLOR_TILE;
-    }
-  }
-  if (units > JD_MAX_TOTAL_UNITS || itiles > JD_MAX_TOTAL_UNITS || ctiles > JD_MAX_TOTAL_UNITS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units, %lld + %lld workgroups in one call (> 2^30)", (long long)units, (long long)itiles, (long long)ctiles);
-  uint8_t* t = static_cast<uint8_t*>(table);
-  std::memset(t, 0, need);
-  attwarp_jpegdec_header h;
-  std::memset(&h, 0, sizeof h);
-  h.magic = JF_MAGIC;
-  h.B = B;
-  h.total_units = (int32_t)units;
-  h.idct_tiles = (int32_t)itiles;
-  h.color_tiles = (int32_t)ctiles;
-  h.table_bytes = need;
-  h.off_images = jd_align(sizeof(attwarp_jpegdec_header), 16);
-  JfImage* im = reinterpret_cast<JfImage*>(t + h.off_images);
-  JdSub* sub = reinterpret_cast<JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JfImage));
-  int32_t nsub = 0;
-  uint64_t soff = jd_data_base(B, (int)units), ooff = 0, stream_bytes = 0;
-  int32_t u0 = 0, it0 = 0, ct0 = 0;
-  for (int b = 0; b < B; ++b) {
-    const attwarp_jpegdec_layout_image& d = images[b];
-    JfImage& r = im[b];
-    jpegfmt_geom(d, b, r);
-    r.stream_off = d.stream_off;
-    r.stream_len = (uint32_t)d.stream_len;
-    r.oc = d.mode == ATTWARP_JPEGDEC_L ? 1 : d.mode == ATTWARP_JPEGDEC_RGB ? 3 : d.ncomp;
-    r.conv = d.mode == ATTWARP_JPEGDEC_L ? JF_CONV_L : d.mode == ATTWARP_JPEGDEC_RGB ? JF_CONV_RGB : JF_CONV_KEEP;
-    r.swap = d.ncomp != 1 && r.oc == 3 && d.order == ATTWARP_BGR;
-    r.unit0 = u0; r.idct_tile0 = it0; r.color_tile0 = ct0;
-    for (int c = 0; c < d.ncomp; ++c) {
-      std::memcpy(r.qt[c], d.qt[c], sizeof r.qt[c]);
-      std::memcpy(r.dc_counts[c], d.dc_counts[c], 16);
-      std::memcpy(r.ac_counts[c], d.ac_counts[c], 16);
-      std::memcpy(r.dc_symbols[c], d.dc_symbols[c], 256);
-      std::memcpy(r.ac_symbols[c], d.ac_symbols[c], 256);
-    }
-    r.period = jf_period(r);
-    r.coef_off = soff;
-    soff += jd_align((uint64_t)r.nblocks * 128u, 256);
-    r.plane_off = soff;
-    soff += jd_align((uint64_t)r.nblocks * 64u, 256);
-    r.out_off = ooff;
-    ooff += (uint64_t)d.H * d.W * r.oc;
-    u0 += r.nunits;
-    it0 += (int32_t)((r.nblocks + JD_IDCT_TILE - 1) / JD_IDCT_TILE);
-    ct0 += (int32_t)(((int64_t)d.H * d.W + JD_COLOR_TILE - 1) / JD_COLOR_TILE);
-    stream_bytes = std::max(stream_bytes, d.stream_off + d.stream_len);
-    const uint64_t nseg = substreams ? (d.stream_len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes : 0;
-    sub[b].segment_bytes = (uint32_t)segment_bytes;
-    sub[b].max_rounds = (uint32_t)max_rounds;
-    if (substreams && r.nunits == 1 && d.stream_len >= 2u * (uint64_t)segment_bytes && nseg <= (uint64_t)JD_SUB_MAX_SEGS) {
-      sub[b].nseg = (uint32_t)nseg;
-      sub[nsub++].image = b;
-    }
-  }
-  const uint64_t info_off = soff;
-  soff += jd_align((uint64_t)B * sizeof(JdSubInfo), 256);
-  for (int b = 0; b < B; ++b) {
-    sub[b].info_off = info_off;
-    sub[b].seg_off = soff;
-    soff += jd_align((uint64_t)sub[b].nseg * (sizeof(JfSegState) + sizeof(JfSegment)), 256);
-  }
-  h.reserved = nsub;
-  h.scratch_bytes = soff;
-  h.out_bytes = ooff;
-  h.stream_bytes = stream_bytes;
-  std::memcpy(t, &h, sizeof h);
-  return ATTWARP_OK;
-}
-
-extern "C" int attwarp_jpegdec_decode_layouts(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
-                                              uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
-  const char* who = "jpegdec_decode_layouts";
-  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "%s: null pointer", who);
-  attwarp_jpegdec_header h;
-  std::memcpy(&h, table_host, sizeof h);
-  ATTWARP_REQUIRE(h.magic == JF_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS &&
-                      h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS && h.total_units >= h.B &&
-                      h.total_units <= JD_MAX_TOTAL_UNITS && h.reserved >= 0 && h.reserved <= h.B,
-                  "%s: not a table of attwarp_jpegdec_plan_layouts", who);
-  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "%s: out of %zu bytes, %llu needed", who, out_bytes, (unsigned long long)h.out_bytes);
-  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
-                      reinterpret_cast<uintptr_t>(status) % 4 == 0,
-                  "%s: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned", who);
-  hipStream_t st = as_stream(stream);
-  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
-  uint8_t* sc = static_cast<uint8_t*>(scratch);
-  hipLaunchKernelGGL(jpegfmt_scan_kernel, dim3(h.B), dim3(JD_NT), 0, st, td, stream_bytes, sc);
-  if (const int rc = check_launch("jpegfmt_scan_kernel")) return rc;
-  hipLaunchKernelGGL(jpegfmt_substream_kernel, dim3(std::max(h.reserved, 1)), dim3(JD_NT), 0, st, td, stream_bytes, sc);
-  if (const int rc = check_launch("jpegfmt_substream_kernel")) return rc;
-  hipLaunchKernelGGL(jpegfmt_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
-  if (const int rc = check_launch("jpegfmt_entropy_kernel")) return rc;
-  hipLaunchKernelGGL(jpegfmt_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegfmt_idct_kernel")) return rc;
-  hipLaunchKernelGGL(jpegfmt_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
-  return check_launch("jpegfmt_color_kernel");
-}
-
 // ---- scans of every layout (attwarp_jpegdec_plan_layout_scans / attwarp_jpegdec_decode_layout_scans): a table of
 // attwarp_jpegdec_plan_layouts for B one-unit images (all the IDCT and colour kernels read; its magic replaced, so that
 // attwarp_jpegdec_decode_layouts refuses it) with a JsHeader and the JsScan records behind it, sorted by (level, image, position) ---
-namespace attwarp {
-
 constexpr uint32_t JS_MAGIC = JD_MAGIC_LAYOUT_SCANS, JS_MAGIC_SCANS = 0x4745504eu;   // of the table's first header / of the JsHeader
-struct JsHeader {
-  uint32_t magic;
-  int32_t nscans, nlevels, total_units;
-  uint64_t off_scans;                  // JsScan[nscans] in the table
-  uint64_t starts_off;                 // uint32 starts[total_units], ends[total_units] in the scratch buffer
-  uint64_t clear_off, clear_bytes;     // every image's coefficients and planes in the scratch buffer, multiples of 16
-  int32_t level_scan0[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // the first record of each level
-  int32_t level_waves[ATTWARP_JPEGDEC_MAX_SCANS + 1];   // waves of each level's launch
-  int32_t level_tables[ATTWARP_JPEGDEC_MAX_SCANS + 1];  // code tables the scans of each level hold in LDS at most (1 .. 8)
-};
-static_assert(sizeof(JsHeader) % 8 == 0, "record layout");
-__host__ __device__ inline uint64_t js_header_off(int B) {
-  return jd_align(sizeof(attwarp_jpegdec_header), 16) + (uint64_t)B * sizeof(JfImage) + (uint64_t)B * sizeof(JdSub);
-}
-
 __global__ __launch_bounds__(JD_NT) void jpegscan_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   const JfView v(table, scratch);
-  const JsHeader* sh = reinterpret_cast<const JsHeader*>(table + js_header_off(v.hdr->B));
+  const JpHeader* sh = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JfImage)));
   jp_clear_body(v, scratch, sh->clear_off, sh->clear_bytes);
 }
 
@@ -1858,7 +1187,7 @@ __global__ __launch_bounds__(JD_NT) void jpegscan_marks_kernel(const uint8_t* __
                                                                uint8_t* __restrict__ scratch) {
   __shared__ uint32_t s_tmp[JD_NT], s_term, s_bad;
   const JfView v(table, scratch);
-  const JsHeader* sh = reinterpret_cast<const JsHeader*>(table + js_header_off(v.hdr->B));
+  const JpHeader* sh = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JfImage)));
   jp_marks_body(v, reinterpret_cast<const JsScan*>(table + sh->off_scans) + blockIdx.x, stream,
                 reinterpret_cast<uint32_t*>(scratch + sh->starts_off), sh->total_units, s_tmp, s_term, s_bad);
 }
@@ -1880,7 +1209,7 @@ __global__ __launch_bounds__(WAVE) void jpegscan_entropy_kernel(const uint8_t* _
   __shared__ uint32_t s_pos, s_err, s_run;
   const int lane = threadIdx.x, w = blockIdx.x;
   const JfView v(table, scratch);
-  const JsHeader* sh = reinterpret_cast<const JsHeader*>(table + js_header_off(v.hdr->B));
+  const JpHeader* sh = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JfImage)));
   const JsScan* scans = reinterpret_cast<const JsScan*>(table + sh->off_scans);
   if (level < 0 || level >= ATTWARP_JPEGDEC_MAX_SCANS) return;
   int lo = sh->level_scan0[level], hi = sh->level_scan0[level + 1] - 1;
@@ -1975,49 +1304,314 @@ __global__ __launch_bounds__(WAVE) void jpegscan_entropy_kernel(const uint8_t* _
 
 }  // namespace attwarp
 
-static size_t jpegscan_bytes(int B, int nscans) { return (size_t)(js_header_off(B) + sizeof(JsHeader) + (uint64_t)nscans * sizeof(JsScan)); }
+using namespace attwarp;
 
-extern "C" size_t attwarp_jpegdec_layout_scans_table_bytes(const attwarp_jpegdec_layout_image* images, int B, int nscans) {
-  if (!images || B <= 0 || B > JD_MAX_B || nscans < B || (int64_t)nscans > (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS) {
-    fail(ATTWARP_E_ARG, "jpegdec_layout_scans_table_bytes: B=%d, %d scans outside the limits", B, nscans);
-    return 0;
-  }
-  return jpegscan_bytes(B, nscans);
+// ---- the host side: planners and entry points of the four families ---------------------------------------------------------------------
+// What is wrong with a Huffman table (counts per length, symbols), in words for the caller's message; nullptr: nothing.
+static const char* jd_huffman_fault(const uint8_t* counts, const uint8_t* symbols, bool dc, char (&what)[48]) {
+  int left = 1, n = 0;
+  for (int l = 0; l < 16 && left >= 0; ++l) { left = 2 * left - counts[l]; n += counts[l]; }
+  if (left < 0) return "an over-subscribed Huffman table";
+  std::snprintf(what, sizeof what, "a Huffman table of %d symbols", n);
+  if (n > 256) return what;
+  for (int k = 0; dc && k < n; ++k)
+    if (symbols[k] > 15) return "a DC category above 15";
+  return nullptr;
 }
 
-extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_image* images, int B, const attwarp_jpegdec_layout_scan* scans,
-                                                 int nscans, void* table, size_t table_bytes, int by_level) {
-  ATTWARP_REQUIRE(images && scans && table, "jpegdec_plan_layout_scans: null pointer");
-  ATTWARP_REQUIRE(B > 0 && B <= JD_MAX_B && nscans >= B && (int64_t)nscans <= (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS,
-                  "jpegdec_plan_layout_scans: B=%d, %d scans outside the limits", B, nscans);
-  const size_t need = jpegscan_bytes(B, nscans);
-  ATTWARP_REQUIRE(table_bytes >= need, "jpegdec_plan_layout_scans: table of %zu bytes, %zu needed", table_bytes, need);
-  for (int b = 0; b < B; ++b)
-    ATTWARP_REQUIRE(images[b].restart_interval == 0, "jpegdec_plan_layout_scans: image %d: the restart interval belongs to the scans", b);
-  // everything is checked before anything is written: the scans come image by image, in file order
-  std::vector<JsScan> rec((size_t)nscans);
-  std::vector<int> count(B, 0);
-  std::vector<int64_t> per(B, 0);
-  std::vector<JfImage> frame(1);
-  int64_t total_units = 0;
-  int nlevels = 0, prev = -1;
-  for (int i = 0, first = 0; i < nscans; ++i) {
-    const attwarp_jpegdec_layout_scan& d = scans[i];
-    ATTWARP_REQUIRE(d.image >= 0 && d.image < B && d.image >= prev, "jpegdec_plan_layout_scans: scan %d: image %d out of order", i, d.image);
-    const attwarp_jpegdec_layout_image& img = images[d.image];
-    if (d.image != prev) {
-      first = i; prev = d.image;
-      if (const int rc = jpegfmt_geom(img, d.image, frame[0])) return rc;
-    }
-    const JfImage& f = frame[0];
-    const int index = i - first;
-    if (index >= ATTWARP_JPEGDEC_MAX_SCANS)
-      return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: more than %d scans", d.image, ATTWARP_JPEGDEC_MAX_SCANS);
-    ++count[d.image];
-    ATTWARP_REQUIRE(d.ncomp >= 1 && d.ncomp <= img.ncomp && d.ncomp <= JF_MAX_COMP, "jpegdec: image %d scan %d: %d components", d.image, index, d.ncomp);
+// What both frames check of the quantisation and Huffman tables of component c (d: an attwarp_jpegdec_image or _layout_image).
+template <class Input>
+static int jd_check_tables(const Input& d, int b, int c) {
+  for (int k = 0; k < 64; ++k) ATTWARP_REQUIRE(d.qt[c][k] <= 255, "jpegdec: image %d: a quantisation value above 255", b);
+  for (int t = 0; t < 2; ++t) {
+    char what[48];
+    const char* fault = t ? jd_huffman_fault(d.ac_counts[c], d.ac_symbols[c], false, what) : jd_huffman_fault(d.dc_counts[c], d.dc_symbols[c], true, what);
+    ATTWARP_REQUIRE(!fault, "jpegdec: image %d: %s", b, fault);
+  }
+  return ATTWARP_OK;
+}
+// ... and of its units, blocks and data, once the geometry is known -> r.ri, r.nunits.
+template <class Input, class Image>
+static int jd_check_sizes(const Input& d, int b, uint64_t blocks, Image& r) {
+  const int64_t nmcu = (int64_t)r.mcux * r.mcuy;
+  const int64_t units = d.restart_interval ? (nmcu + d.restart_interval - 1) / d.restart_interval : 1;
+  if (units > ATTWARP_JPEGDEC_MAX_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld restart intervals (> %d)", b, (long long)units, ATTWARP_JPEGDEC_MAX_UNITS);
+  if (blocks >= ATTWARP_JPEGDEC_MAX_BLOCKS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %llu blocks (>= %d)", b, (unsigned long long)blocks, ATTWARP_JPEGDEC_MAX_BLOCKS);
+  if (d.stream_len >= ((uint64_t)1 << 31) || d.stream_off >= ((uint64_t)1 << 62))
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: entropy data of 2 GiB or more", b);
+  r.ri = d.restart_interval ? d.restart_interval : (int32_t)nmcu;
+  r.nunits = (int32_t)units;
+  return ATTWARP_OK;
+}
+
+// A record family on the host: the caller's image type, its record, segment-state and segment types with the most components
+// and block slots of an MCU, the table's magic, the planner's name in messages, and two steps per image: geom() checks everything the kernels index by
+// and writes the record's geometry (nothing else of r), fill() writes what else is the family's own.  jd_plan_frames does
+// the rest for both.
+struct JdFrames {
+  using Input = attwarp_jpegdec_image;
+  using Image = JdImage;
+  using SegState = JdSegState;
+  using Segment = JdSegment;
+  static constexpr int MAX_COMP = 3, MAX_SLOTS = 6;
+  static constexpr uint32_t MAGIC = JD_MAGIC;
+  static constexpr const char* PLAN = "jpegdec_plan";
+  static int geom(const Input& d, int b, JdImage& r) {
+    ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1 && d.H <= 65535 && d.W <= 65535, "jpegdec: image %d: size %d x %d outside 1..65535", b, d.H, d.W);
+    ATTWARP_REQUIRE(d.ncomp == 1 || d.ncomp == 3, "jpegdec: image %d: %d components (1 or 3)", b, d.ncomp);
+    ATTWARP_REQUIRE((d.hs == 1 && d.vs == 1) || (d.ncomp == 3 && d.hs == 2 && (d.vs == 1 || d.vs == 2)),
+                    "jpegdec: image %d: luma sampling %d x %d (1x1, 2x1, 2x2; grey 1x1)", b, d.hs, d.vs);
+    ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d: restart interval %d", b, d.restart_interval);
+    ATTWARP_REQUIRE(d.mode >= ATTWARP_JPEGDEC_RGB && d.mode <= ATTWARP_JPEGDEC_KEEP, "jpegdec: image %d: unknown mode %d", b, d.mode);
+    ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegdec: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
     for (int c = 0; c < d.ncomp; ++c)
-      ATTWARP_REQUIRE(d.comp[c] >= 0 && d.comp[c] < img.ncomp && (c == 0 || d.comp[c] > d.comp[c - 1]),
-                      "jpegdec: image %d scan %d: components not in frame order", d.image, index);
+      if (const int rc = jd_check_tables(d, b, c)) return rc;
+    r.H = d.H; r.W = d.W; r.ncomp = d.ncomp; r.hs = d.hs; r.vs = d.vs;
+    r.mcux = (d.W + 8 * d.hs - 1) / (8 * d.hs);
+    r.mcuy = (d.H + 8 * d.vs - 1) / (8 * d.vs);
+    int64_t blocks = 0;
+    for (int c = 0; c < 3; ++c) {
+      r.bw[c] = c < d.ncomp ? r.mcux * (c == 0 ? d.hs : 1) : 0;
+      r.bh[c] = c < d.ncomp ? r.mcuy * (c == 0 ? d.vs : 1) : 0;
+      r.block0[c] = (uint32_t)blocks;
+      blocks += (int64_t)r.bw[c] * r.bh[c];
+    }
+    r.nblocks = (uint32_t)blocks;
+    return jd_check_sizes(d, b, (uint64_t)blocks, r);
+  }
+  static void fill(const Input& d, JdImage& r) {
+    r.to_luma = d.ncomp == 3 && r.oc == 1;
+    r.swap = d.ncomp == 3 && r.oc == 3 && d.order == ATTWARP_BGR;
+    std::memcpy(r.qt, d.qt, sizeof r.qt);
+    std::memcpy(r.dc_counts, d.dc_counts, sizeof r.dc_counts);
+    std::memcpy(r.ac_counts, d.ac_counts, sizeof r.ac_counts);
+    std::memcpy(r.dc_symbols, d.dc_symbols, sizeof r.dc_symbols);
+    std::memcpy(r.ac_symbols, d.ac_symbols, sizeof r.ac_symbols);
+  }
+};
+struct JfFrames {
+  using Input = attwarp_jpegdec_layout_image;
+  using Image = JfImage;
+  using SegState = JfSegState;
+  using Segment = JfSegment;
+  static constexpr int MAX_COMP = JF_MAX_COMP, MAX_SLOTS = JF_MAX_SLOTS;
+  static constexpr uint32_t MAGIC = JD_MAGIC_LAYOUTS;
+  static constexpr const char* PLAN = "jpegdec_plan_layouts";
+  static int geom(const Input& d, int b, JfImage& r) {
+    ATTWARP_REQUIRE(d.H >= 1 && d.W >= 1 && d.H <= 65535 && d.W <= 65535, "jpegdec: image %d: size %d x %d outside 1..65535", b, d.H, d.W);
+    ATTWARP_REQUIRE(d.ncomp == 1 || d.ncomp == 3 || d.ncomp == 4, "jpegdec: image %d: %d components (1, 3 or 4)", b, d.ncomp);
+    ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d: restart interval %d", b, d.restart_interval);
+    ATTWARP_REQUIRE(d.mode >= ATTWARP_JPEGDEC_RGB && d.mode <= ATTWARP_JPEGDEC_KEEP, "jpegdec: image %d: unknown mode %d", b, d.mode);
+    ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegdec: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
+    for (int c = 0; c < d.ncomp; ++c) {
+      ATTWARP_REQUIRE(d.h[c] >= 1 && d.h[c] <= 4 && d.v[c] >= 1 && d.v[c] <= 4, "jpegdec: image %d: component %d: sampling factors %d x %d outside 1..4",
+                      b, c, d.h[c], d.v[c]);
+      if (const int rc = jd_check_tables(d, b, c)) return rc;
+    }
+    const uint64_t blocks = jf_blocks(d.W, d.H, d.ncomp, d.h, d.v);
+    const int rc = jf_layout(r, d.W, d.H, d.ncomp, d.h, d.v, d.color);
+    ATTWARP_REQUIRE(rc != JF_E_SLOTS, "jpegdec: image %d: more than %d blocks per MCU", b, JF_MAX_SLOTS);
+    ATTWARP_REQUIRE(rc != JF_E_FRACTION, "jpegdec: image %d: a component's sampling factors do not divide the frame's largest (fractional up-sampling)", b);
+    ATTWARP_REQUIRE(rc != JF_E_COLOR, "jpegdec: image %d: colour rule %d with %d components", b, d.color, d.ncomp);
+    ATTWARP_REQUIRE(rc == JF_OK, "jpegdec: image %d: bad layout", b);
+    return jd_check_sizes(d, b, blocks, r);
+  }
+  static void fill(const Input& d, JfImage& r) {
+    r.conv = d.mode == ATTWARP_JPEGDEC_L ? JF_CONV_L : d.mode == ATTWARP_JPEGDEC_RGB ? JF_CONV_RGB : JF_CONV_KEEP;
+    r.swap = d.ncomp != 1 && r.oc == 3 && d.order == ATTWARP_BGR;
+    for (int c = 0; c < d.ncomp; ++c) {
+      std::memcpy(r.qt[c], d.qt[c], sizeof r.qt[c]);
+      std::memcpy(r.dc_counts[c], d.dc_counts[c], 16);
+      std::memcpy(r.ac_counts[c], d.ac_counts[c], 16);
+      std::memcpy(r.dc_symbols[c], d.dc_symbols[c], 256);
+      std::memcpy(r.ac_symbols[c], d.ac_symbols[c], 256);
+    }
+    r.period = jf_period(r);
+  }
+};
+
+static int jd_substream_args(int segment_bytes, int max_rounds) {
+  ATTWARP_REQUIRE(segment_bytes >= 32 && segment_bytes <= 512 && (segment_bytes & (segment_bytes - 1)) == 0,
+                  "jpegdec: segment_bytes=%d must be a power of two in 32..512", segment_bytes);
+  ATTWARP_REQUIRE(max_rounds >= 1 && max_rounds <= JD_SUB_MAX_ROUNDS, "jpegdec: max_rounds=%d outside 1..%d", max_rounds, JD_SUB_MAX_ROUNDS);
+  return ATTWARP_OK;
+}
+
+// The table of a family's frames: header, image records, sub-stream records; segment_bytes = max_rounds = 0 plans no sub-streams.
+template <class F>
+static int jd_plan_frames(const typename F::Input* images, int B, void* table, size_t table_bytes, int segment_bytes, int max_rounds) {
+  using Image = typename F::Image;
+  ATTWARP_REQUIRE(images, "jpegdec: null image array");
+  const bool substreams = segment_bytes != 0 || max_rounds != 0;
+  if (substreams)
+    if (const int rc = jd_substream_args(segment_bytes, max_rounds)) return rc;
+  ATTWARP_REQUIRE(B > 0, "jpegdec: non-positive batch size");
+  if (B > JD_MAX_B) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: B=%d > 2^20", B);
+  ATTWARP_REQUIRE(table, "%s: null table", F::PLAN);
+  const size_t need = (size_t)jp_header_off(B, sizeof(Image));
+  ATTWARP_REQUIRE(table_bytes >= need, "%s: table of %zu bytes, %zu needed", F::PLAN, table_bytes, need);
+  const auto tiles = [](uint64_t n, uint64_t tile) { return (int64_t)((n + tile - 1) / tile); };
+  int64_t units = 0, itiles = 0, ctiles = 0;
+  {
+    std::vector<Image> probe(1);
+    for (int b = 0; b < B; ++b) {                            // everything is checked before anything is written
+      if (const int rc = F::geom(images[b], b, probe[0])) return rc;
+      units += probe[0].nunits;
+      itiles += tiles(probe[0].nblocks, JD_IDCT_TILE);
+      ctiles += tiles((uint64_t)images[b].H * images[b].W, JD_COLOR_TILE);
+    }
+  }
+  if (units > JD_MAX_TOTAL_UNITS || itiles > JD_MAX_TOTAL_UNITS || ctiles > JD_MAX_TOTAL_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units, %lld + %lld workgroups in one call (> 2^30)", (long long)units, (long long)itiles, (long long)ctiles);
+  uint8_t* t = static_cast<uint8_t*>(table);
+  std::memset(t, 0, need);
+  attwarp_jpegdec_header h;
+  std::memset(&h, 0, sizeof h);
+  h.magic = F::MAGIC;
+  h.B = B;
+  h.total_units = (int32_t)units;
+  h.idct_tiles = (int32_t)itiles;
+  h.color_tiles = (int32_t)ctiles;
+  h.table_bytes = need;
+  h.off_images = jd_align(sizeof(attwarp_jpegdec_header), 16);
+  Image* im = reinterpret_cast<Image*>(t + h.off_images);
+  JdSub* sub = reinterpret_cast<JdSub*>(t + h.off_images + (uint64_t)B * sizeof(Image));
+  int32_t nsub = 0;
+  uint64_t soff = jd_data_base(B, (int)units), ooff = 0, stream_bytes = 0;
+  int32_t u0 = 0, it0 = 0, ct0 = 0;
+  for (int b = 0; b < B; ++b) {
+    const typename F::Input& d = images[b];
+    Image& r = im[b];
+    F::geom(d, b, r);
+    r.stream_off = d.stream_off;
+    r.stream_len = (uint32_t)d.stream_len;
+    r.oc = d.mode == ATTWARP_JPEGDEC_L ? 1 : d.mode == ATTWARP_JPEGDEC_RGB ? 3 : d.ncomp;
+    F::fill(d, r);
+    r.unit0 = u0; r.idct_tile0 = it0; r.color_tile0 = ct0;
+    r.coef_off = soff;
+    soff += jd_align((uint64_t)r.nblocks * 128u, 256);
+    r.plane_off = soff;
+    soff += jd_align((uint64_t)r.nblocks * 64u, 256);
+    r.out_off = ooff;
+    ooff += (uint64_t)d.H * d.W * r.oc;
+    u0 += r.nunits;
+    it0 += (int32_t)tiles(r.nblocks, JD_IDCT_TILE);
+    ct0 += (int32_t)tiles((uint64_t)d.H * d.W, JD_COLOR_TILE);
+    stream_bytes = std::max(stream_bytes, d.stream_off + d.stream_len);
+    // sub-streams: a marker-less image (one unit) whose data is at least two segments long
+    const uint64_t nseg = substreams ? (d.stream_len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes : 0;
+    sub[b].segment_bytes = (uint32_t)segment_bytes;
+    sub[b].max_rounds = (uint32_t)max_rounds;
+    if (substreams && r.nunits == 1 && d.stream_len >= 2u * (uint64_t)segment_bytes && nseg <= (uint64_t)JD_SUB_MAX_SEGS) {
+      sub[b].nseg = (uint32_t)nseg;
+      sub[nsub++].image = b;
+    }
+  }
+  // behind everything there was: the per-image sub-stream results, then the segments of every image planned for them
+  const uint64_t info_off = soff;
+  soff += jd_align((uint64_t)B * sizeof(JdSubInfo), 256);
+  for (int b = 0; b < B; ++b) {
+    sub[b].info_off = info_off;
+    sub[b].seg_off = soff;
+    soff += jd_align((uint64_t)sub[b].nseg * (sizeof(typename F::SegState) + sizeof(typename F::Segment)), 256);
+  }
+  h.reserved = nsub;
+  h.scratch_bytes = soff;
+  h.out_bytes = ooff;
+  h.stream_bytes = stream_bytes;
+  std::memcpy(t, &h, sizeof h);
+  return ATTWARP_OK;
+}
+
+extern "C" size_t attwarp_jpegdec_table_bytes(const attwarp_jpegdec_image* images, int B) {
+  if (!images || B <= 0 || B > JD_MAX_B) {
+    fail(ATTWARP_E_ARG, "jpegdec_table_bytes: B=%d outside the limits", B);
+    return 0;
+  }
+  return (size_t)jp_header_off(B, sizeof(JdImage));
+}
+extern "C" size_t attwarp_jpegdec_layouts_table_bytes(const attwarp_jpegdec_layout_image* images, int B) {
+  if (!images || B <= 0 || B > JD_MAX_B) {
+    fail(ATTWARP_E_ARG, "jpegdec_layouts_table_bytes: B=%d outside the limits", B);
+    return 0;
+  }
+  return (size_t)jp_header_off(B, sizeof(JfImage));
+}
+
+extern "C" int attwarp_jpegdec_plan(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes) {
+  return jd_plan_frames<JdFrames>(images, B, table, table_bytes, 0, 0);
+}
+extern "C" int attwarp_jpegdec_plan_ex(const attwarp_jpegdec_image* images, int B, void* table, size_t table_bytes, int segment_bytes,
+                                       int max_rounds) {
+  return jd_plan_frames<JdFrames>(images, B, table, table_bytes, segment_bytes, max_rounds);
+}
+extern "C" int attwarp_jpegdec_plan_layouts(const attwarp_jpegdec_layout_image* images, int B, void* table, size_t table_bytes,
+                                            int segment_bytes, int max_rounds) {
+  return jd_plan_frames<JfFrames>(images, B, table, table_bytes, segment_bytes, max_rounds);
+}
+
+extern "C" uint64_t attwarp_jpegdec_info_offset(const void* table_host) {
+  if (!table_host) return 0;
+  attwarp_jpegdec_header h;
+  std::memcpy(&h, table_host, sizeof h);
+  if ((h.magic != JD_MAGIC && h.magic != JD_MAGIC_LAYOUTS && h.magic != JD_MAGIC_LAYOUT_SCANS) || h.B <= 0 || h.B > JD_MAX_B) return 0;
+  JdSub s;
+  const size_t record = h.magic == JD_MAGIC ? sizeof(JdImage) : sizeof(JfImage);
+  std::memcpy(&s, static_cast<const uint8_t*>(table_host) + h.off_images + (uint64_t)h.B * record, sizeof s);
+  return s.info_off;
+}
+
+// ---- the plan over all scans of a list of files: a table of the family's frames for B one-unit images (what the IDCT and
+// colour kernels read) with a scan header and the scan records behind it, sorted by (level, image, position) ------------------------
+// A scan family on the host: its frames, the caller's scan type, the record and the header it writes, the magic of the table
+// and of the header, the planner's name in messages, whether a frame is checked in front of its first scan's own fields or
+// behind them (what the caller is told first when both are wrong), and per scan: band() checks the progression, fill()
+// writes the kind and the checked Huffman tables, geometry() says how a component lies in the frame; per level: close().
+struct JpScans {
+  using Frames = JdFrames;
+  using Input = attwarp_jpegdec_scan;
+  using Scan = JpScan;
+  using Header = JpHeader;
+  static constexpr uint32_t TABLE_MAGIC = JD_MAGIC, MAGIC = JP_MAGIC;
+  static constexpr const char* PLAN = "jpegdec_plan_scans";
+  static constexpr bool FRAME_FIRST = false;
+  static JpHeader& scans(Header& h) { return h; }
+  static int band(const Input& d, int index) {
+    ATTWARP_REQUIRE(d.ss >= 0 && d.ss <= d.se && d.se <= 63 && (d.ss != 0 || d.se == 0) && (d.ss == 0 || d.ncomp == 1) && d.al >= 0 &&
+                        d.al <= 13 && d.ah >= 0 && d.ah <= 14 && (d.ah == 0 || d.al == d.ah - 1),
+                    "jpegdec: image %d scan %d: bad progression Ss=%d Se=%d Ah=%d Al=%d", d.image, index, d.ss, d.se, d.ah, d.al);
+    return ATTWARP_OK;
+  }
+  static int fill(const Input& d, int index, JpScan& r) {
+    r.kind = (uint32_t)((d.ss ? 2 : 0) + (d.ah ? 1 : 0));
+    const int ntab = d.ss ? 1 : d.ncomp;
+    for (int t = 0; t < ntab; ++t) {
+      char what[48];
+      const char* fault = jd_huffman_fault(d.counts[t], d.symbols[t], !d.ss, what);
+      ATTWARP_REQUIRE(!fault, "jpegdec: image %d scan %d: %s", d.image, index, fault);
+      std::memcpy(r.counts[t], d.counts[t], 16);
+      std::memcpy(r.symbols[t], d.symbols[t], 256);
+    }
+    return ATTWARP_OK;
+  }
+  static void geometry(const JdImage& f, int c, int& h, int& v, int& dw, int& dh) {
+    h = c == 0 ? f.hs : 1; v = c == 0 ? f.vs : 1;
+    dw = (f.W * h + f.hs - 1) / f.hs; dh = (f.H * v + f.vs - 1) / f.vs;
+  }
+  static void close(Header&, int, const std::vector<JpScan>&) {}
+};
+struct JsScans {
+  using Frames = JfFrames;
+  using Input = attwarp_jpegdec_layout_scan;
+  using Scan = JsScan;
+  using Header = JsHeader;
+  static constexpr uint32_t TABLE_MAGIC = JS_MAGIC, MAGIC = JS_MAGIC_SCANS;
+  static constexpr const char* PLAN = "jpegdec_plan_layout_scans";
+  static constexpr bool FRAME_FIRST = true;
+  static JpHeader& scans(Header& h) { return h.h; }
+  static int band(const Input& d, int index) {
     if (d.sequential)
       ATTWARP_REQUIRE(d.ss == 0 && d.se == 63 && d.ah == 0 && d.al == 0, "jpegdec: image %d scan %d: a sequential scan with Ss=%d Se=%d Ah=%d Al=%d",
                       d.image, index, d.ss, d.se, d.ah, d.al);
@@ -2026,17 +1620,16 @@ extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_im
                           d.al <= 13 && d.ah >= 0 && d.ah <= 14 && (d.ah == 0 || d.al == d.ah - 1),
                       "jpegdec: image %d scan %d: bad progression Ss=%d Se=%d Ah=%d Al=%d in a scan of %d component(s)", d.image, index, d.ss,
                       d.se, d.ah, d.al, d.ncomp);
-    ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d scan %d: restart interval %d", d.image, index,
-                    d.restart_interval);
-    ATTWARP_REQUIRE(d.stream_off <= img.stream_len, "jpegdec: image %d scan %d: data outside the image's", d.image, index);
-    JsScan& r = rec[(size_t)i];
-    std::memset(&r, 0, sizeof r);
-    r.image = (uint32_t)d.image; r.index = (uint32_t)index; r.off = (uint32_t)d.stream_off;
+    return ATTWARP_OK;
+  }
+  // the code tables a scan holds in LDS: a DC and an AC table per component of a sequential scan
+  static int tables(uint32_t kind, int ncomp, bool dc) {
+    return kind == JS_SEQUENTIAL ? ncomp : dc ? (kind == JP_DC_FIRST ? ncomp : 0) : (kind >= JP_AC_FIRST ? 1 : 0);
+  }
+  static int fill(const Input& d, int index, JsScan& r) {
     r.kind = d.sequential ? JS_SEQUENTIAL : (uint32_t)((d.ss ? 2 : 0) + (d.ah ? 1 : 0));
-    r.ss = (uint32_t)d.ss; r.se = (uint32_t)d.se; r.al = (uint32_t)d.al;
     r.ncomp = (uint32_t)d.ncomp;
-    const int ndc = r.kind == JS_SEQUENTIAL || r.kind == JP_DC_FIRST ? d.ncomp : 0;
-    const int nac = r.kind == JS_SEQUENTIAL ? d.ncomp : r.kind >= JP_AC_FIRST ? 1 : 0;
+    const int ndc = tables(r.kind, d.ncomp, true), nac = tables(r.kind, d.ncomp, false);
     for (int t = 0; t < ndc + nac; ++t) {
       const bool isdc = t < ndc;
       const int e = isdc ? t : t - ndc;
@@ -2046,20 +1639,165 @@ extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_im
       std::memcpy(isdc ? r.dc_counts[e] : r.ac_counts[e], isdc ? d.dc_counts[e] : d.ac_counts[e], 16);
       std::memcpy(isdc ? r.dc_symbols[e] : r.ac_symbols[e], isdc ? d.dc_symbols[e] : d.ac_symbols[e], 256);
     }
+    return ATTWARP_OK;
+  }
+  static void geometry(const JfImage& f, int c, int& h, int& v, int& dw, int& dh) {
+    const JfComp& k = f.comp[c];
+    h = k.h; v = k.v; dw = k.dw; dh = k.dh;
+  }
+  static void close(Header& h, int l, const std::vector<JsScan>& rec) {      // the most tables a scan of the level names, at least 1
+    h.level_tables[l] = 1;
+    for (const JsScan& r : rec)
+      if ((int)r.level == l) h.level_tables[l] = std::max(h.level_tables[l], tables(r.kind, (int)r.ncomp, true) + tables(r.kind, (int)r.ncomp, false));
+  }
+};
+
+template <class S>
+static size_t jp_scans_bytes(int B, int nscans) {
+  return (size_t)(jp_header_off(B, sizeof(typename S::Frames::Image)) + sizeof(typename S::Header) + (uint64_t)nscans * sizeof(typename S::Scan));
+}
+static size_t jpegprog_sync_bytes(int nscans) { return sizeof(JpSyncHeader) + (size_t)nscans * sizeof(JpSync); }
+
+extern "C" size_t attwarp_jpegdec_scans_table_bytes(const attwarp_jpegdec_image* images, int B, int nscans) {
+  if (!images || B <= 0 || B > JD_MAX_B || nscans < B || (int64_t)nscans > (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS) {
+    fail(ATTWARP_E_ARG, "jpegdec_scans_table_bytes: B=%d, %d scans outside the limits", B, nscans);
+    return 0;
+  }
+  return jp_scans_bytes<JpScans>(B, nscans);
+}
+extern "C" size_t attwarp_jpegdec_scans_table_bytes_ex(const attwarp_jpegdec_image* images, int B, int nscans, int segment_bytes,
+                                                       int max_rounds) {
+  const size_t base = attwarp_jpegdec_scans_table_bytes(images, B, nscans);
+  return base && (segment_bytes != 0 || max_rounds != 0) ? base + jpegprog_sync_bytes(nscans) : base;
+}
+extern "C" size_t attwarp_jpegdec_layout_scans_table_bytes(const attwarp_jpegdec_layout_image* images, int B, int nscans) {
+  if (!images || B <= 0 || B > JD_MAX_B || nscans < B || (int64_t)nscans > (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS) {
+    fail(ATTWARP_E_ARG, "jpegdec_layout_scans_table_bytes: B=%d, %d scans outside the limits", B, nscans);
+    return 0;
+  }
+  return jp_scans_bytes<JsScans>(B, nscans);
+}
+
+// The sub-stream trailer of attwarp_jpegdec_plan_scans_ex behind the scan records (rec in the caller's order; order: record ->
+// the scan's position there) -> the scratch bytes with it.  Behind everything there was: the per-scan results, then per cut
+// scan its segments and, for an AC refinement, the history masks (8 bytes per block of the scan) and their prefix sums (4
+// bytes per block, one more).
+static uint64_t jp_plan_sync(const std::vector<JpScan>& rec, const std::vector<int>& order, int nlevels, int segment_bytes, int max_rounds,
+                             const uint64_t* data_bytes, uint64_t scratch_bytes, uint8_t* trailer) {
+  const int nscans = (int)rec.size();
+  JpSyncHeader sh;
+  std::memset(&sh, 0, sizeof sh);
+  sh.magic = JP_SYNC_MAGIC;
+  uint64_t soff = jd_align(scratch_bytes, 256);
+  sh.info_off = soff;
+  soff += jd_align((uint64_t)nscans * sizeof(JpSyncInfo), 256);
+  std::vector<JpSync> sy((size_t)nscans);
+  uint32_t ncut = 0;
+  int level = 0;
+  for (int q = 0; q < nscans; ++q) {
+    const JpScan& r = rec[(size_t)order[(size_t)q]];
+    const uint64_t len = data_bytes[order[(size_t)q]];
+    for (; level < (int)r.level; ++level) sh.level_cut0[level + 1] = ncut;
+    JpSync& y = sy[(size_t)q];
+    std::memset(&y, 0, sizeof y);
+    y.segment_bytes = (uint32_t)segment_bytes;
+    y.max_rounds = (uint32_t)max_rounds;
+    y.slot = (uint32_t)order[(size_t)q];
+    const uint64_t nseg = (len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes;
+    // a marker-less scan (one unit) whose data is at least two segments long
+    const int kinds = tune(TUNE_JPEGPROG_SYNC_KINDS);        // (the tuning flavour's per-kind timing; -1 in the product)
+    if (r.nunits == 1 && len >= 2u * (uint64_t)segment_bytes && nseg <= JP_SYNC_MAX_SEGS && (kinds < 0 || ((kinds >> r.kind) & 1))) {
+      y.nseg = (uint32_t)nseg;
+      y.seg_off = soff;
+      soff += jd_align(nseg * sizeof(JpSeg), 256);
+      if (r.kind == JP_AC_REFINE) {
+        y.mask_off = soff;
+        soff += jd_align((uint64_t)r.nmcu * 12u + 4u, 256);
+      }
+      sy[ncut++].cut = (uint32_t)q;
+    }
+  }
+  for (; level < nlevels + 1 && level <= ATTWARP_JPEGDEC_MAX_SCANS; ++level) sh.level_cut0[level + 1] = ncut;
+  sh.ncut = ncut;
+  std::memcpy(trailer, &sh, sizeof sh);
+  std::memcpy(trailer + sizeof sh, sy.data(), (size_t)nscans * sizeof(JpSync));
+  return soff;
+}
+
+// The scan planner of both families.  segment_bytes = max_rounds = 0 plans no sub-streams (the only plan of JsScans) and
+// writes for JpScans the table of attwarp_jpegdec_plan_scans.
+template <class S>
+static int jp_plan_scans(const typename S::Frames::Input* images, int B, const typename S::Input* scans, int nscans, void* table,
+                         size_t table_bytes, int by_level, int segment_bytes, int max_rounds, const uint64_t* data_bytes) {
+  using Image = typename S::Frames::Image;
+  using Scan = typename S::Scan;
+  ATTWARP_REQUIRE(images && scans && table, "%s: null pointer", S::PLAN);
+  ATTWARP_REQUIRE(B > 0 && B <= JD_MAX_B && nscans >= B && (int64_t)nscans <= (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS,
+                  "%s: B=%d, %d scans outside the limits", S::PLAN, B, nscans);
+  const bool substreams = segment_bytes != 0 || max_rounds != 0;
+  if (substreams) {
+    if (const int rc = jd_substream_args(segment_bytes, max_rounds)) return rc;
+    ATTWARP_REQUIRE(data_bytes, "jpegdec_plan_scans_ex: null data_bytes");
+    for (int i = 0; i < nscans; ++i)
+      ATTWARP_REQUIRE(scans[i].image >= 0 && scans[i].image < B && scans[i].stream_off <= images[scans[i].image].stream_len &&
+                          data_bytes[i] <= images[scans[i].image].stream_len - scans[i].stream_off,
+                      "jpegdec_plan_scans_ex: scan %d: data outside the image's", i);
+  }
+  const size_t need = jp_scans_bytes<S>(B, nscans) + (substreams ? jpegprog_sync_bytes(nscans) : 0);
+  ATTWARP_REQUIRE(table_bytes >= need, "%s: table of %zu bytes, %zu needed", S::PLAN, table_bytes, need);
+  for (int b = 0; b < B; ++b)
+    ATTWARP_REQUIRE(images[b].restart_interval == 0, "%s: image %d: the restart interval belongs to the scans", S::PLAN, b);
+  // everything is checked before anything is written: the scans come image by image, in file order
+  std::vector<Scan> rec((size_t)nscans);
+  std::vector<int> count(B, 0);
+  std::vector<int64_t> per(B, 0);                              // the units of an image, over all its scans
+  std::vector<Image> frame(1);
+  int64_t total_units = 0;
+  int nlevels = 0, prev = -1;
+  for (int i = 0, first = 0; i < nscans; ++i) {
+    const typename S::Input& d = scans[i];
+    ATTWARP_REQUIRE(d.image >= 0 && d.image < B && d.image >= prev, "%s: scan %d: image %d out of order", S::PLAN, i, d.image);
+    const typename S::Frames::Input& img = images[d.image];
+    if (d.image != prev) { first = i; prev = d.image; }
+    const int index = i - first;
+    if (index == 0 && S::FRAME_FIRST)
+      if (const int rc = S::Frames::geom(img, d.image, frame[0])) return rc;
+    if (index >= ATTWARP_JPEGDEC_MAX_SCANS)
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: more than %d scans", d.image, ATTWARP_JPEGDEC_MAX_SCANS);
+    ++count[d.image];
+    ATTWARP_REQUIRE(d.ncomp >= 1 && d.ncomp <= img.ncomp && d.ncomp <= S::Frames::MAX_COMP, "jpegdec: image %d scan %d: %d components",
+                    d.image, index, d.ncomp);
+    for (int c = 0; c < d.ncomp; ++c)
+      ATTWARP_REQUIRE(d.comp[c] >= 0 && d.comp[c] < img.ncomp && (c == 0 || d.comp[c] > d.comp[c - 1]),
+                      "jpegdec: image %d scan %d: components not in frame order", d.image, index);
+    if (const int rc = S::band(d, index)) return rc;
+    ATTWARP_REQUIRE(d.restart_interval >= 0 && d.restart_interval <= 65535, "jpegdec: image %d scan %d: restart interval %d", d.image, index,
+                    d.restart_interval);
+    ATTWARP_REQUIRE(d.stream_off <= img.stream_len, "jpegdec: image %d scan %d: data outside the image's", d.image, index);
+    if (index == 0 && !S::FRAME_FIRST)
+      if (const int rc = S::Frames::geom(img, d.image, frame[0])) return rc;
+    const Image& f = frame[0];
+    Scan& r = rec[(size_t)i];
+    std::memset(&r, 0, sizeof r);
+    r.image = (uint32_t)d.image; r.index = (uint32_t)index; r.off = (uint32_t)d.stream_off;
+    r.ss = (uint32_t)d.ss; r.se = (uint32_t)d.se; r.al = (uint32_t)d.al;
+    if (const int rc = S::fill(d, index, r)) return rc;
+    int h, v, dw, dh;
     if (d.ncomp == 1) {                                        // not interleaved: the blocks that cover the component's true size
-      const JfComp& k = f.comp[d.comp[0]];
+      S::geometry(f, d.comp[0], h, v, dw, dh);
       r.nslot = 1;
-      r.mcux = (uint32_t)((k.dw + 7) / 8);
-      r.nmcu = r.mcux * (uint32_t)((k.dh + 7) / 8);
+      r.mcux = (uint32_t)((dw + 7) / 8);
+      r.nmcu = r.mcux * (uint32_t)((dh + 7) / 8);
       r.slot_c[0] = (uint8_t)d.comp[0];
     } else {                                                   // the frame's MCUs, also for a subset of its components
       r.mcux = (uint32_t)f.mcux;
       r.nmcu = (uint32_t)f.mcux * (uint32_t)f.mcuy;
       for (int t = 0; t < d.ncomp; ++t) {
-        const JfComp& k = f.comp[d.comp[t]];
-        for (int y = 0; y < k.v; ++y)
-          for (int x = 0; x < k.h; ++x) {
-            ATTWARP_REQUIRE(r.nslot < (uint32_t)JF_MAX_SLOTS, "jpegdec: image %d scan %d: more than %d blocks per MCU", d.image, index, JF_MAX_SLOTS);
+        S::geometry(f, d.comp[t], h, v, dw, dh);
+        for (int y = 0; y < v; ++y)
+          for (int x = 0; x < h; ++x) {
+            ATTWARP_REQUIRE(r.nslot < (uint32_t)S::Frames::MAX_SLOTS, "jpegdec: image %d scan %d: more than %d blocks per MCU", d.image, index,
+                            S::Frames::MAX_SLOTS);
             r.slot_c[r.nslot] = (uint8_t)d.comp[t]; r.slot_y[r.nslot] = (uint8_t)y; r.slot_x[r.nslot] = (uint8_t)x; r.slot_t[r.nslot] = (uint8_t)t;
             ++r.nslot;
           }
@@ -2071,7 +1809,7 @@ extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_im
     uint32_t level = by_level ? 0u : (uint32_t)index;
     if (by_level)
       for (int j = first; j < i; ++j) {
-        const attwarp_jpegdec_layout_scan& e = scans[j];
+        const typename S::Input& e = scans[j];
         bool share = false;
         for (int a = 0; a < d.ncomp; ++a)
           for (int bb = 0; bb < e.ncomp; ++bb) share = share || d.comp[a] == e.comp[bb];
@@ -2082,29 +1820,31 @@ extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_im
     total_units += r.nunits;
     per[d.image] += r.nunits;
   }
-  for (int b = 0; b < B; ++b) {
-    ATTWARP_REQUIRE(count[b] >= 1, "jpegdec_plan_layout_scans: image %d has no scan", b);
+  for (int b = 0; b < B; ++b) ATTWARP_REQUIRE(count[b] >= 1, "%s: image %d has no scan", S::PLAN, b);
+  for (int b = 0; b < B; ++b)
     if (per[b] > ATTWARP_JPEGDEC_MAX_UNITS)
       return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: image %d: %lld units over its scans (> %d)", b, (long long)per[b], ATTWARP_JPEGDEC_MAX_UNITS);
-  }
   if (total_units > JD_MAX_TOTAL_UNITS) return fail(ATTWARP_E_UNSUPPORTED, "jpegdec: %lld units in one call (> 2^30)", (long long)total_units);
-  if (const int rc = attwarp_jpegdec_plan_layouts(images, B, table, table_bytes, 0, 0)) return rc;
+  if (const int rc = jd_plan_frames<typename S::Frames>(images, B, table, table_bytes, 0, 0)) return rc;
   uint8_t* t = static_cast<uint8_t*>(table);
   attwarp_jpegdec_header h;
   std::memcpy(&h, t, sizeof h);
-  JsHeader sh;
-  std::memset(&sh, 0, sizeof sh);
-  sh.magic = JS_MAGIC_SCANS;
-  sh.nscans = nscans; sh.nlevels = nlevels; sh.total_units = (int32_t)total_units;
-  sh.off_scans = js_header_off(B) + sizeof(JsHeader);
-  const JdSub* sub = reinterpret_cast<const JdSub*>(t + h.off_images + (uint64_t)B * sizeof(JfImage));
-  sh.clear_off = jd_data_base(B, h.total_units);
-  sh.clear_bytes = sub[0].info_off - sh.clear_off;             // (both are multiples of 256)
-  sh.starts_off = jd_align(h.scratch_bytes, 256);
-  h.scratch_bytes = sh.starts_off + jd_align((uint64_t)total_units * 8u, 256);
+  typename S::Header header;
+  std::memset(&header, 0, sizeof header);
+  JpHeader& ph = S::scans(header);
+  const uint64_t header_off = jp_header_off(B, sizeof(Image));
+  ph.magic = S::MAGIC;
+  ph.nscans = nscans; ph.nlevels = nlevels; ph.total_units = (int32_t)total_units;
+  ph.off_scans = header_off + sizeof header;
+  const JdSub* sub = reinterpret_cast<const JdSub*>(t + h.off_images + (uint64_t)B * sizeof(Image));
+  ph.clear_off = jd_data_base(B, h.total_units);
+  ph.clear_bytes = sub[0].info_off - ph.clear_off;             // (both are multiples of 256)
+  ph.starts_off = jd_align(h.scratch_bytes, 256);
+  h.scratch_bytes = ph.starts_off + jd_align((uint64_t)total_units * 8u, 256);
   h.table_bytes = need;
-  h.magic = JS_MAGIC;
-  JsScan* out = reinterpret_cast<JsScan*>(t + sh.off_scans);
+  h.magic = S::TABLE_MAGIC;                                    // (of the layout scans: attwarp_jpegdec_decode_layouts refuses the table)
+  // records sorted by (level, image, position): a stable pass per level over the input order
+  Scan* out = reinterpret_cast<Scan*>(t + ph.off_scans);
   uint32_t unit0 = 0;
   for (int i = 0; i < nscans; ++i) {
     rec[(size_t)i].unit0 = unit0;
@@ -2112,66 +1852,190 @@ extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_im
     rec[(size_t)i].last = i + 1 == nscans || scans[i + 1].image != scans[i].image;
   }
   int at = 0;
-  for (int l = 0; l < nlevels; ++l) {                          // records sorted by (level, image, position): a stable pass per level
-    sh.level_scan0[l] = at;
+  std::vector<int> order((size_t)nscans);                     // record -> the scan's position in the caller's array
+  for (int l = 0; l < nlevels; ++l) {
+    ph.level_scan0[l] = at;
     uint32_t wave = 0;
     for (int i = 0; i < nscans; ++i)
       if ((int)rec[(size_t)i].level == l) {
         rec[(size_t)i].wave0 = wave;
         wave += rec[(size_t)i].nunits;
-        std::memcpy(out + at++, &rec[(size_t)i], sizeof(JsScan));
+        order[(size_t)at] = i;
+        std::memcpy(out + at++, &rec[(size_t)i], sizeof(Scan));
       }
-    sh.level_waves[l] = (int32_t)wave;
-    sh.level_tables[l] = 1;
-    for (int i = 0; i < nscans; ++i)
-      if ((int)rec[(size_t)i].level == l) {
-        const JsScan& r = rec[(size_t)i];
-        const int n = r.kind == JS_SEQUENTIAL ? 2 * (int)r.ncomp : r.kind == JP_DC_FIRST ? (int)r.ncomp : r.kind == JP_DC_REFINE ? 0 : 1;
-        sh.level_tables[l] = std::max(sh.level_tables[l], n);
-      }
+    ph.level_waves[l] = (int32_t)wave;
+    S::close(header, l, rec);
   }
-  sh.level_scan0[nlevels] = at;
-  std::memcpy(t + js_header_off(B), &sh, sizeof sh);
+  ph.level_scan0[nlevels] = at;
+  if constexpr (std::is_same<Scan, JpScan>::value)
+    if (substreams)
+      h.scratch_bytes = jp_plan_sync(rec, order, nlevels, segment_bytes, max_rounds, data_bytes, h.scratch_bytes,
+                                     t + ph.off_scans + (uint64_t)nscans * sizeof(JpScan));
+  std::memcpy(t + header_off, &header, sizeof header);
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
 }
 
-extern "C" int attwarp_jpegdec_decode_layout_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
-                                                   uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
-  const char* who = "jpegdec_decode_layout_scans";
-  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "%s: null pointer", who);
+extern "C" int attwarp_jpegdec_plan_scans(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
+                                          void* table, size_t table_bytes, int by_level) {
+  return jp_plan_scans<JpScans>(images, B, scans, nscans, table, table_bytes, by_level, 0, 0, nullptr);
+}
+extern "C" int attwarp_jpegdec_plan_scans_ex(const attwarp_jpegdec_image* images, int B, const attwarp_jpegdec_scan* scans, int nscans,
+                                             void* table, size_t table_bytes, int by_level, int segment_bytes, int max_rounds,
+                                             const uint64_t* data_bytes) {
+  return jp_plan_scans<JpScans>(images, B, scans, nscans, table, table_bytes, by_level, segment_bytes, max_rounds, data_bytes);
+}
+extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_image* images, int B, const attwarp_jpegdec_layout_scan* scans,
+                                                 int nscans, void* table, size_t table_bytes, int by_level) {
+  return jp_plan_scans<JsScans>(images, B, scans, nscans, table, table_bytes, by_level, 0, 0, nullptr);
+}
+
+extern "C" uint64_t attwarp_jpegdec_scan_info_offset(const void* table_host) {
+  if (!table_host) return 0;
   attwarp_jpegdec_header h;
   std::memcpy(&h, table_host, sizeof h);
-  bool ok = h.magic == JS_MAGIC && h.B > 0 && h.B <= JD_MAX_B && h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS &&
-            h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS && h.total_units == h.B && h.reserved == 0 &&
-            h.table_bytes >= js_header_off(h.B) + sizeof(JsHeader);
-  JsHeader sh;
-  if (ok) {
-    std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + js_header_off(h.B), sizeof sh);
-    ok = sh.magic == JS_MAGIC_SCANS && sh.nscans >= h.B && sh.nlevels >= 1 && sh.nlevels <= ATTWARP_JPEGDEC_MAX_SCANS &&
-         sh.total_units >= sh.nscans && sh.total_units <= JD_MAX_TOTAL_UNITS;
-    for (int l = 0; ok && l < sh.nlevels; ++l) ok = sh.level_waves[l] >= 1 && sh.level_tables[l] >= 1 && sh.level_tables[l] <= 2 * JF_MAX_COMP;
+  const uint64_t header_off = jp_header_off(h.B, sizeof(JdImage));
+  if (h.magic != JD_MAGIC || h.B <= 0 || h.B > JD_MAX_B || h.table_bytes < header_off + sizeof(JpHeader)) return 0;
+  JpHeader ph;
+  std::memcpy(&ph, static_cast<const uint8_t*>(table_host) + header_off, sizeof ph);
+  if (ph.magic != JP_MAGIC || ph.nscans < 1) return 0;
+  const uint64_t at = ph.off_scans + (uint64_t)ph.nscans * sizeof(JpScan);
+  if (h.table_bytes < at + jpegprog_sync_bytes(ph.nscans)) return 0;
+  JpSyncHeader sh;
+  std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + at, sizeof sh);
+  return sh.magic == JP_SYNC_MAGIC ? sh.info_off : 0;
+}
+
+// ---- the four decode entry points ------------------------------------------------------------------------------------------------------
+// What all of them (`who`) check: pointers, the table of `planner` (its magic, image records of `record` bytes -> h; scans:
+// and its scan header of scans_bytes, a JpHeader or a JsHeader, with scans_magic), sizes, alignment.
+static int jd_decode_args(const char* who, const char* planner, uint32_t magic, size_t record, uint32_t scans_magic, void* scans,
+                          size_t scans_bytes, const void* table_host, const void* table_dev, const uint8_t* stream_bytes, const void* scratch,
+                          const uint8_t* out, size_t out_bytes, const int32_t* status, attwarp_jpegdec_header& h) {
+  ATTWARP_REQUIRE(table_host && table_dev && stream_bytes && scratch && out && status, "%s: null pointer", who);
+  std::memcpy(&h, table_host, sizeof h);
+  bool ok = h.magic == magic && h.B > 0 && h.B <= JD_MAX_B && h.idct_tiles >= h.B && h.idct_tiles <= JD_MAX_TOTAL_UNITS &&
+            h.color_tiles >= h.B && h.color_tiles <= JD_MAX_TOTAL_UNITS;
+  if (!scans) ok = ok && h.total_units >= h.B && h.total_units <= JD_MAX_TOTAL_UNITS && h.reserved >= 0 && h.reserved <= h.B;
+  else ok = ok && h.total_units == h.B && h.reserved == 0 && h.table_bytes >= jp_header_off(h.B, record) + scans_bytes;
+  if (ok && scans) {
+    std::memcpy(scans, static_cast<const uint8_t*>(table_host) + jp_header_off(h.B, record), scans_bytes);
+    const JpHeader& ph = *static_cast<const JpHeader*>(scans);                 // (a JsHeader begins with one)
+    ok = ph.magic == scans_magic && ph.nscans >= h.B && ph.nlevels >= 1 && ph.nlevels <= ATTWARP_JPEGDEC_MAX_SCANS &&
+         ph.total_units >= ph.nscans && ph.total_units <= JD_MAX_TOTAL_UNITS;
+    if (scans_bytes == sizeof(JsHeader))                                       // every level launches, with 1..8 tables in LDS
+      for (int l = 0; ok && l < ph.nlevels; ++l)
+        ok = ph.level_waves[l] >= 1 && static_cast<const JsHeader*>(scans)->level_tables[l] >= 1 &&
+             static_cast<const JsHeader*>(scans)->level_tables[l] <= 2 * JF_MAX_COMP;
   }
-  ATTWARP_REQUIRE(ok, "%s: not a table of attwarp_jpegdec_plan_layout_scans", who);
+  ATTWARP_REQUIRE(ok, "%s: not a table of %s", who, planner);
   ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "%s: out of %zu bytes, %llu needed", who, out_bytes, (unsigned long long)h.out_bytes);
   ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 256 == 0 &&
                       reinterpret_cast<uintptr_t>(status) % 4 == 0,
                   "%s: table_dev must be 8-byte, scratch 256-byte, status 4-byte aligned", who);
+  return ATTWARP_OK;
+}
+
+// The last two launches of every entry point: coefficients -> planes -> pixels and statuses, over JdImage or (layouts) JfImage records.
+static int jd_launch_idct_color(bool layouts, const attwarp_jpegdec_header& h, const uint8_t* td, uint8_t* sc, uint8_t* out, int32_t* status,
+                                hipStream_t st) {
+  hipLaunchKernelGGL(layouts ? jpegfmt_idct_kernel : jpegdec_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch(layouts ? "jpegfmt_idct_kernel" : "jpegdec_idct_kernel")) return rc;
+  hipLaunchKernelGGL(layouts ? jpegfmt_color_kernel : jpegdec_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc,
+                     (const JdState*)sc, out, status);
+  return check_launch(layouts ? "jpegfmt_color_kernel" : "jpegdec_color_kernel");
+}
+// The clear launch of the scan families: enough workgroups for the bytes and the states, 4096 at most.
+static unsigned jp_clear_groups(const JpHeader& ph, int B) {
+  return (unsigned)std::min<uint64_t>(std::max<uint64_t>((ph.clear_bytes / 16u + JD_NT - 1) / JD_NT, (uint64_t)(B + JD_NT - 1) / JD_NT), 4096);
+}
+
+// The sequential entry points: restart scan, sub-streams, one wave per unit, then jd_launch_idct_color.
+static int jd_decode_frames(bool layouts, const attwarp_jpegdec_header& h, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                            uint8_t* out, int32_t* status, void* stream) {
   hipStream_t st = as_stream(stream);
   const uint8_t* td = static_cast<const uint8_t*>(table_dev);
   uint8_t* sc = static_cast<uint8_t*>(scratch);
-  const uint64_t clear_groups = std::min<uint64_t>(std::max<uint64_t>((sh.clear_bytes / 16u + JD_NT - 1) / JD_NT, (uint64_t)(h.B + JD_NT - 1) / JD_NT), 4096);
-  hipLaunchKernelGGL(jpegscan_clear_kernel, dim3((unsigned)clear_groups), dim3(JD_NT), 0, st, td, sc);
+  hipLaunchKernelGGL(layouts ? jpegfmt_scan_kernel : jpegdec_scan_kernel, dim3(h.B), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch(layouts ? "jpegfmt_scan_kernel" : "jpegdec_scan_kernel")) return rc;
+  hipLaunchKernelGGL(layouts ? jpegfmt_substream_kernel : jpegdec_substream_kernel, dim3(std::max(h.reserved, 1)), dim3(JD_NT), 0, st, td,
+                     stream_bytes, sc);
+  if (const int rc = check_launch(layouts ? "jpegfmt_substream_kernel" : "jpegdec_substream_kernel")) return rc;
+  hipLaunchKernelGGL(layouts ? jpegfmt_entropy_kernel : jpegdec_entropy_kernel, dim3(h.total_units), dim3(WAVE), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch(layouts ? "jpegfmt_entropy_kernel" : "jpegdec_entropy_kernel")) return rc;
+  return jd_launch_idct_color(layouts, h, td, sc, out, status, st);
+}
+
+extern "C" int attwarp_jpegdec_decode(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                      uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  attwarp_jpegdec_header h;
+  if (const int rc = jd_decode_args("jpegdec_decode", "attwarp_jpegdec_plan", JD_MAGIC, sizeof(JdImage), 0, nullptr, 0, table_host, table_dev,
+                                    stream_bytes, scratch, out, out_bytes, status, h))
+    return rc;
+  return jd_decode_frames(false, h, table_dev, stream_bytes, scratch, out, status, stream);
+}
+extern "C" int attwarp_jpegdec_decode_layouts(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                              uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  attwarp_jpegdec_header h;
+  if (const int rc = jd_decode_args("jpegdec_decode_layouts", "attwarp_jpegdec_plan_layouts", JD_MAGIC_LAYOUTS, sizeof(JfImage), 0, nullptr, 0,
+                                    table_host, table_dev, stream_bytes, scratch, out, out_bytes, status, h))
+    return rc;
+  return jd_decode_frames(true, h, table_dev, stream_bytes, scratch, out, status, stream);
+}
+
+extern "C" int attwarp_jpegdec_decode_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                            uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  attwarp_jpegdec_header h;
+  JpHeader ph;
+  if (const int rc = jd_decode_args("jpegdec_decode_scans", "attwarp_jpegdec_plan_scans", JD_MAGIC, sizeof(JdImage), JP_MAGIC, &ph, sizeof ph,
+                                    table_host, table_dev, stream_bytes, scratch, out, out_bytes, status, h))
+    return rc;
+  hipStream_t st = as_stream(stream);
+  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  hipLaunchKernelGGL(jpegprog_clear_kernel, dim3(jp_clear_groups(ph, h.B)), dim3(JD_NT), 0, st, td, sc);
+  if (const int rc = check_launch("jpegprog_clear_kernel")) return rc;
+  hipLaunchKernelGGL(jpegprog_scan_kernel, dim3(ph.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  if (const int rc = check_launch("jpegprog_scan_kernel")) return rc;
+  JpSyncHeader sh;
+  std::memset(&sh, 0, sizeof sh);
+  const uint64_t sync_at = ph.off_scans + (uint64_t)ph.nscans * sizeof(JpScan);
+  if (h.table_bytes >= sync_at + jpegprog_sync_bytes(ph.nscans)) {       // planned with sub-streams
+    std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + sync_at, sizeof sh);
+    bool ok = sh.magic == JP_SYNC_MAGIC && sh.ncut <= (uint32_t)ph.nscans && sh.level_cut0[0] == 0;
+    for (int l = 0; ok && l < ph.nlevels; ++l) ok = sh.level_cut0[l] <= sh.level_cut0[l + 1] && sh.level_cut0[l + 1] <= sh.ncut;
+    ATTWARP_REQUIRE(ok, "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans_ex");
+  }
+  for (int l = 0; l < ph.nlevels; ++l) {
+    ATTWARP_REQUIRE(ph.level_waves[l] >= 1, "jpegdec_decode_scans: not a table of attwarp_jpegdec_plan_scans");
+    if (const uint32_t ncut = sh.level_cut0[l + 1] - sh.level_cut0[l]) {  // the level holds a cut scan
+      hipLaunchKernelGGL(jpegprog_substream_kernel, dim3(ncut), dim3(JD_NT), 0, st, td, stream_bytes, sc, l);
+      if (const int rc = check_launch("jpegprog_substream_kernel")) return rc;
+    }
+    hipLaunchKernelGGL(jpegprog_entropy_kernel, dim3(ph.level_waves[l]), dim3(WAVE), 0, st, td, stream_bytes, sc, l);
+    if (const int rc = check_launch("jpegprog_entropy_kernel")) return rc;
+  }
+  return jd_launch_idct_color(false, h, td, sc, out, status, st);
+}
+
+extern "C" int attwarp_jpegdec_decode_layout_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes, void* scratch,
+                                                   uint8_t* out, size_t out_bytes, int32_t* status, void* stream) {
+  attwarp_jpegdec_header h;
+  JsHeader sh;
+  if (const int rc = jd_decode_args("jpegdec_decode_layout_scans", "attwarp_jpegdec_plan_layout_scans", JS_MAGIC, sizeof(JfImage), JS_MAGIC_SCANS,
+                                    &sh, sizeof sh, table_host, table_dev, stream_bytes, scratch, out, out_bytes, status, h))
+    return rc;
+  hipStream_t st = as_stream(stream);
+  const uint8_t* td = static_cast<const uint8_t*>(table_dev);
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  hipLaunchKernelGGL(jpegscan_clear_kernel, dim3(jp_clear_groups(sh.h, h.B)), dim3(JD_NT), 0, st, td, sc);
   if (const int rc = check_launch("jpegscan_clear_kernel")) return rc;
-  hipLaunchKernelGGL(jpegscan_marks_kernel, dim3(sh.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
+  hipLaunchKernelGGL(jpegscan_marks_kernel, dim3(sh.h.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegscan_marks_kernel")) return rc;
-  for (int l = 0; l < sh.nlevels; ++l) {
-    hipLaunchKernelGGL(jpegscan_entropy_kernel, dim3(sh.level_waves[l]), dim3(WAVE), (size_t)sh.level_tables[l] * sizeof(JdHuff), st, td,
+  for (int l = 0; l < sh.h.nlevels; ++l) {
+    hipLaunchKernelGGL(jpegscan_entropy_kernel, dim3(sh.h.level_waves[l]), dim3(WAVE), (size_t)sh.level_tables[l] * sizeof(JdHuff), st, td,
                        stream_bytes, sc, l, sh.level_tables[l]);
     if (const int rc = check_launch("jpegscan_entropy_kernel")) return rc;
   }
-  hipLaunchKernelGGL(jpegfmt_idct_kernel, dim3(h.idct_tiles), dim3(JD_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegfmt_idct_kernel")) return rc;
-  hipLaunchKernelGGL(jpegfmt_color_kernel, dim3(h.color_tiles), dim3(JD_NT), 0, st, td, (const uint8_t*)sc, (const JdState*)sc, out, status);
-  return check_launch("jpegfmt_color_kernel");
+  return jd_launch_idct_color(true, h, td, sc, out, status, st);
 }
