@@ -192,6 +192,8 @@ SIGNATURES = {
     # scans of every layout: progressive files of the layout family's frames, sequential files of several scans (jpegscan_blocks.hpp)
     "attwarp_jpegdec_layout_scans_table_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "attwarp_jpegdec_plan_layout_scans": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int]),
+    "attwarp_jpegdec_layout_scans_table_bytes_ex": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "attwarp_jpegdec_plan_layout_scans_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "attwarp_jpegdec_decode_layout_scans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     # JPEG files of a ragged batch written on the device (jpegenc.hip)
     "attwarp_jpegenc_bound": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -47,6 +47,7 @@
 #include "jpegprog_blocks.hpp"
 #include "jpegprog_sync_blocks.hpp"
 #include "jpegscan_blocks.hpp"
+#include "jpegscan_sync_blocks.hpp"
 
 namespace attwarp {
 
@@ -1176,10 +1177,33 @@ __global__ __launch_bounds__(JD_NT) void jpegfmt_color_kernel(const uint8_t* __r
 // attwarp_jpegdec_plan_layouts for B one-unit images (all the IDCT and colour kernels read; its magic replaced, so that
 // attwarp_jpegdec_decode_layouts refuses it) with a JsHeader and the JsScan records behind it, sorted by (level, image, position) ---
 constexpr uint32_t JS_MAGIC = JD_MAGIC_LAYOUT_SCANS, JS_MAGIC_SCANS = 0x4745504eu;   // of the table's first header / of the JsHeader
+// The sub-stream records of a table planned with them (behind the JsScan records) and the per-scan results in scratch.
+struct JsSyncView {
+  const JsSyncHeader* sh;
+  const JsSync* sy;
+  JpSyncInfo* infos;
+};
+__device__ __forceinline__ bool js_sync_view(const JfView& v, const JpHeader* ph, const uint8_t* table, uint8_t* scratch, JsSyncView& y) {
+  const uint64_t at = ph->off_scans + (uint64_t)ph->nscans * sizeof(JsScan);
+  if (v.hdr->table_bytes < at + sizeof(JsSyncHeader) + (uint64_t)ph->nscans * sizeof(JsSync)) return false;   // planned without them
+  y.sh = reinterpret_cast<const JsSyncHeader*>(table + at);
+  y.sy = reinterpret_cast<const JsSync*>(table + at + sizeof(JsSyncHeader));
+  y.infos = reinterpret_cast<JpSyncInfo*>(scratch + y.sh->info_off);
+  return y.sh->magic == JS_SYNC_MAGIC;
+}
 __global__ __launch_bounds__(JD_NT) void jpegscan_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   const JfView v(table, scratch);
   const JpHeader* sh = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JfImage)));
   jp_clear_body(v, scratch, sh->clear_off, sh->clear_bytes);
+  JsSyncView y;
+  if (!js_sync_view(v, sh, table, scratch, y)) return;
+  const JsScan* scans = reinterpret_cast<const JsScan*>(table + sh->off_scans);
+  for (int i = (int)(blockIdx.x * JD_NT + threadIdx.x); i < sh->nscans; i += (int)(gridDim.x * JD_NT)) {
+    JpSyncInfo info;
+    info.route = y.sy[i].nseg ? 1u + scans[i].kind : 0u; info.nseg = y.sy[i].nseg; info.rounds = 0; info.accepted = 0;
+    info.ticks[0] = info.ticks[1] = info.ticks[2] = 0; info.pad = 0;
+    if (y.sy[i].slot < (uint32_t)sh->nscans) y.infos[y.sy[i].slot] = info;
+  }
 }
 
 // grid: one workgroup per SCAN.
@@ -1224,6 +1248,9 @@ __global__ __launch_bounds__(WAVE) void jpegscan_entropy_kernel(const uint8_t* _
   const JfImage* im = v.images + sc->image;
   JdState* state = v.states + sc->image;
   if (state->st_scan != 0) return;                           // (uniform) some scan's limits were never written
+  JsSyncView y;
+  if (js_sync_view(v, sh, table, scratch, y) && y.sy[lo].slot < (uint32_t)sh->nscans && y.infos[y.sy[lo].slot].accepted != 0)
+    return;                                                  // (uniform) the sub-stream kernel decoded this scan's only unit
   const uint32_t k = (uint32_t)w - sc->wave0;
   if (k >= sc->nunits) return;
   const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len, n = im->stream_len - off;
@@ -1300,6 +1327,198 @@ __global__ __launch_bounds__(WAVE) void jpegscan_entropy_kernel(const uint8_t* _
     i += adv;
   }
   if (err && lane == 0) atomicMin(&state->fail, sc->index << 24 | k << 8 | err);
+}
+
+// grid: one workgroup per cut scan of the launch's level: jpegprog_substream_kernel over the general MCU.
+// Segment s goes to lane s % JD_NT in every loop over segments, so a lane reads back its own entry and dirty flag; sums over
+// the segments go by chunks of neighbours.  ntab code tables in dynamic LDS (the most a cut scan of the level names: up to 4
+// DC tables, 1 AC table); a scan that names more is left to the one-lane route.  s_acc: a lane's ten DC sums of the segment
+// it decodes (rounds), then its four predictors (write), lane-strided so that no two lanes share a bank.
+__global__ __launch_bounds__(JD_NT) void jpegscan_substream_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ stream,
+                                                                   uint8_t* scratch, int level, int ntab) {
+  extern __shared__ __align__(16) uint8_t s_tables[];
+  __shared__ uint32_t s_scan[JD_NT];
+  __shared__ uint32_t s_acc[JF_MAX_SLOTS * JD_NT];
+  __shared__ uint8_t s_zig[64];
+  __shared__ uint32_t s_good;
+  const int tid = threadIdx.x;
+  const JfView v(table, scratch);
+  const JpHeader* ph = reinterpret_cast<const JpHeader*>(table + jp_header_off(v.hdr->B, sizeof(JfImage)));
+  const JsScan* scans = reinterpret_cast<const JsScan*>(table + ph->off_scans);
+  JsSyncView y;
+  if (!js_sync_view(v, ph, table, scratch, y) || level < 0 || level >= ph->nlevels || level >= ATTWARP_JPEGDEC_MAX_SCANS) return;
+  const uint32_t w = y.sh->level_cut0[level] + blockIdx.x;
+  if (w >= y.sh->level_cut0[level + 1] || w >= (uint32_t)ph->nscans) return;
+  const uint32_t si = y.sy[w].cut;
+  if (si >= (uint32_t)ph->nscans) return;
+  const JsScan* sc = scans + si;
+  const JsSync sub = y.sy[si];
+  if (sc->image >= (uint32_t)v.hdr->B || sub.nseg < 2u || sub.nseg > JP_SYNC_MAX_SEGS || sc->nunits != 1u || sub.slot >= (uint32_t)ph->nscans) return;
+  const JfImage* im = v.images + sc->image;
+  if (v.states[sc->image].st_scan != 0) return;               // (uniform) the info record already says "not accepted"
+  const uint32_t off = sc->off < im->stream_len ? sc->off : im->stream_len, n = im->stream_len - off;
+  const uint32_t* pstarts = reinterpret_cast<const uint32_t*>(scratch + ph->starts_off) + sc->unit0;
+  uint32_t uend = pstarts[ph->total_units];
+  if (uend > n) uend = n;
+  const uint32_t nseg = sub.nseg, S = sub.segment_bytes;
+  if ((uint64_t)nseg * S < uend) return;                      // (uniform) never: the plan's length is the marker walk's
+  const uint32_t kind = sc->kind, se = sc->se < 63u ? sc->se : 63u, ss = sc->ss < se ? sc->ss : se;
+  if (kind > JP_AC_REFINE) return;                            // (uniform) a sequential scan is never cut
+  const uint32_t nslot = js_nslot(*sc);
+  if (kind >= JP_AC_FIRST && (nslot != 1u || sc->ncomp != 1u)) return;       // (uniform) an AC scan holds one component
+  const uint32_t nc = sc->ncomp >= 1u && sc->ncomp <= (uint32_t)JF_MAX_COMP ? sc->ncomp : 1u;
+  const uint32_t nh = kind == JP_DC_FIRST ? nc : kind == JP_DC_REFINE ? 0u : 1u;
+  if (ntab < 0 || nh > (uint32_t)ntab) return;                // (uniform)
+  JdHuff* s_h = reinterpret_cast<JdHuff*>(s_tables);
+  for (uint32_t c = 0; c < nh; ++c) {
+    const uint8_t* counts = kind == JP_DC_FIRST ? sc->dc_counts[c] : sc->ac_counts[c];
+    if (tid == 0) jd_huff_ranges(s_h[c], counts);
+    jd_huff_clear(s_h[c], kind == JP_DC_FIRST ? sc->dc_symbols[c] : sc->ac_symbols[c], jd_nsym(counts), tid, JD_NT);
+  }
+  if (tid < 64) s_zig[tid] = JD_ZIGZAG[tid];
+  if (tid == 0) s_good = 0;
+  __syncthreads();
+  for (uint32_t c = 0; c < nh; ++c) jd_huff_fill(s_h[c], kind == JP_DC_FIRST ? sc->dc_counts[c] : sc->ac_counts[c], tid, JD_NT);
+  __syncthreads();
+  // the stream is read in place: p is the dword in front of the scan's first byte, lo that byte's offset in it
+  const uint8_t* data = stream + im->stream_off + off;
+  const uint32_t lo = (uint32_t)(reinterpret_cast<uintptr_t>(data) & 3u);
+  const uint8_t* p = data - lo;
+  JsSeg* seg = reinterpret_cast<JsSeg*>(scratch + sub.seg_off);
+  int16_t* coef = reinterpret_cast<int16_t*>(scratch + im->coef_off);
+  const uint64_t nblk = (uint64_t)sc->nmcu * nslot;
+  const uint32_t expected = nblk < JP_SYNC_CAP ? (uint32_t)nblk : JP_SYNC_CAP - 1u;        // (the planner: fewer than 2^24 blocks)
+  const uint32_t period = js_clamp_period(*sc, sub.period);
+  const uint32_t chunk = (nseg + JD_NT - 1) / JD_NT;
+  const uint32_t s0 = min((uint32_t)tid * chunk, nseg), s1 = min(s0 + chunk, nseg);
+  uint32_t rounds = 0, total;
+  bool accepted = false;
+  const uint64_t t0 = wall_clock64();                        // (lane 0's stamps go into the scan's record: 100 MHz)
+  uint64_t t1 = t0, t2 = t0;
+  if (kind == JP_DC_FIRST || kind == JP_AC_FIRST) {
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      JdSync e = jd_segment_guess(data, s, S, uend);
+      if (kind == JP_AC_FIRST) e.bsk = ss;
+      seg[s].entry = e;
+      seg[s].dirty = 1u;
+    }
+    bool converged = false;
+    while (rounds < sub.max_rounds) {                        // (uniform)
+      ++rounds;
+      for (uint32_t s = tid; s < nseg; s += JD_NT)
+        if (seg[s].dirty) {
+          JsSegOut r;
+          js_first_segment(*sc, period, p, lo, seg[s].entry, jd_segment_end(s, S, uend), uend, s_h, nh, r, s_acc + tid, JD_NT);
+          seg[s].exit = r.exit;
+          seg[s].nbeg = r.nbeg; seg[s].nend = r.nend; seg[s].eclean = r.eclean;
+          for (uint32_t i = 0; i < nslot; ++i) seg[s].dc[i] = s_acc[i * JD_NT + tid];
+        }
+      __syncthreads();                                       // every exit of this round is written
+      int changed = 0;
+      for (uint32_t s = tid; s < nseg; s += JD_NT) {
+        uint32_t d = 0;
+        if (s > 0) {
+          const JdSync e = seg[s - 1].exit;
+          if (!jd_sync_equal(e, seg[s].entry)) { seg[s].entry = e; d = 1u; changed = 1; }
+        }
+        seg[s].dirty = d;
+      }
+      if (!__syncthreads_or(changed)) { converged = true; break; }
+    }
+    t1 = wall_clock64();
+    // the blocks in front of every segment, then the DC differences in front of it by component: two exclusive sums
+    uint32_t nb = 0;
+    for (uint32_t s = s0; s < s1; ++s) nb = jp_sat_add(nb, seg[s].nend);
+    nb = jp_excl_sum_sat(nb, s_scan);
+    uint32_t sum[JF_MAX_COMP] = {0, 0, 0, 0}, flags = 0;
+    for (uint32_t s = s0; s < s1; ++s) {
+      seg[s].before = nb;
+      flags |= js_first_check(*sc, period, seg[s].entry, seg[s].nend, seg[s].eclean, nb, expected);
+      if (kind == JP_DC_FIRST) js_component_sums(*sc, seg[s].dc, nb, sum);
+      nb = jp_sat_add(nb, seg[s].nend);
+    }
+    for (int e = 0; e < JF_MAX_COMP; ++e) sum[e] = jd_excl_sum(sum[e], s_scan, total);
+    if (kind == JP_DC_FIRST)
+      for (uint32_t s = s0; s < s1; ++s) {
+        for (int e = 0; e < JF_MAX_COMP; ++e) seg[s].pred[e] = sum[e];
+        js_component_sums(*sc, seg[s].dc, seg[s].before, sum);
+      }
+    const int bad = __syncthreads_or((int)(flags & 1u));
+    const int found = __syncthreads_or((int)(flags & 2u));     // (and every `before` and predictor is written)
+    accepted = converged && found && !bad;
+    t2 = wall_clock64();
+    if (accepted)                                            // (uniform)
+      for (uint32_t s = tid; s < nseg; s += JD_NT) {
+        for (int e = 0; e < JF_MAX_COMP; ++e) s_acc[e * JD_NT + tid] = seg[s].pred[e];
+        js_first_write(*sc, *im, p, lo, seg[s].entry, jd_segment_end(s, S, uend), uend, s_h, nh, seg[s].before, s_acc + tid, JD_NT, expected,
+                       s_zig, coef);
+      }
+  } else {
+    // the data bytes of every segment and of everything in front of it
+    for (uint32_t s = tid; s < nseg; s += JD_NT) {
+      const uint64_t b = (uint64_t)s * S;
+      seg[s].nbeg = jp_data_bytes(data, b < uend ? (uint32_t)b : uend, jd_segment_end(s, S, uend));
+    }
+    __syncthreads();
+    uint32_t bytes = 0;
+    for (uint32_t s = s0; s < s1; ++s) bytes += seg[s].nbeg;
+    bytes = jd_excl_sum(bytes, s_scan, total);
+    for (uint32_t s = s0; s < s1; ++s) {
+      seg[s].pred[1] = bytes;
+      bytes += seg[s].nbeg;
+    }
+    __syncthreads();
+    if (kind == JP_DC_REFINE) {
+      t1 = t2 = wall_clock64();
+      accepted = (uint64_t)total * 8u >= expected;
+      if (accepted)
+        for (uint32_t s = tid; s < nseg; s += JD_NT) {
+          const uint64_t b = (uint64_t)s * S;
+          js_dc_refine_write(*sc, *im, data, b < uend ? (uint32_t)b : uend, jd_segment_end(s, S, uend), seg[s].pred[1], expected, coef);
+        }
+    } else {
+      // phase 1: the history masks of the scan's blocks and the bits set in front of each
+      uint64_t* masks = reinterpret_cast<uint64_t*>(scratch + sub.mask_off);
+      uint32_t* P = reinterpret_cast<uint32_t*>(masks + sc->nmcu);
+      const uint32_t bchunk = (expected + JD_NT - 1) / JD_NT;
+      const uint32_t b0 = min((uint32_t)tid * bchunk, expected), b1 = min(b0 + bchunk, expected);
+      uint32_t bits = 0;
+      for (uint32_t b = b0; b < b1; ++b) {
+        const uint32_t bi = js_block_index(*im, *sc, b, 0);
+        const uint64_t m = bi < im->nblocks ? jp_refine_mask(coef + (size_t)bi * 64u, ss, se, s_zig) : 0u;
+        masks[b] = m;
+        bits += jp_popc64(m);
+      }
+      bits = jd_excl_sum(bits, s_scan, total);
+      for (uint32_t b = b0; b < b1; ++b) {
+        P[b] = bits;
+        bits += jp_popc64(masks[b]);
+      }
+      if (tid == 0) P[expected] = total;
+      __syncthreads();
+      t1 = wall_clock64();
+      // phase 2: the exact skim by one lane
+      if (tid == 0) s_good = js_refine_skim(*sc, p, lo, uend, s_h[0], masks, P, expected, seg, nseg) ? 1u : 0u;
+      __syncthreads();
+      accepted = s_good != 0;
+      t2 = wall_clock64();
+      // phase 3: every segment from its true entry up to the next one's
+      if (accepted)                                          // (uniform)
+        for (uint32_t s = tid; s < nseg; s += JD_NT) {
+          const uint32_t n1 = s + 1u < nseg ? seg[s + 1u].before : expected, k1 = s + 1u < nseg ? seg[s + 1u].entry.bsk & 63u : ss;
+          js_refine_write(*sc, *im, p, lo, jd_segment_guess(data, s, S, uend).byte, uend, s_h[0], seg[s].before, seg[s].entry.bsk, seg[s].pred[0],
+                          seg[s].entry.byte, n1, k1, masks, expected, s_zig, coef);
+        }
+    }
+  }
+  __syncthreads();                                           // every lane's write is done
+  if (tid == 0) {
+    const uint64_t t3 = wall_clock64();
+    JpSyncInfo info;
+    info.route = 1u + kind; info.nseg = nseg; info.rounds = rounds; info.accepted = accepted ? 1u : 0u;
+    info.ticks[0] = (uint32_t)(t1 - t0); info.ticks[1] = (uint32_t)(t2 - t1); info.ticks[2] = (uint32_t)(t3 - t2); info.pad = 0;
+    y.infos[sub.slot] = info;
+  }
 }
 
 }  // namespace attwarp
@@ -1576,6 +1795,8 @@ struct JpScans {
   using Header = JpHeader;
   static constexpr uint32_t TABLE_MAGIC = JD_MAGIC, MAGIC = JP_MAGIC;
   static constexpr const char* PLAN = "jpegdec_plan_scans";
+  static constexpr const char* PLAN_EX = "jpegdec_plan_scans_ex";
+  static size_t sync_bytes(int nscans) { return sizeof(JpSyncHeader) + (size_t)nscans * sizeof(JpSync); }
   static constexpr bool FRAME_FIRST = false;
   static JpHeader& scans(Header& h) { return h; }
   static int band(const Input& d, int index) {
@@ -1609,6 +1830,8 @@ struct JsScans {
   using Header = JsHeader;
   static constexpr uint32_t TABLE_MAGIC = JS_MAGIC, MAGIC = JS_MAGIC_SCANS;
   static constexpr const char* PLAN = "jpegdec_plan_layout_scans";
+  static constexpr const char* PLAN_EX = "jpegdec_plan_layout_scans_ex";
+  static size_t sync_bytes(int nscans) { return sizeof(JsSyncHeader) + (size_t)nscans * sizeof(JsSync); }
   static constexpr bool FRAME_FIRST = true;
   static JpHeader& scans(Header& h) { return h.h; }
   static int band(const Input& d, int index) {
@@ -1656,7 +1879,7 @@ template <class S>
 static size_t jp_scans_bytes(int B, int nscans) {
   return (size_t)(jp_header_off(B, sizeof(typename S::Frames::Image)) + sizeof(typename S::Header) + (uint64_t)nscans * sizeof(typename S::Scan));
 }
-static size_t jpegprog_sync_bytes(int nscans) { return sizeof(JpSyncHeader) + (size_t)nscans * sizeof(JpSync); }
+static size_t jpegprog_sync_bytes(int nscans) { return JpScans::sync_bytes(nscans); }
 
 extern "C" size_t attwarp_jpegdec_scans_table_bytes(const attwarp_jpegdec_image* images, int B, int nscans) {
   if (!images || B <= 0 || B > JD_MAX_B || nscans < B || (int64_t)nscans > (int64_t)B * ATTWARP_JPEGDEC_MAX_SCANS) {
@@ -1724,8 +1947,58 @@ static uint64_t jp_plan_sync(const std::vector<JpScan>& rec, const std::vector<i
   return soff;
 }
 
-// The scan planner of both families.  segment_bytes = max_rounds = 0 plans no sub-streams (the only plan of JsScans) and
-// writes for JpScans the table of attwarp_jpegdec_plan_scans.
+// The same for attwarp_jpegdec_plan_layout_scans_ex: a JsSyncHeader and JsSync records behind the JsScan
+// records, segments of 96 bytes.  A sequential scan, a scan without data_bytes and a scan of 2^24 blocks or more stay on
+// one lane; a cut DC first pass gets the period of its table sequence.
+static uint64_t js_plan_sync(const std::vector<JsScan>& rec, const std::vector<int>& order, int nlevels, int segment_bytes, int max_rounds,
+                             const uint64_t* data_bytes, uint64_t scratch_bytes, uint8_t* trailer) {
+  const int nscans = (int)rec.size();
+  JsSyncHeader sh;
+  std::memset(&sh, 0, sizeof sh);
+  sh.magic = JS_SYNC_MAGIC;
+  uint64_t soff = jd_align(scratch_bytes, 256);
+  sh.info_off = soff;
+  soff += jd_align((uint64_t)nscans * sizeof(JpSyncInfo), 256);
+  std::vector<JsSync> sy((size_t)nscans);
+  uint32_t ncut = 0;
+  int level = 0;
+  const int kinds = tune(TUNE_JPEGPROG_SYNC_KINDS);          // (the tuning flavour's per-kind timing; -1 in the product)
+  for (int q = 0; q < nscans; ++q) {
+    const JsScan& r = rec[(size_t)order[(size_t)q]];
+    const uint64_t len = data_bytes[order[(size_t)q]];
+    for (; level < (int)r.level; ++level) sh.level_cut0[level + 1] = ncut;
+    JsSync& y = sy[(size_t)q];
+    std::memset(&y, 0, sizeof y);
+    y.segment_bytes = (uint32_t)segment_bytes;
+    y.max_rounds = (uint32_t)max_rounds;
+    y.slot = (uint32_t)order[(size_t)q];
+    y.period = 1;
+    const uint64_t nseg = (len + (uint64_t)segment_bytes - 1) / (uint64_t)segment_bytes;
+    if (r.kind <= JP_AC_REFINE && r.nunits == 1 && len >= 2u * (uint64_t)segment_bytes && nseg <= JP_SYNC_MAX_SEGS &&
+        (uint64_t)r.nmcu * r.nslot < JP_SYNC_CAP && (kinds < 0 || ((kinds >> r.kind) & 1))) {
+      y.nseg = (uint32_t)nseg;
+      y.period = js_period(r);
+      y.seg_off = soff;
+      soff += jd_align(nseg * sizeof(JsSeg), 256);
+      if (r.kind == JP_AC_REFINE) {
+        y.mask_off = soff;
+        soff += jd_align((uint64_t)r.nmcu * 12u + 4u, 256);
+      }
+      const uint32_t ntab = r.kind == JP_DC_FIRST ? r.ncomp : r.kind == JP_DC_REFINE ? 0u : 1u;
+      sh.level_tables[r.level] = std::max(sh.level_tables[r.level], ntab);
+      sy[ncut++].cut = (uint32_t)q;
+    }
+  }
+  for (; level < nlevels + 1 && level <= ATTWARP_JPEGDEC_MAX_SCANS; ++level) sh.level_cut0[level + 1] = ncut;
+  for (int l = 0; l < nlevels; ++l) sh.level_tables[l] = std::max(sh.level_tables[l], 1u);
+  sh.ncut = ncut;
+  std::memcpy(trailer, &sh, sizeof sh);
+  std::memcpy(trailer + sizeof sh, sy.data(), (size_t)nscans * sizeof(JsSync));
+  return soff;
+}
+
+// The scan planner of both families.  segment_bytes = max_rounds = 0 plans no sub-streams and writes the table of
+// attwarp_jpegdec_plan_scans / attwarp_jpegdec_plan_layout_scans.
 template <class S>
 static int jp_plan_scans(const typename S::Frames::Input* images, int B, const typename S::Input* scans, int nscans, void* table,
                          size_t table_bytes, int by_level, int segment_bytes, int max_rounds, const uint64_t* data_bytes) {
@@ -1737,13 +2010,13 @@ static int jp_plan_scans(const typename S::Frames::Input* images, int B, const t
   const bool substreams = segment_bytes != 0 || max_rounds != 0;
   if (substreams) {
     if (const int rc = jd_substream_args(segment_bytes, max_rounds)) return rc;
-    ATTWARP_REQUIRE(data_bytes, "jpegdec_plan_scans_ex: null data_bytes");
+    ATTWARP_REQUIRE(data_bytes, "%s: null data_bytes", S::PLAN_EX);
     for (int i = 0; i < nscans; ++i)
       ATTWARP_REQUIRE(scans[i].image >= 0 && scans[i].image < B && scans[i].stream_off <= images[scans[i].image].stream_len &&
                           data_bytes[i] <= images[scans[i].image].stream_len - scans[i].stream_off,
-                      "jpegdec_plan_scans_ex: scan %d: data outside the image's", i);
+                      "%s: scan %d: data outside the image's", S::PLAN_EX, i);
   }
-  const size_t need = jp_scans_bytes<S>(B, nscans) + (substreams ? jpegprog_sync_bytes(nscans) : 0);
+  const size_t need = jp_scans_bytes<S>(B, nscans) + (substreams ? S::sync_bytes(nscans) : 0);
   ATTWARP_REQUIRE(table_bytes >= need, "%s: table of %zu bytes, %zu needed", S::PLAN, table_bytes, need);
   for (int b = 0; b < B; ++b)
     ATTWARP_REQUIRE(images[b].restart_interval == 0, "%s: image %d: the restart interval belongs to the scans", S::PLAN, b);
@@ -1867,10 +2140,13 @@ static int jp_plan_scans(const typename S::Frames::Input* images, int B, const t
     S::close(header, l, rec);
   }
   ph.level_scan0[nlevels] = at;
-  if constexpr (std::is_same<Scan, JpScan>::value)
-    if (substreams)
-      h.scratch_bytes = jp_plan_sync(rec, order, nlevels, segment_bytes, max_rounds, data_bytes, h.scratch_bytes,
-                                     t + ph.off_scans + (uint64_t)nscans * sizeof(JpScan));
+  if (substreams) {
+    uint8_t* trailer = t + ph.off_scans + (uint64_t)nscans * sizeof(Scan);
+    if constexpr (std::is_same<Scan, JpScan>::value)
+      h.scratch_bytes = jp_plan_sync(rec, order, nlevels, segment_bytes, max_rounds, data_bytes, h.scratch_bytes, trailer);
+    else
+      h.scratch_bytes = js_plan_sync(rec, order, nlevels, segment_bytes, max_rounds, data_bytes, h.scratch_bytes, trailer);
+  }
   std::memcpy(t + header_off, &header, sizeof header);
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
@@ -1890,10 +2166,34 @@ extern "C" int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_im
   return jp_plan_scans<JsScans>(images, B, scans, nscans, table, table_bytes, by_level, 0, 0, nullptr);
 }
 
+extern "C" size_t attwarp_jpegdec_layout_scans_table_bytes_ex(const attwarp_jpegdec_layout_image* images, int B, int nscans, int segment_bytes,
+                                                              int max_rounds) {
+  const size_t base = attwarp_jpegdec_layout_scans_table_bytes(images, B, nscans);
+  return base && (segment_bytes != 0 || max_rounds != 0) ? base + JsScans::sync_bytes(nscans) : base;
+}
+extern "C" int attwarp_jpegdec_plan_layout_scans_ex(const attwarp_jpegdec_layout_image* images, int B, const attwarp_jpegdec_layout_scan* scans,
+                                                    int nscans, void* table, size_t table_bytes, int by_level, int segment_bytes, int max_rounds,
+                                                    const uint64_t* data_bytes) {
+  return jp_plan_scans<JsScans>(images, B, scans, nscans, table, table_bytes, by_level, segment_bytes, max_rounds, data_bytes);
+}
+
+// (a table of either scan family)
 extern "C" uint64_t attwarp_jpegdec_scan_info_offset(const void* table_host) {
   if (!table_host) return 0;
   attwarp_jpegdec_header h;
   std::memcpy(&h, table_host, sizeof h);
+  if (h.magic == JS_MAGIC) {
+    const uint64_t at0 = jp_header_off(h.B, sizeof(JfImage));
+    if (h.B <= 0 || h.B > JD_MAX_B || h.table_bytes < at0 + sizeof(JsHeader)) return 0;
+    JsHeader js;
+    std::memcpy(&js, static_cast<const uint8_t*>(table_host) + at0, sizeof js);
+    if (js.h.magic != JS_MAGIC_SCANS || js.h.nscans < 1) return 0;
+    const uint64_t at = js.h.off_scans + (uint64_t)js.h.nscans * sizeof(JsScan);
+    if (h.table_bytes < at + JsScans::sync_bytes(js.h.nscans)) return 0;
+    JsSyncHeader sh;
+    std::memcpy(&sh, static_cast<const uint8_t*>(table_host) + at, sizeof sh);
+    return sh.magic == JS_SYNC_MAGIC ? sh.info_off : 0;
+  }
   const uint64_t header_off = jp_header_off(h.B, sizeof(JdImage));
   if (h.magic != JD_MAGIC || h.B <= 0 || h.B > JD_MAX_B || h.table_bytes < header_off + sizeof(JpHeader)) return 0;
   JpHeader ph;
@@ -2032,7 +2332,23 @@ extern "C" int attwarp_jpegdec_decode_layout_scans(const void* table_host, const
   if (const int rc = check_launch("jpegscan_clear_kernel")) return rc;
   hipLaunchKernelGGL(jpegscan_marks_kernel, dim3(sh.h.nscans), dim3(JD_NT), 0, st, td, stream_bytes, sc);
   if (const int rc = check_launch("jpegscan_marks_kernel")) return rc;
+  JsSyncHeader yh;
+  std::memset(&yh, 0, sizeof yh);
+  const uint64_t sync_at = sh.h.off_scans + (uint64_t)sh.h.nscans * sizeof(JsScan);
+  if (h.table_bytes >= sync_at + JsScans::sync_bytes(sh.h.nscans)) {          // planned with sub-streams
+    std::memcpy(&yh, static_cast<const uint8_t*>(table_host) + sync_at, sizeof yh);
+    bool ok = yh.magic == JS_SYNC_MAGIC && yh.ncut <= (uint32_t)sh.h.nscans && yh.level_cut0[0] == 0;
+    for (int l = 0; ok && l < sh.h.nlevels; ++l)
+      ok = yh.level_cut0[l] <= yh.level_cut0[l + 1] && yh.level_cut0[l + 1] <= yh.ncut && yh.level_tables[l] >= 1 &&
+           yh.level_tables[l] <= (uint32_t)JF_MAX_COMP;
+    ATTWARP_REQUIRE(ok, "jpegdec_decode_layout_scans: not a table of attwarp_jpegdec_plan_layout_scans_ex");
+  }
   for (int l = 0; l < sh.h.nlevels; ++l) {
+    if (const uint32_t ncut = yh.level_cut0[l + 1] - yh.level_cut0[l]) {      // the level holds a cut scan
+      hipLaunchKernelGGL(jpegscan_substream_kernel, dim3(ncut), dim3(JD_NT), (size_t)yh.level_tables[l] * sizeof(JdHuff), st, td, stream_bytes, sc,
+                         l, (int)yh.level_tables[l]);
+      if (const int rc = check_launch("jpegscan_substream_kernel")) return rc;
+    }
     hipLaunchKernelGGL(jpegscan_entropy_kernel, dim3(sh.h.level_waves[l]), dim3(WAVE), (size_t)sh.level_tables[l] * sizeof(JdHuff), st, td,
                        stream_bytes, sc, l, sh.level_tables[l]);
     if (const int rc = check_launch("jpegscan_entropy_kernel")) return rc;

@@ -461,11 +461,23 @@ SCAN_KINDS = ("dc_first", "dc_refine", "ac_first", "ac_refine")
 # The kinds of scan that scan_substreams="auto" cuts: those whose route made JpegFiles.run faster on the marker-less rows of
 # tools/jpegprogsync_bench.py, measured by leaving the kind out of all four.  True cuts every kind.
 AUTO_SCAN_KINDS = ("ac_first", "ac_refine", "dc_refine")
+# The same for the progressive scans of files planned through the layout records (``all_scans``): a constant
+# of its own, measured the same way on the marker-less rows of tools/jpegscansync_bench.py.  All four kinds: here the DC first
+# pass settles in 2 - 4 rounds and saves 8 - 17 ms when added last; without it "auto" was slower than no keyword on the CMYK rows.
+AUTO_LAYOUT_SCAN_KINDS = ("dc_first", "ac_first", "ac_refine", "dc_refine")
 
 
 def scan_kind(scan: dict) -> str:
     """The kind of a progressive scan of :func:`parse_jpeg`: one of :data:`SCAN_KINDS`."""
     return SCAN_KINDS[(2 if scan["ss"] else 0) + (1 if scan["ah"] else 0)]
+
+
+def _layout_scan_cut(scan: dict, scan_substreams) -> bool:
+    """Whether ``scan_substreams`` asks for a scan of a file planned through the layout records to be cut: never a
+    sequential scan; "auto": the kinds of :data:`AUTO_LAYOUT_SCAN_KINDS`."""
+    if scan_substreams is False or scan.get("sequential"):
+        return False
+    return scan_substreams is True or scan_kind(scan) in AUTO_LAYOUT_SCAN_KINDS
 
 
 def scan_segments(nbytes: int, units: int, segment_bytes: int) -> int:
@@ -511,8 +523,11 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
     ``segment_bytes`` long (at most 16384 of them) is cut into such segments, its length known from the marker walk, and
     decoded by one lane per segment in front of its level's entropy launch; ``max_rounds`` caps the rounds
     of the first passes.  ``parsed[i]["scan_segments"]`` holds the segments planned per scan (0: one lane).  Pixels and
-    statuses do not depend on it; False gives the table of ``attwarp_jpegdec_plan_scans``, byte for byte.  Files planned
-    through the layout records (``all_scans``' own kind) are never cut."""
+    statuses do not depend on it; False gives the table of ``attwarp_jpegdec_plan_scans``, byte for byte.  With
+    ``all_scans=True`` the marker-less PROGRESSIVE scans of the files planned through the layout records are cut in the same
+    way through ``attwarp_jpegdec_plan_layout_scans_ex`` ("auto": the kinds of
+    :data:`AUTO_LAYOUT_SCAN_KINDS`); the scans of a sequential file of several scans are never cut (route 0), and False gives
+    the table of ``attwarp_jpegdec_plan_layout_scans``, byte for byte."""
     if not (scan_substreams is True or scan_substreams is False or (isinstance(scan_substreams, str) and scan_substreams == "auto")):
         raise ValueError("jpeg: scan_substreams must be 'auto', True or False")
     if mode not in _lib.JPEGDEC_MODE_IDS or order not in _ORDERS:
@@ -569,7 +584,18 @@ def plan(files, mode: str = "RGB", order: str = "rgb", substreams="auto", segmen
             _put_tables(srec["ac_counts"][i], srec["ac_symbols"][i], ac)
         size = ("attwarp_jpegdec_layout_scans_table_bytes", rp, B, len(scans))
         planner = ("attwarp_jpegdec_plan_layout_scans", rp, B, srec.ctypes.data, len(scans), TABLE, 1 if levels else 0)
-        sb = 0                                              # files planned scan by scan take no sub-streams
+        sb = 0                                              # files planned scan by scan take no sub-streams of the whole file
+        ssb = 0
+        if scan_substreams is not False:                    # their marker-less progressive scans do, each on its own
+            ssb, smr = _substream_plan(True, segment_bytes, max_rounds)
+            cuts = [_layout_scan_cut(s, scan_substreams) for _, s in scans]
+            slen = np.array([s["end"] - s["off"] if c else 0 for (_, s), c in zip(scans, cuts)], dtype=np.uint64)
+            size = ("attwarp_jpegdec_layout_scans_table_bytes_ex", rp, B, len(scans), ssb, smr)
+            planner = ("attwarp_jpegdec_plan_layout_scans_ex", rp, B, srec.ctypes.data, len(scans), TABLE, 1 if levels else 0, ssb, smr,
+                       slen.ctypes.data)
+            for p in parsed:                                # (only with the keyword: without it the parse is what it was)
+                p["scan_segments"] = [scan_segments(s["end"] - s["off"], s["units"], ssb) if _layout_scan_cut(s, scan_substreams) else 0
+                                      for s in p["scans"]]
     if any(prog):
         scans = [(b, s) for b, p in enumerate(parsed) for s in p["scans"]]
         srec = np.zeros(len(scans), dtype=np.dtype(_lib.JpegDecScan))
@@ -638,8 +664,9 @@ class JpegFiles(FileBatch):
     fourth kind with a plan of its own; only files the three other kinds refuse take it, the other parts plan and launch
     exactly as with ``progressive=True, all_layouts=True``, and views and statuses come back in input order.
 
-    ``scan_substreams="auto"`` / True (opt-in) cuts the marker-less scans of the plain progressive files into segments of
-    ``segment_bytes`` decoded by one lane each (:func:`plan`, DESIGN.md 3.23): one more launch in front of the entropy launch
+    ``scan_substreams="auto"`` / True (opt-in) cuts the marker-less scans of the plain progressive files and, with
+    ``all_scans``, the marker-less progressive scans of the files of the fourth kind (never a sequential scan) into segments of
+    ``segment_bytes`` decoded by one lane each (:func:`plan`, DESIGN.md 3.23, 3.25): one more launch in front of the entropy launch
     of every level that holds such a scan, constant per plan.  Pixels and statuses do not depend on it;
     :meth:`scan_substream_info` tells what the device did per scan."""
 
@@ -677,7 +704,7 @@ class JpegFiles(FileBatch):
                        else "attwarp_jpegdec_decode_layout_scans" if self.all_scans else "attwarp_jpegdec_decode")
         self.parsed, self.table_host, self.header = plan(files, mode, order, substreams, segment_bytes, max_rounds, progressive, levels, all_layouts, pre,
                                                          all_scans, scan_substreams)
-        self._scan_info_off = int(_lib.load().attwarp_jpegdec_scan_info_offset(self.table_host.ctypes.data)) if self.progressive else 0
+        self._scan_info_off = int(_lib.load().attwarp_jpegdec_scan_info_offset(self.table_host.ctypes.data)) if self.progressive or self.all_scans else 0
         self.segment_bytes, self.max_rounds = _substream_plan(substreams, segment_bytes, max_rounds)      # (0, 0): off
         self._info_off = int(_lib.load().attwarp_jpegdec_info_offset(self.table_host.ctypes.data))
         self._dev = indexed_device(device, out)
@@ -754,9 +781,9 @@ class JpegFiles(FileBatch):
         """After a :meth:`run` (synchronises): per image a list, in file order, of ``(route, segments, rounds, accepted)`` per
         scan as the device left them: route 0 for a scan on one lane, else 1 DC first pass, 2 DC refinement, 3 AC first pass,
         4 AC refinement; the segments planned; the rounds of a first pass; 1 if the segments decoded the scan, 0 if the
-        one-lane route did.  A plan without ``scan_substreams`` has no such records: all zeros; an image that is not a plain
-        progressive file has no scans here: an empty list.  For measurements and tests."""
-        if not self.progressive:
+        one-lane route did.  A plan without ``scan_substreams`` has no such records: all zeros; a file of one scan (baseline
+        or another layout) has no scans here: an empty list.  For measurements and tests."""
+        if not (self.progressive or self.all_scans):
             return [[] for _ in self.parsed]
         return self._scan_records(slice(0, 4))
 
@@ -776,7 +803,7 @@ class JpegFiles(FileBatch):
         """After a :meth:`run` (synchronises): per image and scan, beside :meth:`scan_substream_info`, the 100 MHz ticks its
         workgroup spent in its three parts: a first pass: rounds, sums and checks, write; a refinement: counts and masks,
         skim (a DC refinement: none), write.  Zeros for a scan on one lane.  For measurements."""
-        if not self.progressive:
+        if not (self.progressive or self.all_scans):
             return [[] for _ in self.parsed]
         return self._scan_records(slice(4, 7))
 

@@ -1205,6 +1205,26 @@ ATTWARP_API int attwarp_jpegdec_plan_layout_scans(const attwarp_jpegdec_layout_i
 ATTWARP_API int attwarp_jpegdec_decode_layout_scans(const void* table_host, const void* table_dev, const uint8_t* stream_bytes,
                        void* scratch, uint8_t* out, size_t out_bytes, int32_t* status, void* stream);
 
+/* Marker-less PROGRESSIVE scans of this family in parallel segments (jpegscan_sync_blocks.hpp):
+ * attwarp_jpegdec_plan_scans_ex for layout scans.  Arguments, cut rule (one unit, data_bytes[i] >= 2 segment_bytes, at most
+ * 16384 segments, fewer than 2^24 blocks; data_bytes[i] = 0 leaves scan i on one lane), routes, acceptance and the
+ * attwarp_jpegdec_scan_info records at attwarp_jpegdec_scan_info_offset are those of the plain family, over the general
+ * MCU: block ordinal n of a scan is MCU n / nslot, slot n % nslot.  A SEQUENTIAL scan is never cut (route 0).  A DC first
+ * pass may find several components on one Huffman table, so its decoder's state carries the slot only modulo the period of
+ * the scan's table sequence (the smallest divisor P of the blocks per MCU whose DC tables repeat, compared by content, kept
+ * in the scan's sub-stream record), a segment sums its DC differences by the block's place in it, and the scan is accepted
+ * only if every segment's entry slot is the count of blocks in front of it modulo P.  With segment_bytes = max_rounds = 0
+ * and data_bytes = NULL the table is attwarp_jpegdec_plan_layout_scans' byte for byte.  Table: behind the scan records a
+ * header and one 64-byte record per scan.  Scratch, behind everything there was: the records, per cut scan 96 bytes per
+ * segment and, for an AC refinement, 12 bytes per block.  attwarp_jpegdec_decode_layout_scans launches
+ * jpegscan_substream_kernel (one workgroup per cut scan) in front of the entropy launch of every level that holds a cut
+ * scan; status[] and the pixels do not depend on the plan. */
+ATTWARP_API size_t attwarp_jpegdec_layout_scans_table_bytes_ex(const attwarp_jpegdec_layout_image* images, int B, int nscans,
+                       int segment_bytes, int max_rounds);
+ATTWARP_API int attwarp_jpegdec_plan_layout_scans_ex(const attwarp_jpegdec_layout_image* images, int B,
+                       const attwarp_jpegdec_layout_scan* scans, int nscans, void* table, size_t table_bytes, int by_level,
+                       int segment_bytes, int max_rounds, const uint64_t* data_bytes);
+
 /* ---- JPEG files of a whole batch of differently sized uint8 images, encoded on the device (jpegenc.hip):
  * the bytes of Pillow's Image.save(f, "JPEG", quality, subsampling, restart_marker_rows), whole file: baseline sequential,
  * JFIF APP0, one DQT per table, SOF0, the four Annex K Huffman tables, DRI when restarts are on, one interleaved scan.
