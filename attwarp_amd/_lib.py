@@ -200,6 +200,9 @@ SIGNATURES = {
     "attwarp_jpegenc_table_bytes": (c_size_t, [c_void_p, c_int]),
     "attwarp_jpegenc_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
     "attwarp_jpegenc_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "attwarp_jpegenc_bound_ex": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "attwarp_jpegenc_table_bytes_ex": (c_size_t, [c_void_p, c_int, c_void_p]),
+    "attwarp_jpegenc_plan_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),
@@ -356,7 +359,7 @@ class JpegEncHeader(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("B", ctypes.c_int32), ("nunits", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("table_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64),
                 ("off_images", ctypes.c_uint64), ("off_units", ctypes.c_uint64), ("off_huffman", ctypes.c_uint64),
-                ("off_image_out", ctypes.c_uint64)]
+                ("off_image_out", ctypes.c_uint64), ("off_optimize", ctypes.c_uint64)]
 
 
 class PngHeader(ctypes.Structure):

@@ -185,6 +185,7 @@ enum TuneKey {
   TUNE_CLIP_RAGGED_VARIANT,  // 1: attwarp_clip_images_plan sends every image down the two-launch route (uint8 intermediate in memory)
   TUNE_PNGDEC_ROUTE,         // 1: attwarp_pngdec_decode sends every image down the serial route (one wave from the stream's start)
   TUNE_JPEGPROG_SYNC_KINDS,  // attwarp_jpegdec_plan_scans_ex cuts only scans of the kinds in this mask (bit JP_DC_FIRST .. JP_AC_REFINE): per-kind timing
+  TUNE_JPEGOPT_GIVEN_HIST,   // 1: attwarp_jpegenc_encode neither clears nor counts: the table kernel runs on the histograms the caller left in the scratch buffer
   TUNE_COUNT
 };
 #ifdef ATTWARP_TUNING

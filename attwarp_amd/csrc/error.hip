@@ -27,7 +27,7 @@ int tune(TuneKey k) { return g_tune[k].load(std::memory_order_relaxed) - 1; }
 static const char* const kTuneNames[TUNE_COUNT] = {
     "remap_variant", "remap_rows", "remap_chw_split", "remap_tiled", "remap_tile_ko", "remap_noswz", "remap_nt",
     "lanczos_variant", "clip_variant", "profiles_variant", "remap_cpw", "attn_hu", "u8_ahead", "trace_lo", "trace_hi",
-    "prep_variant", "clip_ragged_variant", "pngdec_route", "jpegprog_sync_kinds"};
+    "prep_variant", "clip_ragged_variant", "pngdec_route", "jpegprog_sync_kinds", "jpegopt_given_hist"};
 
 #endif
 

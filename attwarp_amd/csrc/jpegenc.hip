@@ -16,10 +16,18 @@
 //                             the first unit, EOI behind the last.
 // A file with restart markers takes the same route: an interval is a stretch at whose start the bit offset returns to zero.
 // Every loop is bounded by a constant or by a size the planner checked; tests/jpegenc_ref.py restates the byte stream.
+// A call with optimised images (attwarp_jpegenc_plan_ex) puts three launches between the first two, which
+// work on those images alone and whose results the later launches read from the scratch buffer:
+//   jpegopt_clear_kernel      one workgroup per optimised image: its four symbol histograms to zero;
+//   jpegopt_histogram_kernel  one workgroup per unit of an optimised image: the symbols the entropy kernel would code (the same
+//                             derivation, je_lane_symbol), counted in LDS, the non-zero counts added to the image's histograms;
+//   jpegopt_tables_kernel     one workgroup per optimised image, one wave per table: libjpeg's optimal table (jpegopt_blocks.hpp),
+//                             its code words and DHT segment; then the header with the DHTs spliced in.
+// tests/jpegopt_ref.py restates the tables.
 #include <algorithm>
 #include <cstring>
 
-#include "jpegenc_blocks.hpp"
+#include "jpegopt_blocks.hpp"
 
 namespace attwarp {
 
@@ -104,29 +112,65 @@ __global__ __launch_bounds__(JE_TNT) void jpegenc_transform_kernel(const uint8_t
 struct JeLane {
   uint32_t nf0, code, len;
 };
-__device__ __forceinline__ JeLane je_lane_code(int lane, int v, const uint32_t* dc, const uint32_t* ac) {
-  JeLane o = {0u, 0u, 0u};
+// The symbol behind it, shared with the histogram of the optimised tables: nf0 symbols F0, then `sym` (lane 0: of the DC table,
+// the difference's category; the others: run << 4 | size of the AC table, 0 = end of block) with n low bits; sym < 0: nothing.
+struct JeSymbol {
+  uint32_t nf0, n;
+  int sym;
+};
+__device__ __forceinline__ JeSymbol je_lane_symbol(int lane, int v) {
+  JeSymbol o = {0u, 0u, -1};
   const unsigned long long mask = __ballot(lane > 0 && v != 0);
   if (lane == 0 || v != 0) {
     const uint32_t mag = (uint32_t)(v < 0 ? -v : v);
-    const uint32_t n = 32u - (uint32_t)__clz(mag);          // (mag = 0: 32 - 32)
-    const uint32_t low = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1u);
-    uint32_t h;
-    if (lane == 0) h = dc[n];
+    o.n = 32u - (uint32_t)__clz(mag);                       // (mag = 0: 32 - 32)
+    if (lane == 0) o.sym = (int)o.n;
     else {
       const unsigned long long below = mask & ((1ull << lane) - 1ull);
       const int prev = below ? 63 - __clzll((long long)below) : 0;
       const uint32_t run = (uint32_t)(lane - 1 - prev);
       o.nf0 = run >> 4;
-      h = ac[(run & 15u) << 4 | n];
+      o.sym = (int)((run & 15u) << 4 | o.n);
     }
-    o.code = (h & 0xffffu) << n | low;
-    o.len = (h >> 16) + n;
   } else if (lane == 63) {
-    o.code = ac[0] & 0xffffu;
-    o.len = ac[0] >> 16;
+    o.sym = 0;
   }
   return o;
+}
+__device__ __forceinline__ JeLane je_lane_code(int lane, int v, const uint32_t* dc, const uint32_t* ac) {
+  JeLane o = {0u, 0u, 0u};
+  const JeSymbol s = je_lane_symbol(lane, v);
+  if (s.sym < 0) return o;
+  const uint32_t h = (lane == 0 ? dc : ac)[s.sym];
+  const uint32_t low = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << s.n) - 1u);       // (the end of block: n = 0, no low bits)
+  o.nf0 = s.nf0;
+  o.code = (h & 0xffffu) << s.n | low;
+  o.len = (h >> 16) + s.n;
+  return o;
+}
+// What lane `lane` sees of block i of unit u: its zigzag coefficient; lane 0: the difference to the DC of the component's
+// previous block, to zero at the start of a restart interval.  comp: the block's component.
+__device__ __forceinline__ int je_block_lane_value(const int16_t* coef, const JeUnit& u, const JeImageDev* im, int i, int lane, int& comp) {
+  const int bpm = im->bpm, ny = im->C == 3 ? im->hmax * im->vmax : 1;
+  const int m = i / bpm, s = i - m * bpm;
+  const int64_t blk = (int64_t)u.mcu0 * bpm + i;
+  int v = coef[blk * 64 + lane];
+  comp = s < ny ? 0 : s - ny + 1;
+  const int first = comp ? s : 0, last = comp ? s : ny - 1;
+  if (lane == 0) {
+    int pred = 0;
+    if (s > first) pred = coef[(blk - 1) * 64];
+    else if ((u.mcu0 + m) % im->interval != 0) pred = coef[(blk - s - bpm + last) * 64];
+    v -= pred;
+  }
+  return v;
+}
+// The optimised image's record in the scratch buffer; nullptr: the image takes the Annex K tables.
+__device__ __forceinline__ const JoImageOut* je_optimized(const uint8_t* table, const attwarp_jpegenc_header* hdr, const JeImageDev* im,
+                                                          const uint8_t* scratch) {
+  if (!im->opt) return nullptr;
+  const JoPlan* plan = reinterpret_cast<const JoPlan*>(table + hdr->off_optimize);
+  return reinterpret_cast<const JoImageOut*>(scratch + plan->off_out) + (im->opt - 1);
 }
 // nbits <= 27 of `value` at bit `pos` of the big-endian words w
 __device__ __forceinline__ void je_put(uint32_t* w, uint32_t pos, uint32_t value, uint32_t nbits) {
@@ -145,26 +189,23 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_entropy_kernel(const uint8_t* _
   const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[blockIdx.x];
   const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
   const uint32_t* huff = reinterpret_cast<const uint32_t*>(table + hdr->off_huffman);
+  const JoImageOut* opt = je_optimized(table, hdr, im, scratch);
   const int bpm = im->bpm, nblk = u.nmcu * bpm, ny = im->C == 3 ? im->hmax * im->vmax : 1;
   const int nwords = min(JE_UNIT_WORDS, (nblk * im->block_bits + 31) / 32 + 2);
   for (int i = tid; i < nwords; i += JE_NT) s_bits[i] = 0;
-  for (int i = tid; i < 4 * 256; i += JE_NT) s_huff[i] = huff[i];
+  if (opt) {                                                // the image's own code words (a grey image: two tables)
+    const int nt = im->C == 3 ? 4 : 2;
+    for (int t = 0; t < 4; ++t) s_huff[256 * t + tid] = t < nt ? opt->table[t].code[tid] : 0u;
+  } else {
+    for (int i = tid; i < 4 * 256; i += JE_NT) s_huff[i] = huff[i];
+  }
   if (tid < 2 * WAVE) s_blen[tid] = 0;
   __syncthreads();
   const int16_t* coef = reinterpret_cast<const int16_t*>(scratch + im->coef_off);
-  const int64_t blk0 = (int64_t)u.mcu0 * bpm;
   // the coefficient of this lane in block i of the unit; lane 0: the difference to the component's previous block
   auto lane_code = [&](int i) {
-    const int m = i / bpm, s = i - m * bpm;
-    const int64_t blk = blk0 + i;
-    int v = coef[blk * 64 + lane];
-    const int comp = s < ny ? 0 : s - ny + 1, first = comp ? s : 0, last = comp ? s : ny - 1;
-    if (lane == 0) {
-      int pred = 0;
-      if (s > first) pred = coef[(blk - 1) * 64];
-      else if ((u.mcu0 + m) % im->interval != 0) pred = coef[(blk - s - bpm + last) * 64];
-      v -= pred;
-    }
+    int comp;
+    const int v = je_block_lane_value(coef, u, im, i, lane, comp);
     const int t = comp ? 2 : 0;
     return je_lane_code(lane, v, s_huff + 256 * t, s_huff + 256 * (t + 1));
   };
@@ -200,6 +241,78 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_entropy_kernel(const uint8_t* _
   uint32_t* dst = reinterpret_cast<uint32_t*>(scratch + u.slot_off);
   for (uint32_t i = tid; i < (total + 31u) / 32u; i += JE_NT) dst[i] = __builtin_bswap32(s_bits[i]);
   if (tid == 0) reinterpret_cast<JeUnitOut*>(scratch)[blockIdx.x].bits = total;
+}
+
+// ---- 1a - 1c. optimised images: histograms, tables, header (launched in front of 2.) -----------------------------------------------
+static_assert(JE_NT == 256 && JE_NT == 4 * WAVE, "a thread per symbol of a table, a wave per table");
+__device__ __forceinline__ const JoPlan* jo_plan(const uint8_t* table) {
+  return reinterpret_cast<const JoPlan*>(table + reinterpret_cast<const attwarp_jpegenc_header*>(table)->off_optimize);
+}
+
+__global__ __launch_bounds__(JE_NT) void jpegopt_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  uint32_t* hist = reinterpret_cast<uint32_t*>(scratch + jo_plan(table)->off_hist) + (size_t)blockIdx.x * 1024;
+  for (int i = threadIdx.x; i < 4 * 256; i += JE_NT) hist[i] = 0u;
+}
+
+__global__ __launch_bounds__(JE_NT) void jpegopt_histogram_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_hist[4 * 256];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JoPlan* plan = jo_plan(table);
+  const int32_t* list = reinterpret_cast<const int32_t*>(reinterpret_cast<const JoImage*>(plan + 1) + plan->nimages);
+  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[list[blockIdx.x]];
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  for (int i = tid; i < 4 * 256; i += JE_NT) s_hist[i] = 0u;
+  __syncthreads();
+  const int16_t* coef = reinterpret_cast<const int16_t*>(scratch + im->coef_off);
+  const int nblk = u.nmcu * im->bpm;
+  for (int i = wave; i < nblk; i += JE_NT / WAVE) {
+    int comp;
+    const int v = je_block_lane_value(coef, u, im, i, lane, comp);
+    const JeSymbol s = je_lane_symbol(lane, v);
+    uint32_t* h = s_hist + (comp ? 512 : 0);                // DHT order: DC 0, AC 0, DC 1, AC 1
+    if (s.sym >= 0) atomicAdd(&h[(lane ? 256 : 0) + (s.sym & 255)], 1u);
+    if (s.nf0) atomicAdd(&h[256 + 0xf0], s.nf0);
+  }
+  __syncthreads();
+  uint32_t* hist = reinterpret_cast<uint32_t*>(scratch + plan->off_hist) + (size_t)(im->opt - 1) * 1024;
+  for (int i = tid; i < 4 * 256; i += JE_NT)
+    if (s_hist[i]) atomicAdd(&hist[i], s_hist[i]);
+}
+
+struct JoWaveMin {                     // the smallest key of the wave's 64 lanes, on every lane
+  __device__ __forceinline__ uint64_t operator()(uint64_t v) const {
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+      const uint32_t lo = __shfl_xor((uint32_t)v, o, WAVE), hi = __shfl_xor((uint32_t)(v >> 32), o, WAVE);
+      const uint64_t other = (uint64_t)hi << 32 | lo;
+      v = other < v ? other : v;
+    }
+    return v;
+  }
+};
+
+__global__ __launch_bounds__(JE_NT) void jpegopt_tables_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ JoWork s_work[JE_NT / WAVE];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const JoPlan* plan = jo_plan(table);
+  const JoImage oi = reinterpret_cast<const JoImage*>(plan + 1)[blockIdx.x];
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + oi.image;
+  const uint32_t* hist = reinterpret_cast<const uint32_t*>(scratch + plan->off_hist) + (size_t)blockIdx.x * 1024;
+  JoImageOut* out = reinterpret_cast<JoImageOut*>(scratch + plan->off_out) + blockIdx.x;
+  if (wave < oi.ntables) jo_optimal_table<WAVE>(hist + 256 * wave, (wave & 1) << 4 | wave >> 1, lane, JoWaveMin(), s_work[wave], out->table[wave]);
+  __syncthreads();
+  // SOI .. SOF0, the image's DHTs, DRI / SOS; the clamp guards the record, the symbol counts keep the header within the standard one's
+  int at = oi.pre_len;
+  for (int i = tid; i < oi.pre_len; i += JE_NT) out->header[i] = im->header[i];
+  for (int t = 0; t < oi.ntables; ++t) {
+    const int n = min(out->table[t].dht_len, JE_HEADER_MAX - oi.suf_len - at);
+    for (int i = tid; i < n; i += JE_NT) out->header[at + i] = out->table[t].dht[i];
+    at += max(n, 0);
+  }
+  for (int i = tid; i < oi.suf_len; i += JE_NT) out->header[at + i] = im->header[oi.pre_len + i];
+  if (tid == 0) out->header_len = at + oi.suf_len;
 }
 
 // ---- 3. bits of the image's earlier units -----------------------------------------------------------------------------------------
@@ -318,9 +431,11 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_scan_bytes_kernel(const uint8_t
     if (s < im->nunits) uo[s].fpos = pre + 2ull * (unsigned long long)(s / im->upi);       // an RSTn behind every earlier interval
     carry += tot;
   }
-  if (tid == 0)
+  if (tid == 0) {
+    const JoImageOut* opt = je_optimized(table, hdr, im, scratch);
     reinterpret_cast<JeImageOut*>(scratch + hdr->off_image_out)[b].file_bytes =
-        (unsigned long long)im->header_len + carry + 2ull * (unsigned long long)(im->nint - 1) + 2ull;
+        (unsigned long long)(opt ? opt->header_len : im->header_len) + carry + 2ull * (unsigned long long)(im->nint - 1) + 2ull;
+  }
 }
 
 // ---- 6. where every file starts: offsets[B + 1] ------------------------------------------------------------------------------------------
@@ -353,7 +468,10 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_write_kernel(const uint8_t* __r
   const JeUnitOut o = reinterpret_cast<const JeUnitOut*>(scratch)[blockIdx.x];
   const int64_t off = offsets[u.image];                      // (jpegenc_scan_files_kernel)
   JE_G uint8_t* file = (JE_G uint8_t*)out + off;
-  JE_G uint8_t* dst = file + im->header_len + o.fpos;
+  const JoImageOut* opt = je_optimized(table, hdr, im, scratch);          // its header: where jpegopt_tables_kernel left it
+  const uint8_t* header = opt ? opt->header : im->header;
+  const int header_len = opt ? opt->header_len : im->header_len;
+  JE_G uint8_t* dst = file + header_len + o.fpos;
   const JE_G uint8_t* ust = (const JE_G uint8_t*)scratch + im->ustream_off + o.upos;
   const uint32_t n = o.nbytes, per = (n + JE_NT - 1) / JE_NT;
   const uint32_t lo = min(n, (uint32_t)tid * per), hi = min(n, lo + per);
@@ -367,7 +485,7 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_write_kernel(const uint8_t* __r
     if (byte == 255u) dst[at++] = 0;
   }
   if (u.index == 0)
-    for (int i = tid; i < im->header_len; i += JE_NT) file[i] = im->header[i];
+    for (int i = tid; i < header_len; i += JE_NT) file[i] = header[i];
   if (tid == 0 && u.last) {
     JE_G uint8_t* m = dst + n + o.nff;
     m[0] = 0xff;
@@ -407,12 +525,14 @@ static bool je_geometry(int H, int W, int C, int quality, int subsampling, int r
   return true;
 }
 static int je_header_len(int C, int restart_rows) { return 2 + 18 + (C == 3 ? 2 : 1) * 69 + (10 + 3 * C) + (C == 3 ? 432 : 216) + (restart_rows ? 6 : 0) + (8 + 2 * C); }
-static uint64_t je_bound64(int C, int quality, int restart_rows, const JeGeometry& g) {
-  const uint64_t bits = (uint64_t)g.nmcu * g.bpm * (uint64_t)je_block_bound_bits(quality, C);
+// optimize: the header is never longer than the standard one (at most 12 and 162 symbols per DHT); a DC code may take 12 bits
+static uint64_t je_bound64(int C, int quality, int restart_rows, const JeGeometry& g, bool optimize = false) {
+  const uint64_t bits = (uint64_t)g.nmcu * g.bpm * (uint64_t)(je_block_bound_bits(quality, C) + (optimize ? JO_EXTRA_BLOCK_BITS : 0));
   return (uint64_t)je_header_len(C, restart_rows) + 2u * ((bits + 7u) / 8u + (uint64_t)g.nint) + 2u * (uint64_t)g.nint + 2u;
 }
 
-static int je_write_header(uint8_t* h, const attwarp_jpegenc_image& d, const JeGeometry& g) {
+// pre_len: the file's DHTs are left out (the device splices the image's own in) and *pre_len receives where they belong
+static int je_write_header(uint8_t* h, const attwarp_jpegenc_image& d, const JeGeometry& g, int* pre_len = nullptr) {
   int n = 0;
   auto put = [&](std::initializer_list<int> b) { for (int v : b) h[n++] = (uint8_t)v; };
   put({0xff, 0xd8, 0xff, 0xe0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00});
@@ -423,7 +543,8 @@ static int je_write_header(uint8_t* h, const attwarp_jpegenc_image& d, const JeG
   }
   put({0xff, 0xc0, 0x00, 8 + 3 * nc, 0x08, d.H >> 8, d.H & 255, d.W >> 8, d.W & 255, nc});
   for (int c = 0; c < nc; ++c) put({c + 1, c == 0 ? (g.hmax << 4 | g.vmax) : 0x11, c ? 1 : 0});
-  for (int t = 0; t < (nc == 3 ? 4 : 2); ++t) {
+  if (pre_len) *pre_len = n;
+  for (int t = 0; t < (nc == 3 ? 4 : 2) && !pre_len; ++t) {
     const int nv = je_nvals(t);
     put({0xff, 0xc4, (19 + nv) >> 8, (19 + nv) & 255, (t & 1) << 4 | t >> 1});
     for (int k = 0; k < 16; ++k) h[n++] = JE_BITS[t][k];
@@ -448,13 +569,25 @@ extern "C" size_t attwarp_jpegenc_bound(int H, int W, int C, int quality, int su
   return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
 }
 
-static int jpegenc_count(const attwarp_jpegenc_image* images, int B, int64_t& nunits) {
+extern "C" size_t attwarp_jpegenc_bound_ex(int H, int W, int C, int quality, int subsampling, int restart_rows, int optimize) {
+  JeGeometry g;
+  const char* what;
+  if (!je_geometry(H, W, C, quality, subsampling, restart_rows, g, what)) return 0;
+  const uint64_t b = je_bound64(C, quality, restart_rows, g, optimize != 0);
+  return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
+}
+
+// nopt / nopt_units: the optimised images of the call (optimize: NULL, or one flag per image) and their units
+static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, int64_t& nunits, int& nopt, int64_t& nopt_units) {
   ATTWARP_REQUIRE(images, "jpegenc: null image array");
   ATTWARP_REQUIRE(B > 0, "jpegenc: non-positive batch size");
   if (B > (1 << 20)) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: B=%d > 2^20", B);
-  nunits = 0;
+  nunits = nopt_units = 0;
+  nopt = 0;
   for (int b = 0; b < B; ++b) {
     const attwarp_jpegenc_image& d = images[b];
+    const bool opt = optimize && optimize[b];
+    ATTWARP_REQUIRE(!optimize || optimize[b] == 0 || optimize[b] == 1, "jpegenc: image %d: optimize must be 0 or 1", b);
     ATTWARP_REQUIRE(d.src, "jpegenc: image %d: null pointer", b);
     ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegenc: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
     JeGeometry g;
@@ -463,35 +596,52 @@ static int jpegenc_count(const attwarp_jpegenc_image* images, int B, int64_t& nu
       return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d (%d x %d x %d, quality %d, subsampling %d, restart_rows %d): %s", b, d.H, d.W, d.C,
                   d.quality, d.subsampling, d.restart_rows, what);
     ATTWARP_REQUIRE((int64_t)d.pitch >= (int64_t)d.W * d.C, "jpegenc: image %d: pitch %d below the row's %lld bytes", b, d.pitch, (long long)d.W * d.C);
-    if (je_bound64(d.C, d.quality, d.restart_rows, g) >= ((uint64_t)1 << 31))
+    if (je_bound64(d.C, d.quality, d.restart_rows, g, opt) >= ((uint64_t)1 << 31))
       return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: the bound of %d x %d x %d is 2 GiB or more", b, d.H, d.W, d.C);
+    // A table's frequencies add up to at most 64 symbols per block.  A block's bound is above 1024 bits (22 + 63 x 17) and the
+    // file's bound, twice its bytes, is below 2^31: fewer than 2^23 blocks and 2^29 symbols, below libjpeg's sentinel (a larger
+    // frequency would never be merged) and far below the 2^32 of the counters.  This refusal can never trigger.
+    if (opt && (uint64_t)g.nmcu * g.bpm * JO_SYMBOLS_PER_BLOCK >= JO_SENTINEL)
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: %lld blocks could hold 10^9 symbols or more", b, (long long)g.nmcu * g.bpm);
     nunits += g.nunits;
+    if (opt) { ++nopt; nopt_units += g.nunits; }
   }
   if (nunits > JE_MAX_UNITS) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld units in one call (> %d)", (long long)nunits, JE_MAX_UNITS);
   return ATTWARP_OK;
 }
 
-static uint64_t jpegenc_table_layout(int B, int64_t nunits, uint64_t& off_images, uint64_t& off_units, uint64_t& off_huffman) {
+// Without an optimised image the table ends behind the units, as it always did; with one, the JoPlan follows them.
+static uint64_t jpegenc_table_layout(int B, int64_t nunits, int nopt, int64_t nopt_units, uint64_t& off_images, uint64_t& off_units,
+                                     uint64_t& off_huffman, uint64_t& off_optimize) {
+  static_assert(sizeof(attwarp_jpegenc_header) == 80, "the header ends where the Annex K code words start");
   off_huffman = align_up(sizeof(attwarp_jpegenc_header), 16);
   off_images = off_huffman + 4 * 256 * sizeof(uint32_t);
   off_units = off_images + align_up((uint64_t)B * sizeof(JeImageDev), 16);
-  return off_units + (uint64_t)nunits * sizeof(JeUnit);
+  const uint64_t end = off_units + (uint64_t)nunits * sizeof(JeUnit);
+  off_optimize = nopt ? end : 0;
+  return nopt ? end + sizeof(JoPlan) + (uint64_t)nopt * sizeof(JoImage) + (uint64_t)nopt_units * sizeof(int32_t) : end;
+}
+
+extern "C" size_t attwarp_jpegenc_table_bytes_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize) {
+  int64_t nunits, nopt_units;
+  int nopt;
+  if (jpegenc_count(images, B, optimize, nunits, nopt, nopt_units) != ATTWARP_OK) return 0;
+  uint64_t a, b, c, d;
+  return (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, a, b, c, d);
 }
 
 extern "C" size_t attwarp_jpegenc_table_bytes(const attwarp_jpegenc_image* images, int B) {
-  int64_t nunits;
-  if (jpegenc_count(images, B, nunits) != ATTWARP_OK) return 0;
-  uint64_t a, b, c;
-  return (size_t)jpegenc_table_layout(B, nunits, a, b, c);
+  return attwarp_jpegenc_table_bytes_ex(images, B, nullptr);
 }
 
-extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, void* table, size_t table_bytes) {
-  int64_t nunits;
-  if (const int rc = jpegenc_count(images, B, nunits)) return rc;
+extern "C" int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, void* table, size_t table_bytes) {
+  int64_t nunits, nopt_units;
+  int nopt;
+  if (const int rc = jpegenc_count(images, B, optimize, nunits, nopt, nopt_units)) return rc;
   ATTWARP_REQUIRE(table, "jpegenc_plan: null table");
   attwarp_jpegenc_header h;
   std::memset(&h, 0, sizeof h);
-  const size_t need = (size_t)jpegenc_table_layout(B, nunits, h.off_images, h.off_units, h.off_huffman);
+  const size_t need = (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, h.off_images, h.off_units, h.off_huffman, h.off_optimize);
   ATTWARP_REQUIRE(table_bytes >= need, "jpegenc_plan: table of %zu bytes, %zu needed", table_bytes, need);
   uint8_t* t = static_cast<uint8_t*>(table);
   std::memset(t, 0, need);
@@ -509,8 +659,14 @@ extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, 
   h.off_image_out = align_up((uint64_t)nunits * sizeof(JeUnitOut), 256);
   uint64_t soff = h.off_image_out + align_up((uint64_t)B * sizeof(JeImageOut), 256), out_bytes = 0;
   int32_t s = 0;
+  JoPlan* plan = nopt ? reinterpret_cast<JoPlan*>(t + h.off_optimize) : nullptr;
+  JoImage* oimg = nopt ? reinterpret_cast<JoImage*>(plan + 1) : nullptr;
+  int32_t* ounit = nopt ? reinterpret_cast<int32_t*>(oimg + nopt) : nullptr;
+  int k_opt = 0;
+  int64_t k_unit = 0;
   for (int b = 0; b < B; ++b) {
     const attwarp_jpegenc_image& d = images[b];
+    const bool opt = optimize && optimize[b];
     JeGeometry g;
     const char* what;
     je_geometry(d.H, d.W, d.C, d.quality, d.subsampling, d.restart_rows, g, what);
@@ -521,13 +677,22 @@ extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, 
     r.mcus_x = g.mcus_x; r.nmcu = (int32_t)g.nmcu;
     r.interval = g.interval; r.nint = g.nint; r.upi = g.upi;
     r.unit0 = s; r.nunits = g.nunits;
-    r.block_bits = je_block_bound_bits(d.quality, d.C);
+    r.block_bits = je_block_bound_bits(d.quality, d.C) + (opt ? JO_EXTRA_BLOCK_BITS : 0);
     for (int tb = 0; tb < 2; ++tb)
       for (int k = 0; k < 64; ++k) {
         r.divisor[tb][k] = (uint16_t)(je_quant_value(d.quality, tb, k) << 3);
         r.recip[tb][k] = je_recip(r.divisor[tb][k]);
       }
-    r.header_len = je_write_header(r.header, d, g);
+    if (opt) {
+      JoImage& o = oimg[k_opt];
+      o.image = b;
+      r.header_len = je_write_header(r.header, d, g, &o.pre_len);
+      o.suf_len = r.header_len - o.pre_len;
+      o.ntables = d.C == 3 ? 4 : 2;
+      r.opt = ++k_opt;
+    } else {
+      r.header_len = je_write_header(r.header, d, g);
+    }
     const uint64_t nblocks = (uint64_t)g.nmcu * g.bpm;
     r.coef_off = soff;
     soff += align_up(nblocks * 128, 256);
@@ -545,14 +710,26 @@ extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, 
         q.index = s - r.unit0;
         q.slot_off = soff;
         soff += align_up(((uint64_t)q.nmcu * g.bpm * r.block_bits + 7) / 8 + 8, 16);
+        if (opt) ounit[k_unit++] = s;
       }
     }
-    out_bytes += je_bound64(d.C, d.quality, d.restart_rows, g);
+    out_bytes += je_bound64(d.C, d.quality, d.restart_rows, g, opt);
+  }
+  if (nopt) {
+    plan->nimages = nopt;
+    plan->nunits = (int32_t)nopt_units;
+    plan->off_hist = align_up(soff, 256);
+    plan->off_out = plan->off_hist + (uint64_t)nopt * 4 * 256 * sizeof(uint32_t);
+    soff = plan->off_out + (uint64_t)nopt * sizeof(JoImageOut);
   }
   h.scratch_bytes = soff;
   h.out_bytes = out_bytes;
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, void* table, size_t table_bytes) {
+  return attwarp_jpegenc_plan_ex(images, B, nullptr, table, table_bytes);
 }
 
 extern "C" int attwarp_jpegenc_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
@@ -570,6 +747,21 @@ extern "C" int attwarp_jpegenc_encode(const void* table_host, const void* table_
   uint8_t* sc = static_cast<uint8_t*>(scratch);
   hipLaunchKernelGGL(jpegenc_transform_kernel, dim3(h.nunits), dim3(JE_TNT), 0, st, td, sc);
   if (const int rc = check_launch("jpegenc_transform_kernel")) return rc;
+  if (h.off_optimize) {                                      // (attwarp_jpegenc_plan_ex: some image takes tables of its own)
+    ATTWARP_REQUIRE(h.off_optimize % 8 == 0 && h.off_optimize + sizeof(JoPlan) <= h.table_bytes, "jpegenc_encode: not a table of attwarp_jpegenc_plan_ex");
+    JoPlan plan;
+    std::memcpy(&plan, static_cast<const uint8_t*>(table_host) + h.off_optimize, sizeof plan);
+    ATTWARP_REQUIRE(plan.nimages > 0 && plan.nimages <= h.B && plan.nunits >= plan.nimages && plan.nunits <= h.nunits,
+                    "jpegenc_encode: not a table of attwarp_jpegenc_plan_ex");
+    if (tune(TUNE_JPEGOPT_GIVEN_HIST) != 1) {                // (tuning flavour, 1: the caller filled the histograms)
+      hipLaunchKernelGGL(jpegopt_clear_kernel, dim3(plan.nimages), dim3(JE_NT), 0, st, td, sc);
+      if (const int rc = check_launch("jpegopt_clear_kernel")) return rc;
+      hipLaunchKernelGGL(jpegopt_histogram_kernel, dim3(plan.nunits), dim3(JE_NT), 0, st, td, sc);
+      if (const int rc = check_launch("jpegopt_histogram_kernel")) return rc;
+    }
+    hipLaunchKernelGGL(jpegopt_tables_kernel, dim3(plan.nimages), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegopt_tables_kernel")) return rc;
+  }
   hipLaunchKernelGGL(jpegenc_entropy_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
   if (const int rc = check_launch("jpegenc_entropy_kernel")) return rc;
   hipLaunchKernelGGL(jpegenc_scan_bits_kernel, dim3(h.B), dim3(JE_NT), 0, st, td, sc);

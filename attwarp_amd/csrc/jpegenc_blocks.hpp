@@ -26,8 +26,8 @@ struct JeImageDev {                    // the per-image record of a planned tabl
   int32_t interval, nint, upi;         // MCUs per restart interval (nmcu without restarts), intervals, units per full interval
   int32_t unit0, nunits;
   int32_t header_len, block_bits;      // bytes of SOI .. SOS; bits one block takes at most at this image's quality
-  int32_t pad;
-  uint64_t coef_off, ustream_off;      // scratch: zigzag int16 coefficients of every block; the unstuffed stream
+  int32_t opt;                         // 0, or 1 + the image's index among the optimised ones (jpegopt_blocks.hpp)
+  uint64_t coef_off, ustream_off;     // scratch: zigzag int16 coefficients of every block; the unstuffed stream
   uint16_t divisor[2][64];             // q << 3, natural order, luma and chroma
   uint32_t recip[2][64];               // ceil(2^32 / divisor)
   uint8_t header[JE_HEADER_MAX];

@@ -899,15 +899,19 @@ class JpegBatch:
     ``restart_rows`` (MCU rows per restart interval, 0: no restart markers), ``order`` "rgb" / "bgr": one value or one per
     image.  The defaults are Pillow's, so a bare call gives the file of ``Image.save``; ``restart_rows=1`` costs two bytes
     per MCU row and is what this project's own reader (:func:`decode_jpeg`) decodes fastest.  ``out``: a uint8 device buffer
-    of at least :attr:`bound` bytes.  ``optimize``, progressive output, CMYK, EXIF / ICC / dpi and custom tables do not
-    exist here.  Limits raise ValueError before any launch.
+    of at least :attr:`bound` bytes.  ``optimize`` (one value or one per image, default False): the image's own Huffman
+    tables, built on the GPU from its symbol counts the way libjpeg builds them, so that the file is byte for byte that of
+    ``Image.save(..., optimize=True)``: the same pixels in fewer bytes, for three more launches.  Images
+    with and without it share a batch; without it in any image the call is what it was before the keyword existed.
+    Progressive output, CMYK, EXIF / ICC / dpi and custom tables do not exist here.  Limits raise ValueError before any launch.
 
     A grey image ignores ``subsampling`` and is always the file of a bare ``Image.save`` of an "L" image, factors 1 x 1.
     Pillow, GIVEN the keyword for an "L" image, writes its factors into the component's SOF0 entry (one byte: 0x21 or 0x22
     in place of 0x11) and the same scan data, so for grey images ``encode_jpeg(..., subsampling=s)`` differs in that one
     byte from ``Image.save(..., subsampling=s)`` unless s is "4:4:4"."""
 
-    def __init__(self, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", out: Optional[torch.Tensor] = None):
+    def __init__(self, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", out: Optional[torch.Tensor] = None,
+                 optimize=False):
         if isinstance(images, torch.Tensor):
             if images.dim() != 4:
                 raise ValueError("JpegBatch: a tensor batch is [B,H,W,C]; pass differently sized images as a list")
@@ -921,6 +925,7 @@ class JpegBatch:
         subs = _enc_per_image(subsampling, B, f"subsampling ({', '.join(SUBSAMPLINGS)})", lambda v: (isinstance(v, str) or _is_int(v)) and v in ids)
         rows = _enc_per_image(restart_rows, B, "restart_rows (0 or more)", lambda v: _is_int(v) and 0 <= v < 1 << 16)
         orders = _enc_per_image(order, B, "order ('rgb' / 'bgr')", lambda v: v in _ORDERS)
+        self.optimize = [bool(v) for v in _enc_per_image(optimize, B, "optimize (True / False)", lambda v: isinstance(v, (bool, np.bool_)))]
         geo = [_enc_geometry(t) for t in images]
         dev = _lib.require_gpu(*images)
         self.images, self.B, self._dev = images, B, dev
@@ -933,7 +938,9 @@ class JpegBatch:
         rec["subsampling"] = [int(ids[s]) for s in subs]
         rec["restart_rows"] = [int(r) for r in rows]
         rp = ctypes.c_void_p(rec.ctypes.data)
-        self.table_host, self.header = planned_table(("attwarp_jpegenc_table_bytes", rp, B), ("attwarp_jpegenc_plan", rp, B, TABLE),
+        flags = np.asarray(self.optimize, np.int32)
+        fp = ctypes.c_void_p(flags.ctypes.data) if flags.any() else None        # NULL: the plain planner's table
+        self.table_host, self.header = planned_table(("attwarp_jpegenc_table_bytes_ex", rp, B, fp), ("attwarp_jpegenc_plan_ex", rp, B, fp, TABLE),
                                                      _lib.JpegEncHeader, ValueError, "JpegBatch: ")
         self._pixels = sum(g[0] * g[1] * g[2] for g in geo)
         with torch.cuda.device(dev):
@@ -948,7 +955,7 @@ class JpegBatch:
 
     @property
     def bound(self) -> int:
-        """Bytes the files of this batch take at most (``attwarp_jpegenc_bound`` summed): the capacity ``out`` needs."""
+        """Bytes the files of this batch take at most (``attwarp_jpegenc_bound_ex`` summed): the capacity ``out`` needs."""
         return int(self.header.out_bytes)
 
     @property
@@ -960,28 +967,29 @@ class JpegBatch:
         return self._pixels
 
     def run(self):
-        """Seven launches on the current stream -> ``(buffer, offsets)``: file b is ``buffer[offsets[b]:offsets[b+1]]``
-        (uint8 and int64 [B+1], both on the device).  No host-dependent argument: capturable in a graph."""
+        """Seven launches on the current stream (ten with an optimised image) -> ``(buffer, offsets)``: file b is
+        ``buffer[offsets[b]:offsets[b+1]]`` (uint8 and int64 [B+1], both on the device).  No host-dependent argument:
+        capturable in a graph."""
         with torch.cuda.device(self._dev):
             call("attwarp_jpegenc_encode", self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.scratch), ptr(self.buffer),
                  self.buffer.numel(), ptr(self.offsets), stream_ptr(self._dev))
         return self.buffer, self.offsets
 
 
-def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb") -> List[bytes]:
+def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False) -> List[bytes]:
     """uint8 GPU images (list of [H,W,3] / [H,W] of any sizes, or [B,H,W,C]) -> the bytes of one JPEG file each, what
-    ``Image.fromarray(a).save(f, "JPEG", quality=..., subsampling=..., restart_marker_rows=...)`` writes.  Raw pixels never
+    ``Image.fromarray(a).save(f, "JPEG", quality=..., subsampling=..., restart_marker_rows=..., optimize=...)`` writes.  Raw pixels never
     leave the device.  See :class:`JpegBatch` for the keywords."""
     from .png import download
-    return download(*JpegBatch(images, quality, subsampling, restart_rows, order).run())
+    return download(*JpegBatch(images, quality, subsampling, restart_rows, order, optimize=optimize).run())
 
 
-def write_jpeg(paths, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb") -> None:
+def write_jpeg(paths, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False) -> None:
     """:func:`encode_jpeg`, each file written to its path."""
     paths = list(paths)
     n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
     if len(paths) != n:
         raise ValueError(f"write_jpeg: {len(paths)} paths for {n} images")
-    for p, f in zip(paths, encode_jpeg(images, quality, subsampling, restart_rows, order)):
+    for p, f in zip(paths, encode_jpeg(images, quality, subsampling, restart_rows, order, optimize)):
         with open(p, "wb") as fh:
             fh.write(f)

@@ -1256,6 +1256,7 @@ typedef struct attwarp_jpegenc_header {            /* first bytes of a table wri
   uint64_t table_bytes, scratch_bytes, out_bytes;
   uint64_t off_images, off_units, off_huffman;     /* in the table */
   uint64_t off_image_out;                          /* in the scratch buffer: per image the file's bytes */
+  uint64_t off_optimize;                           /* in the table: 0, or the record of the optimised images (attwarp_jpegenc_plan_ex) */
 } attwarp_jpegenc_header;
 /* 0: outside the limits */
 ATTWARP_API size_t attwarp_jpegenc_bound(int H, int W, int C, int quality, int subsampling, int restart_rows);
@@ -1263,6 +1264,22 @@ ATTWARP_API size_t attwarp_jpegenc_table_bytes(const attwarp_jpegenc_image* imag
 ATTWARP_API int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, void* table, size_t table_bytes);
 ATTWARP_API int attwarp_jpegenc_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
                        int64_t* offsets, void* stream);
+
+/* Per-image optimised Huffman tables (jpegopt_blocks.hpp): optimize is NULL or one flag (0 / 1) per image.  An
+ * image with optimize[i] = 1 is written as Image.save(..., optimize=True) writes it: the same pixels, its DHT segments (in the
+ * order DC 0, AC 0, DC 1, AC 1, in front of DRI) holding the tables libjpeg's jpeg_gen_optimal_table builds from the image's
+ * own symbol counts: the two smallest non-zero frequencies merged, ties to the larger index, a reserved leaf of frequency 1,
+ * lengths limited to 16 bits, symbols listed by length and then by value.  With optimize = NULL or all zero the table is
+ * attwarp_jpegenc_plan's byte for byte and attwarp_jpegenc_encode runs its seven launches.  Otherwise the table ends with a
+ * record of the optimised images and their units, scratch grows by 4096 + 5928 bytes per optimised image, and
+ * attwarp_jpegenc_encode (unchanged: it reads what to do from the table) puts three launches behind the transform: a clear of
+ * the images' histograms, the histogram (one workgroup per unit), the tables (one workgroup per image, one wave per table,
+ * which also splices the DHTs into the header).  All are capturable.  An optimised DC table holds up to 12 categories and the
+ * reserved leaf, so a DC code may take 12 bits: attwarp_jpegenc_bound_ex(..., 1) is attwarp_jpegenc_bound plus one bit per
+ * block (the header never grows), and header.out_bytes sums attwarp_jpegenc_bound_ex.  The limits are the plain family's. */
+ATTWARP_API size_t attwarp_jpegenc_bound_ex(int H, int W, int C, int quality, int subsampling, int restart_rows, int optimize);
+ATTWARP_API size_t attwarp_jpegenc_table_bytes_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize);
+ATTWARP_API int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, void* table, size_t table_bytes);
 
 #ifdef __cplusplus
 }
