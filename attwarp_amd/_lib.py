@@ -203,6 +203,9 @@ SIGNATURES = {
     "attwarp_jpegenc_bound_ex": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "attwarp_jpegenc_table_bytes_ex": (c_size_t, [c_void_p, c_int, c_void_p]),
     "attwarp_jpegenc_plan_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
+    "attwarp_jpegenc_bound_prog": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "attwarp_jpegenc_table_bytes_prog": (c_size_t, [c_void_p, c_int, c_void_p, c_void_p]),
+    "attwarp_jpegenc_plan_prog": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]),
     # the trainer's debug / validation panels (panel.hip)
     "attwarp_panel_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),

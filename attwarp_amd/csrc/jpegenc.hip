@@ -24,10 +24,27 @@
 //   jpegopt_tables_kernel     one workgroup per optimised image, one wave per table: libjpeg's optimal table (jpegopt_blocks.hpp),
 //                             its code words and DHT segment; then the header with the DHTs spliced in.
 // tests/jpegopt_ref.py restates the tables.
+// A call with progressive images (attwarp_jpegenc_plan_prog) transforms them with the others; none of the six
+// launches above touches them further (they own no entropy unit).  Eight launches of their own write their files, all scans of
+// all images at once, per SEGMENT = (scan, restart interval) and inside it per block (jpegprogenc_blocks.hpp):
+//   jpegprogenc_clear_kernel     one workgroup per progressive image: its eleven symbol histograms to zero;
+//   jpegprogenc_summary_kernel   one workgroup per segment of an AC scan, one wave per block, one lane per coefficient: two
+//                                ballots say whether the block codes a symbol, whether it ends in the run, and how many
+//                                correction bits it leaves behind the run;
+//   jpegprogenc_resolve_kernel   one lane per segment: the walk over the summaries (no coefficient) that splits the end-of-band
+//                                runs at 0x7FFF blocks and above 937 pending bits -> the run in front of every block;
+//   jpegprogenc_count_kernel     one workgroup per segment, one lane per block: jcphuff.c's coder on the block alone, its
+//                                symbols counted in LDS, the counts added to the image's histograms;
+//   jpegprogenc_tables_kernel    one workgroup per image, its waves over the up to ten tables (jo_optimal_table, unchanged);
+//   jpegprogenc_code_kernel      one workgroup per segment, one lane per block: bit lengths and their prefix sums, then every
+//                                block's bits ORed to their place in the segment's zeroed words; counts the FF bytes;
+//   jpegprogenc_place_kernel     one workgroup per image: prefix sums of DHT + DRI + SOS + bytes + FF + marker, the file's length;
+//   jpegprogenc_write_kernel     one workgroup per segment: what precedes the scan, the stuffed bytes, RSTn (numbered per scan) or EOI.
+// tests/jpegprogenc_ref.py restates the files.
 #include <algorithm>
 #include <cstring>
 
-#include "jpegopt_blocks.hpp"
+#include "jpegprogenc_blocks.hpp"
 
 namespace attwarp {
 
@@ -493,6 +510,304 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_write_kernel(const uint8_t* __r
   }
 }
 
+// ---- progressive images -------------------------------------------------------------------------------------------
+__device__ __forceinline__ const PePlan* pe_plan(const uint8_t* table) {
+  return reinterpret_cast<const PePlan*>(table + (uint64_t)reinterpret_cast<const attwarp_jpegenc_header*>(table)->reserved * 16u);
+}
+__device__ __forceinline__ PeWalk pe_walk(const JeImageDev* im, const PeScan& sc, const PeScanPlan& sp, const uint8_t* scratch) {
+  PeWalk w;
+  w.coef = reinterpret_cast<const int16_t*>(scratch + im->coef_off);
+  w.bpm = im->bpm;
+  w.ny = im->C == 3 ? im->hmax * im->vmax : 1;
+  w.hmax = im->hmax; w.vmax = im->vmax; w.mcus_x = im->mcus_x;
+  w.comp = sc.comp;
+  w.wc = sp.wc;
+  return w;
+}
+constexpr int PE_LANES = 64;           // intervals per workgroup of the resolve kernel
+
+// What a workgroup of the per-interval kernels works on: its segment, the walk of the segment's scan, the per-block arrays.
+struct PeWork {
+  PeSeg sg;
+  PeScan sc;
+  PeWalk w;
+  uint64_t* pos;                       // bit position of every block in the interval's string
+  uint32_t* pre;                       // the run in front of every block: EOBRUN | correction bits << 16
+  uint8_t* summary;
+};
+__device__ __forceinline__ PeWork pe_work(const uint8_t* table, uint8_t* scratch, int sidx) {
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const PePlan* plan = pe_plan(table);
+  PeWork k;
+  k.sg = reinterpret_cast<const PeSeg*>(table + plan->off_segs)[sidx];
+  const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + k.sg.pimage;
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image;
+  k.sc = pe_scan(im->C, k.sg.scan);
+  k.w = pe_walk(im, k.sc, pi->scan[k.sg.scan], scratch);
+  k.pos = reinterpret_cast<uint64_t*>(scratch + k.sg.aux_off);
+  k.pre = reinterpret_cast<uint32_t*>(k.pos + k.sg.nblocks);
+  k.summary = reinterpret_cast<uint8_t*>(k.pre + k.sg.nblocks);
+  return k;
+}
+
+__global__ __launch_bounds__(JE_NT) void jpegprogenc_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  uint32_t* hist = reinterpret_cast<uint32_t*>(scratch + pe_plan(table)->off_hist) + (size_t)blockIdx.x * PE_SLOTS * 256;
+  for (int i = threadIdx.x; i < PE_SLOTS * 256; i += JE_NT) hist[i] = 0u;
+}
+
+// one workgroup per segment of an AC scan, one wave per block, one lane per coefficient: two ballots are the block's summary
+__global__ __launch_bounds__(JE_NT) void jpegprogenc_summary_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  const PeWork k = pe_work(table, scratch, blockIdx.x);
+  if (k.sc.ss == 0) return;
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const bool band = lane >= k.sc.ss && lane <= k.sc.se;
+  for (int i = wave; i < k.sg.nblocks; i += JE_NT / WAVE) {
+    int ci;
+    const int v = k.w.block((int64_t)k.sg.block0 + i, ci)[lane];
+    const uint32_t t = (uint32_t)(v < 0 ? -v : v) >> k.sc.al;
+    const unsigned long long nonzero = __ballot(band && t != 0u), newly = __ballot(band && k.sc.ah && t == 1u);
+    if (lane == 0) k.summary[i] = (uint8_t)pe_summary_of(newly, nonzero, k.sc);
+  }
+}
+
+// one lane per segment of an AC scan: the walk over the summaries, four blocks per load
+__global__ __launch_bounds__(PE_LANES) void jpegprogenc_resolve_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  const int sidx = blockIdx.x * PE_LANES + threadIdx.x;
+  if (sidx >= pe_plan(table)->nsegs) return;
+  const PeWork k = pe_work(table, scratch, sidx);
+  if (k.sc.ss == 0) return;
+  PeRun r = {0u, 0u};
+  for (int i = 0; i < k.sg.nblocks; ++i) {
+    k.pre[i] = r.e | r.be << 16;
+    pe_resolve_step(k.summary[i], r);
+  }
+}
+
+struct PeCountSink {                   // the statistics pass: integer counts in LDS, so a file does not depend on the order of the lanes
+  uint32_t* hist;                      // [2][256]: the scan's slot, the DC table of Cb / Cr
+  __device__ void sym(int slot, int s) { atomicAdd(&hist[(slot == PE_DC1_SLOT ? 256 : 0) + (s & 255)], 1u); }
+  __device__ void bits(uint32_t, int) {}
+};
+struct PeLengthSink {
+  const uint32_t* code;                // [2][256] in LDS
+  uint32_t n;
+  __device__ void sym(int slot, int s) { n += code[(slot == PE_DC1_SLOT ? 256 : 0) + (s & 255)] >> 16; }
+  __device__ void bits(uint32_t, int nb) { n += (uint32_t)nb; }
+};
+struct PeBitSink {                     // bits ORed into zeroed big-endian words; nothing at or behind word `nwords`
+  const uint32_t* code;
+  uint32_t* words;
+  uint64_t pos, nwords;
+  __device__ void bits(uint32_t v, int nb) {
+    if (nb == 0) return;
+    const uint64_t x = (uint64_t)v << (64u - (uint32_t)nb - (uint32_t)(pos & 31u));
+    const uint64_t wi = pos >> 5;
+    if (wi < nwords) atomicOr(&words[wi], (uint32_t)(x >> 32));
+    if ((uint32_t)x && wi + 1 < nwords) atomicOr(&words[wi + 1], (uint32_t)x);
+    pos += (uint32_t)nb;
+  }
+  __device__ void sym(int slot, int s) {
+    const uint32_t c = code[(slot == PE_DC1_SLOT ? 256 : 0) + (s & 255)];
+    bits(c & 0xffffu, (int)(c >> 16));
+  }
+};
+__device__ __forceinline__ PeRun pe_run_in_front(const PeWork& k, int i) {
+  PeRun r = {0u, 0u};
+  if (k.sc.ss) { const uint32_t p = k.pre[i]; r.e = p & 0xffffu; r.be = p >> 16; }
+  return r;
+}
+
+// one workgroup per segment, one lane per block: the block's symbols counted in LDS, the counts added to the image's histograms
+__global__ __launch_bounds__(JE_NT) void jpegprogenc_count_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_hist[2 * 256];
+  const int tid = threadIdx.x;
+  const PeWork k = pe_work(table, scratch, blockIdx.x);
+  for (int i = tid; i < 2 * 256; i += JE_NT) s_hist[i] = 0u;
+  __syncthreads();
+  PeState st;
+  PeCountSink sink = {s_hist};
+  for (int i = tid; i < k.sg.nblocks; i += JE_NT)
+    pe_code_block(k.w, k.sc, k.sg.scan, k.sg.block0, k.sg.nblocks, (int64_t)k.sg.block0 + i, k.summary, pe_run_in_front(k, i), st, sink);
+  __syncthreads();
+  uint32_t* hist = reinterpret_cast<uint32_t*>(scratch + pe_plan(table)->off_hist) + (size_t)k.sg.pimage * PE_SLOTS * 256;
+  for (int i = tid; i < 2 * 256; i += JE_NT)
+    if (s_hist[i]) atomicAdd(&hist[(i < 256 ? k.sg.scan : PE_DC1_SLOT) * 256 + (i & 255)], s_hist[i]);
+}
+
+// One workgroup per segment, one lane per block, three passes: every block's bit length and from the prefix sums its place;
+// the words of the interval's string to zero; every block's bits ORed to their place, 1-bits up to the byte's end.  Then the FF
+// bytes are counted for the stuffing, which the write kernel does.
+__global__ __launch_bounds__(JE_NT) void jpegprogenc_code_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ uint32_t s_code[2 * 256];
+  __shared__ unsigned long long s_tmp[JE_NT];
+  __shared__ uint32_t s_ff;
+  const int tid = threadIdx.x;
+  const PeWork k = pe_work(table, scratch, blockIdx.x);
+  const JoTable* tables = reinterpret_cast<const JoTable*>(scratch + pe_plan(table)->off_tables) + (size_t)k.sg.pimage * PE_SLOTS;
+  for (int i = tid; i < 2 * 256; i += JE_NT) s_code[i] = tables[i < 256 ? k.sg.scan : PE_DC1_SLOT].code[i & 255];
+  if (tid == 0) s_ff = 0;
+  __syncthreads();
+  PeState st;
+  unsigned long long carry = 0;
+  for (int base = 0; base < k.sg.nblocks; base += JE_NT) {
+    const int i = base + tid;
+    PeLengthSink ls = {s_code, 0u};
+    if (i < k.sg.nblocks)
+      pe_code_block(k.w, k.sc, k.sg.scan, k.sg.block0, k.sg.nblocks, (int64_t)k.sg.block0 + i, k.summary, pe_run_in_front(k, i), st, ls);
+    unsigned long long tot;
+    const unsigned long long at = carry + je_excl_sum((unsigned long long)ls.n, s_tmp, tot);
+    if (i < k.sg.nblocks) k.pos[i] = at;
+    carry += tot;
+  }
+  // the clamp guards the slot; the planner's bound (pe_interval_bytes) keeps the string within it
+  const uint64_t nwords = ((uint64_t)k.sg.cap + 7u) / 4u;
+  const uint64_t bits = carry < 8ull * (uint64_t)k.sg.cap ? carry : 8ull * (uint64_t)k.sg.cap;
+  const uint32_t nbytes = (uint32_t)((bits + 7u) / 8u);
+  uint32_t* words = reinterpret_cast<uint32_t*>(scratch + k.sg.slot_off);
+  for (uint64_t i = tid; i < ((uint64_t)nbytes + 3u) / 4u + 1u && i < nwords; i += JE_NT) words[i] = 0u;
+  __syncthreads();
+  for (int i = tid; i < k.sg.nblocks; i += JE_NT) {
+    PeBitSink bs = {s_code, words, k.pos[i], nwords};
+    pe_code_block(k.w, k.sc, k.sg.scan, k.sg.block0, k.sg.nblocks, (int64_t)k.sg.block0 + i, k.summary, pe_run_in_front(k, i), st, bs);
+  }
+  if (tid == 0 && (bits & 7u)) {
+    PeBitSink bs = {s_code, words, bits, nwords};
+    bs.bits((1u << (8u - (uint32_t)(bits & 7u))) - 1u, (int)(8u - (uint32_t)(bits & 7u)));
+  }
+  __syncthreads();
+  uint32_t ff = 0;
+  for (uint32_t i = tid; i < nbytes; i += JE_NT) ff += ((words[i >> 2] >> (24u - 8u * (i & 3u))) & 255u) == 255u;
+  for (int o = WAVE / 2; o > 0; o >>= 1) ff += __shfl_xor(ff, o, WAVE);
+  if ((tid & (WAVE - 1)) == 0 && ff) atomicAdd(&s_ff, ff);
+  __syncthreads();
+  if (tid == 0) {
+    PeSegOut& o = reinterpret_cast<PeSegOut*>(scratch + pe_plan(table)->off_seg_out)[blockIdx.x];
+    o.nbytes = nbytes;
+    o.nff = s_ff;
+  }
+}
+
+__global__ __launch_bounds__(JE_NT) void jpegprogenc_tables_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ JoWork s_work[JE_NT / WAVE];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const PePlan* plan = pe_plan(table);
+  const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + blockIdx.x;
+  const int ncomp = (reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image)->C;
+  const uint32_t* hist = reinterpret_cast<const uint32_t*>(scratch + plan->off_hist) + (size_t)blockIdx.x * PE_SLOTS * 256;
+  JoTable* out = reinterpret_cast<JoTable*>(scratch + plan->off_tables) + (size_t)blockIdx.x * PE_SLOTS;
+  for (int slot = wave; slot < PE_SLOTS; slot += JE_NT / WAVE)
+    if (pe_slot_used(ncomp, slot)) jo_optimal_table<WAVE>(hist + 256 * slot, pe_slot_class(ncomp, slot), lane, JoWaveMin(), s_work[wave], out[slot]);
+}
+
+// What precedes a segment's bytes in the file: nothing, or (the first of a scan) the file's header in front of the first scan,
+// the scan's DHTs, a DRI where the interval changes, the SOS.  What follows them: RSTn, nothing (a scan's end) or EOI.
+struct PePieces {
+  int header, dht[2], ndht, dri, sos, tail;
+  __device__ int before() const { return header + dht[0] + dht[1] + (dri ? 6 : 0) + sos; }
+};
+__device__ __forceinline__ PePieces pe_pieces(const PeImage* pi, int ncomp, const PeSeg& sg, const JoTable* tables) {
+  PePieces p = {0, {0, 0}, 0, 0, 0, 2};
+  const PeScanPlan& sp = pi->scan[sg.scan];
+  if (sg.index == sp.nsegs - 1 && sg.scan != pi->nscans - 1) p.tail = 0;
+  if (sg.index != 0) return p;
+  const PeScan sc = pe_scan(ncomp, sg.scan);
+  p.header = sg.scan == 0 ? pi->header_len : 0;
+  if (pe_slot_used(ncomp, sg.scan)) {
+    p.dht[p.ndht++] = min(tables[sg.scan].dht_len, PE_DHT_MAX);
+    if (sc.comp < 0) p.dht[p.ndht++] = min(tables[PE_DC1_SLOT].dht_len, PE_DHT_MAX);
+  }
+  p.dri = sp.dri;
+  p.sos = 6 + 2 * (sc.comp < 0 ? ncomp : 1) + 2;
+  return p;
+}
+
+__global__ __launch_bounds__(JE_NT) void jpegprogenc_place_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
+  __shared__ unsigned long long s_tmp[JE_NT];
+  const int tid = threadIdx.x;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const PePlan* plan = pe_plan(table);
+  const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + blockIdx.x;
+  const int ncomp = (reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image)->C;
+  const PeSeg* segs = reinterpret_cast<const PeSeg*>(table + plan->off_segs) + pi->seg0;
+  PeSegOut* so = reinterpret_cast<PeSegOut*>(scratch + plan->off_seg_out) + pi->seg0;
+  const JoTable* tables = reinterpret_cast<const JoTable*>(scratch + plan->off_tables) + (size_t)blockIdx.x * PE_SLOTS;
+  unsigned long long carry = 0;
+  for (int base = 0; base < pi->nsegs; base += JE_NT) {
+    const int s = base + tid;
+    unsigned long long v = 0;
+    if (s < pi->nsegs) {
+      const PePieces p = pe_pieces(pi, ncomp, segs[s], tables);
+      v = (unsigned long long)p.before() + so[s].nbytes + so[s].nff + (unsigned long long)p.tail;
+    }
+    unsigned long long tot;
+    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
+    if (s < pi->nsegs) so[s].fpos = pre;
+    carry += tot;
+  }
+  if (tid == 0) reinterpret_cast<JeImageOut*>(scratch + hdr->off_image_out)[pi->image].file_bytes = carry;
+}
+
+__global__ __launch_bounds__(JE_NT) void jpegprogenc_write_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
+                                                               uint8_t* __restrict__ out, const int64_t* __restrict__ offsets) {
+  __shared__ uint32_t s_tmp[JE_NT];
+  const int tid = threadIdx.x;
+  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
+  const PePlan* plan = pe_plan(table);
+  const PeSeg sg = reinterpret_cast<const PeSeg*>(table + plan->off_segs)[blockIdx.x];
+  const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + sg.pimage;
+  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image;
+  const PeSegOut o = reinterpret_cast<const PeSegOut*>(scratch + plan->off_seg_out)[blockIdx.x];
+  const JoTable* tables = reinterpret_cast<const JoTable*>(scratch + plan->off_tables) + (size_t)sg.pimage * PE_SLOTS;
+  const PePieces p = pe_pieces(pi, im->C, sg, tables);
+  JE_G uint8_t* dst = (JE_G uint8_t*)out + offsets[pi->image] + o.fpos;
+  if (sg.index == 0) {
+    for (int i = tid; i < p.header; i += JE_NT) dst[i] = im->header[i];
+    dst += p.header;
+    for (int t = 0; t < p.ndht; ++t) {
+      const uint8_t* dht = tables[t ? PE_DC1_SLOT : sg.scan].dht;
+      for (int i = tid; i < p.dht[t]; i += JE_NT) dst[i] = dht[i];
+      dst += p.dht[t];
+    }
+    if (tid == 0) {
+      const PeScan sc = pe_scan(im->C, sg.scan);
+      int n = 0;
+      if (p.dri) {
+        const uint8_t dri[6] = {0xff, 0xdd, 0x00, 0x04, (uint8_t)(p.dri >> 8), (uint8_t)(p.dri & 255)};
+        for (int i = 0; i < 6; ++i) dst[n++] = dri[i];
+      }
+      const int nc = sc.comp < 0 ? im->C : 1;
+      dst[n++] = 0xff; dst[n++] = 0xda; dst[n++] = 0x00; dst[n++] = (uint8_t)(6 + 2 * nc); dst[n++] = (uint8_t)nc;
+      for (int c = 0; c < nc; ++c) {
+        const int ci = sc.comp < 0 ? c : sc.comp;
+        const int id = ci ? 1 : 0;                          // the table a component names: DC in a DC first pass, AC in an AC scan
+        dst[n++] = (uint8_t)(ci + 1);
+        dst[n++] = (uint8_t)(sc.ss ? id : (sc.ah ? 0 : id << 4));
+      }
+      dst[n++] = (uint8_t)sc.ss; dst[n++] = (uint8_t)sc.se; dst[n++] = (uint8_t)(sc.ah << 4 | sc.al);
+    }
+    dst += (p.dri ? 6 : 0) + p.sos;
+  }
+  // the interval's bytes out of its big-endian words, a zero behind every FF (the stuffing of launch 7)
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(scratch + sg.slot_off);
+  auto byte_at = [&](uint32_t i) { return (words[i >> 2] >> (24u - 8u * (i & 3u))) & 255u; };
+  const uint32_t n = o.nbytes, per = (n + JE_NT - 1) / JE_NT;
+  const uint32_t lo = min(n, (uint32_t)tid * per), hi = min(n, lo + per);
+  uint32_t ff = 0;
+  for (uint32_t i = lo; i < hi; ++i) ff += byte_at(i) == 255u;
+  uint32_t tot;
+  uint32_t at = lo + je_excl_sum(ff, s_tmp, tot);
+  for (uint32_t i = lo; i < hi; ++i) {
+    const uint32_t b = byte_at(i);
+    dst[at++] = (uint8_t)b;
+    if (b == 255u) dst[at++] = 0;
+  }
+  if (tid == 0 && p.tail) {
+    dst[n + o.nff] = 0xff;
+    dst[n + o.nff + 1] = sg.index == pi->scan[sg.scan].nsegs - 1 ? 0xd9 : (uint8_t)(0xd0 + (sg.index & 7));
+  }
+}
+
 // ---- host: limits, header, bound, plan -----------------------------------------------------------------------------------------------------
 static uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
@@ -529,6 +844,61 @@ static int je_header_len(int C, int restart_rows) { return 2 + 18 + (C == 3 ? 2 
 static uint64_t je_bound64(int C, int quality, int restart_rows, const JeGeometry& g, bool optimize = false) {
   const uint64_t bits = (uint64_t)g.nmcu * g.bpm * (uint64_t)(je_block_bound_bits(quality, C) + (optimize ? JO_EXTRA_BLOCK_BITS : 0));
   return (uint64_t)je_header_len(C, restart_rows) + 2u * ((bits + 7u) / 8u + (uint64_t)g.nint) + 2u * (uint64_t)g.nint + 2u;
+}
+
+// The scans of a progressive image: blocks, blocks per restart interval, intervals, blocks per row of a one-component walk.
+struct PeScanGeometry {
+  int64_t nblk, step;
+  int nseg, block_bits, ndht, ncomp, wc, interval;          // interval: the DRI value, in MCUs of the scan (0: none)
+};
+struct PeGeometry {
+  int nscans;
+  int64_t nsegs;
+  PeScanGeometry scan[PE_MAX_SCANS];
+};
+// false: a scan's restart interval is above 65535 MCUs (libjpeg would clamp it there, silently, and cut the rows elsewhere)
+static bool pe_geometry(int H, int W, int C, int restart_rows, const JeGeometry& g, PeGeometry& p) {
+  p.nscans = pe_nscans(C);
+  p.nsegs = 0;
+  for (int i = 0; i < p.nscans; ++i) {
+    const PeScan sc = pe_scan(C, i);
+    PeScanGeometry& q = p.scan[i];
+    int64_t per_row, per_mcu = 1;
+    if (sc.comp < 0) {
+      per_row = g.mcus_x;
+      per_mcu = g.bpm;
+      q.nblk = g.nmcu * g.bpm;
+      q.wc = 0;
+    } else {
+      const int fh = sc.comp > 0 ? g.hmax : 1, fv = sc.comp > 0 ? g.vmax : 1;
+      q.wc = ((W + fh - 1) / fh + 7) / 8;
+      per_row = q.wc;
+      q.nblk = (int64_t)q.wc * (((H + fv - 1) / fv + 7) / 8);
+    }
+    const int64_t interval = (int64_t)restart_rows * per_row;
+    if (interval > 65535) return false;
+    q.interval = (int)interval;
+    q.step = restart_rows ? interval * per_mcu : q.nblk;
+    q.nseg = (int)((q.nblk + q.step - 1) / q.step);
+    q.block_bits = pe_block_bits(sc);
+    q.ndht = (sc.ss == 0 && sc.ah) ? 0 : (sc.comp < 0 ? 2 : 1);
+    q.ncomp = sc.comp < 0 ? C : 1;
+    p.nsegs += q.nseg;
+  }
+  return true;
+}
+static int pe_frame_header_len(int C) { return 2 + 18 + (C == 3 ? 2 : 1) * 69 + (10 + 3 * C); }
+// SOI .. SOF2; per scan its DHTs at their longest, a DRI, the SOS, every interval at its bound and a marker behind it; EOI
+static uint64_t pe_bound64(int C, const PeGeometry& p) {
+  uint64_t n = (uint64_t)pe_frame_header_len(C) + 2u;
+  for (int i = 0; i < p.nscans; ++i) {
+    const PeScanGeometry& q = p.scan[i];
+    n += (uint64_t)PE_DHT_MAX * q.ndht + 6u + 6u + 2u * q.ncomp;
+    const uint64_t full = (uint64_t)(q.nblk / q.step), rest = (uint64_t)(q.nblk % q.step);
+    n += full * (pe_interval_bytes((uint64_t)q.step, q.block_bits) + 2u);
+    if (rest) n += pe_interval_bytes(rest, q.block_bits) + 2u;
+  }
+  return n;
 }
 
 // pre_len: the file's DHTs are left out (the device splices the image's own in) and *pre_len receives where they belong
@@ -578,7 +948,14 @@ extern "C" size_t attwarp_jpegenc_bound_ex(int H, int W, int C, int quality, int
 }
 
 // nopt / nopt_units: the optimised images of the call (optimize: NULL, or one flag per image) and their units
-static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, int64_t& nunits, int& nopt, int64_t& nopt_units) {
+// progressive (NULL, or one flag per image): such an image owns no entropy unit; its transform units (nprog_units) and its
+// segments (nsegs) are counted apart, and optimize is ignored for it (a progressive file always has tables of its own)
+struct PeCounts {
+  int nprog = 0;
+  int64_t nprog_units = 0, nsegs = 0;
+};
+static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, int64_t& nunits, int& nopt, int64_t& nopt_units,
+                         const int32_t* progressive = nullptr, PeCounts* pc = nullptr) {
   ATTWARP_REQUIRE(images, "jpegenc: null image array");
   ATTWARP_REQUIRE(B > 0, "jpegenc: non-positive batch size");
   if (B > (1 << 20)) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: B=%d > 2^20", B);
@@ -586,7 +963,9 @@ static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32
   nopt = 0;
   for (int b = 0; b < B; ++b) {
     const attwarp_jpegenc_image& d = images[b];
-    const bool opt = optimize && optimize[b];
+    const bool prog = progressive && progressive[b];
+    const bool opt = optimize && optimize[b] && !prog;
+    ATTWARP_REQUIRE(!progressive || progressive[b] == 0 || progressive[b] == 1, "jpegenc: image %d: progressive must be 0 or 1", b);
     ATTWARP_REQUIRE(!optimize || optimize[b] == 0 || optimize[b] == 1, "jpegenc: image %d: optimize must be 0 or 1", b);
     ATTWARP_REQUIRE(d.src, "jpegenc: image %d: null pointer", b);
     ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegenc: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
@@ -596,6 +975,19 @@ static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32
       return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d (%d x %d x %d, quality %d, subsampling %d, restart_rows %d): %s", b, d.H, d.W, d.C,
                   d.quality, d.subsampling, d.restart_rows, what);
     ATTWARP_REQUIRE((int64_t)d.pitch >= (int64_t)d.W * d.C, "jpegenc: image %d: pitch %d below the row's %lld bytes", b, d.pitch, (long long)d.W * d.C);
+    if (prog) {
+      PeGeometry p;
+      if (!pe_geometry(d.H, d.W, d.C, d.restart_rows, g, p))
+        return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d (%d x %d x %d, restart_rows %d): a progressive scan's restart interval above 65535 "
+                    "(libjpeg clamps it to 65535 and no longer restarts at the rows)", b, d.H, d.W, d.C, d.restart_rows);
+      if (pe_bound64(d.C, p) >= ((uint64_t)1 << 31))
+        return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: the progressive bound of %d x %d x %d is 2 GiB or more", b, d.H, d.W, d.C);
+      // (fewer than 2^23 blocks, as below: a table's frequencies stay far below libjpeg's sentinel)
+      pc->nprog += 1;
+      pc->nprog_units += g.nunits;
+      pc->nsegs += p.nsegs;
+      continue;
+    }
     if (je_bound64(d.C, d.quality, d.restart_rows, g, opt) >= ((uint64_t)1 << 31))
       return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: the bound of %d x %d x %d is 2 GiB or more", b, d.H, d.W, d.C);
     // A table's frequencies add up to at most 64 symbols per block.  A block's bound is above 1024 bits (22 + 63 x 17) and the
@@ -606,43 +998,64 @@ static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32
     nunits += g.nunits;
     if (opt) { ++nopt; nopt_units += g.nunits; }
   }
-  if (nunits > JE_MAX_UNITS) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld units in one call (> %d)", (long long)nunits, JE_MAX_UNITS);
+  if (nunits + (pc ? pc->nprog_units : 0) > JE_MAX_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld units in one call (> %d)", (long long)(nunits + (pc ? pc->nprog_units : 0)), JE_MAX_UNITS);
+  if (pc && pc->nsegs > JE_MAX_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld progressive segments (scans x restart intervals) in one call (> %d)", (long long)pc->nsegs, JE_MAX_UNITS);
   return ATTWARP_OK;
 }
 
 // Without an optimised image the table ends behind the units, as it always did; with one, the JoPlan follows them.
 static uint64_t jpegenc_table_layout(int B, int64_t nunits, int nopt, int64_t nopt_units, uint64_t& off_images, uint64_t& off_units,
-                                     uint64_t& off_huffman, uint64_t& off_optimize) {
+                                     uint64_t& off_huffman, uint64_t& off_optimize, const PeCounts& pc = PeCounts(),
+                                     uint64_t* off_progressive = nullptr) {
   static_assert(sizeof(attwarp_jpegenc_header) == 80, "the header ends where the Annex K code words start");
   off_huffman = align_up(sizeof(attwarp_jpegenc_header), 16);
   off_images = off_huffman + 4 * 256 * sizeof(uint32_t);
   off_units = off_images + align_up((uint64_t)B * sizeof(JeImageDev), 16);
-  const uint64_t end = off_units + (uint64_t)nunits * sizeof(JeUnit);
+  uint64_t end = off_units + (uint64_t)(nunits + pc.nprog_units) * sizeof(JeUnit);   // the progressive images' transform units last
   off_optimize = nopt ? end : 0;
-  return nopt ? end + sizeof(JoPlan) + (uint64_t)nopt * sizeof(JoImage) + (uint64_t)nopt_units * sizeof(int32_t) : end;
+  if (nopt) end += sizeof(JoPlan) + (uint64_t)nopt * sizeof(JoImage) + (uint64_t)nopt_units * sizeof(int32_t);
+  if (pc.nprog) {                                            // the PePlan, its images and segments follow, 16-byte aligned
+    end = align_up(end, 16);
+    *off_progressive = end;
+    end += align_up(sizeof(PePlan), 16) + (uint64_t)pc.nprog * sizeof(PeImage) + (uint64_t)pc.nsegs * sizeof(PeSeg);
+  }
+  return end;
+}
+
+extern "C" size_t attwarp_jpegenc_table_bytes_prog(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, const int32_t* progressive) {
+  int64_t nunits, nopt_units;
+  int nopt;
+  PeCounts pc;
+  if (jpegenc_count(images, B, optimize, nunits, nopt, nopt_units, progressive, &pc) != ATTWARP_OK) return 0;
+  uint64_t a, b, c, d, e;
+  return (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, a, b, c, d, pc, &e);
 }
 
 extern "C" size_t attwarp_jpegenc_table_bytes_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize) {
-  int64_t nunits, nopt_units;
-  int nopt;
-  if (jpegenc_count(images, B, optimize, nunits, nopt, nopt_units) != ATTWARP_OK) return 0;
-  uint64_t a, b, c, d;
-  return (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, a, b, c, d);
+  return attwarp_jpegenc_table_bytes_prog(images, B, optimize, nullptr);
 }
 
 extern "C" size_t attwarp_jpegenc_table_bytes(const attwarp_jpegenc_image* images, int B) {
   return attwarp_jpegenc_table_bytes_ex(images, B, nullptr);
 }
 
-extern "C" int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, void* table, size_t table_bytes) {
+extern "C" int attwarp_jpegenc_plan_prog(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, const int32_t* progressive,
+                                         void* table, size_t table_bytes) {
   int64_t nunits, nopt_units;
   int nopt;
-  if (const int rc = jpegenc_count(images, B, optimize, nunits, nopt, nopt_units)) return rc;
+  PeCounts pc;
+  if (const int rc = jpegenc_count(images, B, optimize, nunits, nopt, nopt_units, progressive, &pc)) return rc;
   ATTWARP_REQUIRE(table, "jpegenc_plan: null table");
   attwarp_jpegenc_header h;
   std::memset(&h, 0, sizeof h);
-  const size_t need = (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, h.off_images, h.off_units, h.off_huffman, h.off_optimize);
+  uint64_t off_progressive = 0;
+  const size_t need = (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, h.off_images, h.off_units, h.off_huffman, h.off_optimize, pc,
+                                                   &off_progressive);
   ATTWARP_REQUIRE(table_bytes >= need, "jpegenc_plan: table of %zu bytes, %zu needed", table_bytes, need);
+  if (off_progressive / 16 > 0x7fffffffull) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: a table of %zu bytes", need);
+  h.reserved = (int32_t)(off_progressive / 16);
   uint8_t* t = static_cast<uint8_t*>(table);
   std::memset(t, 0, need);
   h.magic = JE_MAGIC;
@@ -664,13 +1077,80 @@ extern "C" int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int 
   int32_t* ounit = nopt ? reinterpret_cast<int32_t*>(oimg + nopt) : nullptr;
   int k_opt = 0;
   int64_t k_unit = 0;
+  PePlan* pplan = pc.nprog ? reinterpret_cast<PePlan*>(t + off_progressive) : nullptr;
+  PeImage* pimg = pc.nprog ? reinterpret_cast<PeImage*>(t + off_progressive + align_up(sizeof(PePlan), 16)) : nullptr;
+  PeSeg* pseg = pc.nprog ? reinterpret_cast<PeSeg*>(pimg + pc.nprog) : nullptr;
+  int k_prog = 0;
+  int32_t k_seg = 0, k_tunit = (int32_t)nunits;              // a progressive image's transform units: behind every other unit
   for (int b = 0; b < B; ++b) {
     const attwarp_jpegenc_image& d = images[b];
-    const bool opt = optimize && optimize[b];
+    const bool prog = progressive && progressive[b];
+    const bool opt = optimize && optimize[b] && !prog;
     JeGeometry g;
     const char* what;
     je_geometry(d.H, d.W, d.C, d.quality, d.subsampling, d.restart_rows, g, what);
     JeImageDev& r = im[b];
+    if (prog) {
+      // Its record serves the transform kernel and the jpegprogenc_* kernels; with no unit of its own the scans of launches 3 and
+      // 5 pass over it, and jpegprogenc_place_kernel sets its file's length behind them.
+      PeGeometry p;
+      pe_geometry(d.H, d.W, d.C, d.restart_rows, g, p);
+      r.src = d.src; r.H = d.H; r.W = d.W; r.C = d.C; r.pitch = d.pitch;
+      r.swap = d.C == 3 && d.order == ATTWARP_BGR;
+      r.hmax = g.hmax; r.vmax = g.vmax; r.bpm = g.bpm;
+      r.mcus_x = g.mcus_x; r.nmcu = (int32_t)g.nmcu;
+      r.interval = (int32_t)g.nmcu; r.nint = 1; r.upi = 1;
+      r.unit0 = s; r.nunits = 0;
+      for (int tb = 0; tb < 2; ++tb)
+        for (int k = 0; k < 64; ++k) {
+          r.divisor[tb][k] = (uint16_t)(je_quant_value(d.quality, tb, k) << 3);
+          r.recip[tb][k] = je_recip(r.divisor[tb][k]);
+        }
+      int pre = 0;
+      je_write_header(r.header, d, g, &pre);                  // SOI .. SOF0: the frame becomes SOF2
+      r.header[pre - (10 + 3 * d.C) + 1] = 0xc2;
+      r.header_len = pre;
+      r.coef_off = soff;
+      soff += align_up((uint64_t)g.nmcu * g.bpm * 128, 256);
+      for (int64_t m = 0; m < g.nmcu; m += JE_UNIT_MCUS) {
+        JeUnit& q = un[k_tunit++];
+        q.image = b;
+        q.mcu0 = (int32_t)m;
+        q.nmcu = (int32_t)std::min<int64_t>(JE_UNIT_MCUS, g.nmcu - m);
+      }
+      PeImage& pi = pimg[k_prog];
+      pi.image = b;
+      pi.nscans = p.nscans;
+      pi.seg0 = k_seg;
+      pi.nsegs = (int32_t)p.nsegs;
+      pi.header_len = pre;
+      int last_dri = 0;
+      for (int i = 0; i < p.nscans; ++i) {
+        const PeScanGeometry& q = p.scan[i];
+        PeScanPlan& sp = pi.scan[i];
+        sp.seg0 = k_seg - pi.seg0;
+        sp.nsegs = q.nseg;
+        sp.wc = q.wc;
+        sp.dri = q.interval != last_dri ? q.interval : 0;    // libjpeg writes a DRI when the interval differs from the last one written
+        last_dri = q.interval;
+        for (int k = 0; k < q.nseg; ++k, ++k_seg) {
+          PeSeg& sg = pseg[k_seg];
+          sg.pimage = k_prog;
+          sg.scan = i;
+          sg.block0 = (int32_t)(k * q.step);
+          sg.nblocks = (int32_t)std::min<int64_t>(q.step, q.nblk - k * q.step);
+          sg.index = k;
+          sg.cap = (int32_t)(pe_interval_bytes((uint64_t)sg.nblocks, q.block_bits) / 2u);   // (the file's bound counts every byte twice)
+          sg.slot_off = soff;
+          soff += align_up((uint64_t)sg.cap + 8, 16);
+          sg.aux_off = soff;
+          soff += pe_aux_bytes((uint64_t)sg.nblocks);
+        }
+      }
+      ++k_prog;
+      out_bytes += pe_bound64(d.C, p);
+      continue;
+    }
     r.src = d.src; r.H = d.H; r.W = d.W; r.C = d.C; r.pitch = d.pitch;
     r.swap = d.C == 3 && d.order == ATTWARP_BGR;
     r.hmax = g.hmax; r.vmax = g.vmax; r.bpm = g.bpm;
@@ -722,10 +1202,35 @@ extern "C" int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int 
     plan->off_out = plan->off_hist + (uint64_t)nopt * 4 * 256 * sizeof(uint32_t);
     soff = plan->off_out + (uint64_t)nopt * sizeof(JoImageOut);
   }
+  if (pc.nprog) {
+    pplan->nimages = pc.nprog;
+    pplan->nsegs = (int32_t)pc.nsegs;
+    pplan->ntunits = (int32_t)pc.nprog_units;
+    pplan->off_images = off_progressive + align_up(sizeof(PePlan), 16);
+    pplan->off_segs = pplan->off_images + (uint64_t)pc.nprog * sizeof(PeImage);
+    pplan->off_hist = align_up(soff, 256);
+    pplan->off_tables = pplan->off_hist + (uint64_t)pc.nprog * PE_SLOTS * 256 * sizeof(uint32_t);
+    pplan->off_seg_out = pplan->off_tables + (uint64_t)pc.nprog * PE_SLOTS * sizeof(JoTable);
+    soff = pplan->off_seg_out + (uint64_t)pc.nsegs * sizeof(PeSegOut);
+  }
   h.scratch_bytes = soff;
   h.out_bytes = out_bytes;
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
+}
+
+extern "C" int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, void* table, size_t table_bytes) {
+  return attwarp_jpegenc_plan_prog(images, B, optimize, nullptr, table, table_bytes);
+}
+
+extern "C" size_t attwarp_jpegenc_bound_prog(int H, int W, int C, int quality, int subsampling, int restart_rows, int optimize, int progressive) {
+  if (!progressive) return attwarp_jpegenc_bound_ex(H, W, C, quality, subsampling, restart_rows, optimize);
+  JeGeometry g;
+  PeGeometry p;
+  const char* what;
+  if (!je_geometry(H, W, C, quality, subsampling, restart_rows, g, what) || !pe_geometry(H, W, C, restart_rows, g, p)) return 0;
+  const uint64_t b = pe_bound64(C, p);
+  return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
 }
 
 extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, void* table, size_t table_bytes) {
@@ -737,7 +1242,17 @@ extern "C" int attwarp_jpegenc_encode(const void* table_host, const void* table_
   ATTWARP_REQUIRE(table_host && table_dev && scratch && out && offsets, "jpegenc_encode: null pointer");
   attwarp_jpegenc_header h;
   std::memcpy(&h, table_host, sizeof h);
-  ATTWARP_REQUIRE(h.magic == JE_MAGIC && h.B > 0 && h.nunits >= h.B && h.nunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan");
+  // (attwarp_jpegenc_plan_prog: reserved is where the record of the progressive images lies, in 16-byte steps)
+  PePlan pp;
+  std::memset(&pp, 0, sizeof pp);
+  if (h.magic == JE_MAGIC && h.reserved) {
+    const uint64_t at = (uint64_t)(uint32_t)h.reserved * 16u;
+    ATTWARP_REQUIRE(h.reserved > 0 && at + sizeof(PePlan) <= h.table_bytes, "jpegenc_encode: not a table of attwarp_jpegenc_plan_prog");
+    std::memcpy(&pp, static_cast<const uint8_t*>(table_host) + at, sizeof pp);
+    ATTWARP_REQUIRE(pp.nimages > 0 && pp.nimages <= h.B && pp.ntunits >= pp.nimages && pp.nsegs >= pp.nimages && pp.nsegs <= JE_MAX_UNITS &&
+                        pp.ntunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan_prog");
+  }
+  ATTWARP_REQUIRE(h.magic == JE_MAGIC && h.B > 0 && h.nunits >= h.B - pp.nimages && h.nunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan");
   ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegenc_encode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
   ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
                       reinterpret_cast<uintptr_t>(offsets) % 8 == 0,
@@ -745,7 +1260,7 @@ extern "C" int attwarp_jpegenc_encode(const void* table_host, const void* table_
   hipStream_t st = as_stream(stream);
   const uint8_t* td = static_cast<const uint8_t*>(table_dev);
   uint8_t* sc = static_cast<uint8_t*>(scratch);
-  hipLaunchKernelGGL(jpegenc_transform_kernel, dim3(h.nunits), dim3(JE_TNT), 0, st, td, sc);
+  hipLaunchKernelGGL(jpegenc_transform_kernel, dim3(h.nunits + pp.ntunits), dim3(JE_TNT), 0, st, td, sc);
   if (const int rc = check_launch("jpegenc_transform_kernel")) return rc;
   if (h.off_optimize) {                                      // (attwarp_jpegenc_plan_ex: some image takes tables of its own)
     ATTWARP_REQUIRE(h.off_optimize % 8 == 0 && h.off_optimize + sizeof(JoPlan) <= h.table_bytes, "jpegenc_encode: not a table of attwarp_jpegenc_plan_ex");
@@ -762,17 +1277,49 @@ extern "C" int attwarp_jpegenc_encode(const void* table_host, const void* table_
     hipLaunchKernelGGL(jpegopt_tables_kernel, dim3(plan.nimages), dim3(JE_NT), 0, st, td, sc);
     if (const int rc = check_launch("jpegopt_tables_kernel")) return rc;
   }
-  hipLaunchKernelGGL(jpegenc_entropy_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegenc_entropy_kernel")) return rc;
+  if (pp.nimages) {                                          // progressive images: statistics, tables, bytes
+    const int groups = (pp.nsegs + PE_LANES - 1) / PE_LANES;
+    hipLaunchKernelGGL(jpegprogenc_clear_kernel, dim3(pp.nimages), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegprogenc_clear_kernel")) return rc;
+    hipLaunchKernelGGL(jpegprogenc_summary_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegprogenc_summary_kernel")) return rc;
+    hipLaunchKernelGGL(jpegprogenc_resolve_kernel, dim3(groups), dim3(PE_LANES), 0, st, td, sc);
+    if (const int rc = check_launch("jpegprogenc_resolve_kernel")) return rc;
+    hipLaunchKernelGGL(jpegprogenc_count_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegprogenc_count_kernel")) return rc;
+    hipLaunchKernelGGL(jpegprogenc_tables_kernel, dim3(pp.nimages), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegprogenc_tables_kernel")) return rc;
+    hipLaunchKernelGGL(jpegprogenc_code_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegprogenc_code_kernel")) return rc;
+  }
+  const bool plain = h.nunits > 0;                           // (false: every image of the call is progressive)
+  if (plain) {
+    hipLaunchKernelGGL(jpegenc_entropy_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegenc_entropy_kernel")) return rc;
+  }
   hipLaunchKernelGGL(jpegenc_scan_bits_kernel, dim3(h.B), dim3(JE_NT), 0, st, td, sc);
   if (const int rc = check_launch("jpegenc_scan_bits_kernel")) return rc;
-  hipLaunchKernelGGL(jpegenc_gather_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegenc_gather_kernel")) return rc;
+  if (plain) {
+    hipLaunchKernelGGL(jpegenc_gather_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegenc_gather_kernel")) return rc;
+  }
   hipLaunchKernelGGL(jpegenc_scan_bytes_kernel, dim3(h.B), dim3(JE_NT), 0, st, td, sc);
   if (const int rc = check_launch("jpegenc_scan_bytes_kernel")) return rc;
+  if (pp.nimages) {                                          // behind the scan above, which leaves no length for an image without units
+    hipLaunchKernelGGL(jpegprogenc_place_kernel, dim3(pp.nimages), dim3(JE_NT), 0, st, td, sc);
+    if (const int rc = check_launch("jpegprogenc_place_kernel")) return rc;
+  }
   hipLaunchKernelGGL(jpegenc_scan_files_kernel, dim3(1), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), offsets);
   if (const int rc = check_launch("jpegenc_scan_files_kernel")) return rc;
-  hipLaunchKernelGGL(jpegenc_write_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), out,
-                     static_cast<const int64_t*>(offsets));
-  return check_launch("jpegenc_write_kernel");
+  if (plain) {
+    hipLaunchKernelGGL(jpegenc_write_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), out,
+                       static_cast<const int64_t*>(offsets));
+    if (const int rc = check_launch("jpegenc_write_kernel")) return rc;
+  }
+  if (pp.nimages) {
+    hipLaunchKernelGGL(jpegprogenc_write_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), out,
+                       static_cast<const int64_t*>(offsets));
+    if (const int rc = check_launch("jpegprogenc_write_kernel")) return rc;
+  }
+  return ATTWARP_OK;
 }

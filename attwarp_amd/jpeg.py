@@ -903,7 +903,12 @@ class JpegBatch:
     tables, built on the GPU from its symbol counts the way libjpeg builds them, so that the file is byte for byte that of
     ``Image.save(..., optimize=True)``: the same pixels in fewer bytes, for three more launches.  Images
     with and without it share a batch; without it in any image the call is what it was before the keyword existed.
-    Progressive output, CMYK, EXIF / ICC / dpi and custom tables do not exist here.  Limits raise ValueError before any launch.
+    ``progressive`` (one value or one per image, default False): the file of ``Image.save(..., progressive=True)``, byte for
+    byte: SOF2, libjpeg's ten scans (six for grey), each behind the DHT of its own optimal table; it implies optimised
+    tables whatever ``optimize`` says, as libjpeg does, and with ``restart_rows`` every scan restarts at its own rows, which
+    is the kind of progressive file :func:`decode_jpeg` reads fast.  Plain, optimised and progressive
+    images share a batch; with the keyword absent or all False the call is what it was before the keyword existed.
+    CMYK, EXIF / ICC / dpi, custom tables and custom scan scripts do not exist here.  Limits raise ValueError before any launch.
 
     A grey image ignores ``subsampling`` and is always the file of a bare ``Image.save`` of an "L" image, factors 1 x 1.
     Pillow, GIVEN the keyword for an "L" image, writes its factors into the component's SOF0 entry (one byte: 0x21 or 0x22
@@ -911,7 +916,7 @@ class JpegBatch:
     byte from ``Image.save(..., subsampling=s)`` unless s is "4:4:4"."""
 
     def __init__(self, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", out: Optional[torch.Tensor] = None,
-                 optimize=False):
+                 optimize=False, progressive=False):
         if isinstance(images, torch.Tensor):
             if images.dim() != 4:
                 raise ValueError("JpegBatch: a tensor batch is [B,H,W,C]; pass differently sized images as a list")
@@ -926,6 +931,7 @@ class JpegBatch:
         rows = _enc_per_image(restart_rows, B, "restart_rows (0 or more)", lambda v: _is_int(v) and 0 <= v < 1 << 16)
         orders = _enc_per_image(order, B, "order ('rgb' / 'bgr')", lambda v: v in _ORDERS)
         self.optimize = [bool(v) for v in _enc_per_image(optimize, B, "optimize (True / False)", lambda v: isinstance(v, (bool, np.bool_)))]
+        self.progressive = [bool(v) for v in _enc_per_image(progressive, B, "progressive (True / False)", lambda v: isinstance(v, (bool, np.bool_)))]
         geo = [_enc_geometry(t) for t in images]
         dev = _lib.require_gpu(*images)
         self.images, self.B, self._dev = images, B, dev
@@ -940,8 +946,13 @@ class JpegBatch:
         rp = ctypes.c_void_p(rec.ctypes.data)
         flags = np.asarray(self.optimize, np.int32)
         fp = ctypes.c_void_p(flags.ctypes.data) if flags.any() else None        # NULL: the plain planner's table
-        self.table_host, self.header = planned_table(("attwarp_jpegenc_table_bytes_ex", rp, B, fp), ("attwarp_jpegenc_plan_ex", rp, B, fp, TABLE),
-                                                     _lib.JpegEncHeader, ValueError, "JpegBatch: ")
+        pflags = np.asarray(self.progressive, np.int32)
+        if pflags.any():                                                        # (none: the optimised planner's table, as before)
+            pp = ctypes.c_void_p(pflags.ctypes.data)
+            planners = ("attwarp_jpegenc_table_bytes_prog", rp, B, fp, pp), ("attwarp_jpegenc_plan_prog", rp, B, fp, pp, TABLE)
+        else:
+            planners = ("attwarp_jpegenc_table_bytes_ex", rp, B, fp), ("attwarp_jpegenc_plan_ex", rp, B, fp, TABLE)
+        self.table_host, self.header = planned_table(*planners, _lib.JpegEncHeader, ValueError, "JpegBatch: ")
         self._pixels = sum(g[0] * g[1] * g[2] for g in geo)
         with torch.cuda.device(dev):
             self.table_dev = uploaded(self.table_host, dev)
@@ -955,7 +966,7 @@ class JpegBatch:
 
     @property
     def bound(self) -> int:
-        """Bytes the files of this batch take at most (``attwarp_jpegenc_bound_ex`` summed): the capacity ``out`` needs."""
+        """Bytes the files of this batch take at most (``attwarp_jpegenc_bound_prog`` summed): the capacity ``out`` needs."""
         return int(self.header.out_bytes)
 
     @property
@@ -967,7 +978,7 @@ class JpegBatch:
         return self._pixels
 
     def run(self):
-        """Seven launches on the current stream (ten with an optimised image) -> ``(buffer, offsets)``: file b is
+        """Seven launches on the current stream (ten with an optimised image, six more with a progressive one) -> ``(buffer, offsets)``: file b is
         ``buffer[offsets[b]:offsets[b+1]]`` (uint8 and int64 [B+1], both on the device).  No host-dependent argument:
         capturable in a graph."""
         with torch.cuda.device(self._dev):
@@ -976,20 +987,20 @@ class JpegBatch:
         return self.buffer, self.offsets
 
 
-def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False) -> List[bytes]:
+def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False, progressive=False) -> List[bytes]:
     """uint8 GPU images (list of [H,W,3] / [H,W] of any sizes, or [B,H,W,C]) -> the bytes of one JPEG file each, what
-    ``Image.fromarray(a).save(f, "JPEG", quality=..., subsampling=..., restart_marker_rows=..., optimize=...)`` writes.  Raw pixels never
+    ``Image.fromarray(a).save(f, "JPEG", quality=..., subsampling=..., restart_marker_rows=..., optimize=..., progressive=...)`` writes.  Raw pixels never
     leave the device.  See :class:`JpegBatch` for the keywords."""
     from .png import download
-    return download(*JpegBatch(images, quality, subsampling, restart_rows, order, optimize=optimize).run())
+    return download(*JpegBatch(images, quality, subsampling, restart_rows, order, optimize=optimize, progressive=progressive).run())
 
 
-def write_jpeg(paths, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False) -> None:
+def write_jpeg(paths, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False, progressive=False) -> None:
     """:func:`encode_jpeg`, each file written to its path."""
     paths = list(paths)
     n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
     if len(paths) != n:
         raise ValueError(f"write_jpeg: {len(paths)} paths for {n} images")
-    for p, f in zip(paths, encode_jpeg(images, quality, subsampling, restart_rows, order, optimize)):
+    for p, f in zip(paths, encode_jpeg(images, quality, subsampling, restart_rows, order, optimize, progressive)):
         with open(p, "wb") as fh:
             fh.write(f)

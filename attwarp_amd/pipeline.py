@@ -1782,11 +1782,12 @@ def save_png_ragged(rb: RaggedBatch, paths, what: str = "warped", filter: str = 
 
 
 def save_jpeg_ragged(rb: RaggedBatch, paths, what: str = "warped", quality=75, subsampling="4:2:0", restart_rows=0,
-                     order: str = "rgb", optimize=False):
+                     order: str = "rgb", optimize=False, progressive=False):
     """:func:`save_png_ragged` for JPEG files: the warped images (``what="warped"``) or the up-sampled masks (``what="mota"``,
     grey files) of ``rb``, encoded on the GPU in one :class:`attwarp_amd.jpeg.JpegBatch` with the bytes ``Image.save`` would
     write (Pillow's defaults; ``restart_rows=1`` is what this project's reader decodes fastest).  ``order``: channel order
-    of ``rb.images``.  ``optimize``: the images' own Huffman tables, the files of ``Image.save(..., optimize=True)``."""
+    of ``rb.images``.  ``optimize``: the images' own Huffman tables, the files of ``Image.save(..., optimize=True)``;
+    ``progressive``: those of ``Image.save(..., progressive=True)``."""
     paths = list(paths)
     if len(paths) != rb.B:
         raise ValueError(f"save_jpeg_ragged: {len(paths)} paths for a batch of {rb.B}")
@@ -1798,4 +1799,4 @@ def save_jpeg_ragged(rb: RaggedBatch, paths, what: str = "warped", quality=75, s
         images, order = [rb.mota_of(b) for b in range(rb.B)], "rgb"
     else:
         raise ValueError("save_jpeg_ragged: what is 'warped' or 'mota'")
-    jpeg.write_jpeg(paths, images, quality, subsampling, restart_rows, order, optimize)
+    jpeg.write_jpeg(paths, images, quality, subsampling, restart_rows, order, optimize, progressive)

@@ -1281,6 +1281,28 @@ ATTWARP_API size_t attwarp_jpegenc_bound_ex(int H, int W, int C, int quality, in
 ATTWARP_API size_t attwarp_jpegenc_table_bytes_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize);
 ATTWARP_API int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, void* table, size_t table_bytes);
 
+/* Progressive files (jpegprogenc_blocks.hpp): progressive is NULL or one flag (0 / 1) per image.  An image with
+ * progressive[i] = 1 is written as Image.save(..., progressive=True) writes it, whatever optimize[i] says (libjpeg forces
+ * optimised tables there): SOF2, jpeg_simple_progression's script (colour: ten scans, Cr before Cb; grey: six), in front of
+ * every scan the DHT(s) of its own optimal table(s), a DRI where the scan's restart interval (restart_rows x ITS MCUs per row)
+ * differs from the last one written, and its SOS; the scan data is jcphuff.c's, end-of-band runs flushed at 0x7FFF blocks and
+ * above 937 pending correction bits, RSTn numbered from 0 in every scan.  With progressive = NULL or all zero the table is
+ * attwarp_jpegenc_plan_ex's byte for byte.  Otherwise header.reserved is the offset / 16 of a record of the progressive
+ * images and their segments (one per scan and restart interval) at the table's end; such an image owns no entropy unit
+ * (header.nunits does not count it) and its transform units follow the others.  attwarp_jpegenc_encode (unchanged) adds
+ * eight launches: histogram clear; a summary of every block of the AC scans (one wave per block); one lane per segment
+ * walking the summaries, which resolves the end-of-band runs; one lane per block counting its symbols; tables (one workgroup
+ * per image); one lane per block placing and writing its bits; a scan of the pieces' lengths per image; the write, which
+ * stuffs.  All are capturable.  Scratch grows by 13 bytes per block and scan.
+ * attwarp_jpegenc_bound_prog(..., 0) is attwarp_jpegenc_bound_ex; with progressive = 1 it prices every block of every scan at
+ * 16-bit symbols, every byte as stuffed, and ten DHTs at 277 bytes.  Limits: the plain family's, with the
+ * restart interval of EVERY scan <= 65535 (luma scans walk up to twice the MCUs per row; libjpeg clamps silently instead), and
+ * at most 2^24 segments per call. */
+ATTWARP_API size_t attwarp_jpegenc_bound_prog(int H, int W, int C, int quality, int subsampling, int restart_rows, int optimize, int progressive);
+ATTWARP_API size_t attwarp_jpegenc_table_bytes_prog(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, const int32_t* progressive);
+ATTWARP_API int attwarp_jpegenc_plan_prog(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, const int32_t* progressive,
+                       void* table, size_t table_bytes);
+
 #ifdef __cplusplus
 }
 #endif
