@@ -1,13 +1,14 @@
 """What the planned batch classes share (pipeline.RaggedBatch / ClipBatch, dataloader.PreparedImages, png.PngBatch /
-PngFiles, jpeg.JpegFiles): the pinned staging pool every host-to-device table goes through, the planned-table idiom of the
-library's ``*_table_bytes`` / ``*_plan`` pairs, the base class of a planned batch of FILES, and the helper that decodes a
-list of several kinds group by group.  Internal: nothing here is part of the package's interface.
+PngFiles, jpeg.JpegBatch / JpegFiles): the pinned staging pool every host-to-device table goes through, the planned-table
+idiom of the library's ``*_table_bytes`` / ``*_plan`` pairs, the base classes of a planned batch of FILES to decode and of
+IMAGES to encode, and the helper that decodes a list of several kinds group by group.  Internal: nothing here is part of
+the package's interface.
 """
 from __future__ import annotations
 
 import os
 import threading
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -192,3 +193,109 @@ class FileBatch:
             call(self._entry, self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.stream), ptr(self.scratch),
                  ptr(self.buffer), self.buffer.numel(), ptr(self.status), stream_ptr(self._dev))
         return self.views(), self.status
+
+
+class ImageBatch:
+    """A planned batch of uint8 images to be encoded into files (png.PngBatch, jpeg.JpegBatch), the counterpart of
+    :class:`FileBatch`.  The subclass names itself in its messages -- ``_who`` (the class), ``_prefix`` (the module),
+    ``_dtype_error`` (what a wrong dtype raises) --, its encode entry point ``_entry`` and its size limit (``_max_side``: H and
+    W at most, ``_max_row_bytes``: 1 + W * C at most, ``_too_large``: the message), parses its keywords, and calls
+    :meth:`_views`, :meth:`_records` and, with its planned table, :meth:`_to_device`."""
+    _max_side = _max_row_bytes = 1 << 62
+
+    @classmethod
+    def _views(cls, images, who: Optional[str] = None) -> List[torch.Tensor]:
+        """A [B,H,W,C] tensor -> its B images; anything else: the list it is."""
+        if isinstance(images, torch.Tensor):
+            if images.dim() != 4:
+                raise ValueError(f"{who or cls._who}: a tensor batch is [B,H,W,C]; pass differently sized images as a list")
+            return [images[b] for b in range(images.shape[0])]
+        return list(images)
+
+    @classmethod
+    def _geometry(cls, images) -> list:
+        """[(H, W, C, pitch)] of uint8 [H,W,C] / [H,W] views whose pixels are dense along a row."""
+        pre, max_side, max_row = cls._prefix, cls._max_side, cls._max_row_bytes
+        out = []
+        for t in images:
+            if t.dtype != torch.uint8 or t.dim() not in (2, 3):
+                raise cls._dtype_error(f"{pre}: uint8 [H,W,C] / [H,W] tensors expected, got {t.dtype} {tuple(t.shape)}")
+            H, W = int(t.shape[0]), int(t.shape[1])
+            C = int(t.shape[2]) if t.dim() == 3 else 1
+            if H < 1 or W < 1:
+                raise ValueError(f"{pre}: empty image {tuple(t.shape)}")
+            if C not in (1, 3):
+                raise ValueError(f"{pre}: {C} channels (grey [H,W] / [H,W,1] or RGB [H,W,3] only)")
+            if H > max_side or W > max_side or 1 + W * C > max_row:
+                raise ValueError(cls._too_large(H, W, C))
+            st = t.stride()
+            if (t.dim() == 3 and C > 1 and st[2] != 1) or (W > 1 and st[1] != C):
+                raise ValueError(f"{pre}: unsupported strides {st} for shape {tuple(t.shape)}: the pixels of a row must be dense")
+            pitch = int(st[0]) if H > 1 else W * C
+            if pitch < W * C or pitch >= 1 << 31:
+                raise ValueError(f"{pre}: unsupported row stride {st[0]} for rows of {W * C} bytes")
+            out.append((H, W, C, pitch))
+        return out
+
+    def _records(self, images, dtype, orders) -> "np.ndarray":
+        """Checks every image and fills what the two record types share: src, H, W, C, pitch, order (ids).  Sets ``images``,
+        ``B`` and the device; the images must live on one GPU."""
+        geo = self._geometry(images)
+        self.images, self.B, self._dev = images, len(images), _lib.require_gpu(*images)
+        self._pixels = sum(g[0] * g[1] * g[2] for g in geo)
+        rec = np.zeros(self.B, dtype=dtype)
+        rec["src"] = [t.data_ptr() for t in images]
+        rec["H"] = [g[0] for g in geo]; rec["W"] = [g[1] for g in geo]; rec["C"] = [g[2] for g in geo]
+        rec["pitch"] = [g[3] for g in geo]
+        rec["order"] = orders
+        return rec
+
+    def _to_device(self, table_host, header, out):
+        """The upload of the table the subclass planned (:func:`planned_table`), and what a run writes (``out``: the caller's
+        buffer or None)."""
+        who, dev = self._who, self._dev
+        self.table_host, self.header = table_host, header
+        with torch.cuda.device(dev):
+            self.table_dev = uploaded(self.table_host, dev)
+            self.scratch = torch.empty(int(self.header.scratch_bytes), device=dev, dtype=torch.uint8)
+            if out is None:
+                out = torch.empty(self.bound, device=dev, dtype=torch.uint8)
+            elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < self.bound:
+                raise ValueError(f"{who}: out must be a dense uint8 buffer of at least {self.bound} bytes on the images' device")
+            self.buffer = out
+            self.offsets = torch.empty(self.B + 1, device=dev, dtype=torch.int64)
+
+    @property
+    def bound(self) -> int:
+        """Bytes the files of this batch take at most (the planner's sum over the images): the capacity ``out`` needs."""
+        return int(self.header.out_bytes)
+
+    def algorithmic_bytes(self) -> int:
+        """Pixel bytes the encoder has to read (the compressed bytes written depend on the content)."""
+        return self._pixels
+
+    def run(self):
+        """The launches of the subclass's entry point on the current stream -> ``(buffer, offsets)``: file b is
+        ``buffer[offsets[b]:offsets[b+1]]`` (uint8 and int64 [B+1], both on the device).  No host-dependent argument:
+        capturable in a graph."""
+        with torch.cuda.device(self._dev):
+            call(self._entry, self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.scratch), ptr(self.buffer),
+                 self.buffer.numel(), ptr(self.offsets), stream_ptr(self._dev))
+        return self.buffer, self.offsets
+
+
+def download(buffer: torch.Tensor, offsets: torch.Tensor) -> List[bytes]:
+    """The files of an :meth:`ImageBatch.run`: one device-to-host copy of the offsets, one of the used bytes."""
+    offs = offsets.cpu().tolist()
+    data = buffer[:offs[-1]].cpu().numpy().tobytes()
+    return [data[a:b] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def write_files(who: str, paths, n: int, encode) -> None:
+    """``encode()``'s n files, each written to its path; ``who``: the caller's name in the error."""
+    paths = list(paths)
+    if len(paths) != n:
+        raise ValueError(f"{who}: {len(paths)} paths for {n} images")
+    for p, f in zip(paths, encode()):
+        with open(p, "wb") as fh:
+            fh.write(f)

@@ -41,6 +41,11 @@
 //   jpegprogenc_place_kernel     one workgroup per image: prefix sums of DHT + DRI + SOS + bytes + FF + marker, the file's length;
 //   jpegprogenc_write_kernel     one workgroup per segment: what precedes the scan, the stuffed bytes, RSTn (numbered per scan) or EOI.
 // tests/jpegprogenc_ref.py restates the files.
+// The host side plans all three kinds at once: je_image_plan derives one image's geometry, bound and refusal (the bound entries,
+// jpegenc_count and the planner call it), attwarp_jpegenc_plan_prog is je_fill_image + je_plan_units / je_plan_progressive per
+// image and je_close_plans behind the last, with scratch offsets from one JeCursor; attwarp_jpegenc_encode reads the table's
+// header and optional records once (je_read_table) and launches through JE_LAUNCH.  tests/test_jpegenc_recording_cpu.py
+// holds the tables, bounds and refusals to a recording.
 #include <algorithm>
 #include <cstring>
 
@@ -75,6 +80,51 @@ __device__ __forceinline__ T je_excl_sum(T v, T* tmp, T& total) {
   return incl - v;
 }
 
+// Exclusive prefix sums over n elements, JE_NT of them at a time with a carry: value(s) is element s, put(s, sum) receives the
+// sum of the elements in front of it; the total comes back on every thread (tmp: JE_NT values).
+template <typename Value, typename Put>
+__device__ __forceinline__ unsigned long long je_chunked_excl_sum(int n, unsigned long long* tmp, Value value, Put put) {
+  unsigned long long carry = 0;
+  for (int base = 0; base < n; base += JE_NT) {
+    const int s = base + threadIdx.x;
+    const unsigned long long v = s < n ? (unsigned long long)value(s) : 0ull;
+    unsigned long long tot;
+    const unsigned long long pre = carry + je_excl_sum(v, tmp, tot);
+    if (s < n) put(s, pre);
+    carry += tot;
+  }
+  return carry;
+}
+
+// The stuffing of both write kernels: the n bytes byte(i) of an unstuffed stretch go to dst with a zero behind every FF.  Every
+// lane takes one run of them; the prefix sums of the runs' FF counts say where each lands (tmp: JE_NT values).
+template <typename Byte>
+__device__ __forceinline__ void je_stuff(Byte byte, uint32_t n, JE_G uint8_t* dst, uint32_t* tmp) {
+  const uint32_t per = (n + JE_NT - 1) / JE_NT;
+  const uint32_t lo = min(n, (uint32_t)threadIdx.x * per), hi = min(n, lo + per);
+  uint32_t ff = 0;
+  for (uint32_t i = lo; i < hi; ++i) ff += byte(i) == 255u;
+  uint32_t tot;
+  uint32_t at = lo + je_excl_sum(ff, tmp, tot);
+  for (uint32_t i = lo; i < hi; ++i) {
+    const uint32_t b = byte(i);
+    dst[at++] = (uint8_t)b;
+    if (b == 255u) dst[at++] = 0;
+  }
+}
+
+// n histogram words to zero (the clear kernels of the optimised and the progressive images)
+__device__ __forceinline__ void je_clear_words(uint32_t* hist, int n) {
+  for (int i = threadIdx.x; i < n; i += JE_NT) hist[i] = 0u;
+}
+
+__device__ __forceinline__ JeImageOut* je_image_out(const uint8_t* table, uint8_t* scratch) {
+  return reinterpret_cast<JeImageOut*>(scratch + je_header(table)->off_image_out);
+}
+__device__ __forceinline__ const JeImageOut* je_image_out(const uint8_t* table, const uint8_t* scratch) {
+  return reinterpret_cast<const JeImageOut*>(scratch + je_header(table)->off_image_out);
+}
+
 __device__ __forceinline__ uint32_t je_wave_incl_sum(uint32_t v) {
   const int lane = threadIdx.x & (WAVE - 1);
 #pragma unroll
@@ -96,9 +146,8 @@ __device__ __forceinline__ JeSrc je_source(const JeImageDev* im) {
 
 // ---- 1. pixels -> quantised coefficients ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(JE_TNT) void jpegenc_transform_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
-  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[blockIdx.x];
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  const JeUnit u = je_unit(table, blockIdx.x);
+  const JeImageDev* im = je_image(table, u.image);
   const int bpm = im->bpm, i = threadIdx.x;
   if (i >= u.nmcu * bpm) return;
   const int mcu = u.mcu0 + i / bpm, s = i - (i / bpm) * bpm;
@@ -183,11 +232,12 @@ __device__ __forceinline__ int je_block_lane_value(const int16_t* coef, const Je
   return v;
 }
 // The optimised image's record in the scratch buffer; nullptr: the image takes the Annex K tables.
-__device__ __forceinline__ const JoImageOut* je_optimized(const uint8_t* table, const attwarp_jpegenc_header* hdr, const JeImageDev* im,
-                                                          const uint8_t* scratch) {
+__device__ __forceinline__ const JoPlan* jo_plan(const uint8_t* table) {
+  return reinterpret_cast<const JoPlan*>(table + je_header(table)->off_optimize);
+}
+__device__ __forceinline__ const JoImageOut* je_optimized(const uint8_t* table, const JeImageDev* im, const uint8_t* scratch) {
   if (!im->opt) return nullptr;
-  const JoPlan* plan = reinterpret_cast<const JoPlan*>(table + hdr->off_optimize);
-  return reinterpret_cast<const JoImageOut*>(scratch + plan->off_out) + (im->opt - 1);
+  return reinterpret_cast<const JoImageOut*>(scratch + jo_plan(table)->off_out) + (im->opt - 1);
 }
 // nbits <= 27 of `value` at bit `pos` of the big-endian words w
 __device__ __forceinline__ void je_put(uint32_t* w, uint32_t pos, uint32_t value, uint32_t nbits) {
@@ -202,11 +252,10 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_entropy_kernel(const uint8_t* _
   __shared__ uint32_t s_blen[2 * WAVE], s_bstart[2 * WAVE];
   __shared__ uint32_t s_total;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
-  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[blockIdx.x];
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
-  const uint32_t* huff = reinterpret_cast<const uint32_t*>(table + hdr->off_huffman);
-  const JoImageOut* opt = je_optimized(table, hdr, im, scratch);
+  const JeUnit u = je_unit(table, blockIdx.x);
+  const JeImageDev* im = je_image(table, u.image);
+  const uint32_t* huff = reinterpret_cast<const uint32_t*>(table + je_header(table)->off_huffman);
+  const JoImageOut* opt = je_optimized(table, im, scratch);
   const int bpm = im->bpm, nblk = u.nmcu * bpm, ny = im->C == 3 ? im->hmax * im->vmax : 1;
   const int nwords = min(JE_UNIT_WORDS, (nblk * im->block_bits + 31) / 32 + 2);
   for (int i = tid; i < nwords; i += JE_NT) s_bits[i] = 0;
@@ -262,23 +311,17 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_entropy_kernel(const uint8_t* _
 
 // ---- 1a - 1c. optimised images: histograms, tables, header (launched in front of 2.) -----------------------------------------------
 static_assert(JE_NT == 256 && JE_NT == 4 * WAVE, "a thread per symbol of a table, a wave per table");
-__device__ __forceinline__ const JoPlan* jo_plan(const uint8_t* table) {
-  return reinterpret_cast<const JoPlan*>(table + reinterpret_cast<const attwarp_jpegenc_header*>(table)->off_optimize);
-}
-
 __global__ __launch_bounds__(JE_NT) void jpegopt_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
-  uint32_t* hist = reinterpret_cast<uint32_t*>(scratch + jo_plan(table)->off_hist) + (size_t)blockIdx.x * 1024;
-  for (int i = threadIdx.x; i < 4 * 256; i += JE_NT) hist[i] = 0u;
+  je_clear_words(reinterpret_cast<uint32_t*>(scratch + jo_plan(table)->off_hist) + (size_t)blockIdx.x * 4 * 256, 4 * 256);
 }
 
 __global__ __launch_bounds__(JE_NT) void jpegopt_histogram_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   __shared__ uint32_t s_hist[4 * 256];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
   const JoPlan* plan = jo_plan(table);
   const int32_t* list = reinterpret_cast<const int32_t*>(reinterpret_cast<const JoImage*>(plan + 1) + plan->nimages);
-  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[list[blockIdx.x]];
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  const JeUnit u = je_unit(table, list[blockIdx.x]);
+  const JeImageDev* im = je_image(table, u.image);
   for (int i = tid; i < 4 * 256; i += JE_NT) s_hist[i] = 0u;
   __syncthreads();
   const int16_t* coef = reinterpret_cast<const int16_t*>(scratch + im->coef_off);
@@ -312,10 +355,9 @@ struct JoWaveMin {                     // the smallest key of the wave's 64 lane
 __global__ __launch_bounds__(JE_NT) void jpegopt_tables_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   __shared__ JoWork s_work[JE_NT / WAVE];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
   const JoPlan* plan = jo_plan(table);
   const JoImage oi = reinterpret_cast<const JoImage*>(plan + 1)[blockIdx.x];
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + oi.image;
+  const JeImageDev* im = je_image(table, oi.image);
   const uint32_t* hist = reinterpret_cast<const uint32_t*>(scratch + plan->off_hist) + (size_t)blockIdx.x * 1024;
   JoImageOut* out = reinterpret_cast<JoImageOut*>(scratch + plan->off_out) + blockIdx.x;
   if (wave < oi.ntables) jo_optimal_table<WAVE>(hist + 256 * wave, (wave & 1) << 4 | wave >> 1, lane, JoWaveMin(), s_work[wave], out->table[wave]);
@@ -335,20 +377,11 @@ __global__ __launch_bounds__(JE_NT) void jpegopt_tables_kernel(const uint8_t* __
 // ---- 3. bits of the image's earlier units -----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(JE_NT) void jpegenc_scan_bits_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   __shared__ unsigned long long s_tmp[JE_NT];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + b;
+  const JeImageDev* im = je_image(table, blockIdx.x);
   JeUnitOut* uo = reinterpret_cast<JeUnitOut*>(scratch) + im->unit0;
-  unsigned long long carry = 0;
-  for (int base = 0; base < im->nunits; base += JE_NT) {
-    const int s = base + tid;
-    const unsigned long long v = s < im->nunits ? uo[s].bits : 0ull;
-    unsigned long long tot;
-    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
-    if (s < im->nunits) uo[s].pre = pre;
-    carry += tot;
-  }
-  if (tid == 0) reinterpret_cast<JeImageOut*>(scratch + hdr->off_image_out)[b].bits = carry;
+  const unsigned long long bits = je_chunked_excl_sum(im->nunits, s_tmp, [&](int s) { return uo[s].bits; },
+                                                      [&](int s, unsigned long long pre) { uo[s].pre = pre; });
+  if (threadIdx.x == 0) je_image_out(table, scratch)[blockIdx.x].bits = bits;
 }
 
 // Where the unit's bytes lie in its interval's stream: bits [off, off + bits) of `ibits`; it owns bytes [j0, j1), the bytes
@@ -377,12 +410,10 @@ __device__ __forceinline__ JePlace je_place(const JeUnit& u, const JeImageDev* i
 __global__ __launch_bounds__(JE_NT) void jpegenc_gather_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   __shared__ uint32_t s_ff;
   const int tid = threadIdx.x;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
-  const JeUnit* units = reinterpret_cast<const JeUnit*>(table + hdr->off_units);
-  const JeUnit u = units[blockIdx.x];
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  const JeUnit u = je_unit(table, blockIdx.x);
+  const JeImageDev* im = je_image(table, u.image);
   JeUnitOut* uo = reinterpret_cast<JeUnitOut*>(scratch) + im->unit0;
-  const JePlace p = je_place(u, im, uo, reinterpret_cast<const JeImageOut*>(scratch + hdr->off_image_out));
+  const JePlace p = je_place(u, im, uo, je_image_out(table, scratch));
   if (tid == 0) s_ff = 0;
   __syncthreads();
   const JE_G uint8_t* slot = (const JE_G uint8_t*)scratch + u.slot_off;
@@ -413,7 +444,7 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_gather_kernel(const uint8_t* __
       uint32_t bit = 1;
       if (pos < p.ibits) {
         const uint32_t q = (uint32_t)(pos - voff);
-        const JE_G uint8_t* sv = (const JE_G uint8_t*)scratch + units[im->unit0 + v].slot_off;
+        const JE_G uint8_t* sv = (const JE_G uint8_t*)scratch + je_unit(table, im->unit0 + v).slot_off;
         bit = (sv[q >> 3] >> (7u - (q & 7u))) & 1u;
       }
       byte = byte << 1 | bit;
@@ -435,23 +466,15 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_gather_kernel(const uint8_t* __
 // ---- 5. where every unit's stuffed bytes go; the file's length ----------------------------------------------------------------------
 __global__ __launch_bounds__(JE_NT) void jpegenc_scan_bytes_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   __shared__ unsigned long long s_tmp[JE_NT];
-  const int tid = threadIdx.x, b = blockIdx.x;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + b;
+  const JeImageDev* im = je_image(table, blockIdx.x);
   JeUnitOut* uo = reinterpret_cast<JeUnitOut*>(scratch) + im->unit0;
-  unsigned long long carry = 0;
-  for (int base = 0; base < im->nunits; base += JE_NT) {
-    const int s = base + tid;
-    const unsigned long long v = s < im->nunits ? (unsigned long long)uo[s].nbytes + uo[s].nff : 0ull;
-    unsigned long long tot;
-    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
-    if (s < im->nunits) uo[s].fpos = pre + 2ull * (unsigned long long)(s / im->upi);       // an RSTn behind every earlier interval
-    carry += tot;
-  }
-  if (tid == 0) {
-    const JoImageOut* opt = je_optimized(table, hdr, im, scratch);
-    reinterpret_cast<JeImageOut*>(scratch + hdr->off_image_out)[b].file_bytes =
-        (unsigned long long)(opt ? opt->header_len : im->header_len) + carry + 2ull * (unsigned long long)(im->nint - 1) + 2ull;
+  const unsigned long long bytes = je_chunked_excl_sum(
+      im->nunits, s_tmp, [&](int s) { return (unsigned long long)uo[s].nbytes + uo[s].nff; },
+      [&](int s, unsigned long long pre) { uo[s].fpos = pre + 2ull * (unsigned long long)(s / im->upi); });   // an RSTn behind every earlier interval
+  if (threadIdx.x == 0) {
+    const JoImageOut* opt = je_optimized(table, im, scratch);
+    je_image_out(table, scratch)[blockIdx.x].file_bytes =
+        (unsigned long long)(opt ? opt->header_len : im->header_len) + bytes + 2ull * (unsigned long long)(im->nint - 1) + 2ull;
   }
 }
 
@@ -459,19 +482,11 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_scan_bytes_kernel(const uint8_t
 __global__ __launch_bounds__(JE_NT) void jpegenc_scan_files_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
                                                                    int64_t* __restrict__ offsets) {
   __shared__ unsigned long long s_tmp[JE_NT];
-  const int tid = threadIdx.x;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
-  const JeImageOut* io = reinterpret_cast<const JeImageOut*>(scratch + hdr->off_image_out);
-  unsigned long long carry = 0;
-  for (int base = 0; base < hdr->B; base += JE_NT) {
-    const int b = base + tid;
-    const unsigned long long v = b < hdr->B ? io[b].file_bytes : 0ull;
-    unsigned long long tot;
-    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
-    if (b < hdr->B) offsets[b] = (int64_t)pre;
-    carry += tot;
-  }
-  if (tid == 0) offsets[hdr->B] = (int64_t)carry;
+  const int B = je_header(table)->B;
+  const JeImageOut* io = je_image_out(table, scratch);
+  const unsigned long long all = je_chunked_excl_sum(B, s_tmp, [&](int b) { return io[b].file_bytes; },
+                                                     [&](int b, unsigned long long pre) { offsets[b] = (int64_t)pre; });
+  if (threadIdx.x == 0) offsets[B] = (int64_t)all;
 }
 
 // ---- 7. the files -----------------------------------------------------------------------------------------------------------------------
@@ -479,32 +494,21 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_write_kernel(const uint8_t* __r
                                                               uint8_t* __restrict__ out, const int64_t* __restrict__ offsets) {
   __shared__ uint32_t s_tmp[JE_NT];
   const int tid = threadIdx.x;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
-  const JeUnit u = reinterpret_cast<const JeUnit*>(table + hdr->off_units)[blockIdx.x];
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + u.image;
+  const JeUnit u = je_unit(table, blockIdx.x);
+  const JeImageDev* im = je_image(table, u.image);
   const JeUnitOut o = reinterpret_cast<const JeUnitOut*>(scratch)[blockIdx.x];
   const int64_t off = offsets[u.image];                      // (jpegenc_scan_files_kernel)
   JE_G uint8_t* file = (JE_G uint8_t*)out + off;
-  const JoImageOut* opt = je_optimized(table, hdr, im, scratch);          // its header: where jpegopt_tables_kernel left it
+  const JoImageOut* opt = je_optimized(table, im, scratch);          // its header: where jpegopt_tables_kernel left it
   const uint8_t* header = opt ? opt->header : im->header;
   const int header_len = opt ? opt->header_len : im->header_len;
   JE_G uint8_t* dst = file + header_len + o.fpos;
   const JE_G uint8_t* ust = (const JE_G uint8_t*)scratch + im->ustream_off + o.upos;
-  const uint32_t n = o.nbytes, per = (n + JE_NT - 1) / JE_NT;
-  const uint32_t lo = min(n, (uint32_t)tid * per), hi = min(n, lo + per);
-  uint32_t ff = 0;
-  for (uint32_t i = lo; i < hi; ++i) ff += ust[i] == 255u;
-  uint32_t tot;
-  uint32_t at = lo + je_excl_sum(ff, s_tmp, tot);
-  for (uint32_t i = lo; i < hi; ++i) {
-    const uint8_t byte = ust[i];
-    dst[at++] = byte;
-    if (byte == 255u) dst[at++] = 0;
-  }
+  je_stuff([&](uint32_t i) { return (uint32_t)ust[i]; }, o.nbytes, dst, s_tmp);
   if (u.index == 0)
     for (int i = tid; i < header_len; i += JE_NT) file[i] = header[i];
   if (tid == 0 && u.last) {
-    JE_G uint8_t* m = dst + n + o.nff;
+    JE_G uint8_t* m = dst + o.nbytes + o.nff;
     m[0] = 0xff;
     m[1] = u.index == im->nunits - 1 ? 0xd9 : (uint8_t)(0xd0 + (u.interval & 7));
   }
@@ -512,7 +516,7 @@ __global__ __launch_bounds__(JE_NT) void jpegenc_write_kernel(const uint8_t* __r
 
 // ---- progressive images -------------------------------------------------------------------------------------------
 __device__ __forceinline__ const PePlan* pe_plan(const uint8_t* table) {
-  return reinterpret_cast<const PePlan*>(table + (uint64_t)reinterpret_cast<const attwarp_jpegenc_header*>(table)->reserved * 16u);
+  return reinterpret_cast<const PePlan*>(table + (uint64_t)je_header(table)->reserved * 16u);
 }
 __device__ __forceinline__ PeWalk pe_walk(const JeImageDev* im, const PeScan& sc, const PeScanPlan& sp, const uint8_t* scratch) {
   PeWalk w;
@@ -536,12 +540,11 @@ struct PeWork {
   uint8_t* summary;
 };
 __device__ __forceinline__ PeWork pe_work(const uint8_t* table, uint8_t* scratch, int sidx) {
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
   const PePlan* plan = pe_plan(table);
   PeWork k;
   k.sg = reinterpret_cast<const PeSeg*>(table + plan->off_segs)[sidx];
   const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + k.sg.pimage;
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image;
+  const JeImageDev* im = je_image(table, pi->image);
   k.sc = pe_scan(im->C, k.sg.scan);
   k.w = pe_walk(im, k.sc, pi->scan[k.sg.scan], scratch);
   k.pos = reinterpret_cast<uint64_t*>(scratch + k.sg.aux_off);
@@ -551,8 +554,7 @@ __device__ __forceinline__ PeWork pe_work(const uint8_t* table, uint8_t* scratch
 }
 
 __global__ __launch_bounds__(JE_NT) void jpegprogenc_clear_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
-  uint32_t* hist = reinterpret_cast<uint32_t*>(scratch + pe_plan(table)->off_hist) + (size_t)blockIdx.x * PE_SLOTS * 256;
-  for (int i = threadIdx.x; i < PE_SLOTS * 256; i += JE_NT) hist[i] = 0u;
+  je_clear_words(reinterpret_cast<uint32_t*>(scratch + pe_plan(table)->off_hist) + (size_t)blockIdx.x * PE_SLOTS * 256, PE_SLOTS * 256);
 }
 
 // one workgroup per segment of an AC scan, one wave per block, one lane per coefficient: two ballots are the block's summary
@@ -648,17 +650,14 @@ __global__ __launch_bounds__(JE_NT) void jpegprogenc_code_kernel(const uint8_t* 
   if (tid == 0) s_ff = 0;
   __syncthreads();
   PeState st;
-  unsigned long long carry = 0;
-  for (int base = 0; base < k.sg.nblocks; base += JE_NT) {
-    const int i = base + tid;
-    PeLengthSink ls = {s_code, 0u};
-    if (i < k.sg.nblocks)
-      pe_code_block(k.w, k.sc, k.sg.scan, k.sg.block0, k.sg.nblocks, (int64_t)k.sg.block0 + i, k.summary, pe_run_in_front(k, i), st, ls);
-    unsigned long long tot;
-    const unsigned long long at = carry + je_excl_sum((unsigned long long)ls.n, s_tmp, tot);
-    if (i < k.sg.nblocks) k.pos[i] = at;
-    carry += tot;
-  }
+  const unsigned long long carry = je_chunked_excl_sum(
+      k.sg.nblocks, s_tmp,
+      [&](int i) {
+        PeLengthSink ls = {s_code, 0u};
+        pe_code_block(k.w, k.sc, k.sg.scan, k.sg.block0, k.sg.nblocks, (int64_t)k.sg.block0 + i, k.summary, pe_run_in_front(k, i), st, ls);
+        return ls.n;
+      },
+      [&](int i, unsigned long long at) { k.pos[i] = at; });
   // the clamp guards the slot; the planner's bound (pe_interval_bytes) keeps the string within it
   const uint64_t nwords = ((uint64_t)k.sg.cap + 7u) / 4u;
   const uint64_t bits = carry < 8ull * (uint64_t)k.sg.cap ? carry : 8ull * (uint64_t)k.sg.cap;
@@ -690,10 +689,9 @@ __global__ __launch_bounds__(JE_NT) void jpegprogenc_code_kernel(const uint8_t* 
 __global__ __launch_bounds__(JE_NT) void jpegprogenc_tables_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   __shared__ JoWork s_work[JE_NT / WAVE];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
   const PePlan* plan = pe_plan(table);
   const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + blockIdx.x;
-  const int ncomp = (reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image)->C;
+  const int ncomp = je_image(table, pi->image)->C;
   const uint32_t* hist = reinterpret_cast<const uint32_t*>(scratch + plan->off_hist) + (size_t)blockIdx.x * PE_SLOTS * 256;
   JoTable* out = reinterpret_cast<JoTable*>(scratch + plan->off_tables) + (size_t)blockIdx.x * PE_SLOTS;
   for (int slot = wave; slot < PE_SLOTS; slot += JE_NT / WAVE)
@@ -724,39 +722,30 @@ __device__ __forceinline__ PePieces pe_pieces(const PeImage* pi, int ncomp, cons
 
 __global__ __launch_bounds__(JE_NT) void jpegprogenc_place_kernel(const uint8_t* __restrict__ table, uint8_t* __restrict__ scratch) {
   __shared__ unsigned long long s_tmp[JE_NT];
-  const int tid = threadIdx.x;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
   const PePlan* plan = pe_plan(table);
   const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + blockIdx.x;
-  const int ncomp = (reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image)->C;
+  const int ncomp = je_image(table, pi->image)->C;
   const PeSeg* segs = reinterpret_cast<const PeSeg*>(table + plan->off_segs) + pi->seg0;
   PeSegOut* so = reinterpret_cast<PeSegOut*>(scratch + plan->off_seg_out) + pi->seg0;
   const JoTable* tables = reinterpret_cast<const JoTable*>(scratch + plan->off_tables) + (size_t)blockIdx.x * PE_SLOTS;
-  unsigned long long carry = 0;
-  for (int base = 0; base < pi->nsegs; base += JE_NT) {
-    const int s = base + tid;
-    unsigned long long v = 0;
-    if (s < pi->nsegs) {
-      const PePieces p = pe_pieces(pi, ncomp, segs[s], tables);
-      v = (unsigned long long)p.before() + so[s].nbytes + so[s].nff + (unsigned long long)p.tail;
-    }
-    unsigned long long tot;
-    const unsigned long long pre = carry + je_excl_sum(v, s_tmp, tot);
-    if (s < pi->nsegs) so[s].fpos = pre;
-    carry += tot;
-  }
-  if (tid == 0) reinterpret_cast<JeImageOut*>(scratch + hdr->off_image_out)[pi->image].file_bytes = carry;
+  const unsigned long long bytes = je_chunked_excl_sum(
+      pi->nsegs, s_tmp,
+      [&](int s) {
+        const PePieces p = pe_pieces(pi, ncomp, segs[s], tables);
+        return (unsigned long long)p.before() + so[s].nbytes + so[s].nff + (unsigned long long)p.tail;
+      },
+      [&](int s, unsigned long long pre) { so[s].fpos = pre; });
+  if (threadIdx.x == 0) je_image_out(table, scratch)[pi->image].file_bytes = bytes;
 }
 
 __global__ __launch_bounds__(JE_NT) void jpegprogenc_write_kernel(const uint8_t* __restrict__ table, const uint8_t* __restrict__ scratch,
                                                                uint8_t* __restrict__ out, const int64_t* __restrict__ offsets) {
   __shared__ uint32_t s_tmp[JE_NT];
   const int tid = threadIdx.x;
-  const attwarp_jpegenc_header* hdr = reinterpret_cast<const attwarp_jpegenc_header*>(table);
   const PePlan* plan = pe_plan(table);
   const PeSeg sg = reinterpret_cast<const PeSeg*>(table + plan->off_segs)[blockIdx.x];
   const PeImage* pi = reinterpret_cast<const PeImage*>(table + plan->off_images) + sg.pimage;
-  const JeImageDev* im = reinterpret_cast<const JeImageDev*>(table + hdr->off_images) + pi->image;
+  const JeImageDev* im = je_image(table, pi->image);
   const PeSegOut o = reinterpret_cast<const PeSegOut*>(scratch + plan->off_seg_out)[blockIdx.x];
   const JoTable* tables = reinterpret_cast<const JoTable*>(scratch + plan->off_tables) + (size_t)sg.pimage * PE_SLOTS;
   const PePieces p = pe_pieces(pi, im->C, sg, tables);
@@ -790,21 +779,10 @@ __global__ __launch_bounds__(JE_NT) void jpegprogenc_write_kernel(const uint8_t*
   }
   // the interval's bytes out of its big-endian words, a zero behind every FF (the stuffing of launch 7)
   const uint32_t* words = reinterpret_cast<const uint32_t*>(scratch + sg.slot_off);
-  auto byte_at = [&](uint32_t i) { return (words[i >> 2] >> (24u - 8u * (i & 3u))) & 255u; };
-  const uint32_t n = o.nbytes, per = (n + JE_NT - 1) / JE_NT;
-  const uint32_t lo = min(n, (uint32_t)tid * per), hi = min(n, lo + per);
-  uint32_t ff = 0;
-  for (uint32_t i = lo; i < hi; ++i) ff += byte_at(i) == 255u;
-  uint32_t tot;
-  uint32_t at = lo + je_excl_sum(ff, s_tmp, tot);
-  for (uint32_t i = lo; i < hi; ++i) {
-    const uint32_t b = byte_at(i);
-    dst[at++] = (uint8_t)b;
-    if (b == 255u) dst[at++] = 0;
-  }
+  je_stuff([&](uint32_t i) { return (words[i >> 2] >> (24u - 8u * (i & 3u))) & 255u; }, o.nbytes, dst, s_tmp);
   if (tid == 0 && p.tail) {
-    dst[n + o.nff] = 0xff;
-    dst[n + o.nff + 1] = sg.index == pi->scan[sg.scan].nsegs - 1 ? 0xd9 : (uint8_t)(0xd0 + (sg.index & 7));
+    dst[o.nbytes + o.nff] = 0xff;
+    dst[o.nbytes + o.nff + 1] = sg.index == pi->scan[sg.scan].nsegs - 1 ? 0xd9 : (uint8_t)(0xd0 + (sg.index & 7));
   }
 }
 
@@ -927,110 +905,316 @@ static int je_write_header(uint8_t* h, const attwarp_jpegenc_image& d, const JeG
   return n;
 }
 
+// Everything the callers need of one image, derived once: its geometry, the scans' when it is progressive, and its file's
+// bound.  optimize is ignored for a progressive image (such a file always has tables of its own).
+struct JeImagePlan {
+  bool prog, opt;
+  JeGeometry g;
+  PeGeometry p;                        // (prog)
+  uint64_t bound;                      // the file's length at most, below 2 GiB
+  bool geometry;                       // false: the refusal is je_geometry's (the later checks were not reached)
+  char why[256];                       // the reason of a refusal: what follows "jpegenc: image <b>" in the error
+};
+// false: refused, and pl.why says why
+static bool je_image_plan(const attwarp_jpegenc_image& d, bool optimize, bool progressive, JeImagePlan& pl) {
+  pl.prog = progressive;
+  pl.opt = optimize && !progressive;
+  pl.bound = 0;
+  const char* what;
+  pl.geometry = je_geometry(d.H, d.W, d.C, d.quality, d.subsampling, d.restart_rows, pl.g, what);
+  if (!pl.geometry) {
+    std::snprintf(pl.why, sizeof pl.why, " (%d x %d x %d, quality %d, subsampling %d, restart_rows %d): %s", d.H, d.W, d.C, d.quality, d.subsampling,
+                  d.restart_rows, what);
+    return false;
+  }
+  if (pl.prog && !pe_geometry(d.H, d.W, d.C, d.restart_rows, pl.g, pl.p)) {
+    std::snprintf(pl.why, sizeof pl.why, " (%d x %d x %d, restart_rows %d): a progressive scan's restart interval above 65535 "
+                  "(libjpeg clamps it to 65535 and no longer restarts at the rows)", d.H, d.W, d.C, d.restart_rows);
+    return false;
+  }
+  const uint64_t bound = pl.prog ? pe_bound64(d.C, pl.p) : je_bound64(d.C, d.quality, d.restart_rows, pl.g, pl.opt);
+  if (bound >= ((uint64_t)1 << 31)) {
+    std::snprintf(pl.why, sizeof pl.why, ": the %sbound of %d x %d x %d is 2 GiB or more", pl.prog ? "progressive " : "", d.H, d.W, d.C);
+    return false;
+  }
+  pl.bound = bound;
+  return true;
+}
+static size_t je_bound_of(int H, int W, int C, int quality, int subsampling, int restart_rows, bool optimize, bool progressive) {
+  attwarp_jpegenc_image d;
+  std::memset(&d, 0, sizeof d);
+  d.H = H; d.W = W; d.C = C; d.quality = quality; d.subsampling = subsampling; d.restart_rows = restart_rows;
+  JeImagePlan pl;
+  return je_image_plan(d, optimize, progressive, pl) ? (size_t)pl.bound : 0;
+}
+
+// What a call holds.  A progressive image owns no entropy unit: its transform units and its segments are counted apart.
+struct JeCounts {
+  int64_t nunits = 0;                  // units of the plain and the optimised images
+  int nopt = 0;                        // optimised images
+  int64_t nopt_units = 0;              // and their units
+  int nprog = 0;                       // progressive images
+  int64_t nprog_units = 0, nsegs = 0;  // their transform units; their segments (scans x restart intervals)
+};
+// optimize, progressive: NULL, or one flag per image
+static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, const int32_t* progressive, JeCounts& n) {
+  ATTWARP_REQUIRE(images, "jpegenc: null image array");
+  ATTWARP_REQUIRE(B > 0, "jpegenc: non-positive batch size");
+  if (B > (1 << 20)) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: B=%d > 2^20", B);
+  n = JeCounts();
+  for (int b = 0; b < B; ++b) {
+    const attwarp_jpegenc_image& d = images[b];
+    ATTWARP_REQUIRE(!progressive || progressive[b] == 0 || progressive[b] == 1, "jpegenc: image %d: progressive must be 0 or 1", b);
+    ATTWARP_REQUIRE(!optimize || optimize[b] == 0 || optimize[b] == 1, "jpegenc: image %d: optimize must be 0 or 1", b);
+    ATTWARP_REQUIRE(d.src, "jpegenc: image %d: null pointer", b);
+    ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegenc: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
+    JeImagePlan pl;
+    const bool ok = je_image_plan(d, optimize && optimize[b], progressive && progressive[b], pl);
+    if (!pl.geometry) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d%s", b, pl.why);
+    ATTWARP_REQUIRE((int64_t)d.pitch >= (int64_t)d.W * d.C, "jpegenc: image %d: pitch %d below the row's %lld bytes", b, d.pitch, (long long)d.W * d.C);
+    if (!ok) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d%s", b, pl.why);
+    // A table's frequencies add up to at most 64 symbols per block.  A block's bound is above 1024 bits (22 + 63 x 17) and the
+    // file's bound, twice its bytes, is below 2^31: fewer than 2^23 blocks and 2^29 symbols, below libjpeg's sentinel (a larger
+    // frequency would never be merged) and far below the 2^32 of the counters (a progressive image's too).  This refusal can never trigger.
+    if (pl.opt && (uint64_t)pl.g.nmcu * pl.g.bpm * JO_SYMBOLS_PER_BLOCK >= JO_SENTINEL)
+      return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: %lld blocks could hold 10^9 symbols or more", b, (long long)pl.g.nmcu * pl.g.bpm);
+    if (pl.prog) { n.nprog += 1; n.nprog_units += pl.g.nunits; n.nsegs += pl.p.nsegs; }
+    else n.nunits += pl.g.nunits;
+    if (pl.opt) { n.nopt += 1; n.nopt_units += pl.g.nunits; }
+  }
+  if (n.nunits + n.nprog_units > JE_MAX_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld units in one call (> %d)", (long long)(n.nunits + n.nprog_units), JE_MAX_UNITS);
+  if (n.nsegs > JE_MAX_UNITS)
+    return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld progressive segments (scans x restart intervals) in one call (> %d)", (long long)n.nsegs, JE_MAX_UNITS);
+  return ATTWARP_OK;
+}
+
+// Where the parts of a table lie.  Without an optimised image the table ends behind the units, as it always did; with one, the
+// JoPlan follows them; the PePlan, its images and segments follow that, 16-byte aligned.
+struct JeLayout {
+  uint64_t off_huffman, off_images, off_units, off_optimize, off_progressive, bytes;       // (off_optimize, off_progressive 0: none)
+};
+static JeLayout jpegenc_table_layout(int B, const JeCounts& n) {
+  static_assert(sizeof(attwarp_jpegenc_header) == 80, "the header ends where the Annex K code words start");
+  JeLayout at;
+  at.off_huffman = align_up(sizeof(attwarp_jpegenc_header), 16);
+  at.off_images = at.off_huffman + 4 * 256 * sizeof(uint32_t);
+  at.off_units = at.off_images + align_up((uint64_t)B * sizeof(JeImageDev), 16);
+  uint64_t end = at.off_units + (uint64_t)(n.nunits + n.nprog_units) * sizeof(JeUnit);     // the progressive images' transform units last
+  at.off_optimize = n.nopt ? end : 0;
+  if (n.nopt) end += sizeof(JoPlan) + (uint64_t)n.nopt * sizeof(JoImage) + (uint64_t)n.nopt_units * sizeof(int32_t);
+  at.off_progressive = n.nprog ? align_up(end, 16) : 0;
+  if (n.nprog) end = at.off_progressive + align_up(sizeof(PePlan), 16) + (uint64_t)n.nprog * sizeof(PeImage) + (uint64_t)n.nsegs * sizeof(PeSeg);
+  at.bytes = end;
+  return at;
+}
+
+struct JeCursor {                      // the next free byte of the scratch buffer
+  uint64_t at = 0;
+  uint64_t take(uint64_t bytes, uint64_t align = 1) {        // where `bytes` go; the cursor moves on by them, rounded up to `align`
+    const uint64_t off = at;
+    at += align_up(bytes, align);
+    return off;
+  }
+  void align(uint64_t a) { at = align_up(at, a); }
+};
+
+// The planner's state: the records it fills in the table and how far it got in each of them.
+struct JePlanner {
+  const JeCounts n;
+  const JeLayout at;
+  JeCursor scratch;
+  JeUnit* units;
+  int32_t unit = 0, tunit;             // the next entropy unit; the next transform unit of a progressive image (behind every other unit)
+  JoPlan* jo;                          // nullptr: no optimised image; then its JoImage[nopt], int32 unit[nopt_units]
+  JoImage* jo_image;
+  int32_t* jo_unit;
+  PePlan* pe;                          // nullptr: no progressive image; then (16-byte aligned) PeImage[nprog], PeSeg[nsegs]
+  PeImage* pe_image;
+  PeSeg* pe_seg;
+  int k_opt = 0, k_prog = 0;           // the next optimised image and its next unit, the next progressive image and its next segment
+  int64_t k_opt_unit = 0;
+  int32_t k_seg = 0;
+
+  JePlanner(uint8_t* t, const JeCounts& n, const JeLayout& at)
+      : n(n), at(at), units(reinterpret_cast<JeUnit*>(t + at.off_units)), tunit((int32_t)n.nunits),
+        jo(n.nopt ? reinterpret_cast<JoPlan*>(t + at.off_optimize) : nullptr), jo_image(jo ? reinterpret_cast<JoImage*>(jo + 1) : nullptr),
+        jo_unit(jo ? reinterpret_cast<int32_t*>(jo_image + n.nopt) : nullptr),
+        pe(n.nprog ? reinterpret_cast<PePlan*>(t + at.off_progressive) : nullptr),
+        pe_image(pe ? reinterpret_cast<PeImage*>(t + at.off_progressive + align_up(sizeof(PePlan), 16)) : nullptr),
+        pe_seg(pe ? reinterpret_cast<PeSeg*>(pe_image + n.nprog) : nullptr) {}
+};
+
+// The part of its record every image shares: source, swap, factors, quantisation divisors and reciprocals, header.
+// own_tables: the header's DHTs are left out; returns where they belong (else 0).
+static int je_fill_image(JeImageDev& r, const attwarp_jpegenc_image& d, const JeGeometry& g, bool own_tables) {
+  r.src = d.src; r.H = d.H; r.W = d.W; r.C = d.C; r.pitch = d.pitch;
+  r.swap = d.C == 3 && d.order == ATTWARP_BGR;
+  r.hmax = g.hmax; r.vmax = g.vmax; r.bpm = g.bpm;
+  r.mcus_x = g.mcus_x; r.nmcu = (int32_t)g.nmcu;
+  for (int tb = 0; tb < 2; ++tb)
+    for (int k = 0; k < 64; ++k) {
+      r.divisor[tb][k] = (uint16_t)(je_quant_value(d.quality, tb, k) << 3);
+      r.recip[tb][k] = je_recip(r.divisor[tb][k]);
+    }
+  int pre = 0;
+  r.header_len = je_write_header(r.header, d, g, own_tables ? &pre : nullptr);
+  return pre;
+}
+
+// A plain or optimised image: its intervals, cut into units; pre: je_fill_image's answer.
+static void je_plan_units(JePlanner& P, int b, JeImageDev& r, const JeImagePlan& pl, int quality, int pre) {
+  const JeGeometry& g = pl.g;
+  r.interval = g.interval; r.nint = g.nint; r.upi = g.upi;
+  r.nunits = g.nunits;
+  r.block_bits = je_block_bound_bits(quality, r.C) + (pl.opt ? JO_EXTRA_BLOCK_BITS : 0);
+  if (pl.opt) {
+    JoImage& o = P.jo_image[P.k_opt];
+    o.image = b;
+    o.pre_len = pre;
+    o.suf_len = r.header_len - pre;
+    o.ntables = r.C == 3 ? 4 : 2;
+    r.opt = ++P.k_opt;
+  }
+  const uint64_t nblocks = (uint64_t)g.nmcu * g.bpm;
+  r.coef_off = P.scratch.take(nblocks * 128, 256);
+  r.ustream_off = P.scratch.take((nblocks * r.block_bits + 7) / 8 + (uint64_t)g.nint + 8, 256);
+  for (int i = 0; i < g.nint; ++i) {
+    const int m0 = i * g.interval, m1 = (int)std::min<int64_t>(g.nmcu, (int64_t)m0 + g.interval);
+    for (int m = m0; m < m1; m += JE_UNIT_MCUS, ++P.unit) {
+      JeUnit& q = P.units[P.unit];
+      q.image = b;
+      q.mcu0 = m;
+      q.nmcu = std::min(JE_UNIT_MCUS, m1 - m);
+      q.interval = i;
+      q.last = m + JE_UNIT_MCUS >= m1;
+      q.index = P.unit - r.unit0;
+      q.slot_off = P.scratch.take(((uint64_t)q.nmcu * g.bpm * r.block_bits + 7) / 8 + 8, 16);
+      if (pl.opt) P.jo_unit[P.k_opt_unit++] = P.unit;
+    }
+  }
+}
+
+// A progressive image.  Its record serves the transform kernel and the jpegprogenc_* kernels; with no unit of its own the scans
+// of launches 3 and 5 pass over it, and jpegprogenc_place_kernel sets its file's length behind them.  pre: SOI .. SOF0.
+static void je_plan_progressive(JePlanner& P, int b, JeImageDev& r, const JeImagePlan& pl, int pre) {
+  const JeGeometry& g = pl.g;
+  r.interval = (int32_t)g.nmcu; r.nint = 1; r.upi = 1;
+  r.nunits = 0;
+  r.header[pre - (10 + 3 * r.C) + 1] = 0xc2;                  // the frame becomes SOF2
+  r.header_len = pre;
+  r.coef_off = P.scratch.take((uint64_t)g.nmcu * g.bpm * 128, 256);
+  for (int64_t m = 0; m < g.nmcu; m += JE_UNIT_MCUS) {
+    JeUnit& q = P.units[P.tunit++];
+    q.image = b;
+    q.mcu0 = (int32_t)m;
+    q.nmcu = (int32_t)std::min<int64_t>(JE_UNIT_MCUS, g.nmcu - m);
+  }
+  PeImage& pi = P.pe_image[P.k_prog];
+  pi.image = b;
+  pi.nscans = pl.p.nscans;
+  pi.seg0 = P.k_seg;
+  pi.nsegs = (int32_t)pl.p.nsegs;
+  pi.header_len = pre;
+  int last_dri = 0;
+  for (int i = 0; i < pl.p.nscans; ++i) {
+    const PeScanGeometry& q = pl.p.scan[i];
+    PeScanPlan& sp = pi.scan[i];
+    sp.seg0 = P.k_seg - pi.seg0;
+    sp.nsegs = q.nseg;
+    sp.wc = q.wc;
+    sp.dri = q.interval != last_dri ? q.interval : 0;        // libjpeg writes a DRI when the interval differs from the last one written
+    last_dri = q.interval;
+    for (int k = 0; k < q.nseg; ++k, ++P.k_seg) {
+      PeSeg& sg = P.pe_seg[P.k_seg];
+      sg.pimage = P.k_prog;
+      sg.scan = i;
+      sg.block0 = (int32_t)(k * q.step);
+      sg.nblocks = (int32_t)std::min<int64_t>(q.step, q.nblk - k * q.step);
+      sg.index = k;
+      sg.cap = (int32_t)(pe_interval_bytes((uint64_t)sg.nblocks, q.block_bits) / 2u);   // (the file's bound counts every byte twice)
+      sg.slot_off = P.scratch.take((uint64_t)sg.cap + 8, 16);
+      sg.aux_off = P.scratch.take(pe_aux_bytes((uint64_t)sg.nblocks));
+    }
+  }
+  ++P.k_prog;
+}
+
+// Behind the last image: what the kernels of the optimised and of the progressive images keep in the scratch buffer.
+static void je_close_plans(JePlanner& P) {
+  if (P.jo) {
+    P.jo->nimages = P.n.nopt;
+    P.jo->nunits = (int32_t)P.n.nopt_units;
+    P.scratch.align(256);
+    P.jo->off_hist = P.scratch.take((uint64_t)P.n.nopt * 4 * 256 * sizeof(uint32_t));
+    P.jo->off_out = P.scratch.take((uint64_t)P.n.nopt * sizeof(JoImageOut));
+  }
+  if (P.pe) {
+    P.pe->nimages = P.n.nprog;
+    P.pe->nsegs = (int32_t)P.n.nsegs;
+    P.pe->ntunits = (int32_t)P.n.nprog_units;
+    P.pe->off_images = P.at.off_progressive + align_up(sizeof(PePlan), 16);
+    P.pe->off_segs = P.pe->off_images + (uint64_t)P.n.nprog * sizeof(PeImage);
+    P.scratch.align(256);
+    P.pe->off_hist = P.scratch.take((uint64_t)P.n.nprog * PE_SLOTS * 256 * sizeof(uint32_t));
+    P.pe->off_tables = P.scratch.take((uint64_t)P.n.nprog * PE_SLOTS * sizeof(JoTable));
+    P.pe->off_seg_out = P.scratch.take((uint64_t)P.n.nsegs * sizeof(PeSegOut));
+  }
+}
+
+// The header of a planned table and its two optional records, read once and checked (jo.nimages, pe.nimages 0: no such record).
+struct JeTableHead {
+  attwarp_jpegenc_header h;
+  JoPlan jo;
+  PePlan pe;
+};
+static int je_read_table(const void* table_host, const void* table_dev, const void* scratch, const uint8_t* out, size_t out_bytes,
+                         const int64_t* offsets, JeTableHead& T) {
+  ATTWARP_REQUIRE(table_host && table_dev && scratch && out && offsets, "jpegenc_encode: null pointer");
+  std::memset(&T, 0, sizeof T);
+  attwarp_jpegenc_header& h = T.h;
+  std::memcpy(&h, table_host, sizeof h);
+  if (h.magic == JE_MAGIC && h.reserved) {                   // reserved: where the PePlan lies, in 16-byte steps
+    const uint64_t at = (uint64_t)(uint32_t)h.reserved * 16u;
+    ATTWARP_REQUIRE(h.reserved > 0 && at + sizeof(PePlan) <= h.table_bytes, "jpegenc_encode: not a table of attwarp_jpegenc_plan_prog");
+    std::memcpy(&T.pe, static_cast<const uint8_t*>(table_host) + at, sizeof T.pe);
+    ATTWARP_REQUIRE(T.pe.nimages > 0 && T.pe.nimages <= h.B && T.pe.ntunits >= T.pe.nimages && T.pe.nsegs >= T.pe.nimages && T.pe.nsegs <= JE_MAX_UNITS &&
+                        T.pe.ntunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan_prog");
+  }
+  ATTWARP_REQUIRE(h.magic == JE_MAGIC && h.B > 0 && h.nunits >= h.B - T.pe.nimages && h.nunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan");
+  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegenc_encode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
+  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
+                      reinterpret_cast<uintptr_t>(offsets) % 8 == 0,
+                  "jpegenc_encode: table_dev / offsets must be 8-byte, scratch 16-byte aligned");
+  if (h.off_optimize) {                                      // (attwarp_jpegenc_plan_ex: some image takes tables of its own)
+    ATTWARP_REQUIRE(h.off_optimize % 8 == 0 && h.off_optimize + sizeof(JoPlan) <= h.table_bytes, "jpegenc_encode: not a table of attwarp_jpegenc_plan_ex");
+    std::memcpy(&T.jo, static_cast<const uint8_t*>(table_host) + h.off_optimize, sizeof T.jo);
+    ATTWARP_REQUIRE(T.jo.nimages > 0 && T.jo.nimages <= h.B && T.jo.nunits >= T.jo.nimages && T.jo.nunits <= h.nunits,
+                    "jpegenc_encode: not a table of attwarp_jpegenc_plan_ex");
+  }
+  return ATTWARP_OK;
+}
+
 }  // namespace attwarp
 
 using namespace attwarp;
 
 extern "C" size_t attwarp_jpegenc_bound(int H, int W, int C, int quality, int subsampling, int restart_rows) {
-  JeGeometry g;
-  const char* what;
-  if (!je_geometry(H, W, C, quality, subsampling, restart_rows, g, what)) return 0;
-  const uint64_t b = je_bound64(C, quality, restart_rows, g);
-  return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
+  return je_bound_of(H, W, C, quality, subsampling, restart_rows, false, false);
 }
 
 extern "C" size_t attwarp_jpegenc_bound_ex(int H, int W, int C, int quality, int subsampling, int restart_rows, int optimize) {
-  JeGeometry g;
-  const char* what;
-  if (!je_geometry(H, W, C, quality, subsampling, restart_rows, g, what)) return 0;
-  const uint64_t b = je_bound64(C, quality, restart_rows, g, optimize != 0);
-  return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
+  return je_bound_of(H, W, C, quality, subsampling, restart_rows, optimize != 0, false);
 }
 
-// nopt / nopt_units: the optimised images of the call (optimize: NULL, or one flag per image) and their units
-// progressive (NULL, or one flag per image): such an image owns no entropy unit; its transform units (nprog_units) and its
-// segments (nsegs) are counted apart, and optimize is ignored for it (a progressive file always has tables of its own)
-struct PeCounts {
-  int nprog = 0;
-  int64_t nprog_units = 0, nsegs = 0;
-};
-static int jpegenc_count(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, int64_t& nunits, int& nopt, int64_t& nopt_units,
-                         const int32_t* progressive = nullptr, PeCounts* pc = nullptr) {
-  ATTWARP_REQUIRE(images, "jpegenc: null image array");
-  ATTWARP_REQUIRE(B > 0, "jpegenc: non-positive batch size");
-  if (B > (1 << 20)) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: B=%d > 2^20", B);
-  nunits = nopt_units = 0;
-  nopt = 0;
-  for (int b = 0; b < B; ++b) {
-    const attwarp_jpegenc_image& d = images[b];
-    const bool prog = progressive && progressive[b];
-    const bool opt = optimize && optimize[b] && !prog;
-    ATTWARP_REQUIRE(!progressive || progressive[b] == 0 || progressive[b] == 1, "jpegenc: image %d: progressive must be 0 or 1", b);
-    ATTWARP_REQUIRE(!optimize || optimize[b] == 0 || optimize[b] == 1, "jpegenc: image %d: optimize must be 0 or 1", b);
-    ATTWARP_REQUIRE(d.src, "jpegenc: image %d: null pointer", b);
-    ATTWARP_REQUIRE(d.order == ATTWARP_RGB || d.order == ATTWARP_BGR, "jpegenc: image %d: channel order must be ATTWARP_RGB or ATTWARP_BGR", b);
-    JeGeometry g;
-    const char* what;
-    if (!je_geometry(d.H, d.W, d.C, d.quality, d.subsampling, d.restart_rows, g, what))
-      return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d (%d x %d x %d, quality %d, subsampling %d, restart_rows %d): %s", b, d.H, d.W, d.C,
-                  d.quality, d.subsampling, d.restart_rows, what);
-    ATTWARP_REQUIRE((int64_t)d.pitch >= (int64_t)d.W * d.C, "jpegenc: image %d: pitch %d below the row's %lld bytes", b, d.pitch, (long long)d.W * d.C);
-    if (prog) {
-      PeGeometry p;
-      if (!pe_geometry(d.H, d.W, d.C, d.restart_rows, g, p))
-        return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d (%d x %d x %d, restart_rows %d): a progressive scan's restart interval above 65535 "
-                    "(libjpeg clamps it to 65535 and no longer restarts at the rows)", b, d.H, d.W, d.C, d.restart_rows);
-      if (pe_bound64(d.C, p) >= ((uint64_t)1 << 31))
-        return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: the progressive bound of %d x %d x %d is 2 GiB or more", b, d.H, d.W, d.C);
-      // (fewer than 2^23 blocks, as below: a table's frequencies stay far below libjpeg's sentinel)
-      pc->nprog += 1;
-      pc->nprog_units += g.nunits;
-      pc->nsegs += p.nsegs;
-      continue;
-    }
-    if (je_bound64(d.C, d.quality, d.restart_rows, g, opt) >= ((uint64_t)1 << 31))
-      return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: the bound of %d x %d x %d is 2 GiB or more", b, d.H, d.W, d.C);
-    // A table's frequencies add up to at most 64 symbols per block.  A block's bound is above 1024 bits (22 + 63 x 17) and the
-    // file's bound, twice its bytes, is below 2^31: fewer than 2^23 blocks and 2^29 symbols, below libjpeg's sentinel (a larger
-    // frequency would never be merged) and far below the 2^32 of the counters.  This refusal can never trigger.
-    if (opt && (uint64_t)g.nmcu * g.bpm * JO_SYMBOLS_PER_BLOCK >= JO_SENTINEL)
-      return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: image %d: %lld blocks could hold 10^9 symbols or more", b, (long long)g.nmcu * g.bpm);
-    nunits += g.nunits;
-    if (opt) { ++nopt; nopt_units += g.nunits; }
-  }
-  if (nunits + (pc ? pc->nprog_units : 0) > JE_MAX_UNITS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld units in one call (> %d)", (long long)(nunits + (pc ? pc->nprog_units : 0)), JE_MAX_UNITS);
-  if (pc && pc->nsegs > JE_MAX_UNITS)
-    return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: %lld progressive segments (scans x restart intervals) in one call (> %d)", (long long)pc->nsegs, JE_MAX_UNITS);
-  return ATTWARP_OK;
-}
-
-// Without an optimised image the table ends behind the units, as it always did; with one, the JoPlan follows them.
-static uint64_t jpegenc_table_layout(int B, int64_t nunits, int nopt, int64_t nopt_units, uint64_t& off_images, uint64_t& off_units,
-                                     uint64_t& off_huffman, uint64_t& off_optimize, const PeCounts& pc = PeCounts(),
-                                     uint64_t* off_progressive = nullptr) {
-  static_assert(sizeof(attwarp_jpegenc_header) == 80, "the header ends where the Annex K code words start");
-  off_huffman = align_up(sizeof(attwarp_jpegenc_header), 16);
-  off_images = off_huffman + 4 * 256 * sizeof(uint32_t);
-  off_units = off_images + align_up((uint64_t)B * sizeof(JeImageDev), 16);
-  uint64_t end = off_units + (uint64_t)(nunits + pc.nprog_units) * sizeof(JeUnit);   // the progressive images' transform units last
-  off_optimize = nopt ? end : 0;
-  if (nopt) end += sizeof(JoPlan) + (uint64_t)nopt * sizeof(JoImage) + (uint64_t)nopt_units * sizeof(int32_t);
-  if (pc.nprog) {                                            // the PePlan, its images and segments follow, 16-byte aligned
-    end = align_up(end, 16);
-    *off_progressive = end;
-    end += align_up(sizeof(PePlan), 16) + (uint64_t)pc.nprog * sizeof(PeImage) + (uint64_t)pc.nsegs * sizeof(PeSeg);
-  }
-  return end;
+extern "C" size_t attwarp_jpegenc_bound_prog(int H, int W, int C, int quality, int subsampling, int restart_rows, int optimize, int progressive) {
+  return je_bound_of(H, W, C, quality, subsampling, restart_rows, optimize != 0, progressive != 0);
 }
 
 extern "C" size_t attwarp_jpegenc_table_bytes_prog(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, const int32_t* progressive) {
-  int64_t nunits, nopt_units;
-  int nopt;
-  PeCounts pc;
-  if (jpegenc_count(images, B, optimize, nunits, nopt, nopt_units, progressive, &pc) != ATTWARP_OK) return 0;
-  uint64_t a, b, c, d, e;
-  return (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, a, b, c, d, pc, &e);
+  JeCounts n;
+  if (jpegenc_count(images, B, optimize, progressive, n) != ATTWARP_OK) return 0;
+  return (size_t)jpegenc_table_layout(B, n).bytes;
 }
 
 extern "C" size_t attwarp_jpegenc_table_bytes_ex(const attwarp_jpegenc_image* images, int B, const int32_t* optimize) {
@@ -1043,178 +1227,43 @@ extern "C" size_t attwarp_jpegenc_table_bytes(const attwarp_jpegenc_image* image
 
 extern "C" int attwarp_jpegenc_plan_prog(const attwarp_jpegenc_image* images, int B, const int32_t* optimize, const int32_t* progressive,
                                          void* table, size_t table_bytes) {
-  int64_t nunits, nopt_units;
-  int nopt;
-  PeCounts pc;
-  if (const int rc = jpegenc_count(images, B, optimize, nunits, nopt, nopt_units, progressive, &pc)) return rc;
+  JeCounts n;
+  if (const int rc = jpegenc_count(images, B, optimize, progressive, n)) return rc;
   ATTWARP_REQUIRE(table, "jpegenc_plan: null table");
-  attwarp_jpegenc_header h;
-  std::memset(&h, 0, sizeof h);
-  uint64_t off_progressive = 0;
-  const size_t need = (size_t)jpegenc_table_layout(B, nunits, nopt, nopt_units, h.off_images, h.off_units, h.off_huffman, h.off_optimize, pc,
-                                                   &off_progressive);
+  const JeLayout at = jpegenc_table_layout(B, n);
+  const size_t need = (size_t)at.bytes;
   ATTWARP_REQUIRE(table_bytes >= need, "jpegenc_plan: table of %zu bytes, %zu needed", table_bytes, need);
-  if (off_progressive / 16 > 0x7fffffffull) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: a table of %zu bytes", need);
-  h.reserved = (int32_t)(off_progressive / 16);
+  if (at.off_progressive / 16 > 0x7fffffffull) return fail(ATTWARP_E_UNSUPPORTED, "jpegenc: a table of %zu bytes", need);
   uint8_t* t = static_cast<uint8_t*>(table);
   std::memset(t, 0, need);
+  attwarp_jpegenc_header h;
+  std::memset(&h, 0, sizeof h);
   h.magic = JE_MAGIC;
   h.B = B;
-  h.nunits = (int32_t)nunits;
+  h.nunits = (int32_t)n.nunits;
+  h.reserved = (int32_t)(at.off_progressive / 16);           // where the PePlan lies, in 16-byte steps (0: no progressive image)
   h.table_bytes = need;
+  h.off_images = at.off_images; h.off_units = at.off_units; h.off_huffman = at.off_huffman; h.off_optimize = at.off_optimize;
   for (int k = 0; k < 4; ++k) {
     uint32_t code[256];
     je_build_huffman(k, code);
     std::memcpy(t + h.off_huffman + (size_t)k * 1024, code, sizeof code);
   }
+  JePlanner P(t, n, at);
+  P.scratch.take((uint64_t)n.nunits * sizeof(JeUnitOut), 256);                 // the units' JeUnitOut lead the scratch buffer
+  h.off_image_out = P.scratch.take((uint64_t)B * sizeof(JeImageOut), 256);
   JeImageDev* im = reinterpret_cast<JeImageDev*>(t + h.off_images);
-  JeUnit* un = reinterpret_cast<JeUnit*>(t + h.off_units);
-  h.off_image_out = align_up((uint64_t)nunits * sizeof(JeUnitOut), 256);
-  uint64_t soff = h.off_image_out + align_up((uint64_t)B * sizeof(JeImageOut), 256), out_bytes = 0;
-  int32_t s = 0;
-  JoPlan* plan = nopt ? reinterpret_cast<JoPlan*>(t + h.off_optimize) : nullptr;
-  JoImage* oimg = nopt ? reinterpret_cast<JoImage*>(plan + 1) : nullptr;
-  int32_t* ounit = nopt ? reinterpret_cast<int32_t*>(oimg + nopt) : nullptr;
-  int k_opt = 0;
-  int64_t k_unit = 0;
-  PePlan* pplan = pc.nprog ? reinterpret_cast<PePlan*>(t + off_progressive) : nullptr;
-  PeImage* pimg = pc.nprog ? reinterpret_cast<PeImage*>(t + off_progressive + align_up(sizeof(PePlan), 16)) : nullptr;
-  PeSeg* pseg = pc.nprog ? reinterpret_cast<PeSeg*>(pimg + pc.nprog) : nullptr;
-  int k_prog = 0;
-  int32_t k_seg = 0, k_tunit = (int32_t)nunits;              // a progressive image's transform units: behind every other unit
   for (int b = 0; b < B; ++b) {
-    const attwarp_jpegenc_image& d = images[b];
-    const bool prog = progressive && progressive[b];
-    const bool opt = optimize && optimize[b] && !prog;
-    JeGeometry g;
-    const char* what;
-    je_geometry(d.H, d.W, d.C, d.quality, d.subsampling, d.restart_rows, g, what);
-    JeImageDev& r = im[b];
-    if (prog) {
-      // Its record serves the transform kernel and the jpegprogenc_* kernels; with no unit of its own the scans of launches 3 and
-      // 5 pass over it, and jpegprogenc_place_kernel sets its file's length behind them.
-      PeGeometry p;
-      pe_geometry(d.H, d.W, d.C, d.restart_rows, g, p);
-      r.src = d.src; r.H = d.H; r.W = d.W; r.C = d.C; r.pitch = d.pitch;
-      r.swap = d.C == 3 && d.order == ATTWARP_BGR;
-      r.hmax = g.hmax; r.vmax = g.vmax; r.bpm = g.bpm;
-      r.mcus_x = g.mcus_x; r.nmcu = (int32_t)g.nmcu;
-      r.interval = (int32_t)g.nmcu; r.nint = 1; r.upi = 1;
-      r.unit0 = s; r.nunits = 0;
-      for (int tb = 0; tb < 2; ++tb)
-        for (int k = 0; k < 64; ++k) {
-          r.divisor[tb][k] = (uint16_t)(je_quant_value(d.quality, tb, k) << 3);
-          r.recip[tb][k] = je_recip(r.divisor[tb][k]);
-        }
-      int pre = 0;
-      je_write_header(r.header, d, g, &pre);                  // SOI .. SOF0: the frame becomes SOF2
-      r.header[pre - (10 + 3 * d.C) + 1] = 0xc2;
-      r.header_len = pre;
-      r.coef_off = soff;
-      soff += align_up((uint64_t)g.nmcu * g.bpm * 128, 256);
-      for (int64_t m = 0; m < g.nmcu; m += JE_UNIT_MCUS) {
-        JeUnit& q = un[k_tunit++];
-        q.image = b;
-        q.mcu0 = (int32_t)m;
-        q.nmcu = (int32_t)std::min<int64_t>(JE_UNIT_MCUS, g.nmcu - m);
-      }
-      PeImage& pi = pimg[k_prog];
-      pi.image = b;
-      pi.nscans = p.nscans;
-      pi.seg0 = k_seg;
-      pi.nsegs = (int32_t)p.nsegs;
-      pi.header_len = pre;
-      int last_dri = 0;
-      for (int i = 0; i < p.nscans; ++i) {
-        const PeScanGeometry& q = p.scan[i];
-        PeScanPlan& sp = pi.scan[i];
-        sp.seg0 = k_seg - pi.seg0;
-        sp.nsegs = q.nseg;
-        sp.wc = q.wc;
-        sp.dri = q.interval != last_dri ? q.interval : 0;    // libjpeg writes a DRI when the interval differs from the last one written
-        last_dri = q.interval;
-        for (int k = 0; k < q.nseg; ++k, ++k_seg) {
-          PeSeg& sg = pseg[k_seg];
-          sg.pimage = k_prog;
-          sg.scan = i;
-          sg.block0 = (int32_t)(k * q.step);
-          sg.nblocks = (int32_t)std::min<int64_t>(q.step, q.nblk - k * q.step);
-          sg.index = k;
-          sg.cap = (int32_t)(pe_interval_bytes((uint64_t)sg.nblocks, q.block_bits) / 2u);   // (the file's bound counts every byte twice)
-          sg.slot_off = soff;
-          soff += align_up((uint64_t)sg.cap + 8, 16);
-          sg.aux_off = soff;
-          soff += pe_aux_bytes((uint64_t)sg.nblocks);
-        }
-      }
-      ++k_prog;
-      out_bytes += pe_bound64(d.C, p);
-      continue;
-    }
-    r.src = d.src; r.H = d.H; r.W = d.W; r.C = d.C; r.pitch = d.pitch;
-    r.swap = d.C == 3 && d.order == ATTWARP_BGR;
-    r.hmax = g.hmax; r.vmax = g.vmax; r.bpm = g.bpm;
-    r.mcus_x = g.mcus_x; r.nmcu = (int32_t)g.nmcu;
-    r.interval = g.interval; r.nint = g.nint; r.upi = g.upi;
-    r.unit0 = s; r.nunits = g.nunits;
-    r.block_bits = je_block_bound_bits(d.quality, d.C) + (opt ? JO_EXTRA_BLOCK_BITS : 0);
-    for (int tb = 0; tb < 2; ++tb)
-      for (int k = 0; k < 64; ++k) {
-        r.divisor[tb][k] = (uint16_t)(je_quant_value(d.quality, tb, k) << 3);
-        r.recip[tb][k] = je_recip(r.divisor[tb][k]);
-      }
-    if (opt) {
-      JoImage& o = oimg[k_opt];
-      o.image = b;
-      r.header_len = je_write_header(r.header, d, g, &o.pre_len);
-      o.suf_len = r.header_len - o.pre_len;
-      o.ntables = d.C == 3 ? 4 : 2;
-      r.opt = ++k_opt;
-    } else {
-      r.header_len = je_write_header(r.header, d, g);
-    }
-    const uint64_t nblocks = (uint64_t)g.nmcu * g.bpm;
-    r.coef_off = soff;
-    soff += align_up(nblocks * 128, 256);
-    r.ustream_off = soff;
-    soff += align_up((nblocks * r.block_bits + 7) / 8 + (uint64_t)g.nint + 8, 256);
-    for (int i = 0; i < g.nint; ++i) {
-      const int m0 = i * g.interval, m1 = (int)std::min<int64_t>(g.nmcu, (int64_t)m0 + g.interval);
-      for (int m = m0; m < m1; m += JE_UNIT_MCUS, ++s) {
-        JeUnit& q = un[s];
-        q.image = b;
-        q.mcu0 = m;
-        q.nmcu = std::min(JE_UNIT_MCUS, m1 - m);
-        q.interval = i;
-        q.last = m + JE_UNIT_MCUS >= m1;
-        q.index = s - r.unit0;
-        q.slot_off = soff;
-        soff += align_up(((uint64_t)q.nmcu * g.bpm * r.block_bits + 7) / 8 + 8, 16);
-        if (opt) ounit[k_unit++] = s;
-      }
-    }
-    out_bytes += je_bound64(d.C, d.quality, d.restart_rows, g, opt);
+    JeImagePlan pl;
+    je_image_plan(images[b], optimize && optimize[b], progressive && progressive[b], pl);     // (jpegenc_count accepted it)
+    const int pre = je_fill_image(im[b], images[b], pl.g, pl.opt || pl.prog);
+    im[b].unit0 = P.unit;
+    if (pl.prog) je_plan_progressive(P, b, im[b], pl, pre);
+    else je_plan_units(P, b, im[b], pl, images[b].quality, pre);
+    h.out_bytes += pl.bound;
   }
-  if (nopt) {
-    plan->nimages = nopt;
-    plan->nunits = (int32_t)nopt_units;
-    plan->off_hist = align_up(soff, 256);
-    plan->off_out = plan->off_hist + (uint64_t)nopt * 4 * 256 * sizeof(uint32_t);
-    soff = plan->off_out + (uint64_t)nopt * sizeof(JoImageOut);
-  }
-  if (pc.nprog) {
-    pplan->nimages = pc.nprog;
-    pplan->nsegs = (int32_t)pc.nsegs;
-    pplan->ntunits = (int32_t)pc.nprog_units;
-    pplan->off_images = off_progressive + align_up(sizeof(PePlan), 16);
-    pplan->off_segs = pplan->off_images + (uint64_t)pc.nprog * sizeof(PeImage);
-    pplan->off_hist = align_up(soff, 256);
-    pplan->off_tables = pplan->off_hist + (uint64_t)pc.nprog * PE_SLOTS * 256 * sizeof(uint32_t);
-    pplan->off_seg_out = pplan->off_tables + (uint64_t)pc.nprog * PE_SLOTS * sizeof(JoTable);
-    soff = pplan->off_seg_out + (uint64_t)pc.nsegs * sizeof(PeSegOut);
-  }
-  h.scratch_bytes = soff;
-  h.out_bytes = out_bytes;
+  je_close_plans(P);
+  h.scratch_bytes = P.scratch.at;
   std::memcpy(t, &h, sizeof h);
   return ATTWARP_OK;
 }
@@ -1223,103 +1272,51 @@ extern "C" int attwarp_jpegenc_plan_ex(const attwarp_jpegenc_image* images, int 
   return attwarp_jpegenc_plan_prog(images, B, optimize, nullptr, table, table_bytes);
 }
 
-extern "C" size_t attwarp_jpegenc_bound_prog(int H, int W, int C, int quality, int subsampling, int restart_rows, int optimize, int progressive) {
-  if (!progressive) return attwarp_jpegenc_bound_ex(H, W, C, quality, subsampling, restart_rows, optimize);
-  JeGeometry g;
-  PeGeometry p;
-  const char* what;
-  if (!je_geometry(H, W, C, quality, subsampling, restart_rows, g, what) || !pe_geometry(H, W, C, restart_rows, g, p)) return 0;
-  const uint64_t b = pe_bound64(C, p);
-  return b < ((uint64_t)1 << 31) ? (size_t)b : 0;
-}
-
 extern "C" int attwarp_jpegenc_plan(const attwarp_jpegenc_image* images, int B, void* table, size_t table_bytes) {
   return attwarp_jpegenc_plan_ex(images, B, nullptr, table, table_bytes);
 }
 
+// One launch: the kernel over `grid` workgroups of `block` threads on st; its own name goes into the error text.
+#define JE_LAUNCH(kernel, grid, block, ...)                                          \
+  do {                                                                               \
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);         \
+    if (const int rc = check_launch(#kernel)) return rc;                             \
+  } while (0)
+
 extern "C" int attwarp_jpegenc_encode(const void* table_host, const void* table_dev, void* scratch, uint8_t* out, size_t out_bytes,
                                       int64_t* offsets, void* stream) {
-  ATTWARP_REQUIRE(table_host && table_dev && scratch && out && offsets, "jpegenc_encode: null pointer");
-  attwarp_jpegenc_header h;
-  std::memcpy(&h, table_host, sizeof h);
-  // (attwarp_jpegenc_plan_prog: reserved is where the record of the progressive images lies, in 16-byte steps)
-  PePlan pp;
-  std::memset(&pp, 0, sizeof pp);
-  if (h.magic == JE_MAGIC && h.reserved) {
-    const uint64_t at = (uint64_t)(uint32_t)h.reserved * 16u;
-    ATTWARP_REQUIRE(h.reserved > 0 && at + sizeof(PePlan) <= h.table_bytes, "jpegenc_encode: not a table of attwarp_jpegenc_plan_prog");
-    std::memcpy(&pp, static_cast<const uint8_t*>(table_host) + at, sizeof pp);
-    ATTWARP_REQUIRE(pp.nimages > 0 && pp.nimages <= h.B && pp.ntunits >= pp.nimages && pp.nsegs >= pp.nimages && pp.nsegs <= JE_MAX_UNITS &&
-                        pp.ntunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan_prog");
-  }
-  ATTWARP_REQUIRE(h.magic == JE_MAGIC && h.B > 0 && h.nunits >= h.B - pp.nimages && h.nunits <= JE_MAX_UNITS, "jpegenc_encode: not a table of attwarp_jpegenc_plan");
-  ATTWARP_REQUIRE(out_bytes >= h.out_bytes, "jpegenc_encode: out of %zu bytes, %llu needed", out_bytes, (unsigned long long)h.out_bytes);
-  ATTWARP_REQUIRE(reinterpret_cast<uintptr_t>(table_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 &&
-                      reinterpret_cast<uintptr_t>(offsets) % 8 == 0,
-                  "jpegenc_encode: table_dev / offsets must be 8-byte, scratch 16-byte aligned");
+  JeTableHead T;
+  if (const int rc = je_read_table(table_host, table_dev, scratch, out, out_bytes, offsets, T)) return rc;
+  const attwarp_jpegenc_header& h = T.h;
   hipStream_t st = as_stream(stream);
   const uint8_t* td = static_cast<const uint8_t*>(table_dev);
   uint8_t* sc = static_cast<uint8_t*>(scratch);
-  hipLaunchKernelGGL(jpegenc_transform_kernel, dim3(h.nunits + pp.ntunits), dim3(JE_TNT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegenc_transform_kernel")) return rc;
-  if (h.off_optimize) {                                      // (attwarp_jpegenc_plan_ex: some image takes tables of its own)
-    ATTWARP_REQUIRE(h.off_optimize % 8 == 0 && h.off_optimize + sizeof(JoPlan) <= h.table_bytes, "jpegenc_encode: not a table of attwarp_jpegenc_plan_ex");
-    JoPlan plan;
-    std::memcpy(&plan, static_cast<const uint8_t*>(table_host) + h.off_optimize, sizeof plan);
-    ATTWARP_REQUIRE(plan.nimages > 0 && plan.nimages <= h.B && plan.nunits >= plan.nimages && plan.nunits <= h.nunits,
-                    "jpegenc_encode: not a table of attwarp_jpegenc_plan_ex");
-    if (tune(TUNE_JPEGOPT_GIVEN_HIST) != 1) {                // (tuning flavour, 1: the caller filled the histograms)
-      hipLaunchKernelGGL(jpegopt_clear_kernel, dim3(plan.nimages), dim3(JE_NT), 0, st, td, sc);
-      if (const int rc = check_launch("jpegopt_clear_kernel")) return rc;
-      hipLaunchKernelGGL(jpegopt_histogram_kernel, dim3(plan.nunits), dim3(JE_NT), 0, st, td, sc);
-      if (const int rc = check_launch("jpegopt_histogram_kernel")) return rc;
-    }
-    hipLaunchKernelGGL(jpegopt_tables_kernel, dim3(plan.nimages), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegopt_tables_kernel")) return rc;
-  }
-  if (pp.nimages) {                                          // progressive images: statistics, tables, bytes
-    const int groups = (pp.nsegs + PE_LANES - 1) / PE_LANES;
-    hipLaunchKernelGGL(jpegprogenc_clear_kernel, dim3(pp.nimages), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegprogenc_clear_kernel")) return rc;
-    hipLaunchKernelGGL(jpegprogenc_summary_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegprogenc_summary_kernel")) return rc;
-    hipLaunchKernelGGL(jpegprogenc_resolve_kernel, dim3(groups), dim3(PE_LANES), 0, st, td, sc);
-    if (const int rc = check_launch("jpegprogenc_resolve_kernel")) return rc;
-    hipLaunchKernelGGL(jpegprogenc_count_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegprogenc_count_kernel")) return rc;
-    hipLaunchKernelGGL(jpegprogenc_tables_kernel, dim3(pp.nimages), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegprogenc_tables_kernel")) return rc;
-    hipLaunchKernelGGL(jpegprogenc_code_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegprogenc_code_kernel")) return rc;
-  }
+  const uint8_t* csc = sc;
+  const int64_t* coffsets = offsets;
   const bool plain = h.nunits > 0;                           // (false: every image of the call is progressive)
-  if (plain) {
-    hipLaunchKernelGGL(jpegenc_entropy_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegenc_entropy_kernel")) return rc;
+  JE_LAUNCH(jpegenc_transform_kernel, h.nunits + T.pe.ntunits, JE_TNT, td, sc);
+  if (T.jo.nimages) {                                        // optimised images: histograms, tables, header
+    if (tune(TUNE_JPEGOPT_GIVEN_HIST) != 1) {                // (tuning flavour, 1: the caller filled the histograms)
+      JE_LAUNCH(jpegopt_clear_kernel, T.jo.nimages, JE_NT, td, sc);
+      JE_LAUNCH(jpegopt_histogram_kernel, T.jo.nunits, JE_NT, td, sc);
+    }
+    JE_LAUNCH(jpegopt_tables_kernel, T.jo.nimages, JE_NT, td, sc);
   }
-  hipLaunchKernelGGL(jpegenc_scan_bits_kernel, dim3(h.B), dim3(JE_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegenc_scan_bits_kernel")) return rc;
-  if (plain) {
-    hipLaunchKernelGGL(jpegenc_gather_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegenc_gather_kernel")) return rc;
+  if (T.pe.nimages) {                                        // progressive images: statistics, tables, bytes
+    JE_LAUNCH(jpegprogenc_clear_kernel, T.pe.nimages, JE_NT, td, sc);
+    JE_LAUNCH(jpegprogenc_summary_kernel, T.pe.nsegs, JE_NT, td, sc);
+    JE_LAUNCH(jpegprogenc_resolve_kernel, (T.pe.nsegs + PE_LANES - 1) / PE_LANES, PE_LANES, td, sc);
+    JE_LAUNCH(jpegprogenc_count_kernel, T.pe.nsegs, JE_NT, td, sc);
+    JE_LAUNCH(jpegprogenc_tables_kernel, T.pe.nimages, JE_NT, td, sc);
+    JE_LAUNCH(jpegprogenc_code_kernel, T.pe.nsegs, JE_NT, td, sc);
   }
-  hipLaunchKernelGGL(jpegenc_scan_bytes_kernel, dim3(h.B), dim3(JE_NT), 0, st, td, sc);
-  if (const int rc = check_launch("jpegenc_scan_bytes_kernel")) return rc;
-  if (pp.nimages) {                                          // behind the scan above, which leaves no length for an image without units
-    hipLaunchKernelGGL(jpegprogenc_place_kernel, dim3(pp.nimages), dim3(JE_NT), 0, st, td, sc);
-    if (const int rc = check_launch("jpegprogenc_place_kernel")) return rc;
-  }
-  hipLaunchKernelGGL(jpegenc_scan_files_kernel, dim3(1), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), offsets);
-  if (const int rc = check_launch("jpegenc_scan_files_kernel")) return rc;
-  if (plain) {
-    hipLaunchKernelGGL(jpegenc_write_kernel, dim3(h.nunits), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), out,
-                       static_cast<const int64_t*>(offsets));
-    if (const int rc = check_launch("jpegenc_write_kernel")) return rc;
-  }
-  if (pp.nimages) {
-    hipLaunchKernelGGL(jpegprogenc_write_kernel, dim3(pp.nsegs), dim3(JE_NT), 0, st, td, static_cast<const uint8_t*>(sc), out,
-                       static_cast<const int64_t*>(offsets));
-    if (const int rc = check_launch("jpegprogenc_write_kernel")) return rc;
-  }
+  if (plain) JE_LAUNCH(jpegenc_entropy_kernel, h.nunits, JE_NT, td, sc);
+  JE_LAUNCH(jpegenc_scan_bits_kernel, h.B, JE_NT, td, sc);
+  if (plain) JE_LAUNCH(jpegenc_gather_kernel, h.nunits, JE_NT, td, sc);
+  JE_LAUNCH(jpegenc_scan_bytes_kernel, h.B, JE_NT, td, sc);
+  if (T.pe.nimages) JE_LAUNCH(jpegprogenc_place_kernel, T.pe.nimages, JE_NT, td, sc);   // behind the scan above, which leaves no length for an image without units
+  JE_LAUNCH(jpegenc_scan_files_kernel, 1, JE_NT, td, csc, offsets);
+  if (plain) JE_LAUNCH(jpegenc_write_kernel, h.nunits, JE_NT, td, csc, out, coffsets);
+  if (T.pe.nimages) JE_LAUNCH(jpegprogenc_write_kernel, T.pe.nsegs, JE_NT, td, csc, out, coffsets);
   return ATTWARP_OK;
 }

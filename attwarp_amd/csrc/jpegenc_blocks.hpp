@@ -50,6 +50,17 @@ struct JeUnitOut {                     // what the kernels leave per unit at the
 };
 static_assert(sizeof(JeUnitOut) == 32, "record layout");
 
+// The parts of a planned table: its header, image i, unit i.
+__host__ __device__ inline const attwarp_jpegenc_header* je_header(const uint8_t* table) {
+  return reinterpret_cast<const attwarp_jpegenc_header*>(table);
+}
+__host__ __device__ inline const JeImageDev* je_image(const uint8_t* table, int i) {
+  return reinterpret_cast<const JeImageDev*>(table + je_header(table)->off_images) + i;
+}
+__host__ __device__ inline const JeUnit& je_unit(const uint8_t* table, int i) {
+  return reinterpret_cast<const JeUnit*>(table + je_header(table)->off_units)[i];
+}
+
 __host__ __device__ inline int je_min(int a, int b) { return a < b ? a : b; }
 
 // ---- Annex K ---------------------------------------------------------------------------------------------------------------

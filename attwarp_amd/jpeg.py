@@ -26,9 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._batch import (TABLE, FileBatch, file_bytes, indexed_device, planned_table, raise_first_broken, scattered, split_indices,
-                     uploaded)
-from ._lib import call, ptr, stream_ptr
+from ._batch import (TABLE, FileBatch, ImageBatch, download, file_bytes, indexed_device, planned_table, raise_first_broken, scattered,
+                     split_indices, write_files)
 
 JPEGDEC_MAX_UNITS = _lib.JPEGDEC_MAX_UNITS              # restart intervals per image
 JPEGDEC_MAX_BLOCKS = _lib.JPEGDEC_MAX_BLOCKS            # 8x8 blocks per image, all components (exclusive)
@@ -858,27 +857,6 @@ JPEGENC_MAX_DIM = _lib.JPEGENC_MAX_DIM                  # W and H at most
 _ENC_IMAGE_DTYPE = np.dtype(_lib.JpegEncImage)
 
 
-def _enc_geometry(t: torch.Tensor):
-    """(H, W, C, pitch) of a uint8 [H,W,C] / [H,W] view whose pixels are dense along a row."""
-    if t.dtype != torch.uint8 or t.dim() not in (2, 3):
-        raise ValueError(f"jpeg: uint8 [H,W,C] / [H,W] tensors expected, got {t.dtype} {tuple(t.shape)}")
-    H, W = int(t.shape[0]), int(t.shape[1])
-    C = int(t.shape[2]) if t.dim() == 3 else 1
-    if H < 1 or W < 1:
-        raise ValueError(f"jpeg: empty image {tuple(t.shape)}")
-    if C not in (1, 3):
-        raise ValueError(f"jpeg: {C} channels (grey [H,W] / [H,W,1] or RGB [H,W,3] only)")
-    if H > JPEGENC_MAX_DIM or W > JPEGENC_MAX_DIM:
-        raise ValueError(f"jpeg: {W} x {H} exceeds JPEGENC_MAX_DIM = {JPEGENC_MAX_DIM}")
-    st = t.stride()
-    if (t.dim() == 3 and C > 1 and st[2] != 1) or (W > 1 and st[1] != C):
-        raise ValueError(f"jpeg: unsupported strides {st} for shape {tuple(t.shape)}: the pixels of a row must be dense")
-    pitch = int(st[0]) if H > 1 else W * C
-    if pitch < W * C or pitch >= 1 << 31:
-        raise ValueError(f"jpeg: unsupported row stride {st[0]} for rows of {W * C} bytes")
-    return H, W, C, pitch
-
-
 def _is_int(v) -> bool:
     return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
@@ -890,7 +868,7 @@ def _enc_per_image(value, B: int, what: str, ok):
     return vals
 
 
-class JpegBatch:
+class JpegBatch(ImageBatch):
     """One batch of differently sized uint8 images on the GPU, planned for ``attwarp_jpegenc_encode``: list of [H,W,3] /
     [H,W] / [H,W,1] tensors or one [B,H,W,C] tensor.  The images are referenced, not copied (any byte address, any row
     pitch): keep them alive; their CONTENT is read at every :meth:`run`, so a captured run re-encodes what they hold then.
@@ -913,15 +891,20 @@ class JpegBatch:
     A grey image ignores ``subsampling`` and is always the file of a bare ``Image.save`` of an "L" image, factors 1 x 1.
     Pillow, GIVEN the keyword for an "L" image, writes its factors into the component's SOF0 entry (one byte: 0x21 or 0x22
     in place of 0x11) and the same scan data, so for grey images ``encode_jpeg(..., subsampling=s)`` differs in that one
-    byte from ``Image.save(..., subsampling=s)`` unless s is "4:4:4"."""
+    byte from ``Image.save(..., subsampling=s)`` unless s is "4:4:4".
+
+    :meth:`run` takes seven launches, three more with an optimised image and eight more with a progressive one (the lists at
+    the top of csrc/jpegenc.hip)."""
+
+    _who, _prefix, _dtype_error, _entry, _max_side = "JpegBatch", "jpeg", ValueError, "attwarp_jpegenc_encode", JPEGENC_MAX_DIM
+
+    @staticmethod
+    def _too_large(H: int, W: int, C: int) -> str:
+        return f"jpeg: {W} x {H} exceeds JPEGENC_MAX_DIM = {JPEGENC_MAX_DIM}"
 
     def __init__(self, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", out: Optional[torch.Tensor] = None,
                  optimize=False, progressive=False):
-        if isinstance(images, torch.Tensor):
-            if images.dim() != 4:
-                raise ValueError("JpegBatch: a tensor batch is [B,H,W,C]; pass differently sized images as a list")
-            images = [images[b] for b in range(images.shape[0])]
-        images = list(images)
+        images = self._views(images)
         if not images:
             raise ValueError("JpegBatch: empty batch")
         B = len(images)
@@ -932,14 +915,7 @@ class JpegBatch:
         orders = _enc_per_image(order, B, "order ('rgb' / 'bgr')", lambda v: v in _ORDERS)
         self.optimize = [bool(v) for v in _enc_per_image(optimize, B, "optimize (True / False)", lambda v: isinstance(v, (bool, np.bool_)))]
         self.progressive = [bool(v) for v in _enc_per_image(progressive, B, "progressive (True / False)", lambda v: isinstance(v, (bool, np.bool_)))]
-        geo = [_enc_geometry(t) for t in images]
-        dev = _lib.require_gpu(*images)
-        self.images, self.B, self._dev = images, B, dev
-        rec = np.zeros(B, dtype=_ENC_IMAGE_DTYPE)
-        rec["src"] = [t.data_ptr() for t in images]
-        rec["H"] = [g[0] for g in geo]; rec["W"] = [g[1] for g in geo]; rec["C"] = [g[2] for g in geo]
-        rec["pitch"] = [g[3] for g in geo]
-        rec["order"] = [_ORDERS[o] for o in orders]
+        rec = self._records(images, _ENC_IMAGE_DTYPE, [_ORDERS[o] for o in orders])
         rec["quality"] = [int(q) for q in qualities]
         rec["subsampling"] = [int(ids[s]) for s in subs]
         rec["restart_rows"] = [int(r) for r in rows]
@@ -952,55 +928,21 @@ class JpegBatch:
             planners = ("attwarp_jpegenc_table_bytes_prog", rp, B, fp, pp), ("attwarp_jpegenc_plan_prog", rp, B, fp, pp, TABLE)
         else:
             planners = ("attwarp_jpegenc_table_bytes_ex", rp, B, fp), ("attwarp_jpegenc_plan_ex", rp, B, fp, TABLE)
-        self.table_host, self.header = planned_table(*planners, _lib.JpegEncHeader, ValueError, "JpegBatch: ")
-        self._pixels = sum(g[0] * g[1] * g[2] for g in geo)
-        with torch.cuda.device(dev):
-            self.table_dev = uploaded(self.table_host, dev)
-            self.scratch = torch.empty(int(self.header.scratch_bytes), device=dev, dtype=torch.uint8)
-            if out is None:
-                out = torch.empty(self.bound, device=dev, dtype=torch.uint8)
-            elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < self.bound:
-                raise ValueError(f"JpegBatch: out must be a dense uint8 buffer of at least {self.bound} bytes on the images' device")
-            self.buffer = out
-            self.offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
-
-    @property
-    def bound(self) -> int:
-        """Bytes the files of this batch take at most (``attwarp_jpegenc_bound_prog`` summed): the capacity ``out`` needs."""
-        return int(self.header.out_bytes)
+        self._to_device(*planned_table(*planners, _lib.JpegEncHeader, ValueError, "JpegBatch: "), out)
 
     @property
     def units(self) -> int:
         return int(self.header.nunits)
-
-    def algorithmic_bytes(self) -> int:
-        """Pixel bytes the encoder has to read (the compressed bytes written depend on the content)."""
-        return self._pixels
-
-    def run(self):
-        """Seven launches on the current stream (ten with an optimised image, six more with a progressive one) -> ``(buffer, offsets)``: file b is
-        ``buffer[offsets[b]:offsets[b+1]]`` (uint8 and int64 [B+1], both on the device).  No host-dependent argument:
-        capturable in a graph."""
-        with torch.cuda.device(self._dev):
-            call("attwarp_jpegenc_encode", self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.scratch), ptr(self.buffer),
-                 self.buffer.numel(), ptr(self.offsets), stream_ptr(self._dev))
-        return self.buffer, self.offsets
 
 
 def encode_jpeg(images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False, progressive=False) -> List[bytes]:
     """uint8 GPU images (list of [H,W,3] / [H,W] of any sizes, or [B,H,W,C]) -> the bytes of one JPEG file each, what
     ``Image.fromarray(a).save(f, "JPEG", quality=..., subsampling=..., restart_marker_rows=..., optimize=..., progressive=...)`` writes.  Raw pixels never
     leave the device.  See :class:`JpegBatch` for the keywords."""
-    from .png import download
     return download(*JpegBatch(images, quality, subsampling, restart_rows, order, optimize=optimize, progressive=progressive).run())
 
 
 def write_jpeg(paths, images, quality=75, subsampling="4:2:0", restart_rows=0, order="rgb", optimize=False, progressive=False) -> None:
     """:func:`encode_jpeg`, each file written to its path."""
-    paths = list(paths)
     n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
-    if len(paths) != n:
-        raise ValueError(f"write_jpeg: {len(paths)} paths for {n} images")
-    for p, f in zip(paths, encode_jpeg(images, quality, subsampling, restart_rows, order, optimize, progressive)):
-        with open(p, "wb") as fh:
-            fh.write(f)
+    write_files("write_jpeg", paths, n, lambda: encode_jpeg(images, quality, subsampling, restart_rows, order, optimize, progressive))

@@ -1761,23 +1761,27 @@ def heatmap_overlay_ragged(rb: RaggedBatch, alpha: float = 0.5, order: str = "rg
     return packed, views
 
 
+def _ragged_images_to_save(rb: RaggedBatch, paths, what: str, order: str, who: str):
+    """What ``save_png_ragged`` / ``save_jpeg_ragged`` (``who``) write: ``(paths, images, their channel order)``."""
+    paths = list(paths)
+    if len(paths) != rb.B:
+        raise ValueError(f"{who}: {len(paths)} paths for a batch of {rb.B}")
+    if what == "warped":
+        if rb.C not in (1, 3):
+            raise ValueError(f"{who}: one- or three-channel images only")
+        return paths, rb.out, order
+    if what == "mota":
+        return paths, [rb.mota_of(b) for b in range(rb.B)], "rgb"
+    raise ValueError(f"{who}: what is 'warped' or 'mota'")
+
+
 def save_png_ragged(rb: RaggedBatch, paths, what: str = "warped", filter: str = "sub", order: str = "rgb", match="rle"):
     """The file-writing leg of the driver loop (main_batched.py:243-303) for a whole ragged batch: the warped images
     (``what="warped"``: ``rb.out``) or the up-sampled masks (``what="mota"``: :meth:`RaggedBatch.mota_of`, grey files) of
     ``rb`` as PNG files, encoded on the GPU in one :class:`attwarp_amd.png.PngBatch` -- only compressed bytes are copied
     to the host.  Enqueue it after the launches that produced what it saves; ``order``: channel order of ``rb.images``;
     ``match``: "rle" / "lz", one value or one per image (:class:`attwarp_amd.png.PngBatch`)."""
-    paths = list(paths)
-    if len(paths) != rb.B:
-        raise ValueError(f"save_png_ragged: {len(paths)} paths for a batch of {rb.B}")
-    if what == "warped":
-        if rb.C not in (1, 3):
-            raise ValueError("save_png_ragged: one- or three-channel images only")
-        images = rb.out
-    elif what == "mota":
-        images, order = [rb.mota_of(b) for b in range(rb.B)], "rgb"
-    else:
-        raise ValueError("save_png_ragged: what is 'warped' or 'mota'")
+    paths, images, order = _ragged_images_to_save(rb, paths, what, order, "save_png_ragged")
     png.write_png(paths, images, filter=filter, order=order, match=match)
 
 
@@ -1788,15 +1792,5 @@ def save_jpeg_ragged(rb: RaggedBatch, paths, what: str = "warped", quality=75, s
     write (Pillow's defaults; ``restart_rows=1`` is what this project's reader decodes fastest).  ``order``: channel order
     of ``rb.images``.  ``optimize``: the images' own Huffman tables, the files of ``Image.save(..., optimize=True)``;
     ``progressive``: those of ``Image.save(..., progressive=True)``."""
-    paths = list(paths)
-    if len(paths) != rb.B:
-        raise ValueError(f"save_jpeg_ragged: {len(paths)} paths for a batch of {rb.B}")
-    if what == "warped":
-        if rb.C not in (1, 3):
-            raise ValueError("save_jpeg_ragged: one- or three-channel images only")
-        images = rb.out
-    elif what == "mota":
-        images, order = [rb.mota_of(b) for b in range(rb.B)], "rgb"
-    else:
-        raise ValueError("save_jpeg_ragged: what is 'warped' or 'mota'")
+    paths, images, order = _ragged_images_to_save(rb, paths, what, order, "save_jpeg_ragged")
     jpeg.write_jpeg(paths, images, quality, subsampling, restart_rows, order, optimize, progressive)

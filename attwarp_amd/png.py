@@ -20,8 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._batch import TABLE, FileBatch, file_bytes, indexed_device, planned_table, raise_first_broken, uploaded
-from ._lib import call, ptr, stream_ptr
+from ._batch import TABLE, FileBatch, ImageBatch, download, file_bytes, indexed_device, planned_table, raise_first_broken, write_files
 
 PNG_SEG_BYTES = _lib.PNG_SEG_BYTES              # filtered bytes one workgroup encodes at most
 PNG_MAX_ROW_BYTES = _lib.PNG_MAX_ROW_BYTES      # 1 + W * C at most: W <= 8191 for RGB, 24575 for grey
@@ -32,14 +31,6 @@ _ORDERS = {"rgb": _lib.RGB, "bgr": _lib.BGR}
 _PNG_IMAGE_DTYPE = np.dtype(_lib.PngImage)
 
 
-def _views(images) -> List[torch.Tensor]:
-    if isinstance(images, torch.Tensor):
-        if images.dim() != 4:
-            raise ValueError("png: a tensor batch is [B,H,W,C]; pass differently sized images as a list")
-        return [images[b] for b in range(images.shape[0])]
-    return list(images)
-
-
 def _per_image(value, names, B: int, what: str):
     vals = [value] * B if isinstance(value, str) else list(value)
     if len(vals) != B or any(v not in names for v in vals):
@@ -47,95 +38,47 @@ def _per_image(value, names, B: int, what: str):
     return vals
 
 
-def _geometry(t: torch.Tensor):
-    """(H, W, C, pitch) of a uint8 [H,W,C] / [H,W] view whose pixels are dense along a row."""
-    if t.dtype != torch.uint8 or t.dim() not in (2, 3):
-        raise TypeError(f"png: uint8 [H,W,C] / [H,W] tensors expected, got {t.dtype} {tuple(t.shape)}")
-    H, W = int(t.shape[0]), int(t.shape[1])
-    C = int(t.shape[2]) if t.dim() == 3 else 1
-    if H < 1 or W < 1:
-        raise ValueError(f"png: empty image {tuple(t.shape)}")
-    if C not in (1, 3):
-        raise ValueError(f"png: {C} channels (grey [H,W] / [H,W,1] or RGB [H,W,3] only)")
-    if 1 + W * C > PNG_MAX_ROW_BYTES:
-        raise ValueError(f"png: a row of 1 + {W} x {C} bytes exceeds PNG_MAX_ROW_BYTES = {PNG_MAX_ROW_BYTES}")
-    st = t.stride()
-    if (t.dim() == 3 and C > 1 and st[2] != 1) or (W > 1 and st[1] != C):
-        raise ValueError(f"png: unsupported strides {st} for shape {tuple(t.shape)}: the pixels of a row must be dense")
-    pitch = int(st[0]) if H > 1 else W * C
-    if pitch < W * C or pitch >= 1 << 31:
-        raise ValueError(f"png: unsupported row stride {st[0]} for rows of {W * C} bytes")
-    return H, W, C, pitch
-
-
-class PngBatch:
+class PngBatch(ImageBatch):
     """One batch of differently sized uint8 images on the GPU, planned for ``attwarp_png_encode``: list of [H,W,C] / [H,W]
     tensors or one [B,H,W,C] tensor, C 1 or 3.  The images are referenced, not copied (any byte address, any row pitch):
     keep them alive; their CONTENT is read at every :meth:`run`, so a captured run re-encodes whatever they hold then.
 
     ``filter``: "none" / "sub" / "up" / "average" / "paeth" / "adaptive", ``order``: "rgb" / "bgr", ``match``: "rle" / "lz"
-    -- one value or one per image.  ``out``: a uint8 device buffer of at least :attr:`bound` bytes.  Limits raise ValueError
-    before any launch.
+    -- one value or one per image.  ``out``: a uint8 device buffer of at least :attr:`bound` bytes (every segment stored).
+    Limits raise ValueError before any launch.
 
     ``match="lz"`` (the default "rle" is OpenCV's Z_RLE) also looks for repeated content inside each segment
     and keeps, per segment, the shortest of the two token streams and the stored form: pages of text, up-sampled masks and
     panels come out much smaller, photographs the same bytes as with "rle", never longer; the encode launch takes longer.
-    tests/pnglz_ref.py restates the bytes; :meth:`routes` says what each segment chose."""
+    tests/pnglz_ref.py restates the bytes; :meth:`routes` says what each segment chose.
+
+    :meth:`run` takes three launches (four when the batch mixes ``match="rle"`` and ``"lz"`` images: one encode launch per
+    route)."""
+    _who, _prefix, _dtype_error, _entry, _max_row_bytes = "PngBatch", "png", TypeError, "attwarp_png_encode", PNG_MAX_ROW_BYTES
+
+    @staticmethod
+    def _too_large(H: int, W: int, C: int) -> str:
+        return f"png: a row of 1 + {W} x {C} bytes exceeds PNG_MAX_ROW_BYTES = {PNG_MAX_ROW_BYTES}"
 
     def __init__(self, images, filter: Union[str, Sequence[str]] = "sub", order: Union[str, Sequence[str]] = "rgb",
                  out: Optional[torch.Tensor] = None, match: Union[str, Sequence[str]] = "rle"):
-        images = _views(images)
+        images = self._views(images, "png")
         if not images:
             raise ValueError("PngBatch: empty batch")
         B = len(images)
         filters = _per_image(filter, _lib.PNG_FILTER_IDS, B, "filter")
         orders = _per_image(order, _ORDERS, B, "order")
         matches = np.array([_lib.PNG_MATCH_IDS[m] for m in _per_image(match, _lib.PNG_MATCH_IDS, B, "match")], np.int32)
-        geo = [_geometry(t) for t in images]
-        dev = _lib.require_gpu(*images)
-        self.images, self.B, self._dev = images, B, dev
-        rec = np.zeros(B, dtype=_PNG_IMAGE_DTYPE)
-        rec["src"] = [t.data_ptr() for t in images]
-        rec["H"] = [g[0] for g in geo]; rec["W"] = [g[1] for g in geo]; rec["C"] = [g[2] for g in geo]
-        rec["pitch"] = [g[3] for g in geo]
-        rec["order"] = [_ORDERS[o] for o in orders]
+        rec = self._records(images, _PNG_IMAGE_DTYPE, [_ORDERS[o] for o in orders])
         rec["filter"] = [_lib.PNG_FILTER_IDS[f] for f in filters]
         rp = ctypes.c_void_p(rec.ctypes.data)
         mp = ctypes.c_void_p(matches.ctypes.data) if matches.any() else None      # (NULL: the plain planners' table)
-        self.table_host, self.header = planned_table(("attwarp_png_table_bytes_ex", rp, B, mp), ("attwarp_png_plan_ex", rp, B, mp, TABLE),
-                                                     _lib.PngHeader, ValueError, "PngBatch: ")
-        self._pixels = sum(g[0] * g[1] * g[2] for g in geo)
-        with torch.cuda.device(dev):
-            self.table_dev = uploaded(self.table_host, dev)
-            self.scratch = torch.empty(int(self.header.scratch_bytes), device=dev, dtype=torch.uint8)
-            if out is None:
-                out = torch.empty(self.bound, device=dev, dtype=torch.uint8)
-            elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < self.bound:
-                raise ValueError(f"PngBatch: out must be a dense uint8 buffer of at least {self.bound} bytes on the images' device")
-            self.buffer = out
-            self.offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
-
-    @property
-    def bound(self) -> int:
-        """Bytes the files of this batch take at most (every segment stored): the capacity ``out`` needs."""
-        return int(self.header.out_bytes)
+        self._to_device(*planned_table(("attwarp_png_table_bytes_ex", rp, B, mp), ("attwarp_png_plan_ex", rp, B, mp, TABLE),
+                                       _lib.PngHeader, ValueError, "PngBatch: "), out)
 
     @property
     def segments(self) -> int:
         return int(self.header.nseg)
-
-    def algorithmic_bytes(self) -> int:
-        """Pixel bytes the encoder has to read (the compressed bytes written depend on the content)."""
-        return self._pixels
-
-    def run(self):
-        """Three launches on the current stream (four when the batch mixes ``match="rle"`` and ``"lz"`` images: one encode
-        launch per route) -> ``(buffer, offsets)``: file b is ``buffer[offsets[b]:offsets[b+1]]``
-        (uint8 and int64 [B+1], both on the device).  No host-dependent argument: capturable in a graph."""
-        with torch.cuda.device(self._dev):
-            call("attwarp_png_encode", self.table_host.ctypes.data, ptr(self.table_dev), ptr(self.scratch), ptr(self.buffer),
-                 self.buffer.numel(), ptr(self.offsets), stream_ptr(self._dev))
-        return self.buffer, self.offsets
 
     def routes(self) -> List[int]:
         """After a :meth:`run` (synchronises): what every segment was written as, in file order -- 0 the distance-1 block,
@@ -143,13 +86,6 @@ class PngBatch:
         and tests."""
         rec = self.scratch[:self.segments * 24].cpu().numpy().view(np.uint32).reshape(self.segments, 6)
         return [int(r) for r in rec[:, 5]]
-
-
-def download(buffer: torch.Tensor, offsets: torch.Tensor) -> List[bytes]:
-    """The files of a :meth:`PngBatch.run`: one device-to-host copy of the offsets, one of the used bytes."""
-    offs = offsets.cpu().tolist()
-    data = buffer[:offs[-1]].cpu().numpy().tobytes()
-    return [data[a:b] for a, b in zip(offs[:-1], offs[1:])]
 
 
 def encode_png(images, filter="sub", order="rgb", match="rle") -> List[bytes]:
@@ -161,13 +97,8 @@ def encode_png(images, filter="sub", order="rgb", match="rle") -> List[bytes]:
 
 def write_png(paths, images, filter="sub", order="rgb", match="rle") -> None:
     """:func:`encode_png`, each file written to its path."""
-    paths, images = list(paths), _views(images)
-    if len(paths) != len(images):
-        raise ValueError(f"write_png: {len(paths)} paths for {len(images)} images")
-    files = encode_png(images, filter, order, match)
-    for p, f in zip(paths, files):
-        with open(p, "wb") as fh:
-            fh.write(f)
+    paths, images = list(paths), PngBatch._views(images, "png")
+    write_files("write_png", paths, len(images), lambda: encode_png(images, filter, order, match))
 
 
 # ---- decoding ---------------------------------------------------------------------------------------------------------------

@@ -100,6 +100,17 @@ def test_big_cases_in_batches_of_their_own(name):
     assert m["flush_7fff"] + m["flush_be"] >= 1 or m["max_depth"] > 16
 
 
+def test_more_segments_than_one_chunk_of_the_place_scan():
+    """A grey image 8 wide and 352 high with a restart per block row: 44 intervals in each of the six scans, 264 segments, so
+    the prefix sums of jpegprogenc_place_kernel carry from their first chunk of 256 into a second."""
+    from attwarp_amd import jpeg
+    import jpegenc_cases as K
+    img = K.noise(352, 8, 1, 77)
+    assert sum(g[2] for g in P.scan_geometry(352, 8, 1, "4:2:0", 1)) == 264
+    got = jpeg.encode_jpeg([torch.from_numpy(img).to(DEV)], progressive=True, restart_rows=1)
+    same_bytes(got[0], P.encode(img, restart_rows=1), "264 segments")
+
+
 def test_a_case_alone_first_last_and_in_the_middle(corpus):
     from attwarp_amd import jpeg
     items, tens, b, files = corpus
