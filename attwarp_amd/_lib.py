@@ -499,6 +499,21 @@ def debug_override(**settings: int):
         _lib = outer
 
 
+def remap_plan(B: int, C: int, H: int, W: int, H_out: int, W_out: int, mode: str = "cv2", channels_last: bool = True):
+    """Test / measurement hook (tuning flavour, no GPU needed): what the float32 staged resample would launch for 16-byte
+    aligned images of this shape, under the overrides in force -- ``{"rows", "cpw", "group", "stream"}`` (output rows per
+    block, row blocks per workgroup, XCD group, 1 when the launch takes the streaming variant: nontemporal stores),
+    or None when the request takes the generic gather kernel."""
+    tl = load_tuning()
+    key = "remap_plan:%d,%d,%d,%d,%d,%d,%d,%d" % (0 if channels_last else 1, {"exact": 0, "cv2": 1}[mode], B, C, H, W, H_out, W_out)
+    packed = c_int(-1)
+    rc = tl.attwarp_debug_set(key.encode(), 0, ctypes.byref(packed))
+    if rc != 0:
+        raise AttWarpError(f"attwarp_debug_set failed ({rc}): {tl.attwarp_last_error().decode('utf-8', 'replace')}")
+    v = packed.value
+    return None if v < 0 else {"rows": v & 255, "cpw": (v >> 8) & 255, "group": (v >> 16) & 255, "stream": (v >> 24) & 1}
+
+
 def ptr(t: torch.Tensor | None):
     return None if t is None else c_void_p(t.data_ptr())
 

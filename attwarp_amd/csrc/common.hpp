@@ -186,6 +186,7 @@ enum TuneKey {
   TUNE_PNGDEC_ROUTE,         // 1: attwarp_pngdec_decode sends every image down the serial route (one wave from the stream's start)
   TUNE_JPEGPROG_SYNC_KINDS,  // attwarp_jpegdec_plan_scans_ex cuts only scans of the kinds in this mask (bit JP_DC_FIRST .. JP_AC_REFINE): per-kind timing
   TUNE_JPEGOPT_GIVEN_HIST,   // 1: attwarp_jpegenc_encode neither clears nor counts: the table kernel runs on the histograms the caller left in the scratch buffer
+  TUNE_REMAP_STREAM,         // cache policy of the 1024 x 3 float32 resample whatever the batch size: 0 cached, 1 streaming (nontemporal stores)
   TUNE_COUNT
 };
 #ifdef ATTWARP_TUNING

@@ -10,11 +10,33 @@ int launch_rows_exact(const RowsParams& p, int tile_ko, hipStream_t st, const St
   return launch_rows_mode<ATTWARP_EXACT, false, 1, 4, false>(p, tile_ko, st, nullptr);
 }
 
+// Cache policy of a launch (STREAM of remap_rows_block), decided here and nowhere else.
+// A workgroup's output rows are written once and never read by this kernel, yet with the default policy every one of those
+// lines allocates in an L2 that 96 resident workgroups per XCD turn over in under two row-steps.  The streaming variant
+// (remap_rows_stream_kernel) stores them nontemporal.  It exists for ONE class: whole interleaved rows of 10-12 KB with
+// affine store offsets (1024 x 3: KI = 3, KO = 12), both arithmetic modes.  Measured at 1024x1024x3 float32 B=256, product
+// builds in alternating processes on two leases (docs/experiments.md, "Cache policy by reuse"): the kernel alone does not
+// move; the benchmark's step, whose kernels follow one another without a pause, takes 2.3-2.4 % less.
+// Nontemporal look-ahead loads on top lose 5-9 % and are not built.
+// Streaming is wrong for a batch that can stay in the 256 MiB Infinity Cache, where the next kernel finds the output (the
+// nontemporal hook: -15 % there): only a launch whose source plus destination bytes exceed the cache takes it.
+constexpr long long ROWS_STREAM_MIN_BYTES = 256LL << 20;
+static int rows_stream_policy(bool eligible, long long bytes) {
+  if (!eligible) return 0;
+  if (const int v = tune(TUNE_REMAP_STREAM); v >= 0) return v != 0;      // test hook: 0 cached, 1 streaming, whatever the size
+  return bytes > ROWS_STREAM_MIN_BYTES;
+}
+
+// what the planner chose for a request (tuning flavour: readable without a launch, attwarp_debug_set "remap_plan:...")
+struct RowsPlan { int R, cpw, group, stream; };
+
 // Returns via *handled whether the fast path took the request.
 // ex != nullptr: the fused step (block ranges for the map construction and the attention reduce of other batches are
 // appended to the resample's grid; ex->nR8 is filled in here).
-int launch_remap_rows(const float* src, float* dst, int layout, int B, int C, int H, int W, int Ho, int Wo,
-                      const float* mx, const float* my, int mode, hipStream_t st, bool* handled, StepExtra* ex) {
+// plan_only != nullptr: nothing is launched, the plan is returned (no pointer is dereferenced; src counts for its alignment).
+static int plan_and_launch_rows(const float* src, float* dst, int layout, int B, int C, int H, int W, int Ho, int Wo,
+                                const float* mx, const float* my, int mode, hipStream_t st, bool* handled, StepExtra* ex,
+                                RowsPlan* plan_only) {
   *handled = false;
   if (tune(TUNE_REMAP_VARIANT) == 1) return ATTWARP_OK;  // force the generic gather kernel (A/B measurements, tests)
   RowsParams p;
@@ -119,6 +141,9 @@ int launch_remap_rows(const float* src, float* dst, int layout, int B, int C, in
   while (cpw > 1 && (long long)((p.nblk + cpw - 1) / cpw) * B * p.ntiles < 4096) cpw >>= 1;   // keep the chip filled
   if (cpw * R > RMAX) cpw = RMAX / R;        // a workgroup's rows are one list in LDS (remap_rows_block)
   p.wpi = (p.nblk + cpw - 1) / cpw;
+  p.stream = rows_stream_policy(!tiled && !ua && !ex && p.NP == 1 && row_bytes >= 10 * 1024 && p.VLV > 2 * NT_BIG &&
+                                    p.VLV <= 3 * NT_BIG && p.OVL == 12 * NT_BIG,
+                                (long long)B * (p.img_stride + p.oimg_stride) * (long long)sizeof(float));
   const long long nb = (long long)p.wpi * B * p.ntiles;
   if (nb > 2147483647LL) return ATTWARP_OK;
   p.nblocks = (int)nb;
@@ -128,6 +153,10 @@ int launch_remap_rows(const float* src, float* dst, int layout, int B, int C, in
   p.nt_loads = tune(TUNE_REMAP_NT) > 0 ? tune(TUNE_REMAP_NT) : 0;      // bit 0: nontemporal loads of block-private rows, bit 1: nontemporal stores
 #endif
   *handled = true;
+  if (plan_only) {
+    *plan_only = RowsPlan{p.R, cpw, p.no_swz, p.stream};
+    return ATTWARP_OK;
+  }
   // (one-wave workgroups for rows <= 4 KB were measured too: 336x336x3, B=256: 0.136 ms vs 0.134 ms with
   //  4-wave workgroups -- no gain, so a single workgroup size is instantiated)
   const int tile_ko = tiled ? TILE_KO : 0;
@@ -136,6 +165,25 @@ int launch_remap_rows(const float* src, float* dst, int layout, int B, int C, in
   if (mode == ATTWARP_CV2) return launch_rows_cv2(p, tile_ko, st, ex);
   return launch_rows_exact(p, tile_ko, st, ex);
 }
+
+int launch_remap_rows(const float* src, float* dst, int layout, int B, int C, int H, int W, int Ho, int Wo,
+                      const float* mx, const float* my, int mode, hipStream_t st, bool* handled, StepExtra* ex) {
+  return plan_and_launch_rows(src, dst, layout, B, C, H, W, Ho, Wo, mx, my, mode, st, handled, ex, nullptr);
+}
+
+#ifdef ATTWARP_TUNING
+// The plan of the plain float32 resample of 16-byte aligned images, packed R | cpw << 8 | group << 16 | stream << 24
+// (-1: the request takes the generic gather kernel).  Nothing is launched and no GPU is needed.
+int remap_rows_plan_query(int layout, int mode, int B, int C, int H, int W, int Ho, int Wo, int* packed) {
+  bool handled = false;
+  RowsPlan pl{0, 0, 0, 0};
+  const float* aligned = reinterpret_cast<const float*>(uintptr_t(4096));     // never dereferenced
+  const int rc = plan_and_launch_rows(aligned, nullptr, layout, B, C, H, W, Ho, Wo, nullptr, nullptr, mode, nullptr, &handled,
+                                      nullptr, &pl);
+  *packed = handled ? (pl.R | pl.cpw << 8 | pl.group << 16 | pl.stream << 24) : -1;
+  return rc;
+}
+#endif
 
 }  // namespace attwarp
 

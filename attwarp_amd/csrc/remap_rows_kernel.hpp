@@ -24,6 +24,14 @@
 // neighbour (1/R extra), and the XCD-aware block order makes that halo an L2 hit.  Algorithmic bytes per
 // image = 2*S*S*C*4; no MFMA: there is no contraction here, the kernel is HBM-bound.
 //
+// What is cached.  Source rows take the default policy: the halo rows must stay in L2 until the neighbouring row block
+// comes, and loads marked nontemporal lose 5-9 % here (docs/experiments.md, "Cache policy by reuse").  Output rows are
+// written once and never read: the STREAM instantiation (remap_rows_stream_kernel: 1024 x 3 rows, launches larger than the
+// Infinity Cache: rows_stream_policy in remap_rows.hip) stores them nontemporal.  Alone the kernel runs as fast either way
+// (same traffic, same L2 hit rate); inside the benchmark's step, where kernels follow one another without a pause and the next
+// one starts on an L2 full of this one's dirty lines, the step is 2.3 % shorter (1024 x 1024 x 3, B=256).  A batch that fits the Infinity Cache keeps the
+// default policy: its output is the next kernel's input and should stay cached.
+//
 // Arithmetic is identical to remap_gather_kernel / the oracle in both modes.
 #pragma once
 #include "common.hpp"
@@ -33,8 +41,8 @@
 
 // Source-row loads and output stores.  Tuning flavour only (test hook "remap_nt"): bit 0 = NONTEMPORAL loads of the source
 // rows, bit 1 = nontemporal stores.  Measured on MI355X, 1024x1024x3 float32 B=256 (rounds 2-3, docs/experiments.md): never
-// a gain worth a lease-dependent loss; -15 % on a batch that fits the Infinity Cache.  The product library always issues
-// plain loads and stores.
+// a gain worth a lease-dependent loss; -15 % on a batch that fits the Infinity Cache.  The product library issues plain
+// loads, and plain stores everywhere but in the STREAM instantiation (above), which needs no run-time bit.
 // (the register sets are clang vectors, not HIP's float4 struct: struct copies are memcpy's, and the row loop's control flow
 // left an array of them in scratch memory)
 typedef float rows_v4f __attribute__((ext_vector_type(4)));
@@ -145,6 +153,7 @@ struct RowsParams {
   int map_div;       // maps belong to image b / map_div (planes of a planar image dispatched as images)
   int ntiles;        // TILED: column tiles per row (each KO*NT output elements), else 1
   int unaligned;     // rows / images that are not 16-byte aligned: the UA instantiations (remap_rows_ua.hip)
+  int stream;        // host side only: 1 = this launch takes the STREAM instantiation (rows_stream_policy, remap_rows.hip)
 };
 
 constexpr int RMAX = 64;
@@ -178,9 +187,10 @@ constexpr int NT_BIG = 256;    // threads per workgroup (4 waves share a row)
 // relative to the ROW start (unaligned access mode); the row's last vector is loaded END-aligned -- the four floats that
 // end with the row: nothing behind the image is read -- and staged at its own float index in the LDS row (it overlaps the
 // vector in front of it with the same values), so the gather needs no change at all.
-template <int NT, int KI, int KO, bool HWC, bool AFF, bool TILED, int MODE, bool SINGLE, bool UA = false>
+template <int NT, int KI, int KO, bool HWC, bool AFF, bool TILED, int MODE, bool SINGLE, bool UA = false, bool STREAM = false>
 __device__ __forceinline__ void remap_rows_block(const RowsParams& p, const int block_index, float* smem) {
   static_assert(!UA || (HWC && !TILED && !AFF), "unaligned rows: interleaved, not column-tiled, per-element output offsets");
+  static_assert(!STREAM || (!UA && !TILED), "streaming stores: whole aligned rows only");
   constexpr bool CV = MODE == ATTWARP_CV2;
   float* s_my = smem;                                   // RMAX floats
   constexpr int ROWF = KI * NT * 4;                     // floats per staged source row (padded to whole waves)
@@ -380,7 +390,8 @@ __device__ __forceinline__ void remap_rows_block(const RowsParams& p, const int 
           } else {                                                                                  \
             o_ = lerp_rn(v0[kk], v1[kk], fxr[k]);                                                   \
           }                                                                                         \
-          ATTWARP_ROW_STORE(reinterpret_cast<float*>(orow + off), o_);                              \
+          if constexpr (STREAM) __builtin_nontemporal_store(o_, reinterpret_cast<float*>(orow + off)); \
+          else ATTWARP_ROW_STORE(reinterpret_cast<float*>(orow + off), o_);                         \
         }                                                                                           \
       }                                                                                             \
       __builtin_amdgcn_sched_barrier(0);                                                            \
@@ -539,6 +550,20 @@ __global__ __launch_bounds__(NT) void remap_rows_kernel(const RowsParams p) {
 #endif
 }
 
+// The streaming variant: whole interleaved rows with affine store offsets, two LDS buffers, nontemporal stores.  A kernel of
+// its own name, so that every other instantiation keeps its symbol and its code.
+template <int NT, int KI, int KO, int MODE>
+__global__ __launch_bounds__(NT) void remap_rows_stream_kernel(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+#ifdef ATTWARP_TUNING
+  const TraceStart t0 = trace_now();
+#endif
+  remap_rows_block<NT, KI, KO, true, true, false, MODE, false, false, true>(p, blockIdx.x, smem);
+#ifdef ATTWARP_TUNING
+  trace_block(p.trace, t0, 2);
+#endif
+}
+
 // ---- the fused step: ONE launch = the resample of batch k + the map construction of batch k+1 + the attention
 // reduce of batch k+2 (three independent pieces of work on different buffers; attwarp_warp_step_fused).  The three
 // kernels of a step are 41 / 14 / 22 us at B=64 336x336: launched one behind the other -- on one stream or as graph
@@ -661,6 +686,12 @@ static int launch_rows_t(const RowsParams& p, hipStream_t st, const StepExtra* e
     return check_launch("warp_step_kernel");
   } else {
     const dim3 g(p.nblocks);
+    if constexpr (KI == 3 && KO == 12 && !SINGLE) {   // the one class with a streaming variant (rows_stream_policy: HWC, AFF)
+      if (p.stream) {
+        hipLaunchKernelGGL((remap_rows_stream_kernel<NT, KI, KO, MODE>), g, t, lds, st, p);
+        return check_launch("remap_rows_stream_kernel");
+      }
+    }
     if (p.NP == 1 && p.OVL == KO * NT)   // every (lane, k) is a distinct in-row element: affine store offsets
       hipLaunchKernelGGL((remap_rows_kernel<NT, KI, KO, true, true, false, MODE, SINGLE>), g, t, lds, st, p);
     else if (p.NP == 1)

@@ -70,7 +70,11 @@ ATTWARP_API const char* attwarp_last_error(void);
  * to check the variants against each other (e.g. key "remap_variant" = 1: generic gather kernel only; "remap_rows" =
  * R).  value < 0 restores "automatic", key "reset" restores every key; the previous value of the key is returned
  * through *previous when it is not NULL.  Keys: see kTuneNames in csrc/error.hip.  Process wide, single threaded,
- * test only. */
+ * test only.
+ * One key is a query and sets nothing: "remap_plan:<layout>,<mode>,<B>,<C>,<H>,<W>,<H_out>,<W_out>" writes to *previous
+ * what the float32 staged resample would launch for 16-byte aligned images of that shape under the overrides in force,
+ * packed as rows per block | row blocks per workgroup << 8 | XCD group << 16 | streaming policy << 24, or -1 when the
+ * request takes the generic gather kernel.  Nothing is launched; no GPU is needed. */
 #ifdef ATTWARP_TUNING
 ATTWARP_API int attwarp_debug_set(const char* key, int value, int* previous);
 /* measurement yardstick (csrc/calib.hip): ONE launch that reads read_bytes from src and writes write_bytes to dst (16-byte
